@@ -3,7 +3,7 @@
 Headline benchmark: denoised 64^3 PET sub-volumes per second at 250 DDPM
 steps (BASELINE.json), published architecture, fp32, synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -33,6 +33,14 @@ parity       : the metric's "PSNR vs ref".  (a) the first timed volume against t
 cpu_baseline : oracle/ (the CPU restatement pinned to the reference) timed on
                this box's host cores on a bounded sample (a few p_sample steps
                of the same workload), extrapolated to volumes/s.  N=1, rank 0.
+
+--dump-outputs DIR : after the timed steps rank 0 writes what the last timed step
+               returned -- the finished samples of every rank, in rank order, as the
+               all_gather hands them over -- to DIR/sample.npy (float32).  Weights,
+               conditioning volume and noise are seeded, so the same arguments give the
+               same inputs on every run and two builds can be compared file for file.
+               Above 64 MB a fixed, seeded subset of the elements is written instead
+               (DIR/sample_subset.npy, flat).
 """
 
 import argparse
@@ -202,6 +210,24 @@ def rel_err(got, ref):
     return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as float32 .npy files under out_dir; above DUMP_LIMIT_BYTES in all, every array is cut to
+    the same seeded choice of a proportional share of its elements (flattened, ascending index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_subset"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        log("[bench] wrote %s.npy %s" % (name, a.shape))
+
+
 def cpu_baseline(arch, sd, size, respacing, n_steps, threads):
     """Time the oracle's p_sample steps on the host cores (bounded sample).  Returns the record
     and the oracle's state after those steps (the checker of parity (b))."""
@@ -246,7 +272,7 @@ def cpu_baseline(arch, sd, size, respacing, n_steps, threads):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (volumes per GPU), at least 1")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--ddpm-steps", type=int, default=250)
     ap.add_argument("--size", type=int, default=64)
@@ -276,7 +302,11 @@ def main():
                          "default: the model's own setting")
     ap.add_argument("--sampler", choices=["ddpm", "ddim"], default="ddpm",
                     help="ddim: --ddpm-steps DDIM steps (timestep_respacing ddimN, eta 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples of the last timed step to DIR/*.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `bench.py --gpus N` by itself: start the N ranks as a CHILD process (this parent has made no
     # GPU call and never makes one), relay rank 0's JSON line, exit with the child's status.
@@ -372,6 +402,7 @@ def main():
     T = diff.num_timesteps
 
     loop = diff.ddim_sample_loop_progressive if args.sampler == "ddim" else diff.p_sample_loop_progressive
+    received = []   # what the last full volume handed its caller: every rank's sample, in rank order
 
     def one_volume(step_index, measure, max_steps=None):
         # per-volume noise keyed by the GLOBAL volume index, so results do not depend on world size
@@ -395,6 +426,9 @@ def main():
             mine = sample.to(coll_dev)
             gathered = [torch.empty_like(mine) for _ in range(world)]
             dist.all_gather(gathered, mine)
+            received[:] = gathered
+        else:
+            received[:] = [sample]
         return sample, timing
 
     def sync():
@@ -427,6 +461,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(sample).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sample": torch.cat([r.cpu() for r in received])})
 
     # roofline of the conv kernel family, from the instrumented forwards
     by_tag = {}

@@ -29,6 +29,9 @@ def _fake_denoise(index):
 
 def _worker(rank, world, rdv_file, n_items, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    # host-only ranks, also on a GPU box: setup_dist would otherwise bind rank r to cuda:r, and a one-GPU
+    # box has no cuda:1
+    torch.cuda.is_available = lambda: False
     # file rendezvous: no TCP port to race for when the whole suite runs
     dist_util.setup_dist(backend="gloo", init_method="file://" + rdv_file)
     assert dist_util.rank() == rank and dist_util.world_size() == world

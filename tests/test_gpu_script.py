@@ -143,7 +143,7 @@ def test_two_rank_run_equals_one_rank_and_loads_checkpoint(tmp_path):
     assert not np.array_equal(a, c)
 
 
-def test_bench_starts_its_own_ranks():
+def test_bench_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (the reference's launcher is
     one command, test_DDPM_3d_mpi.sh:5): the parent starts a two-rank torch.distributed.run child,
     relays rank 0's ONE JSON line and its exit status.  Rehearsal on the one-GPU box: gloo, both ranks
@@ -155,7 +155,7 @@ def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo",
            "--steps", "1", "--warmup", "0", "--ddpm-steps", "5", "--arch", "tiny", "--size", "16",
-           "--cpu-steps", "0", "--probe-ms", "5"]
+           "--cpu-steps", "0", "--probe-ms", "5", "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -164,7 +164,11 @@ def test_bench_starts_its_own_ranks():
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak"
     # the collective library that ran is named: this rehearsal is gloo, so the line claims no RCCL ranks
     assert rec["collective_ranks"] == 2 and rec["collective_backend"] == "gloo" and rec["rccl_ranks"] is None
-    assert rec["steps"] == 1 and rec["value"] > 0
+    assert rec["steps"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    # --dump-outputs: the last timed step's samples as rank 0 received them, both ranks in rank order
+    out = np.load(tmp_path / "dump" / "sample.npy")
+    assert out.dtype == np.float32 and out.shape == (2, 1, 16, 16, 16) and np.isfinite(out).all()
+    assert not np.array_equal(out[0], out[1])                            # each rank sampled its own volume
     # a launcher that hands over the wrong world size is refused, not silently accepted
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1"],
                          env=dict(env, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0"), capture_output=True, text=True,
