@@ -383,6 +383,60 @@ int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise,
                     "ddim_step");
 }
 
+// ------------------------------------------------------------ variational bound
+// grid.y carries the sample index of the element-wise launches
+static bool vb_shape_ok(int N, int voxels, int T) { return N > 0 && N <= 65535 && voxels > 0 && T > 0; }
+
+int ddpm3d_q_sample(const float* x_start, const float* noise, const float* qcoef, const int64_t* t_idx, int N,
+                    int voxels, int T, float* x_t, void* stream) {
+    if (!x_start || !noise || !qcoef || !t_idx || !x_t || !vb_shape_ok(N, voxels, T))
+        return fail(DDPM3D_EINVAL, "q_sample: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    return launched(ddpm3d_launch_q_sample(x_start, noise, qcoef, t_idx, N, voxels, T, x_t, (hipStream_t)stream),
+                    "q_sample");
+}
+
+size_t ddpm3d_vb_terms_workspace_bytes(int N, int voxels) {
+    if (N <= 0 || voxels <= 0) return 0;
+    return (size_t)N * (size_t)ddpm3d_vb_parts(voxels) * 4 * sizeof(double);
+}
+
+static int vb_ws_ok(const char* what, int N, int voxels, const void* ws, size_t ws_bytes) {
+    const size_t need = ddpm3d_vb_terms_workspace_bytes(N, voxels);
+    if (!ws || ws_bytes < need || !aligned16(ws))
+        return fail(DDPM3D_EINVAL, "%s: needs %zu bytes of 16-byte aligned workspace (got %zu)", what, need,
+                    ws ? ws_bytes : (size_t)0);
+    return DDPM3D_OK;
+}
+
+int ddpm3d_vb_terms(const float* model_out, const float* x_start, const float* x_t, const float* noise,
+                    const float* coef, const float* qcoef, const int64_t* t_idx, int N, int voxels, int T,
+                    int flags, void* ws, size_t ws_bytes, float* vb, float* xstart_mse, float* mse, int ld_out,
+                    float* pred_xstart, void* stream) {
+    if (!model_out || !x_start || !x_t || !coef || !qcoef || !t_idx || !vb || !vb_shape_ok(N, voxels, T) ||
+        ld_out <= 0)
+        return fail(DDPM3D_EINVAL, "vb_terms: bad arguments (N=%d voxels=%d T=%d ld_out=%d)", N, voxels, T, ld_out);
+    if ((noise == nullptr) != (mse == nullptr))
+        return fail(DDPM3D_EINVAL, "vb_terms: noise and mse must come together");
+    if (flags & ~(DDPM3D_F_LEARN_SIGMA | DDPM3D_F_PREDICT_XSTART | DDPM3D_F_CLIP))
+        return fail(DDPM3D_EINVAL, "vb_terms: unknown flag bits %#x", flags);
+    const int rc = vb_ws_ok("vb_terms", N, voxels, ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_vb_terms(model_out, x_start, x_t, noise, coef, qcoef, t_idx, N, voxels, T, flags,
+                                           (double*)ws, vb, xstart_mse, mse, ld_out, pred_xstart,
+                                           (hipStream_t)stream),
+                    "vb_terms");
+}
+
+int ddpm3d_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels, int T, void* ws, size_t ws_bytes,
+                     float* out, void* stream) {
+    if (!x_start || !qcoef || !out || !vb_shape_ok(N, voxels, T))
+        return fail(DDPM3D_EINVAL, "prior_bpd: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    const int rc = vb_ws_ok("prior_bpd", N, voxels, ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_prior_bpd(x_start, qcoef, N, voxels, T, (double*)ws, out, (hipStream_t)stream),
+                    "prior_bpd");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

@@ -24,6 +24,16 @@ hipError_t ddpm3d_launch_subsample_hw2(const float* in, int N, int D, int H, int
 hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
                                      const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
                                      float eta, float* sample, float* pred_xstart, hipStream_t st);
+// variational bound (calc_bpd_loop): ws holds ddpm3d_vb_parts(voxels) 32-byte records per sample
+int ddpm3d_vb_parts(int voxels);
+hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,
+                                  int N, int voxels, int T, float* xt, hipStream_t st);
+hipError_t ddpm3d_launch_vb_terms(const float* mo, const float* x_start, const float* x_t, const float* noise,
+                                  const float* coef, const float* qcoef, const int64_t* t_idx, int N, int voxels,
+                                  int T, int flags, double* ws, float* vb, float* xstart_mse, float* mse, int ld,
+                                  float* pred_xstart, hipStream_t st);
+hipError_t ddpm3d_launch_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels, int T, double* ws,
+                                   float* out, hipStream_t st);
 hipError_t ddpm3d_launch_attention(const float* qkv, int N, int T, int heads, int ch, int precision,
                                    const float* bound, int bound_count, int bound_stride, float* out,
                                    hipStream_t st);

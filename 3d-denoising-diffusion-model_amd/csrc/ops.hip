@@ -709,3 +709,228 @@ hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x,
                            voxels, flags, eta, sample, pred_xstart);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------- variational bound
+// calc_bpd_loop's per-step work after the network call (gaussian_diffusion.py:709-742, :872-880) and its helpers
+// (q_sample :188-206, _prior_bpd :821-837, losses.py normal_kl / discretized_gaussian_log_likelihood).  Every element
+// follows the reference's fp32 expression order (contraction is still off here).  Per-sample means: each of
+// ddpm3d_vb_parts(voxels) workgroups sums a fixed slice of the volume in fp64 and writes one 32-byte record
+// {term, xstart sq, eps sq, 0} to the caller's workspace; a second launch folds the records of a sample in a fixed
+// order.  No atomics: the same bits on every run, whatever the launch order.
+#define VB_THREADS 256
+#define VB_UNROLL 4                  // elements per thread per pass, loads issued together
+#define VB_MAX_PARTS 1024
+#define VB_REC 4                     // doubles per record
+
+int ddpm3d_vb_parts(int voxels) {
+    const int per = VB_THREADS * VB_UNROLL;
+    const int p = voxels / per + (voxels % per != 0);
+    return p < VB_MAX_PARTS ? p : VB_MAX_PARTS;
+}
+
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                       const float* __restrict__ qcoef,
+                                                       const int64_t* __restrict__ t_idx, int voxels, int T,
+                                                       float* __restrict__ xt) {
+    const int n = blockIdx.y;
+    const int64_t ti = t_idx[n];
+    float a = __builtin_nanf(""), b = a;          // t outside [0, T): no table row is read, x_t is NaN
+    if (ti >= 0 && ti < T) {
+        a = qcoef[(size_t)ti * DDPM3D_NQCOEF + DDPM3D_Q_SQRT_ACP];
+        b = qcoef[(size_t)ti * DDPM3D_NQCOEF + DDPM3D_Q_SQRT_1M_ACP];
+    }
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += gridDim.x * blockDim.x) {
+        const size_t i = (size_t)n * voxels + v;
+        xt[i] = a * x0[i] + b * noise[i];         // :202-206
+    }
+}
+
+// exp / log / tanh of an fp32 value evaluated in fp64 and rounded once: the correctly rounded fp32 result, which the
+// reference's <=1-ulp fp32 libm returns almost always.  The bound's terms cancel (-1 + lv2 - lv1 + exp(lv1 - lv2) is
+// ~1e-6 at the last steps), so an ulp of a fast fp32 exp would be a per-cent of a term; fp64 VALU work is free here.
+__device__ __forceinline__ float exp_r(float x) { return (float)exp((double)x); }
+__device__ __forceinline__ float log_r(float x) { return (float)log((double)x); }
+
+// losses.py approx_standard_normal_cdf.  th.pow(x, 3) is x * x * x; the double constants reach the fp32 ops rounded
+// to fp32, as torch applies a Python scalar to a float tensor.
+__device__ __forceinline__ float approx_std_normal_cdf(float x) {
+    const float u = (float)0.7978845608028654 * (x + (float)0.044715 * (x * x * x));
+    return 0.5f * (1.0f + (float)tanh((double)u));
+}
+
+// Block sum of three fp64 partials in a fixed order, written as record `rec` by eight lanes with one 4-byte store
+// each (halves of the doubles; no wide store whose data registers could be rewritten behind it).
+__device__ __forceinline__ void vb_write_record(double s0, double s1, double s2, double* __restrict__ rec) {
+    __shared__ double red[3][VB_THREADS / 64];
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; red[2][wave] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2 * VB_REC) {
+        const int k = threadIdx.x >> 1;
+        double tot = 0.0;
+        if (k < 3)
+            for (int w = 0; w < VB_THREADS / 64; ++w) tot += red[k][w];
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(tot);
+        reinterpret_cast<unsigned*>(rec)[threadIdx.x] = (threadIdx.x & 1) ? (unsigned)(bits >> 32) : (unsigned)bits;
+    }
+}
+
+__global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
+    const float* __restrict__ mo, const float* __restrict__ xs_p, const float* __restrict__ xt_p,
+    const float* __restrict__ noise, const float* __restrict__ coef, const float* __restrict__ qcoef,
+    const int64_t* __restrict__ t_idx, int voxels, int T, int flags, int parts, double* __restrict__ slab,
+    float* __restrict__ pred_xstart) {
+    const int n = blockIdx.y, part = blockIdx.x;
+    const int64_t ti = t_idx[n];
+    double s_vb = 0.0, s_x0 = 0.0, s_eps = 0.0;
+    if (ti >= 0 && ti < T) {
+        const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
+        const float c_recip = c[DDPM3D_C_SQRT_RECIP_ACP], c_recipm1 = c[DDPM3D_C_SQRT_RECIPM1_ACP];
+        const float c1 = c[DDPM3D_C_POST_MEAN_COEF1], c2 = c[DDPM3D_C_POST_MEAN_COEF2];
+        const float min_log = c[DDPM3D_C_MIN_LOG], max_log = c[DDPM3D_C_MAX_LOG];
+        const float true_log = qcoef[(size_t)ti * DDPM3D_NQCOEF + DDPM3D_Q_POST_LOG_VAR];
+        const bool learn = flags & DDPM3D_F_LEARN_SIGMA;
+        const int ch = learn ? 2 : 1;
+        const float BIN = (float)(1.0 / 255.0);
+        const int chunk = voxels / parts + (voxels % parts != 0);
+        const long long v0 = (long long)part * chunk;
+        const long long v1 = v0 + chunk < voxels ? v0 + chunk : voxels;
+        for (long long base = v0; base < v1; base += VB_THREADS * VB_UNROLL) {
+#pragma unroll
+            for (int j = 0; j < VB_UNROLL; ++j) {
+                const long long v = base + j * VB_THREADS + threadIdx.x;
+                if (v >= v1) continue;
+                const size_t i = (size_t)n * voxels + v;
+                const float xv = xt_p[i], xs = xs_p[i];
+                const float e = mo[((size_t)n * ch) * voxels + v];
+                // p_mean_variance (:262-318), as sample_step_kernel
+                float x0 = (flags & DDPM3D_F_PREDICT_XSTART) ? e : c_recip * xv - c_recipm1 * e;
+                if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+                float logvar = min_log;
+                if (learn) {
+                    const float vv = mo[((size_t)n * ch + 1) * voxels + v];
+                    const float frac = (vv + 1.0f) / 2.0f;
+                    logvar = frac * max_log + (1.0f - frac) * min_log;
+                }
+                const float mean = c1 * x0 + c2 * xv;
+                float term;
+                if (ti == 0) {
+                    // -discretized_gaussian_log_likelihood(x_start, mean, 0.5 * logvar)  (losses.py)
+                    const float centered = xs - mean;
+                    const float inv_stdv = exp_r(-(0.5f * logvar));
+                    const float cdf_plus = approx_std_normal_cdf(inv_stdv * (centered + BIN));
+                    const float cdf_min = approx_std_normal_cdf(inv_stdv * (centered - BIN));
+                    float lp;
+                    if (xs < -0.999f) lp = log_r(fmaxf(cdf_plus, 1e-12f));
+                    else if (xs > 0.999f) lp = log_r(fmaxf(1.0f - cdf_min, 1e-12f));
+                    else lp = log_r(fmaxf(cdf_plus - cdf_min, 1e-12f));
+                    term = -lp;
+                } else {
+                    // normal_kl(true posterior mean, posterior_log_variance_clipped, mean, logvar)  (:723-728)
+                    const float tmean = c1 * xs + c2 * xv;
+                    const float d = tmean - mean;
+                    term = 0.5f * ((((-1.0f + logvar) - true_log) + exp_r(true_log - logvar)) + (d * d) * exp_r(-logvar));
+                }
+                s_vb += (double)term;
+                const float dx = x0 - xs;                                   // :877
+                s_x0 += (double)(dx * dx);
+                if (noise != nullptr) {
+                    const float eps = (c_recip * xv - x0) / c_recipm1;      // :879 (_predict_eps_from_xstart)
+                    const float de = eps - noise[i];
+                    s_eps += (double)(de * de);
+                }
+                if (pred_xstart != nullptr) pred_xstart[i] = x0;
+            }
+        }
+    } else {
+        s_vb = s_x0 = s_eps = __builtin_nan("");
+    }
+    vb_write_record(s_vb, s_x0, s_eps, slab + ((size_t)n * parts + part) * VB_REC);
+}
+
+// _prior_bpd: normal_kl(sqrt_acp[T-1] * x_start, log_1m_acp[T-1], 0, 0) per element; with mean2 = logvar2 = 0 the
+// reference's expression is 0.5 * (((-1 - lv) + exp(lv)) + m * m) exactly (x - 0 = x, exp(-0) = 1).
+__global__ __launch_bounds__(VB_THREADS) void prior_bpd_kernel(const float* __restrict__ xs_p,
+                                                               const float* __restrict__ qcoef, int voxels, int T,
+                                                               int parts, double* __restrict__ slab) {
+    const int n = blockIdx.y, part = blockIdx.x;
+    const float sa = qcoef[(size_t)(T - 1) * DDPM3D_NQCOEF + DDPM3D_Q_SQRT_ACP];
+    const float lv = qcoef[(size_t)(T - 1) * DDPM3D_NQCOEF + DDPM3D_Q_LOG_1M_ACP];
+    double s = 0.0;
+    const int chunk = voxels / parts + (voxels % parts != 0);
+    const long long v0 = (long long)part * chunk;
+    const long long v1 = v0 + chunk < voxels ? v0 + chunk : voxels;
+    for (long long base = v0; base < v1; base += VB_THREADS * VB_UNROLL) {
+#pragma unroll
+        for (int j = 0; j < VB_UNROLL; ++j) {
+            const long long v = base + j * VB_THREADS + threadIdx.x;
+            if (v >= v1) continue;
+            const float m = sa * xs_p[(size_t)n * voxels + v];
+            s += (double)(0.5f * (((-1.0f - lv) + exp_r(lv)) + m * m));
+        }
+    }
+    vb_write_record(s, 0.0, 0.0, slab + ((size_t)n * parts + part) * VB_REC);
+}
+
+// One workgroup per sample: the sample's records in a fixed order, then mean (/ ln 2 for the bound's term).
+__global__ __launch_bounds__(256) void vb_fold_kernel(const double* __restrict__ slab, int parts, double count,
+                                                      float* __restrict__ vb, float* __restrict__ xstart_mse,
+                                                      float* __restrict__ mse, int ld) {
+    const int n = blockIdx.x;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int p = threadIdx.x; p < parts; p += 256) {
+        const double* r = slab + ((size_t)n * parts + p) * VB_REC;
+        s0 += r[0];
+        s1 += r[1];
+        s2 += r[2];
+    }
+    __shared__ double red[3][4];
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; red[2][wave] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s0 = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        s1 = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        s2 = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
+        vb[(size_t)n * ld] = (float)(s0 / count / 0.69314718055994530942);   // mean_flat(.) / np.log(2.0)
+        if (xstart_mse != nullptr) xstart_mse[(size_t)n * ld] = (float)(s1 / count);
+        if (mse != nullptr) mse[(size_t)n * ld] = (float)(s2 / count);
+    }
+}
+
+hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,
+                                  int N, int voxels, int T, float* xt, hipStream_t st) {
+    int bx = (voxels + 255) / 256;
+    if (bx > 1024) bx = 1024;
+    hipLaunchKernelGGL(q_sample_kernel, dim3(bx, N), dim3(256), 0, st, x0, noise, qcoef, t_idx, voxels, T, xt);
+    return hipGetLastError();
+}
+
+hipError_t ddpm3d_launch_vb_terms(const float* mo, const float* x_start, const float* x_t, const float* noise,
+                                  const float* coef, const float* qcoef, const int64_t* t_idx, int N, int voxels,
+                                  int T, int flags, double* ws, float* vb, float* xstart_mse, float* mse, int ld,
+                                  float* pred_xstart, hipStream_t st) {
+    const int parts = ddpm3d_vb_parts(voxels);
+    hipLaunchKernelGGL(vb_terms_kernel, dim3(parts, N), dim3(VB_THREADS), 0, st, mo, x_start, x_t, noise, coef, qcoef,
+                       t_idx, voxels, T, flags, parts, ws, pred_xstart);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vb_fold_kernel, dim3(N), dim3(256), 0, st, ws, parts, (double)voxels, vb, xstart_mse, mse, ld);
+    return hipGetLastError();
+}
+
+hipError_t ddpm3d_launch_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels, int T, double* ws,
+                                   float* out, hipStream_t st) {
+    const int parts = ddpm3d_vb_parts(voxels);
+    hipLaunchKernelGGL(prior_bpd_kernel, dim3(parts, N), dim3(VB_THREADS), 0, st, x_start, qcoef, voxels, T, parts, ws);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vb_fold_kernel, dim3(N), dim3(256), 0, st, ws, parts, (double)voxels, out, nullptr, nullptr, 1);
+    return hipGetLastError();
+}

@@ -21,6 +21,8 @@ ACT_NONE, ACT_SILU = 0, 1
 OUT_NDHWC, OUT_NCDHW = 0, 1
 F_LEARN_SIGMA, F_PREDICT_XSTART, F_CLIP = 1, 2, 4
 NCOEF = 8
+NQCOEF = 4      # [T][NQCOEF] forward-process table of the variational bound: sqrt_acp, sqrt_1m_acp, log_1m_acp,
+                # posterior_log_variance_clipped
 PREC_F32, PREC_F16X3, PREC_F16, PREC_F16X3_WZ, PREC_F16_WZ, PREC_BF16, PREC_BF16_WZ = 0, 1, 2, 3, 4, 5, 6
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3, "f16": PREC_F16, "bf16": PREC_BF16}
 # the Winograd-along-depth form of a mode (same arithmetic, 2/3 of the MFMAs), where one exists
@@ -28,7 +30,7 @@ WINOGRAD_OF = {PREC_F16X3: PREC_F16X3_WZ, PREC_F16: PREC_F16_WZ, PREC_BF16: PREC
 # ddpm3d_conv_desc.io_dtype bits: which activation tensors hold bf16
 IO_SRC0_BF16, IO_SRC1_BF16, IO_OUT_BF16, IO_RES_BF16 = 1, 2, 4, 8
 IO_HALF_IS_F16 = 16    # the flagged tensors hold IEEE f16 (the --use_fp16 storage), not bf16
-ABI_VERSION = 12
+ABI_VERSION = 13
 # ddpm3d_conv_desc.kernel_hint bits (launch orders of identical arithmetic; tests and A/B measurements)
 HINT_WSTAT_OFF, HINT_WSTAT_ON = 0x100, 0x200
 HINT_SPLITK_SHIFT = 16      # bits 16..21: forced split factor (measurement only, tools/splitk_sweep.py)
@@ -116,6 +118,11 @@ EXPORTS = {
     "ddpm3d_add_embedding": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     "ddpm3d_pool_act": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp,
                                   C.c_int, _fp]),
+    "ddpm3d_q_sample": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ddpm3d_vb_terms_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ddpm3d_vb_terms": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp,
+                                  C.c_size_t, _fp, _fp, _fp, C.c_int, _fp, _fp]),
+    "ddpm3d_prior_bpd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

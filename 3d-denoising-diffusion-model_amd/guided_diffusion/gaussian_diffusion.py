@@ -9,8 +9,11 @@ UNet launch plan (engine.py) + ONE fused update kernel
 table that was uploaded once.  The timestep-embedding path is evaluated for
 all T steps before the loop, because it does not depend on x.
 
-Sampling only: the training / VLB half of the reference class (:709-894) is
-out of scope.
+Evaluation by the variational bound (q_sample, _vb_terms_bpd, _prior_bpd,
+calc_bpd_loop; :171-230, :709-742, :821-894) runs on two more kernels: one
+q_sample launch and one VLB-terms launch (with its fixed-order fold) per step,
+reading a second [T][4] table of the forward process.  training_losses (:744)
+is out of scope: it implies a backward pass this library does not have.
 """
 
 import enum
@@ -130,12 +133,24 @@ class GaussianDiffusion:
         tab[:, 7] = self.alphas_cumprod_prev
         return tab
 
+    def qcoef_table(self):
+        """[T][4] fp32: the per-step scalars of q_sample / q_mean_variance and the true posterior's
+        log-variance (:171-230), computed in fp64 and rounded once.  The last column is NOT the sampler
+        table's MIN_LOG column under FIXED_LARGE."""
+        tab = np.zeros((self.num_timesteps, H.NQCOEF), dtype=np.float32)
+        tab[:, 0] = self.sqrt_alphas_cumprod
+        tab[:, 1] = self.sqrt_one_minus_alphas_cumprod
+        tab[:, 2] = self.log_one_minus_alphas_cumprod
+        tab[:, 3] = self.posterior_log_variance_clipped
+        return tab
+
     def _device_state(self, device):
         key = str(device)
         st = self._dev_tables.get(key)
         if st is None:
             coef = th.from_numpy(self.coef_table()).to(device)
-            st = {"coef": coef}
+            qcoef = th.from_numpy(self.qcoef_table()).to(device)
+            st = {"coef": coef, "qcoef": qcoef}
             self._dev_tables[key] = st
         return st
 
@@ -287,3 +302,156 @@ class GaussianDiffusion:
                                                        step_noise):
             pass
         return final["sample"]
+
+    # ------------------------------------------------------ variational bound
+    def _check_t(self, t, N):
+        """User-supplied step indices: shape (N,), every entry in [0, T) -- checked on the host before anything
+        is launched (the kernels themselves turn an out-of-range t into NaN without reading past the tables)."""
+        if not isinstance(t, th.Tensor):
+            t = th.as_tensor(t)
+        if t.dim() != 1 or t.shape[0] != N:
+            raise ValueError("t must have shape (%d,), got %s" % (N, tuple(t.shape)))
+        if t.dtype.is_floating_point or t.dtype == th.bool:
+            raise ValueError("t must hold integer step indices, got %s" % t.dtype)
+        tc = t.detach().cpu()
+        if N and (int(tc.min()) < 0 or int(tc.max()) >= self.num_timesteps):
+            raise ValueError("t out of range [0, %d): %s" % (self.num_timesteps, tc.tolist()))
+        return t
+
+    def _extract(self, arr, t, x):
+        """_extract_into_tensor (:897-910): fp64 table -> fp32 values at t, broadcast like x."""
+        res = th.from_numpy(np.asarray(arr, dtype=np.float64)).to(x.device)[t.to(x.device)].float()
+        return res.reshape((-1,) + (1,) * (x.dim() - 1)).expand(x.shape)
+
+    def q_mean_variance(self, x_start, t):
+        """gaussian_diffusion.py:171-186 (device torch math; not on the hot path)."""
+        H.require_device(x_start, "x_start")
+        t = self._check_t(t, x_start.shape[0])
+        mean = self._extract(self.sqrt_alphas_cumprod, t, x_start) * x_start
+        variance = self._extract(1.0 - self.alphas_cumprod, t, x_start)
+        log_variance = self._extract(self.log_one_minus_alphas_cumprod, t, x_start)
+        return mean, variance, log_variance
+
+    def q_posterior_mean_variance(self, x_start, x_t, t):
+        """gaussian_diffusion.py:208-230 (device torch math; not on the hot path)."""
+        H.require_device(x_start, "x_start")
+        H.require_device(x_t, "x_t")
+        assert x_start.shape == x_t.shape
+        t = self._check_t(t, x_t.shape[0])
+        mean = (self._extract(self.posterior_mean_coef1, t, x_t) * x_start
+                + self._extract(self.posterior_mean_coef2, t, x_t) * x_t)
+        variance = self._extract(self.posterior_variance, t, x_t)
+        log_variance = self._extract(self.posterior_log_variance_clipped, t, x_t)
+        return mean, variance, log_variance
+
+    def _q_sample(self, x_start, t, noise, out):
+        st = self._device_state(x_start.device)
+        H.check(H.load().ddpm3d_q_sample(H.ptr(x_start), H.ptr(noise), H.ptr(st["qcoef"]), H.ptr(t), x_start.shape[0],
+                                         x_start[0].numel(), self.num_timesteps, H.ptr(out), H.stream()))
+        return out
+
+    def q_sample(self, x_start, t, noise=None):
+        """gaussian_diffusion.py:188-206: sqrt_acp[t] x_start + sqrt_1m_acp[t] noise, on the q_sample kernel."""
+        H.require_device(x_start, "x_start")
+        t = self._check_t(t, x_start.shape[0])
+        if noise is None:
+            noise = th.randn_like(x_start)
+        assert noise.shape == x_start.shape
+        H.require_device(noise, "noise")
+        t = t.to(device=x_start.device, dtype=th.int64).contiguous()
+        with th.cuda.device(x_start.device):
+            return self._q_sample(x_start, t, noise, th.empty_like(x_start))
+
+    def _vb_terms(self, model_output, x_start, x_t, t, noise, flags, ws, vb, xstart_mse, mse, ld, pred_xstart):
+        """One ddpm3d_vb_terms launch; the outputs are written through pointers (column views allowed)."""
+        N = x_t.shape[0]
+        C = x_t.shape[1]
+        want = 2 * C if flags & H.F_LEARN_SIGMA else C
+        assert tuple(model_output.shape) == (N, want, *x_t.shape[2:]), \
+            "model output shape %s for input %s" % (tuple(model_output.shape), tuple(x_t.shape))
+        H.require_device(model_output, "model_output")
+        st = self._device_state(x_t.device)
+        H.check(H.load().ddpm3d_vb_terms(H.ptr(model_output), H.ptr(x_start), H.ptr(x_t), H.ptr(noise),
+                                         H.ptr(st["coef"]), H.ptr(st["qcoef"]), H.ptr(t), N, x_t[0].numel(),
+                                         self.num_timesteps, flags, H.ptr(ws), ws.numel(), H.ptr(vb),
+                                         H.ptr(xstart_mse), H.ptr(mse), ld, H.ptr(pred_xstart), H.stream()))
+
+    def _workspace(self, x):
+        nbytes = H.load().ddpm3d_vb_terms_workspace_bytes(x.shape[0], x[0].numel())
+        return th.empty(nbytes, dtype=th.uint8, device=x.device)
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """gaussian_diffusion.py:709-742: {"output": [N] KL (t > 0) or decoder NLL (t == 0) in bits,
+        "pred_xstart"}."""
+        H.require_device(x_start, "x_start")
+        H.require_device(x_t, "x_t")
+        assert x_start.shape == x_t.shape
+        N = x_t.shape[0]
+        t = self._check_t(t, N)
+        flags = self._flags(clip_denoised)
+        with th.no_grad(), th.cuda.device(x_t.device):
+            t = t.to(device=x_t.device, dtype=th.int64).contiguous()
+            out = self._call_model(model, x_t, t, model_kwargs)
+            vb = th.empty(N, dtype=th.float32, device=x_t.device)
+            x0 = th.empty_like(x_t)
+            self._vb_terms(out, x_start, x_t, t, None, flags, self._workspace(x_t), vb, None, None, 1, x0)
+        return {"output": vb, "pred_xstart": x0}
+
+    def _prior_bpd(self, x_start):
+        """gaussian_diffusion.py:821-837: [N] KL(q(x_T | x_0) || N(0, I)) in bits."""
+        H.require_device(x_start, "x_start")
+        N = x_start.shape[0]
+        out = th.empty(N, dtype=th.float32, device=x_start.device)
+        with th.cuda.device(x_start.device):
+            st = self._device_state(x_start.device)
+            ws = self._workspace(x_start)
+            H.check(H.load().ddpm3d_prior_bpd(H.ptr(x_start), H.ptr(st["qcoef"]), N, x_start[0].numel(),
+                                              self.num_timesteps, H.ptr(ws), ws.numel(), H.ptr(out), H.stream()))
+        return out
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, step_noise=None):
+        """gaussian_diffusion.py:839-894: the whole variational bound in bits per dim.  Returns total_bpd,
+        prior_bpd [N] and vb, xstart_mse, mse [N, T], fp32 on the device; column k is the loop's k-th step,
+        t = T - 1 - k.  `step_noise` (extension, as in the sampler loops): a sequence of T tensors, or a callable
+        (k, x_start) -> tensor, used instead of randn_like in draw order.  Per step: one q_sample launch, the
+        network (one plan replay on the engine path), one VLB-terms launch and its fold writing column k in
+        place; nothing inside the loop waits for the device."""
+        H.require_device(x_start, "x_start")
+        device = x_start.device
+        N = x_start.shape[0]
+        T = self.num_timesteps
+        flags = self._flags(clip_denoised)
+        model_kwargs = model_kwargs or {}
+        fast = hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and x_start.dim() == 5
+        with th.no_grad(), th.cuda.device(device):
+            vb = th.empty((N, T), dtype=th.float32, device=device)
+            xstart_mse = th.empty_like(vb)
+            mse = th.empty_like(vb)
+            ws = self._workspace(x_start)
+            x_t = th.empty_like(x_start)
+            t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, N).contiguous()
+            if fast:
+                eng = model.engine()
+                low_res = model_kwargs["low_res"].to(device).contiguous()
+                t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
+                film = eng.film_rows(t_model.to(th.float32).contiguous())
+            for k, i in enumerate(range(T - 1, -1, -1)):
+                t = t_all[i]
+                if step_noise is None:
+                    noise = th.randn_like(x_start)
+                elif callable(step_noise):
+                    noise = step_noise(k, x_start)
+                else:
+                    noise = step_noise[k]
+                H.require_device(noise, "noise")
+                assert noise.shape == x_start.shape
+                self._q_sample(x_start, t, noise, x_t)
+                if fast:
+                    out = eng.forward(x_t, low_res, film[i], 0)
+                else:
+                    out = self._call_model(model, x_t, t, model_kwargs)
+                self._vb_terms(out, x_start, x_t, t, noise, flags, ws, vb[:, k], xstart_mse[:, k], mse[:, k], T,
+                               None)
+            prior_bpd = self._prior_bpd(x_start)
+            total_bpd = vb.sum(dim=1) + prior_bpd
+        return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}

@@ -62,3 +62,28 @@ def synth_noise(shape, count, seed=10):
     scripts/test.py:62 then gaussian_diffusion.py:430 once per step)."""
     g = np.random.default_rng(int(seed))
     return [g.standard_normal(tuple(shape), dtype=np.float32) for _ in range(count)]
+
+
+def synth_x_start(shape, seed=21):
+    """Clean volume for the variational bound: uniform [-1, 1) with every 97th element exactly +1 or -1 and every
+    89th at +-0.9995, so that all three branches of the decoder likelihood (losses.py: x < -0.999, x > 0.999,
+    interior) are taken."""
+    g = np.random.default_rng(int(seed))
+    x = (g.random(tuple(shape), dtype=np.float32) * np.float32(2.0) - np.float32(1.0)).astype(np.float32)
+    flat = x.reshape(-1)
+    flat[0::194] = 1.0
+    flat[97::194] = -1.0
+    flat[1::178] = np.float32(0.9995)
+    flat[90::178] = np.float32(-0.9995)
+    return x
+
+
+def synth_model_output(shape, learn_sigma, seed=23):
+    """A fixed network output for (N, C, ...) inputs: standard normal in the mean channels, and with learn_sigma a
+    second block of C channels uniform in [-1, 1) (LEARNED_RANGE's interpolation fraction, unet output range)."""
+    g = np.random.default_rng(int(seed))
+    mean = g.standard_normal(tuple(shape), dtype=np.float32)
+    if not learn_sigma:
+        return mean
+    var = (g.random(tuple(shape), dtype=np.float32) * np.float32(2.0) - np.float32(1.0)).astype(np.float32)
+    return np.concatenate([mean, var], axis=1)

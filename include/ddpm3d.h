@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define DDPM3D_ABI_VERSION 12
+#define DDPM3D_ABI_VERSION 13
 
 enum {
     DDPM3D_OK = 0,
@@ -437,6 +437,47 @@ int ddpm3d_p_sample_step(const float* model_out, const float* x, const float* no
 int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise,
                      const float* coef, const int64_t* t_idx, int N, int voxels,
                      int flags, float eta, float* sample, float* pred_xstart, void* stream);
+
+/*
+ * Evaluation of a model by its variational bound (gaussian_diffusion.py:188-206 q_sample,
+ * :709-742 _vb_terms_bpd, :821-837 _prior_bpd, :839-894 calc_bpd_loop; losses.py normal_kl and
+ * discretized_gaussian_log_likelihood).  qcoef = [T][DDPM3D_NQCOEF] fp32 table of the forward
+ * process (fp64-computed, rounded once); coef is the sampler table above.  T is the row count of
+ * both: a sample whose t_idx lies outside [0, T) reads no table row and gets NaN results.
+ * Per-sample means are summed in fp64 over a fixed partition of the volume (partial slabs in the
+ * caller's workspace, then a fixed-order fold): bitwise repeatable, no atomics.
+ */
+enum {
+    DDPM3D_Q_SQRT_ACP = 0,            /* sqrt_alphas_cumprod                 */
+    DDPM3D_Q_SQRT_1M_ACP = 1,         /* sqrt_one_minus_alphas_cumprod       */
+    DDPM3D_Q_LOG_1M_ACP = 2,          /* log_one_minus_alphas_cumprod        */
+    DDPM3D_Q_POST_LOG_VAR = 3,        /* posterior_log_variance_clipped (the true posterior's; under
+                                         FIXED_LARGE not the sampler table's MIN_LOG column) */
+    DDPM3D_NQCOEF = 4
+};
+/* x_t = sqrt_acp[t] * x_start + sqrt_1m_acp[t] * noise, one t per sample (:188-206).
+ * x_start, noise, x_t: (N, voxels) fp32. */
+int ddpm3d_q_sample(const float* x_start, const float* noise, const float* qcoef, const int64_t* t_idx,
+                    int N, int voxels, int T, float* x_t, void* stream);
+/* Bytes of workspace ddpm3d_vb_terms and ddpm3d_prior_bpd need for (N, voxels); 0 for a bad shape.
+ * Host only. */
+size_t ddpm3d_vb_terms_workspace_bytes(int N, int voxels);
+/* One step of calc_bpd_loop after the network call (:709-742, :872-880).  From model_out (NCDHW,
+ * (N, 2 or 1, voxels) as for ddpm3d_p_sample_step) it rebuilds pred_xstart, the model mean and
+ * log-variance, and writes per sample n:
+ *   vb[n * ld_out]         = mean normal_kl(true posterior || model) / ln 2, or, where t == 0, the
+ *                            mean discretized-Gaussian NLL of x_start / ln 2 (:737-741);
+ *   xstart_mse[n * ld_out] = mean (pred_xstart - x_start)^2                     (may be NULL);
+ *   mse[n * ld_out]        = mean (eps - noise)^2, eps recomputed from the clipped pred_xstart
+ *                            (:879-880; noise and mse both NULL or both given).
+ * ws: ddpm3d_vb_terms_workspace_bytes(N, voxels) bytes, 16-byte aligned.  pred_xstart may be NULL. */
+int ddpm3d_vb_terms(const float* model_out, const float* x_start, const float* x_t, const float* noise,
+                    const float* coef, const float* qcoef, const int64_t* t_idx, int N, int voxels, int T,
+                    int flags, void* ws, size_t ws_bytes, float* vb, float* xstart_mse, float* mse,
+                    int ld_out, float* pred_xstart, void* stream);
+/* _prior_bpd (:821-837): out[n] = mean normal_kl(N(sqrt_acp[T-1] x_start, 1 - acp[T-1]) || N(0, 1)) / ln 2. */
+int ddpm3d_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels, int T, void* ws,
+                     size_t ws_bytes, float* out, void* stream);
 
 /*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
