@@ -437,6 +437,37 @@ int ddpm3d_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels
                     "prior_bpd");
 }
 
+// ------------------------------------------------- p_mean_variance, DDIM inversion (added within ABI 13)
+// shapes as vb_shape_ok (grid.y carries the sample index); flags are the sampler's
+static const int STEP_FLAGS = DDPM3D_F_LEARN_SIGMA | DDPM3D_F_PREDICT_XSTART | DDPM3D_F_CLIP;
+
+int ddpm3d_p_mean_variance(const float* model_out, const float* x, const float* coef, const int64_t* t_idx, int N,
+                           int voxels, int T, int flags, float* mean, float* variance, float* log_variance,
+                           float* pred_xstart, void* stream) {
+    if (!model_out || !x || !coef || !t_idx || !mean || !pred_xstart || !vb_shape_ok(N, voxels, T))
+        return fail(DDPM3D_EINVAL, "p_mean_variance: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "p_mean_variance: unknown flag bits %#x", flags);
+    if (flags & DDPM3D_F_LEARN_SIGMA) {
+        if (!variance || !log_variance)
+            return fail(DDPM3D_EINVAL, "p_mean_variance: F_LEARN_SIGMA needs variance and log_variance");
+    } else if (variance || log_variance) {
+        return fail(DDPM3D_EINVAL, "p_mean_variance: variance and log_variance must be NULL without F_LEARN_SIGMA");
+    }
+    return launched(ddpm3d_launch_p_mean_variance(model_out, x, coef, t_idx, N, voxels, T, flags, mean, variance,
+                                                  log_variance, pred_xstart, (hipStream_t)stream),
+                    "p_mean_variance");
+}
+
+int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float* coef, const int64_t* t_idx, int N,
+                             int voxels, int T, int flags, float* sample, float* pred_xstart, void* stream) {
+    if (!model_out || !x || !coef || !t_idx || !sample || !vb_shape_ok(N, voxels, T))
+        return fail(DDPM3D_EINVAL, "ddim_reverse_step: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "ddim_reverse_step: unknown flag bits %#x", flags);
+    return launched(ddpm3d_launch_ddim_reverse_step(model_out, x, coef, t_idx, N, voxels, T, flags, sample,
+                                                    pred_xstart, (hipStream_t)stream),
+                    "ddim_reverse_step");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

@@ -24,6 +24,13 @@ hipError_t ddpm3d_launch_subsample_hw2(const float* in, int N, int D, int H, int
 hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
                                      const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
                                      float eta, float* sample, float* pred_xstart, hipStream_t st);
+// p_mean_variance and the DDIM reverse (inversion) step; T = rows of coef, t outside [0, T) gives NaN
+hipError_t ddpm3d_launch_p_mean_variance(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
+                                         int N, int voxels, int T, int flags, float* mean, float* variance,
+                                         float* log_variance, float* pred_xstart, hipStream_t st);
+hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
+                                           int N, int voxels, int T, int flags, float* sample, float* pred_xstart,
+                                           hipStream_t st);
 // variational bound (calc_bpd_loop): ws holds ddpm3d_vb_parts(voxels) 32-byte records per sample
 int ddpm3d_vb_parts(int voxels);
 hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,

@@ -710,6 +710,113 @@ hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x,
     return hipGetLastError();
 }
 
+// ------------------------------------------------- p_mean_variance, DDIM inversion
+// The reference's public per-step call (gaussian_diffusion.py:232-326) and the reverse ODE step built on it
+// (:587-623), as sample_step_kernel derives x0: same expressions, same rounding order.  A sample whose t lies
+// outside [0, T) reads no table row and gets NaN in every output (fminf / fmaxf would turn NaN coefficients into
+// the clip bounds, so that case is a branch of its own).
+
+__device__ __forceinline__ float step_x0(float xv, float e, float c_recip, float c_recipm1, int flags) {
+    float x0 = (flags & DDPM3D_F_PREDICT_XSTART) ? e : c_recip * xv - c_recipm1 * e;   // :305-311, :328-333
+    if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                     // :296-297
+    return x0;
+}
+
+__global__ __launch_bounds__(256) void p_mean_variance_kernel(
+    const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ coef,
+    const int64_t* __restrict__ t_idx, int voxels, int T, int flags, float* __restrict__ mean,
+    float* __restrict__ variance, float* __restrict__ log_variance, float* __restrict__ pred_xstart) {
+    const int n = blockIdx.y;
+    const int64_t ti = t_idx[n];
+    const bool learn = flags & DDPM3D_F_LEARN_SIGMA;
+    const int ch = learn ? 2 : 1;
+    const int stride = gridDim.x * blockDim.x;
+    if (ti < 0 || ti >= T) {
+        const float nan = __builtin_nanf("");
+        for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+            const size_t i = (size_t)n * voxels + v;
+            mean[i] = nan;
+            pred_xstart[i] = nan;
+            if (learn) { log_variance[i] = nan; variance[i] = nan; }
+        }
+        return;
+    }
+    const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
+    const float c_recip = c[DDPM3D_C_SQRT_RECIP_ACP], c_recipm1 = c[DDPM3D_C_SQRT_RECIPM1_ACP];
+    const float c1 = c[DDPM3D_C_POST_MEAN_COEF1], c2 = c[DDPM3D_C_POST_MEAN_COEF2];
+    const float min_log = c[DDPM3D_C_MIN_LOG], max_log = c[DDPM3D_C_MAX_LOG];
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+        const size_t i = (size_t)n * voxels + v;
+        const float xv = x[i];
+        const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
+        mean[i] = c1 * x0 + c2 * xv;                                    // :312-314, :216-219
+        pred_xstart[i] = x0;
+        if (learn) {
+            const float vv = mo[((size_t)n * ch + 1) * voxels + v];
+            const float frac = (vv + 1.0f) / 2.0f;                      // :274
+            const float lv = frac * max_log + (1.0f - frac) * min_log;  // :275
+            log_variance[i] = lv;
+            variance[i] = expf(lv);                                     // :276
+        }
+    }
+}
+
+// x_t -> x_{t+1} along the deterministic DDIM ODE (:587-623).  alphas_cumprod_next[t] is alphas_cumprod[t + 1] in
+// fp64 (0 at t = T - 1), so its fp32 value is the ACP column of row t + 1: no table of its own.  Reads only the eps
+// half of model_out.
+__global__ __launch_bounds__(256) void ddim_reverse_step_kernel(
+    const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ coef,
+    const int64_t* __restrict__ t_idx, int voxels, int T, int flags, float* __restrict__ sample,
+    float* __restrict__ pred_xstart) {
+    const int n = blockIdx.y;
+    const int64_t ti = t_idx[n];
+    const int ch = (flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1;
+    const int stride = gridDim.x * blockDim.x;
+    if (ti < 0 || ti >= T) {
+        const float nan = __builtin_nanf("");
+        for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+            const size_t i = (size_t)n * voxels + v;
+            sample[i] = nan;
+            if (pred_xstart != nullptr) pred_xstart[i] = nan;
+        }
+        return;
+    }
+    const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
+    const float c_recip = c[DDPM3D_C_SQRT_RECIP_ACP], c_recipm1 = c[DDPM3D_C_SQRT_RECIPM1_ACP];
+    const float ab_next = ti + 1 < T ? coef[(size_t)(ti + 1) * DDPM3D_NCOEF + DDPM3D_C_ACP] : 0.0f;
+    const float s_next = sqrtf(ab_next), s_next_1m = sqrtf(1.0f - ab_next);
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+        const size_t i = (size_t)n * voxels + v;
+        const float xv = x[i];
+        const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
+        const float eps = (c_recip * xv - x0) / c_recipm1;              // :611-614
+        sample[i] = x0 * s_next + s_next_1m * eps;                      // :615-621
+        if (pred_xstart != nullptr) pred_xstart[i] = x0;
+    }
+}
+
+static dim3 step_grid(int N, int voxels) {
+    int bx = (voxels + 255) / 256;
+    if (bx > 1024) bx = 1024;
+    return dim3(bx, N);
+}
+
+hipError_t ddpm3d_launch_p_mean_variance(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
+                                         int N, int voxels, int T, int flags, float* mean, float* variance,
+                                         float* log_variance, float* pred_xstart, hipStream_t st) {
+    hipLaunchKernelGGL(p_mean_variance_kernel, step_grid(N, voxels), dim3(256), 0, st, mo, x, coef, t_idx, voxels, T,
+                       flags, mean, variance, log_variance, pred_xstart);
+    return hipGetLastError();
+}
+
+hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
+                                           int N, int voxels, int T, int flags, float* sample, float* pred_xstart,
+                                           hipStream_t st) {
+    hipLaunchKernelGGL(ddim_reverse_step_kernel, step_grid(N, voxels), dim3(256), 0, st, mo, x, coef, t_idx, voxels,
+                       T, flags, sample, pred_xstart);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------- variational bound
 // calc_bpd_loop's per-step work after the network call (gaussian_diffusion.py:709-742, :872-880) and its helpers
 // (q_sample :188-206, _prior_bpd :821-837, losses.py normal_kl / discretized_gaussian_log_likelihood).  Every element

@@ -123,6 +123,9 @@ EXPORTS = {
     "ddpm3d_vb_terms": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp,
                                   C.c_size_t, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     "ddpm3d_prior_bpd": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t, _fp, _fp]),
+    "ddpm3d_p_mean_variance": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp,
+                                         _fp, _fp]),
+    "ddpm3d_ddim_reverse_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

@@ -14,6 +14,10 @@ calc_bpd_loop; :171-230, :709-742, :821-894) runs on two more kernels: one
 q_sample launch and one VLB-terms launch (with its fixed-order fold) per step,
 reading a second [T][4] table of the forward process.  training_losses (:744)
 is out of scope: it implies a backward pass this library does not have.
+
+p_mean_variance (:232-326) and DDIM inversion (ddim_reverse_sample, :587-623,
+and the package's ddim_reverse_sample_loop) run on one kernel each, reading the
+sampler table: one plan replay plus one launch per inversion step.
 """
 
 import enum
@@ -455,3 +459,131 @@ class GaussianDiffusion:
             prior_bpd = self._prior_bpd(x_start)
             total_bpd = vb.sum(dim=1) + prior_bpd
         return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
+    # ------------------------------------------- p_mean_variance, DDIM inversion
+    def _fixed_variances(self):
+        """:277-287: the (variance, log-variance) fp64 tables of the fixed variance types."""
+        if self.model_var_type == ModelVarType.FIXED_LARGE:
+            var = np.append(self.posterior_variance[1], self.betas[1:])
+            return var, np.log(var)
+        return self.posterior_variance, self.posterior_log_variance_clipped
+
+    def _model_step_output(self, model_output, x, flags):
+        N, C = x.shape[:2]
+        want = 2 * C if flags & H.F_LEARN_SIGMA else C
+        assert tuple(model_output.shape) == (N, want, *x.shape[2:]), \
+            "model output shape %s for input %s" % (tuple(model_output.shape), tuple(x.shape))
+        H.require_device(model_output, "model_output")
+
+    def _p_mean_variance(self, model_output, x, t, flags):
+        """One ddpm3d_p_mean_variance launch; t: int64 on x's device."""
+        self._model_step_output(model_output, x, flags)
+        st = self._device_state(x.device)
+        mean = th.empty_like(x)
+        x0 = th.empty_like(x)
+        if flags & H.F_LEARN_SIGMA:
+            variance, log_variance = th.empty_like(x), th.empty_like(x)
+        else:
+            var, logvar = self._fixed_variances()
+            variance, log_variance = self._extract(var, t, x), self._extract(logvar, t, x)
+        learn = flags & H.F_LEARN_SIGMA
+        H.check(H.load().ddpm3d_p_mean_variance(H.ptr(model_output), H.ptr(x), H.ptr(st["coef"]), H.ptr(t),
+                                                x.shape[0], x[0].numel(), self.num_timesteps, flags, H.ptr(mean),
+                                                H.ptr(variance) if learn else None,
+                                                H.ptr(log_variance) if learn else None, H.ptr(x0), H.stream()))
+        return {"mean": mean, "variance": variance, "log_variance": log_variance, "pred_xstart": x0}
+
+    def _reverse_step(self, model_output, x, t, flags):
+        """One ddpm3d_ddim_reverse_step launch; t: int64 on x's device."""
+        self._model_step_output(model_output, x, flags)
+        st = self._device_state(x.device)
+        sample = th.empty_like(x)
+        x0 = th.empty_like(x)
+        H.check(H.load().ddpm3d_ddim_reverse_step(H.ptr(model_output), H.ptr(x), H.ptr(st["coef"]), H.ptr(t),
+                                                  x.shape[0], x[0].numel(), self.num_timesteps, flags,
+                                                  H.ptr(sample), H.ptr(x0), H.stream()))
+        return {"sample": sample, "pred_xstart": x0}
+
+    def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
+        """gaussian_diffusion.py:232-326: {"mean", "variance", "log_variance", "pred_xstart"}, each shaped like x.
+        LEARNED_RANGE: all four from the kernel; FIXED_*: variance and log_variance are the fp32 values of the fp64
+        tables at t, expanded per sample as _extract_into_tensor does (:897-910)."""
+        self._reject_hooks(denoised_fn, None)
+        H.require_device(x, "x")
+        t = self._check_t(t, x.shape[0])
+        flags = self._flags(clip_denoised)
+        with th.no_grad(), th.cuda.device(x.device):
+            t = t.to(device=x.device, dtype=th.int64).contiguous()
+            out = self._call_model(model, x, t, model_kwargs)
+            return self._p_mean_variance(out, x, t, flags)
+
+    @staticmethod
+    def _reverse_eta(eta):
+        # the reference's `assert eta == 0.0` (:601), raised explicitly so that python -O keeps it
+        if eta != 0.0:
+            raise AssertionError("Reverse ODE only for deterministic path")
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """gaussian_diffusion.py:587-623: x_t -> x_{t+1} along the deterministic DDIM ODE,
+        {"sample", "pred_xstart"}."""
+        self._reverse_eta(eta)
+        self._reject_hooks(denoised_fn, None)
+        H.require_device(x, "x")
+        t = self._check_t(t, x.shape[0])
+        flags = self._flags(clip_denoised)
+        with th.no_grad(), th.cuda.device(x.device):
+            t = t.to(device=x.device, dtype=th.int64).contiguous()
+            out = self._call_model(model, x, t, model_kwargs)
+            return self._reverse_step(out, x, t, flags)
+
+    def ddim_reverse_sample_loop_progressive(self, model, x_start, clip_denoised=True, denoised_fn=None,
+                                             model_kwargs=None, device=None, progress=False, eta=0.0):
+        """DDIM inversion (extension; the reference has the step, :587-623, but no loop): starting from
+        x = x_start, x <- ddim_reverse_sample(x, t=k)["sample"] for k = 0 ... T-1, yielding each step's dict.
+        Draws no noise.  With model_kwargs == {"low_res"} on a 5-D input it takes the samplers' engine path: the
+        film rows for the whole schedule once, then one plan replay (eager or model.step_graph) and one
+        reverse-step launch per step; nothing inside the loop waits for the device."""
+        self._reverse_eta(eta)
+        self._reject_hooks(denoised_fn, None)
+        H.require_device(x_start, "x_start")
+        device = th.device(x_start.device if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError("DDIM inversion runs on HIP kernels only; got device %s" % device)
+        flags = self._flags(clip_denoised)
+        N = x_start.shape[0]
+        T = self.num_timesteps
+        indices = list(range(T))
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        model_kwargs = model_kwargs or {}
+        fast = hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and x_start.dim() == 5
+        # as in _loop: grad mode and the current device change around each step's compute only
+        with th.no_grad(), th.cuda.device(device):
+            img = x_start.to(device)
+            t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, N).contiguous()
+            if fast:
+                eng = model.engine()
+                low_res = model_kwargs["low_res"].to(device).contiguous()
+                t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
+                film = eng.film_rows(t_model.to(th.float32).contiguous())
+        for i in indices:
+            with th.no_grad(), th.cuda.device(device):
+                t = t_all[i]
+                if fast:
+                    out = eng.forward(img, low_res, film[i], 0)
+                else:
+                    out = self._call_model(model, img, t, model_kwargs)
+                res = self._reverse_step(out, img, t, flags)
+            yield res
+            img = res["sample"]
+
+    def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                 device=None, progress=False, eta=0.0):
+        """DDIM inversion (extension): x_T from a clean x_start, the last sample of
+        ddim_reverse_sample_loop_progressive."""
+        final = None
+        for final in self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised, denoised_fn,
+                                                               model_kwargs, device, progress, eta):
+            pass
+        return final["sample"]

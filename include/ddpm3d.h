@@ -480,6 +480,31 @@ int ddpm3d_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels
                      size_t ws_bytes, float* out, void* stream);
 
 /*
+ * The model's per-step distribution and DDIM inversion (added within ABI 13: new entries only, no
+ * existing contract changed).  Inputs and layouts as ddpm3d_p_sample_step: model_out is NCDHW
+ * (N, 2 or 1, voxels), x and every output (N, voxels) fp32; coef is the [T][DDPM3D_NCOEF] sampler
+ * table and T its row count.  A sample whose t_idx lies outside [0, T) reads no table row and gets
+ * NaN in every output.  N <= 65535; flags: DDPM3D_F_* above, no other bit.
+ */
+/* p_mean_variance (gaussian_diffusion.py:232-326): pred_xstart from eps (:328-333) or, under
+ * DDPM3D_F_PREDICT_XSTART, the model output itself, clipped to [-1, 1] under DDPM3D_F_CLIP;
+ * mean = coef1 * pred_xstart + coef2 * x (:208-219).  Under DDPM3D_F_LEARN_SIGMA (LEARNED_RANGE,
+ * :268-276) also the per-voxel log_variance = frac * log(beta) + (1 - frac) * min_log and
+ * variance = expf(log_variance); both pointers are required then and must be NULL otherwise (the
+ * fixed variances are per-step constants the caller takes from its fp64 tables, :277-287). */
+int ddpm3d_p_mean_variance(const float* model_out, const float* x, const float* coef, const int64_t* t_idx,
+                           int N, int voxels, int T, int flags, float* mean, float* variance,
+                           float* log_variance, float* pred_xstart, void* stream);
+/* ddim_reverse_sample (:587-623), eta = 0: x_t -> x_{t+1} along the deterministic DDIM ODE.
+ * eps = (sqrt_recip_acp * x - pred_xstart) / sqrt_recipm1_acp (:611-614);
+ * sample = pred_xstart * sqrt(ab_next) + sqrt(1 - ab_next) * eps (:615-621), where ab_next =
+ * alphas_cumprod_next[t] is the DDPM3D_C_ACP column of row t + 1, and 0 at t = T - 1.  Reads only
+ * the eps half of model_out.  pred_xstart may be NULL. */
+int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float* coef, const int64_t* t_idx,
+                             int N, int voxels, int T, int flags, float* sample, float* pred_xstart,
+                             void* stream);
+
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
