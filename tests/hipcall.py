@@ -102,9 +102,12 @@ def conv3d(srcs, w, b, out_dhw, in_mode=H.IN_SAME, aff=None, act=H.ACT_NONE, res
     if want_stats and out_layout == H.OUT_NDHWC:
         stats = torch.full((N, co, rows, 2), float("nan"), dtype=torch.float64, device=dev)
         d.stats, d.stats_rows = H.ptr(stats), rows
+    # the kernel family the library routes this descriptor to (ddpm3d_conv_kernel_family)
+    name = C.create_string_buffer(64)
+    H.check(lib.ddpm3d_conv_kernel_family(C.byref(d), name, 64))
     H.check(lib.ddpm3d_conv3d(C.byref(d), H.stream()))
     torch.cuda.synchronize()
-    LAST_PLAN.update(split=split, rows=rows)
+    LAST_PLAN.update(split=split, rows=rows, family=name.value.decode())
     return out, stats, rows
 
 
