@@ -468,6 +468,21 @@ int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float
                     "ddim_reverse_step");
 }
 
+// ------------------------------------------------- DPM-Solver++ multistep step (added within ABI 13)
+int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
+                           const float* noise, const float* coef, const float* scoef, const int64_t* t_idx, int N,
+                           int voxels, int T, int flags, int order, float* sample, float* pred_xstart, void* stream) {
+    if (!model_out || !x || !coef || !scoef || !t_idx || !sample || !pred_xstart || !vb_shape_ok(N, voxels, T))
+        return fail(DDPM3D_EINVAL, "dpm_solver_step: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d is not 1, 2 or 3", order);
+    if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
+        return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d needs %d earlier x0 predictions", order, order - 1);
+    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "dpm_solver_step: unknown flag bits %#x", flags);
+    return launched(ddpm3d_launch_dpm_solver_step(model_out, x, x0_prev1, x0_prev2, noise, coef, scoef, t_idx, N,
+                                                  voxels, T, flags, order, sample, pred_xstart, (hipStream_t)stream),
+                    "dpm_solver_step");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

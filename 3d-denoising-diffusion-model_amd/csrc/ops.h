@@ -31,6 +31,12 @@ hipError_t ddpm3d_launch_p_mean_variance(const float* mo, const float* x, const 
 hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
                                            int N, int voxels, int T, int flags, float* sample, float* pred_xstart,
                                            hipStream_t st);
+// one DPM-Solver++ multistep step; scoef = [T][DDPM3D_NSCOEF] weights, m1 / m2 read at order >= 2 / 3, noise may be
+// NULL; t outside [0, T) gives NaN
+hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* x, const float* m1, const float* m2,
+                                         const float* noise, const float* coef, const float* scoef,
+                                         const int64_t* t_idx, int N, int voxels, int T, int flags, int order,
+                                         float* sample, float* pred_xstart, hipStream_t st);
 // variational bound (calc_bpd_loop): ws holds ddpm3d_vb_parts(voxels) 32-byte records per sample
 int ddpm3d_vb_parts(int voxels);
 hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,

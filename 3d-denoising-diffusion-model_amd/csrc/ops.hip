@@ -817,6 +817,56 @@ hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, cons
     return hipGetLastError();
 }
 
+// ------------------------------------------------- DPM-Solver++ multistep step
+// One step of DPM-Solver++ (Lu et al. 2022, arXiv:2211.01095): x0 exactly as sample_step_kernel derives it (step_x0),
+// then the update as a weighted sum whose weights the host expanded in fp64 into row t of scoef
+// ([T][DDPM3D_NSCOEF]: c_x, w0, w1, w2, c_z), summed in that order.  m1 is read only at order >= 2, m2 only at
+// order 3, z only when noise is non-null.  A sample whose t lies outside [0, T) reads neither table and gets NaN.
+__global__ __launch_bounds__(256) void dpm_solver_step_kernel(
+    const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ m1,
+    const float* __restrict__ m2, const float* __restrict__ noise, const float* __restrict__ coef,
+    const float* __restrict__ scoef, const int64_t* __restrict__ t_idx, int voxels, int T, int flags, int order,
+    float* __restrict__ sample, float* __restrict__ pred_xstart) {
+    const int n = blockIdx.y;
+    const int64_t ti = t_idx[n];
+    const int ch = (flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1;
+    const int stride = gridDim.x * blockDim.x;
+    if (ti < 0 || ti >= T) {
+        const float nan = __builtin_nanf("");
+        for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+            const size_t i = (size_t)n * voxels + v;
+            sample[i] = nan;
+            pred_xstart[i] = nan;
+        }
+        return;
+    }
+    const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
+    const float c_recip = c[DDPM3D_C_SQRT_RECIP_ACP], c_recipm1 = c[DDPM3D_C_SQRT_RECIPM1_ACP];
+    const float* w = scoef + (size_t)ti * DDPM3D_NSCOEF;
+    const float c_x = w[DDPM3D_S_CX], w0 = w[DDPM3D_S_W0], w1 = w[DDPM3D_S_W1], w2 = w[DDPM3D_S_W2];
+    const float c_z = w[DDPM3D_S_CZ];
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+        const size_t i = (size_t)n * voxels + v;
+        const float xv = x[i];
+        const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
+        float out = c_x * xv + w0 * x0;
+        if (order >= 2) out = out + w1 * m1[i];
+        if (order >= 3) out = out + w2 * m2[i];
+        if (noise != nullptr) out = out + c_z * noise[i];
+        sample[i] = out;
+        pred_xstart[i] = x0;
+    }
+}
+
+hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* x, const float* m1, const float* m2,
+                                         const float* noise, const float* coef, const float* scoef,
+                                         const int64_t* t_idx, int N, int voxels, int T, int flags, int order,
+                                         float* sample, float* pred_xstart, hipStream_t st) {
+    hipLaunchKernelGGL(dpm_solver_step_kernel, step_grid(N, voxels), dim3(256), 0, st, mo, x, m1, m2, noise, coef,
+                       scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------- variational bound
 // calc_bpd_loop's per-step work after the network call (gaussian_diffusion.py:709-742, :872-880) and its helpers
 // (q_sample :188-206, _prior_bpd :821-837, losses.py normal_kl / discretized_gaussian_log_likelihood).  Every element

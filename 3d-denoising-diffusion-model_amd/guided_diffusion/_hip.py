@@ -23,6 +23,8 @@ F_LEARN_SIGMA, F_PREDICT_XSTART, F_CLIP = 1, 2, 4
 NCOEF = 8
 NQCOEF = 4      # [T][NQCOEF] forward-process table of the variational bound: sqrt_acp, sqrt_1m_acp, log_1m_acp,
                 # posterior_log_variance_clipped
+NSCOEF = 8      # [T][NSCOEF] DPM-Solver++ table: weights of x, m0, m1, m2, z (ddpm3d_dpm_solver_step)
+S_CX, S_W0, S_W1, S_W2, S_CZ = 0, 1, 2, 3, 4
 PREC_F32, PREC_F16X3, PREC_F16, PREC_F16X3_WZ, PREC_F16_WZ, PREC_BF16, PREC_BF16_WZ = 0, 1, 2, 3, 4, 5, 6
 PRECISIONS = {"f32": PREC_F32, "f16x3": PREC_F16X3, "f16": PREC_F16, "bf16": PREC_BF16}
 # the Winograd-along-depth form of a mode (same arithmetic, 2/3 of the MFMAs), where one exists
@@ -126,6 +128,8 @@ EXPORTS = {
     "ddpm3d_p_mean_variance": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp,
                                          _fp, _fp]),
     "ddpm3d_ddim_reverse_step": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "ddpm3d_dpm_solver_step": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, _fp, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

@@ -156,7 +156,7 @@ def create_gaussian_diffusion(*, steps=1000, learn_sigma=False, sigma_small=Fals
     else:
         var_type = gd.ModelVarType.FIXED_SMALL if sigma_small else gd.ModelVarType.FIXED_LARGE
     return SpacedDiffusion(
-        use_timesteps=space_timesteps(steps, timestep_respacing if timestep_respacing else [steps]),
+        use_timesteps=space_timesteps(steps, timestep_respacing if timestep_respacing else [steps], betas=betas),
         betas=betas,
         model_mean_type=gd.ModelMeanType.START_X if predict_xstart else gd.ModelMeanType.EPSILON,
         model_var_type=var_type, loss_type=loss_type, rescale_timesteps=rescale_timesteps)

@@ -14,6 +14,9 @@ Differences from the reference script, all on the host side: `.npz`/`.npy`
 inputs are accepted besides `.tif` (README.md:67 asks users to edit the loader;
 scripts/test.py:187 rejects them); volumes need not be 200x200; `--use_ddim`
 is honoured (the reference parses it but always runs DDPM, scripts/test.py:63);
+`--use_dpm_solver True` (with `--solver_order`, `--solver_stochastic`) samples
+with DPM-Solver++ instead and takes precedence over `--use_ddim`; pair it with
+`--timestep_respacing logsnrN`;
 ranks get an evenly padded work list (the reference hangs in all_gather on an
 uneven one); `--model_path ""` uses seeded synthetic weights (no checkpoint
 ships with the reference).
@@ -40,6 +43,8 @@ from guided_diffusion.script_util import (
 def create_argparser():
     defaults = dict(save_dir="", clip_denoised=True, batch_size=1, use_ddim=False, eta=0.0,
                     timestep_respacing="", base_samples="", model_path="",
+                    # DPM-Solver++ multistep sampling (not in the reference); takes precedence over use_ddim
+                    use_dpm_solver=False, solver_order=2, solver_stochastic=False,
                     # launch-side extras (not in the reference): collective backend ("" = RCCL on
                     # GPUs) and all ranks on cuda:0, to rehearse the multi-rank flow on a one-GPU box
                     dist_backend="", share_gpu=False,
@@ -85,8 +90,13 @@ def main(argv=None):
     bs = max(1, args.batch_size)
     n_batches = (len(grid) + bs - 1) // bs
     done = {}
-    sample_loop = diffusion.ddim_sample_loop if args.use_ddim else diffusion.p_sample_loop
-    extra = dict(eta=args.eta) if args.use_ddim else {}
+    if args.use_dpm_solver:
+        sample_loop = diffusion.dpm_solver_sample_loop
+        extra = dict(order=args.solver_order, stochastic=args.solver_stochastic)
+    elif args.use_ddim:
+        sample_loop, extra = diffusion.ddim_sample_loop, dict(eta=args.eta)
+    else:
+        sample_loop, extra = diffusion.p_sample_loop, {}
     for b in dist_util.partition(n_batches):
         block = th.zeros(bs, 1, res, res, res, device=dev)                  # padded so collectives stay aligned
         if b is not None:
