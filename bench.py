@@ -3,7 +3,7 @@
 Headline benchmark: denoised 64^3 PET sub-volumes per second at 250 DDPM
 steps (BASELINE.json), published architecture, fp32, synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,12 @@ GPU, i.e. 250 UNet forwards + 250 fused sampler updates, device RNG included,
 inputs resident in HBM.  Ranks work on independent volumes (weak scaling, no
 collective inside a sample; one all_gather of the finished sample per step, as
 scripts/test.py:74-78 does).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line: `roofline` (from the timed steps' own events), `parity`, `exact_f32` and
+`cpu_baseline` null.  `--full` adds, after the timed region, everything that takes
+runs of its own: the MFMA calibration of `roofline`, `exact_f32`, every `parity` and
+`cpu_baseline`.  The headline fields mean the same in both.
 
 `--gpus N` with N > 1 and no RANK in the environment starts the N ranks itself
 (a torch.distributed.run child process; this parent never touches a GPU), relays
@@ -24,13 +30,13 @@ roofline     : the conv3d implicit-GEMM kernel family (100 % of the path's
                forward per timed step; achieved = algorithmic FLOPs / event time.
                device_sustained_tflops = what THIS board's matrix pipes sustain in a
                register-only MFMA loop of the instruction the dominant kernel issues
-               (ddpm3d_mfma_probe, ~50 ms, outside the timed region): boards of one
-               pool differ by several per cent, frac_of_sustained does not.
-parity       : the metric's "PSNR vs ref".  (a) the first timed volume against the same
+               (ddpm3d_mfma_probe, ~50 ms, outside the timed region; --full): boards of
+               one pool differ by several per cent, frac_of_sustained does not.
+parity       : (--full) the metric's "PSNR vs ref".  (a) the first timed volume against the same
                volume (same noise) in the exact-fp32 arithmetic of this library, all 250
                steps; (b) the first `--cpu-steps`+1 reverse steps against the CPU oracle
                (oracle/, pinned to the reference's own outputs) on the same injected noise.
-cpu_baseline : oracle/ (the CPU restatement pinned to the reference) timed on
+cpu_baseline : (--full) oracle/ (the CPU restatement pinned to the reference) timed on
                this box's host cores on a bounded sample (a few p_sample steps
                of the same workload), extrapolated to volumes/s.  N=1, rank 0.
 
@@ -278,16 +284,22 @@ def main():
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--batch", type=int, default=1, help="volumes per GPU per step")
     ap.add_argument("--arch", choices=["published", "tiny"], default="published")
-    ap.add_argument("--cpu-steps", type=int, default=3, help="timed oracle steps for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check what takes runs of its own: the MFMA "
+                         "calibration, exact_f32, parity and cpu_baseline (the options below marked --full)")
+    ap.add_argument("--cpu-steps", type=int, default=3,
+                    help="timed oracle steps for cpu_baseline (0 = skip); --full")
     ap.add_argument("--f32-steps", type=int, default=-1,
                     help="DDPM steps of the first timed volume repeated in the exact-fp32 arithmetic "
                          "(exact_f32 sub-record and parity (a)); -1 = all of them, 0 = skip; only "
-                         "with the default f16x3 precision")
+                         "with the default f16x3 precision; --full")
     ap.add_argument("--probe-ms", type=float, default=50.0,
-                    help="length of the MFMA calibration loop (roofline.device_sustained_tflops; 0 = skip)")
-    ap.add_argument("--cpu-threads", type=int, default=16, help="host threads for cpu_baseline")
+                    help="length of the MFMA calibration loop (roofline.device_sustained_tflops; 0 = skip); "
+                         "--full")
+    ap.add_argument("--cpu-threads", type=int, default=16, help="host threads for cpu_baseline; --full")
     ap.add_argument("--golden", type=int, choices=[0, 1], default=1,
-                    help="one more volume against the reference's own 250-step sample (tests/golden/sampler250_64.npz)")
+                    help="one more volume against the reference's own 250-step sample (tests/golden/sampler250_64.npz); "
+                         "--full")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--precision", choices=["f32", "f16x3", "f16", "bf16"],
@@ -514,10 +526,10 @@ def main():
         }
 
     # MFMA calibration of this board (outside the timed region): the instruction the dominant kernel
-    # issues, two waves per SIMD like that kernel, register-only, ~50 ms
-    from guided_diffusion import _hip as HH
+    # issues, two waves per SIMD like that kernel, register-only, ~50 ms; --full
     sustained = None
-    if roof is not None and args.probe_ms > 0 and rank == 0:
+    if args.full and roof is not None and args.probe_ms > 0 and rank == 0:
+        from guided_diffusion import _hip as HH
         lib = HH.load()
         kind = {"f32": HH.PROBE_F32_32X32X2, "bf16": HH.PROBE_BF16_32X32X16}.get(args.precision, HH.PROBE_F16_32X32X16)
         cus = torch.cuda.get_device_properties(device).multi_processor_count
@@ -551,10 +563,10 @@ def main():
 
     # The first timed volume again (same noise, same per-step draws) in the EXACT fp32 arithmetic
     # (v_mfma_f32_32x32x2_f32): the driver-timed record then carries an exact-arithmetic number beside
-    # the default one, and -- over all T steps -- the parity of the default arithmetic against it.
+    # the default one, and -- over all T steps -- the parity of the default arithmetic against it.  --full
     exact = None
     parity = {}
-    if args.precision == "f16x3" and args.f32_steps != 0 and rank == 0 and world == 1:
+    if args.full and args.precision == "f16x3" and args.f32_steps != 0 and rank == 0 and world == 1:
         model.conv_precision = "f32"
         eng32 = model.engine()
         k_steps = T if args.f32_steps < 0 else min(args.f32_steps, T)
@@ -590,8 +602,8 @@ def main():
     # 250-step run of BASELINE config 2 (generated in the build container, tests/golden/make_golden.py) -- against
     # that file's final sample.  A fixture, not the oracle: nothing under /root/reference is read here.
     gold = os.path.join(ROOT, "tests", "golden", "sampler250_64.npz")
-    if (rank == 0 and world == 1 and args.arch == "published" and S == 64 and T == 250 and args.sampler == "ddpm"
-            and not overrides and os.path.exists(gold) and args.golden):
+    if (args.full and rank == 0 and world == 1 and args.arch == "published" and S == 64 and T == 250
+            and args.sampler == "ddpm" and not overrides and os.path.exists(gold) and args.golden):
         from guided_diffusion import synth as _synth
         g = np.load(gold)
         shp = (1, 1, S, S, S)
@@ -645,8 +657,10 @@ def main():
             "roofline": roof,
             "exact_f32": exact,
             "parity": parity or None,
+            # plain run (false): roofline from the timed steps' events only; exact_f32, parity, cpu_baseline null
+            "full": args.full,
         }
-        if world == 1 and args.cpu_steps > 0:
+        if args.full and world == 1 and args.cpu_steps > 0:
             threads = os.cpu_count() or 1
             try:
                 threads = len(os.sched_getaffinity(0))

@@ -176,6 +176,45 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert bad.returncode != 0 and "WORLD_SIZE" in bad.stderr
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain `bench.py` run times its steps and prints the headline with the roofline of those steps only;
+    `--full` adds what takes runs of its own (MFMA calibration, exact_f32, parity, cpu_baseline) after the
+    timed region and leaves the headline fields and the dumped samples as they are.  Tiny network, 16^3."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--ddpm-steps", "5",
+              "--arch", "tiny", "--size", "16", "--cpu-steps", "1", "--probe-ms", "5"]
+    recs = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run(common + extra + ["--dump-outputs", str(tmp_path / name)], env=env, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        recs[name] = json.loads(lines[0])
+    plain, full = recs["plain"], recs["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "config"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["full"] is False and full["full"] is True
+    # plain: the timed steps' own roofline, nothing that needs another run
+    assert plain["roofline"]["launches_timed"] > 0 and "device_sustained_tflops" not in plain["roofline"]
+    assert plain["exact_f32"] is None and plain["parity"] is None and plain["cpu_baseline"] is None
+    # --full: all of it, as before the option existed
+    assert full["roofline"]["device_sustained_tflops"] > 0 and full["roofline"]["frac_of_sustained"] > 0
+    assert full["exact_f32"]["steps_timed"] == 5
+    assert set(full["parity"]) == {"vs_exact_f32", "vs_cpu_oracle"}
+    assert full["parity"]["vs_exact_f32"]["rel_err"] < 1e-3 and full["parity"]["vs_cpu_oracle"]["rel_err"] < 1e-3
+    assert full["cpu_baseline"]["value"] > 0
+    # the timed steps are the same in both: same seeded inputs, same samples
+    a, b = np.load(tmp_path / "plain" / "sample.npy"), np.load(tmp_path / "full" / "sample.npy")
+    assert a.shape == (1, 1, 16, 16, 16) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
+
+
 def test_c_abi_from_plain_cpp(tmp_path):
     """The boundary is a C ABI, not a Python extension: tests/c_abi/conv_from_c.cpp (no Python, no torch:
     hipMalloc'd buffers, `ddpm3d.h`, -lddpm3d) packs weights and runs one fused conv in the exact and the
