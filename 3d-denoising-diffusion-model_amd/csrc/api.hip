@@ -387,6 +387,18 @@ int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise,
 // grid.y carries the sample index of the element-wise launches
 static bool vb_shape_ok(int N, int voxels, int T) { return N > 0 && N <= 65535 && voxels > 0 && T > 0; }
 
+// flags are the sampler's
+static const int STEP_FLAGS = DDPM3D_F_LEARN_SIGMA | DDPM3D_F_PREDICT_XSTART | DDPM3D_F_CLIP;
+
+// The checks the step entries that take T share: the entry's own pointer checks (ptrs_ok) and the shape, then the
+// flags.  Entry-specific checks follow it.
+static int step_entry_ok(const char* what, bool ptrs_ok, int N, int voxels, int T, int flags) {
+    if (!ptrs_ok || !vb_shape_ok(N, voxels, T))
+        return fail(DDPM3D_EINVAL, "%s: bad arguments (N=%d voxels=%d T=%d)", what, N, voxels, T);
+    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "%s: unknown flag bits %#x", what, flags);
+    return DDPM3D_OK;
+}
+
 int ddpm3d_q_sample(const float* x_start, const float* noise, const float* qcoef, const int64_t* t_idx, int N,
                     int voxels, int T, float* x_t, void* stream) {
     if (!x_start || !noise || !qcoef || !t_idx || !x_t || !vb_shape_ok(N, voxels, T))
@@ -412,14 +424,14 @@ int ddpm3d_vb_terms(const float* model_out, const float* x_start, const float* x
                     const float* coef, const float* qcoef, const int64_t* t_idx, int N, int voxels, int T,
                     int flags, void* ws, size_t ws_bytes, float* vb, float* xstart_mse, float* mse, int ld_out,
                     float* pred_xstart, void* stream) {
+    // its bad-arguments message reports ld_out too, so step_entry_ok adds only the flag check here
     if (!model_out || !x_start || !x_t || !coef || !qcoef || !t_idx || !vb || !vb_shape_ok(N, voxels, T) ||
         ld_out <= 0)
         return fail(DDPM3D_EINVAL, "vb_terms: bad arguments (N=%d voxels=%d T=%d ld_out=%d)", N, voxels, T, ld_out);
     if ((noise == nullptr) != (mse == nullptr))
         return fail(DDPM3D_EINVAL, "vb_terms: noise and mse must come together");
-    if (flags & ~(DDPM3D_F_LEARN_SIGMA | DDPM3D_F_PREDICT_XSTART | DDPM3D_F_CLIP))
-        return fail(DDPM3D_EINVAL, "vb_terms: unknown flag bits %#x", flags);
-    const int rc = vb_ws_ok("vb_terms", N, voxels, ws, ws_bytes);
+    int rc = step_entry_ok("vb_terms", true, N, voxels, T, flags);
+    if (rc == DDPM3D_OK) rc = vb_ws_ok("vb_terms", N, voxels, ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_vb_terms(model_out, x_start, x_t, noise, coef, qcoef, t_idx, N, voxels, T, flags,
                                            (double*)ws, vb, xstart_mse, mse, ld_out, pred_xstart,
@@ -438,15 +450,13 @@ int ddpm3d_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels
 }
 
 // ------------------------------------------------- p_mean_variance, DDIM inversion (added within ABI 13)
-// shapes as vb_shape_ok (grid.y carries the sample index); flags are the sampler's
-static const int STEP_FLAGS = DDPM3D_F_LEARN_SIGMA | DDPM3D_F_PREDICT_XSTART | DDPM3D_F_CLIP;
 
 int ddpm3d_p_mean_variance(const float* model_out, const float* x, const float* coef, const int64_t* t_idx, int N,
                            int voxels, int T, int flags, float* mean, float* variance, float* log_variance,
                            float* pred_xstart, void* stream) {
-    if (!model_out || !x || !coef || !t_idx || !mean || !pred_xstart || !vb_shape_ok(N, voxels, T))
-        return fail(DDPM3D_EINVAL, "p_mean_variance: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
-    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "p_mean_variance: unknown flag bits %#x", flags);
+    const int rc = step_entry_ok("p_mean_variance", model_out && x && coef && t_idx && mean && pred_xstart, N, voxels,
+                                 T, flags);
+    if (rc != DDPM3D_OK) return rc;
     if (flags & DDPM3D_F_LEARN_SIGMA) {
         if (!variance || !log_variance)
             return fail(DDPM3D_EINVAL, "p_mean_variance: F_LEARN_SIGMA needs variance and log_variance");
@@ -460,9 +470,8 @@ int ddpm3d_p_mean_variance(const float* model_out, const float* x, const float* 
 
 int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float* coef, const int64_t* t_idx, int N,
                              int voxels, int T, int flags, float* sample, float* pred_xstart, void* stream) {
-    if (!model_out || !x || !coef || !t_idx || !sample || !vb_shape_ok(N, voxels, T))
-        return fail(DDPM3D_EINVAL, "ddim_reverse_step: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
-    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "ddim_reverse_step: unknown flag bits %#x", flags);
+    const int rc = step_entry_ok("ddim_reverse_step", model_out && x && coef && t_idx && sample, N, voxels, T, flags);
+    if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_ddim_reverse_step(model_out, x, coef, t_idx, N, voxels, T, flags, sample,
                                                     pred_xstart, (hipStream_t)stream),
                     "ddim_reverse_step");
@@ -472,12 +481,12 @@ int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float
 int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
                            const float* noise, const float* coef, const float* scoef, const int64_t* t_idx, int N,
                            int voxels, int T, int flags, int order, float* sample, float* pred_xstart, void* stream) {
-    if (!model_out || !x || !coef || !scoef || !t_idx || !sample || !pred_xstart || !vb_shape_ok(N, voxels, T))
-        return fail(DDPM3D_EINVAL, "dpm_solver_step: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    const int rc = step_entry_ok("dpm_solver_step", model_out && x && coef && scoef && t_idx && sample && pred_xstart,
+                                 N, voxels, T, flags);
+    if (rc != DDPM3D_OK) return rc;
     if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d is not 1, 2 or 3", order);
     if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
         return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d needs %d earlier x0 predictions", order, order - 1);
-    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "dpm_solver_step: unknown flag bits %#x", flags);
     return launched(ddpm3d_launch_dpm_solver_step(model_out, x, x0_prev1, x0_prev2, noise, coef, scoef, t_idx, N,
                                                   voxels, T, flags, order, sample, pred_xstart, (hipStream_t)stream),
                     "dpm_solver_step");

@@ -643,8 +643,49 @@ hipError_t ddpm3d_launch_subsample_hw2(const float* in, int N, int D, int H, int
 
 // ---------------------------------------------------------- sampler update
 // The arithmetic order mirrors the reference's torch expressions one rounding
-// at a time, so contraction into FMAs is switched off here.
+// at a time, so contraction into FMAs is switched off here.  The step kernels
+// below share the helpers that follow, so every step derives x0, eps and the
+// learned variance the same way.
 #pragma clang fp contract(off)
+
+// x0 from the model output's first half (x_start itself, or eps), then the clip
+__device__ __forceinline__ float step_x0(float xv, float e, float c_recip, float c_recipm1, int flags) {
+    float x0 = (flags & DDPM3D_F_PREDICT_XSTART) ? e : c_recip * xv - c_recipm1 * e;   // :305-311, :328-333
+    if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                     // :296-297
+    return x0;
+}
+
+// LEARNED_RANGE: the model's second half vv in [-1, 1] between the two log-variances
+__device__ __forceinline__ float learned_logvar(float vv, float min_log, float max_log) {
+    const float frac = (vv + 1.0f) / 2.0f;                      // :274
+    return frac * max_log + (1.0f - frac) * min_log;            // :275
+}
+
+// _predict_eps_from_xstart
+__device__ __forceinline__ float eps_from_x0(float xv, float x0, float c_recip, float c_recipm1) {
+    return (c_recip * xv - x0) / c_recipm1;                     // :345-349
+}
+
+// A sample whose t lies outside [0, T) reads no table row and gets NaN in every per-voxel output (fminf / fmaxf
+// would turn NaN coefficients into the clip bounds, so that case is a branch of its own): a and b, b only when
+// has_b, then c and d only when has_cd.
+__device__ __forceinline__ void step_nan_fill(int n, int voxels, int stride, float* a, float* b, bool has_b, float* c,
+                                              float* d, bool has_cd) {
+    const float nan = __builtin_nanf("");
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
+        const size_t i = (size_t)n * voxels + v;
+        a[i] = nan;
+        if (has_b) b[i] = nan;
+        if (has_cd) { c[i] = nan; d[i] = nan; }
+    }
+}
+
+// element-wise step launches: one grid row per sample, at most 1024 workgroups striding over its voxels
+static dim3 step_grid(int N, int voxels) {
+    int bx = (voxels + 255) / 256;
+    if (bx > 1024) bx = 1024;
+    return dim3(bx, N);
+}
 
 template <bool DDIM>
 __global__ __launch_bounds__(256) void sample_step_kernel(
@@ -664,28 +705,15 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += gridDim.x * blockDim.x) {
         const size_t i = (size_t)n * voxels + v;
         const float xv = x[i];
-        const float e = mo[((size_t)n * ch) * voxels + v];
-        float x0;
-        if (flags & DDPM3D_F_PREDICT_XSTART) {
-            x0 = e;
-        } else {
-            x0 = c_recip * xv - c_recipm1 * e;  // gaussian_diffusion.py:330-333
-        }
-        if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
         float out;
         if (!DDIM) {
-            float logvar;
-            if (learn) {
-                const float vv = mo[((size_t)n * ch + 1) * voxels + v];
-                const float frac = (vv + 1.0f) / 2.0f;                      // :274
-                logvar = frac * max_log + (1.0f - frac) * min_log;          // :275
-            } else {
-                logvar = min_log;
-            }
+            const float logvar = learn ? learned_logvar(mo[((size_t)n * ch + 1) * voxels + v], min_log, max_log)
+                                       : min_log;
             const float mean = c1 * x0 + c2 * xv;                           // :216-219
             out = mean + mask * expf(0.5f * logvar) * noise[i];             // :438
         } else {
-            const float eps = (c_recip * xv - x0) / c_recipm1;              // :345-349
+            const float eps = eps_from_x0(xv, x0, c_recip, c_recipm1);
             const float sigma = eta * sqrtf((1.0f - ab_prev) / (1.0f - ab)) * sqrtf(1.0f - ab / ab_prev);
             const float mean_pred = x0 * sqrtf(ab_prev) + sqrtf(1.0f - ab_prev - sigma * sigma) * eps;
             out = mean_pred + mask * sigma * noise[i];                      // :584
@@ -698,29 +726,18 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
 hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
                                      const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
                                      float eta, float* sample, float* pred_xstart, hipStream_t st) {
-    int bx = (voxels + 255) / 256;
-    if (bx > 1024) bx = 1024;
-    dim3 grid(bx, N);
     if (ddim)
-        hipLaunchKernelGGL(sample_step_kernel<true>, grid, dim3(256), 0, st, mo, x, noise, coef, t_idx, voxels,
-                           flags, eta, sample, pred_xstart);
+        hipLaunchKernelGGL(sample_step_kernel<true>, step_grid(N, voxels), dim3(256), 0, st, mo, x, noise, coef,
+                           t_idx, voxels, flags, eta, sample, pred_xstart);
     else
-        hipLaunchKernelGGL(sample_step_kernel<false>, grid, dim3(256), 0, st, mo, x, noise, coef, t_idx,
-                           voxels, flags, eta, sample, pred_xstart);
+        hipLaunchKernelGGL(sample_step_kernel<false>, step_grid(N, voxels), dim3(256), 0, st, mo, x, noise, coef,
+                           t_idx, voxels, flags, eta, sample, pred_xstart);
     return hipGetLastError();
 }
 
 // ------------------------------------------------- p_mean_variance, DDIM inversion
 // The reference's public per-step call (gaussian_diffusion.py:232-326) and the reverse ODE step built on it
-// (:587-623), as sample_step_kernel derives x0: same expressions, same rounding order.  A sample whose t lies
-// outside [0, T) reads no table row and gets NaN in every output (fminf / fmaxf would turn NaN coefficients into
-// the clip bounds, so that case is a branch of its own).
-
-__device__ __forceinline__ float step_x0(float xv, float e, float c_recip, float c_recipm1, int flags) {
-    float x0 = (flags & DDPM3D_F_PREDICT_XSTART) ? e : c_recip * xv - c_recipm1 * e;   // :305-311, :328-333
-    if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                     // :296-297
-    return x0;
-}
+// (:587-623), on the step helpers above.
 
 __global__ __launch_bounds__(256) void p_mean_variance_kernel(
     const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ coef,
@@ -732,13 +749,7 @@ __global__ __launch_bounds__(256) void p_mean_variance_kernel(
     const int ch = learn ? 2 : 1;
     const int stride = gridDim.x * blockDim.x;
     if (ti < 0 || ti >= T) {
-        const float nan = __builtin_nanf("");
-        for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
-            const size_t i = (size_t)n * voxels + v;
-            mean[i] = nan;
-            pred_xstart[i] = nan;
-            if (learn) { log_variance[i] = nan; variance[i] = nan; }
-        }
+        step_nan_fill(n, voxels, stride, mean, pred_xstart, true, log_variance, variance, learn);
         return;
     }
     const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
@@ -752,9 +763,7 @@ __global__ __launch_bounds__(256) void p_mean_variance_kernel(
         mean[i] = c1 * x0 + c2 * xv;                                    // :312-314, :216-219
         pred_xstart[i] = x0;
         if (learn) {
-            const float vv = mo[((size_t)n * ch + 1) * voxels + v];
-            const float frac = (vv + 1.0f) / 2.0f;                      // :274
-            const float lv = frac * max_log + (1.0f - frac) * min_log;  // :275
+            const float lv = learned_logvar(mo[((size_t)n * ch + 1) * voxels + v], min_log, max_log);
             log_variance[i] = lv;
             variance[i] = expf(lv);                                     // :276
         }
@@ -773,12 +782,7 @@ __global__ __launch_bounds__(256) void ddim_reverse_step_kernel(
     const int ch = (flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1;
     const int stride = gridDim.x * blockDim.x;
     if (ti < 0 || ti >= T) {
-        const float nan = __builtin_nanf("");
-        for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
-            const size_t i = (size_t)n * voxels + v;
-            sample[i] = nan;
-            if (pred_xstart != nullptr) pred_xstart[i] = nan;
-        }
+        step_nan_fill(n, voxels, stride, sample, pred_xstart, pred_xstart != nullptr, nullptr, nullptr, false);
         return;
     }
     const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
@@ -789,16 +793,10 @@ __global__ __launch_bounds__(256) void ddim_reverse_step_kernel(
         const size_t i = (size_t)n * voxels + v;
         const float xv = x[i];
         const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
-        const float eps = (c_recip * xv - x0) / c_recipm1;              // :611-614
+        const float eps = eps_from_x0(xv, x0, c_recip, c_recipm1);      // :611-614
         sample[i] = x0 * s_next + s_next_1m * eps;                      // :615-621
         if (pred_xstart != nullptr) pred_xstart[i] = x0;
     }
-}
-
-static dim3 step_grid(int N, int voxels) {
-    int bx = (voxels + 255) / 256;
-    if (bx > 1024) bx = 1024;
-    return dim3(bx, N);
 }
 
 hipError_t ddpm3d_launch_p_mean_variance(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
@@ -818,10 +816,10 @@ hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, cons
 }
 
 // ------------------------------------------------- DPM-Solver++ multistep step
-// One step of DPM-Solver++ (Lu et al. 2022, arXiv:2211.01095): x0 exactly as sample_step_kernel derives it (step_x0),
-// then the update as a weighted sum whose weights the host expanded in fp64 into row t of scoef
-// ([T][DDPM3D_NSCOEF]: c_x, w0, w1, w2, c_z), summed in that order.  m1 is read only at order >= 2, m2 only at
-// order 3, z only when noise is non-null.  A sample whose t lies outside [0, T) reads neither table and gets NaN.
+// One step of DPM-Solver++ (Lu et al. 2022, arXiv:2211.01095): x0 from step_x0, then the update as a weighted sum
+// whose weights the host expanded in fp64 into row t of scoef ([T][DDPM3D_NSCOEF]: c_x, w0, w1, w2, c_z), summed in
+// that order.  m1 is read only at order >= 2, m2 only at order 3, z only when noise is non-null.  A sample whose t
+// lies outside [0, T) reads neither table and gets NaN.
 __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
     const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ m1,
     const float* __restrict__ m2, const float* __restrict__ noise, const float* __restrict__ coef,
@@ -832,12 +830,7 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
     const int ch = (flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1;
     const int stride = gridDim.x * blockDim.x;
     if (ti < 0 || ti >= T) {
-        const float nan = __builtin_nanf("");
-        for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
-            const size_t i = (size_t)n * voxels + v;
-            sample[i] = nan;
-            pred_xstart[i] = nan;
-        }
+        step_nan_fill(n, voxels, stride, sample, pred_xstart, true, nullptr, nullptr, false);
         return;
     }
     const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
@@ -883,6 +876,13 @@ int ddpm3d_vb_parts(int voxels) {
     const int per = VB_THREADS * VB_UNROLL;
     const int p = voxels / per + (voxels % per != 0);
     return p < VB_MAX_PARTS ? p : VB_MAX_PARTS;
+}
+
+// The voxels [v0, v1) that workgroup `part` of `parts` sums: equal chunks, the last one short.
+__device__ __forceinline__ void vb_chunk(int voxels, int parts, int part, long long& v0, long long& v1) {
+    const int chunk = voxels / parts + (voxels % parts != 0);
+    v0 = (long long)part * chunk;
+    v1 = v0 + chunk < voxels ? v0 + chunk : voxels;
 }
 
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
@@ -952,9 +952,8 @@ __global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
         const bool learn = flags & DDPM3D_F_LEARN_SIGMA;
         const int ch = learn ? 2 : 1;
         const float BIN = (float)(1.0 / 255.0);
-        const int chunk = voxels / parts + (voxels % parts != 0);
-        const long long v0 = (long long)part * chunk;
-        const long long v1 = v0 + chunk < voxels ? v0 + chunk : voxels;
+        long long v0, v1;
+        vb_chunk(voxels, parts, part, v0, v1);
         for (long long base = v0; base < v1; base += VB_THREADS * VB_UNROLL) {
 #pragma unroll
             for (int j = 0; j < VB_UNROLL; ++j) {
@@ -962,16 +961,10 @@ __global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
                 if (v >= v1) continue;
                 const size_t i = (size_t)n * voxels + v;
                 const float xv = xt_p[i], xs = xs_p[i];
-                const float e = mo[((size_t)n * ch) * voxels + v];
-                // p_mean_variance (:262-318), as sample_step_kernel
-                float x0 = (flags & DDPM3D_F_PREDICT_XSTART) ? e : c_recip * xv - c_recipm1 * e;
-                if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+                // p_mean_variance (:262-318)
+                const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
                 float logvar = min_log;
-                if (learn) {
-                    const float vv = mo[((size_t)n * ch + 1) * voxels + v];
-                    const float frac = (vv + 1.0f) / 2.0f;
-                    logvar = frac * max_log + (1.0f - frac) * min_log;
-                }
+                if (learn) logvar = learned_logvar(mo[((size_t)n * ch + 1) * voxels + v], min_log, max_log);
                 const float mean = c1 * x0 + c2 * xv;
                 float term;
                 if (ti == 0) {
@@ -995,7 +988,7 @@ __global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
                 const float dx = x0 - xs;                                   // :877
                 s_x0 += (double)(dx * dx);
                 if (noise != nullptr) {
-                    const float eps = (c_recip * xv - x0) / c_recipm1;      // :879 (_predict_eps_from_xstart)
+                    const float eps = eps_from_x0(xv, x0, c_recip, c_recipm1);   // :879
                     const float de = eps - noise[i];
                     s_eps += (double)(de * de);
                 }
@@ -1017,9 +1010,8 @@ __global__ __launch_bounds__(VB_THREADS) void prior_bpd_kernel(const float* __re
     const float sa = qcoef[(size_t)(T - 1) * DDPM3D_NQCOEF + DDPM3D_Q_SQRT_ACP];
     const float lv = qcoef[(size_t)(T - 1) * DDPM3D_NQCOEF + DDPM3D_Q_LOG_1M_ACP];
     double s = 0.0;
-    const int chunk = voxels / parts + (voxels % parts != 0);
-    const long long v0 = (long long)part * chunk;
-    const long long v1 = v0 + chunk < voxels ? v0 + chunk : voxels;
+    long long v0, v1;
+    vb_chunk(voxels, parts, part, v0, v1);
     for (long long base = v0; base < v1; base += VB_THREADS * VB_UNROLL) {
 #pragma unroll
         for (int j = 0; j < VB_UNROLL; ++j) {
@@ -1063,9 +1055,8 @@ __global__ __launch_bounds__(256) void vb_fold_kernel(const double* __restrict__
 
 hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,
                                   int N, int voxels, int T, float* xt, hipStream_t st) {
-    int bx = (voxels + 255) / 256;
-    if (bx > 1024) bx = 1024;
-    hipLaunchKernelGGL(q_sample_kernel, dim3(bx, N), dim3(256), 0, st, x0, noise, qcoef, t_idx, voxels, T, xt);
+    hipLaunchKernelGGL(q_sample_kernel, step_grid(N, voxels), dim3(256), 0, st, x0, noise, qcoef, t_idx, voxels, T,
+                       xt);
     return hipGetLastError();
 }
 

@@ -261,15 +261,9 @@ class GaussianDiffusion:
         N = x.shape[0]
         vox = x[0].numel()
         flags = self._flags(clip_denoised)
-        C = x.shape[1]
-        want = 2 * C if flags & H.F_LEARN_SIGMA else C
-        # th.split(model_output, C, dim=1) (gaussian_diffusion.py:264) of a contiguous (N, 2C, ...)
-        # tensor = two contiguous halves per sample: the kernel's (N, 2, C * voxels) view
-        assert tuple(model_output.shape) == (N, want, *x.shape[2:]), \
-            "model output shape %s for input %s" % (tuple(model_output.shape), tuple(x.shape))
+        self._model_step_output(model_output, x, flags)
         H.require_device(x, "x")
-        H.require_device(model_output, "model_output")
-        H.require_device(noise, "noise")
+        self._check_noise(noise, x)
         st = self._device_state(x.device)
         sample = th.empty_like(x)
         x0 = th.empty_like(x)
@@ -283,8 +277,57 @@ class GaussianDiffusion:
                                          H.stream()))
         return {"sample": sample, "pred_xstart": x0}
 
+    @staticmethod
+    def _indices(indices, progress):
+        indices = list(indices)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        return indices
+
     def _call_model(self, model, x, t, model_kwargs):
         return model(x, self._model_timesteps(t), **(model_kwargs or {}))
+
+    @staticmethod
+    def _model_step_output(model_output, x, flags):
+        # th.split(model_output, C, dim=1) (gaussian_diffusion.py:264) of a contiguous (N, 2C, ...)
+        # tensor = two contiguous halves per sample: the kernel's (N, 2, C * voxels) view
+        N, C = x.shape[:2]
+        want = 2 * C if flags & H.F_LEARN_SIGMA else C
+        assert tuple(model_output.shape) == (N, want, *x.shape[2:]), \
+            "model output shape %s for input %s" % (tuple(model_output.shape), tuple(x.shape))
+        H.require_device(model_output, "model_output")
+
+    @staticmethod
+    def _check_noise(noise, x):
+        """Every noise tensor a step kernel reads: the kernels read one draw per element of x."""
+        H.require_device(noise, "noise")
+        assert noise.shape == x.shape
+
+    @staticmethod
+    def _draw_noise(step_noise, k, like):
+        """The k-th step's noise: randn_like, or `step_noise` (extension, for parity runs): a sequence of
+        tensors in draw order, or a callable (k, like) -> tensor (e.g. per-volume generators, scripts/test.py)."""
+        if step_noise is None:
+            return th.randn_like(like)
+        if callable(step_noise):
+            return step_noise(k, like)
+        return step_noise[k]
+
+    def _step_model(self, model, shape, model_kwargs, device):
+        """A loop's per-step network call, set up under no_grad on `device`: (t table [T][N] int64,
+        call (x, i) -> model output at step index i).  With model_kwargs == {"low_res"} on a 5-D shape it
+        takes the engine path: the x-independent timestep path (film rows) for the whole schedule once, then
+        one plan replay per step."""
+        T = self.num_timesteps
+        t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, shape[0]).contiguous()
+        if not (hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and len(shape) == 5):
+            return t_all, lambda img, i: self._call_model(model, img, t_all[i], model_kwargs)
+        eng = model.engine()
+        low_res = model_kwargs["low_res"].to(device).contiguous()
+        t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
+        film = eng.film_rows(t_model.to(th.float32).contiguous())
+        return t_all, lambda img, i: eng.forward(img, low_res, film[i], 0)
 
     @staticmethod
     def _reject_hooks(denoised_fn, cond_fn):
@@ -323,40 +366,18 @@ class GaussianDiffusion:
         assert isinstance(shape, (tuple, list))
         img = noise if noise is not None else th.randn(*shape, device=device)
         H.require_device(img, "noise")
-        N = shape[0]
-        T = self.num_timesteps
-        indices = list(range(T))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        model_kwargs = model_kwargs or {}
-        fast = hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and len(shape) == 5
+        indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
         # grad mode and the current device are changed around the COMPUTE of a step only and are
         # back to the caller's before every yield (the reference wraps p_sample alone in no_grad and
         # yields outside it, gaussian_diffusion.py:524-535): an abandoned *_progressive generator
         # leaves nothing changed.
         with th.no_grad(), th.cuda.device(device):
-            t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, N).contiguous()
-            if fast:
-                # x-independent timestep path for the whole schedule, then one plan replay per step
-                eng = model.engine()
-                low_res = model_kwargs["low_res"].to(device).contiguous()
-                t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
-                film = eng.film_rows(t_model.to(th.float32).contiguous())
+            t_all, net = self._step_model(model, shape, model_kwargs or {}, device)
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
-                t = t_all[i]
-                if fast:
-                    out = eng.forward(img, low_res, film[i], 0)
-                else:
-                    out = self._call_model(model, img, t, model_kwargs)
-                if step_noise is None:
-                    z = th.randn_like(img)
-                elif callable(step_noise):
-                    z = step_noise(k, img)       # e.g. per-volume generators (scripts/test.py)
-                else:
-                    z = step_noise[k]
-                res = self._update(kind, out, img, t, z, clip_denoised, eta)
+                out = net(img, i)
+                z = self._draw_noise(step_noise, k, img)
+                res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta)
             yield res
             img = res["sample"]
 
@@ -456,11 +477,7 @@ class GaussianDiffusion:
     def _vb_terms(self, model_output, x_start, x_t, t, noise, flags, ws, vb, xstart_mse, mse, ld, pred_xstart):
         """One ddpm3d_vb_terms launch; the outputs are written through pointers (column views allowed)."""
         N = x_t.shape[0]
-        C = x_t.shape[1]
-        want = 2 * C if flags & H.F_LEARN_SIGMA else C
-        assert tuple(model_output.shape) == (N, want, *x_t.shape[2:]), \
-            "model output shape %s for input %s" % (tuple(model_output.shape), tuple(x_t.shape))
-        H.require_device(model_output, "model_output")
+        self._model_step_output(model_output, x_t, flags)
         st = self._device_state(x_t.device)
         H.check(H.load().ddpm3d_vb_terms(H.ptr(model_output), H.ptr(x_start), H.ptr(x_t), H.ptr(noise),
                                          H.ptr(st["coef"]), H.ptr(st["qcoef"]), H.ptr(t), N, x_t[0].numel(),
@@ -512,35 +529,19 @@ class GaussianDiffusion:
         N = x_start.shape[0]
         T = self.num_timesteps
         flags = self._flags(clip_denoised)
-        model_kwargs = model_kwargs or {}
-        fast = hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and x_start.dim() == 5
         with th.no_grad(), th.cuda.device(device):
             vb = th.empty((N, T), dtype=th.float32, device=device)
             xstart_mse = th.empty_like(vb)
             mse = th.empty_like(vb)
             ws = self._workspace(x_start)
             x_t = th.empty_like(x_start)
-            t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, N).contiguous()
-            if fast:
-                eng = model.engine()
-                low_res = model_kwargs["low_res"].to(device).contiguous()
-                t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
-                film = eng.film_rows(t_model.to(th.float32).contiguous())
+            t_all, net = self._step_model(model, x_start.shape, model_kwargs or {}, device)
             for k, i in enumerate(range(T - 1, -1, -1)):
                 t = t_all[i]
-                if step_noise is None:
-                    noise = th.randn_like(x_start)
-                elif callable(step_noise):
-                    noise = step_noise(k, x_start)
-                else:
-                    noise = step_noise[k]
-                H.require_device(noise, "noise")
-                assert noise.shape == x_start.shape
+                noise = self._draw_noise(step_noise, k, x_start)
+                self._check_noise(noise, x_start)
                 self._q_sample(x_start, t, noise, x_t)
-                if fast:
-                    out = eng.forward(x_t, low_res, film[i], 0)
-                else:
-                    out = self._call_model(model, x_t, t, model_kwargs)
+                out = net(x_t, i)
                 self._vb_terms(out, x_start, x_t, t, noise, flags, ws, vb[:, k], xstart_mse[:, k], mse[:, k], T,
                                None)
             prior_bpd = self._prior_bpd(x_start)
@@ -554,13 +555,6 @@ class GaussianDiffusion:
             var = np.append(self.posterior_variance[1], self.betas[1:])
             return var, np.log(var)
         return self.posterior_variance, self.posterior_log_variance_clipped
-
-    def _model_step_output(self, model_output, x, flags):
-        N, C = x.shape[:2]
-        want = 2 * C if flags & H.F_LEARN_SIGMA else C
-        assert tuple(model_output.shape) == (N, want, *x.shape[2:]), \
-            "model output shape %s for input %s" % (tuple(model_output.shape), tuple(x.shape))
-        H.require_device(model_output, "model_output")
 
     def _p_mean_variance(self, model_output, x, t, flags):
         """One ddpm3d_p_mean_variance launch; t: int64 on x's device."""
@@ -637,31 +631,14 @@ class GaussianDiffusion:
         if device.type != "cuda":
             raise RuntimeError("DDIM inversion runs on HIP kernels only; got device %s" % device)
         flags = self._flags(clip_denoised)
-        N = x_start.shape[0]
-        T = self.num_timesteps
-        indices = list(range(T))
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        model_kwargs = model_kwargs or {}
-        fast = hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and x_start.dim() == 5
+        indices = self._indices(range(self.num_timesteps), progress)
         # as in _loop: grad mode and the current device change around each step's compute only
         with th.no_grad(), th.cuda.device(device):
             img = x_start.to(device)
-            t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, N).contiguous()
-            if fast:
-                eng = model.engine()
-                low_res = model_kwargs["low_res"].to(device).contiguous()
-                t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
-                film = eng.film_rows(t_model.to(th.float32).contiguous())
+            t_all, net = self._step_model(model, x_start.shape, model_kwargs or {}, device)
         for i in indices:
             with th.no_grad(), th.cuda.device(device):
-                t = t_all[i]
-                if fast:
-                    out = eng.forward(img, low_res, film[i], 0)
-                else:
-                    out = self._call_model(model, img, t, model_kwargs)
-                res = self._reverse_step(out, img, t, flags)
+                res = self._reverse_step(net(img, i), img, t_all[i], flags)
             yield res
             img = res["sample"]
 
@@ -678,6 +655,8 @@ class GaussianDiffusion:
     # ------------------------------------------------- DPM-Solver++ multistep
     def _solver_step(self, model_output, x, m1, m2, z, t, flags, order, stochastic, p):
         """One ddpm3d_dpm_solver_step launch at effective order p; t: int64 on x's device."""
+        if z is not None:
+            self._check_noise(z, x)
         self._model_step_output(model_output, x, flags)
         st = self._device_state(x.device)
         scoef = self._solver_state(x.device, order, stochastic)
@@ -717,43 +696,20 @@ class GaussianDiffusion:
 
     def _solver_loop(self, model, shape, noise, flags, model_kwargs, device, progress, order, stochastic,
                      step_noise):
-        N = shape[0]
-        T = self.num_timesteps
-        indices = list(range(T))[::-1]
-        if progress:
-            from tqdm.auto import tqdm
-            indices = tqdm(indices)
-        fast = hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and len(shape) == 5
+        indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
         # as in _loop: grad mode and the current device change around each step's compute only
         with th.no_grad(), th.cuda.device(device):
             img = noise if noise is not None else th.randn(*shape, device=device)
             H.require_device(img, "noise")
-            t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, N).contiguous()
-            if fast:
-                eng = model.engine()
-                low_res = model_kwargs["low_res"].to(device).contiguous()
-                t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
-                film = eng.film_rows(t_model.to(th.float32).contiguous())
+            t_all, net = self._step_model(model, shape, model_kwargs, device)
         hist = []                       # pred_xstart of the last one or two steps, newest first
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
-                t = t_all[i]
-                if fast:
-                    out = eng.forward(img, low_res, film[i], 0)
-                else:
-                    out = self._call_model(model, img, t, model_kwargs)
-                z = None
-                if stochastic:
-                    if step_noise is None:
-                        z = th.randn_like(img)
-                    elif callable(step_noise):
-                        z = step_noise(k, img)
-                    else:
-                        z = step_noise[k]
-                    H.require_device(z, "noise")
+                out = net(img, i)
+                z = self._draw_noise(step_noise, k, img) if stochastic else None
                 p = 1 if i == 0 else min(order, k + 1)
-                res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z, t,
-                                        flags, order, stochastic, p)
+                res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z,
+                                        t_all[i], flags, order, stochastic, p)
             yield res
             img = res["sample"]
             hist = [res["pred_xstart"]] + hist[:1]

@@ -543,3 +543,37 @@ def test_native_plan_runs_the_2d_network_and_refuses_bad_arenas():
     assert b"the plan needs" in lib.ddpm3d_unet_last_error()
     assert lib.ddpm3d_unet_plan_create(C.byref(desc), 1, 1, 32, 48, 0, need, C.byref(handle)) == H.E_INVAL
     assert lib.ddpm3d_unet_plan_bytes(C.byref(desc), 0, 1, 32, 48) == 0
+
+
+# ---------------------------------------------------------------- step noise of the wrong shape
+# The step kernels read one noise draw per element of x, so a noise tensor of another shape is refused before the
+# step launches.  The tensors here are oversized: a kernel that took one would still read only inside it.
+def _oversized(shape):
+    return torch.zeros((shape[0] + 1,) + tuple(shape[1:]), device="cuda")
+
+
+@pytest.mark.parametrize("loop", ["p_sample", "ddim_sample", "dpm_solver_sde", "calc_bpd"])
+def test_loop_step_noise_of_wrong_shape_is_refused(loop):
+    model, diff = build(TINY, "2")
+    shape = (1, 1, 4, 16, 16)
+    x, lr = inputs(shape)
+    kw = {"low_res": lr.cuda()}
+    bad = [_oversized(shape)] * diff.num_timesteps
+    with pytest.raises(AssertionError):
+        if loop == "calc_bpd":
+            diff.calc_bpd_loop(model, x.cuda(), model_kwargs=kw, step_noise=bad)
+        elif loop == "dpm_solver_sde":
+            next(diff.dpm_solver_sample_loop_progressive(model, shape, x.cuda(), model_kwargs=kw, order=1,
+                                                         stochastic=True, step_noise=bad))
+        else:
+            next(getattr(diff, loop + "_loop_progressive")(model, shape, x.cuda(), model_kwargs=kw, step_noise=bad))
+
+
+@pytest.mark.parametrize("step", ["p_sample", "ddim_sample"])
+def test_step_noise_of_wrong_shape_is_refused(step):
+    model, diff = build(TINY, "2")
+    shape = (1, 1, 4, 16, 16)
+    x, lr = inputs(shape)
+    with pytest.raises(AssertionError):
+        getattr(diff, step)(model, x.cuda(), torch.tensor([1]).cuda(), model_kwargs={"low_res": lr.cuda()},
+                            noise=_oversized(shape))
