@@ -360,30 +360,37 @@ PUBLISHED = dict(large_size=96, small_size=96, num_channels=128, num_res_blocks=
 @pytest.mark.parametrize("precision", ["f16", "bf16"])
 def test_plan_tuples_are_covered(precision):
     """Build (do not run) the Python plans of the published architecture at BASELINE config 4's volume
-    (1x1x64^3) and at test_native_plan_equals_python_plan's 1x1x8x32x32.  Every conv descriptor's
+    (1x1x64^3), at the reference launcher's own --use_fp16 patch (1x1x96^3) and at
+    test_native_plan_equals_python_plan's 1x1x8x32x32, and of config 5's network (attention at 16) at
+    1x1x128^3.  Every conv descriptor's
     (family, precision, in_mode, res_mode, act, io flags, split > 1) must match a case of the table above: a
     routing change that sends a 16-bit layer down an untested path fails here until a case is added."""
     import guided_diffusion._hip as H
     from guided_diffusion import script_util as su
-    fl = su.sr_model_and_diffusion_defaults()
-    fl.update(PUBLISHED)
-    model, _ = su.sr_create_model_and_diffusion(**fl)
-    model.conv_precision = precision
-    model.to("cuda").eval()          # (parameters are the initialiser's: the plan depends on shapes only)
-    eng = model.engine()
     found = {}
-    for shape in ((1, 64, 64, 64), (1, 8, 32, 32)):
-        pl = eng.plan(*shape)
-        for i, (tag, _) in pl.conv_meta.items():
-            fn, args = pl.steps[i]
-            if not tag.startswith("conv"):
-                continue
-            d = args[0]._obj
-            _, _, split = H.conv_plan(d)
-            key = (tag, d.precision, d.in_mode, d.res_mode, d.act, d.io_dtype, split > 1)
-            found.setdefault(key, []).append(shape)
-        eng.plans.clear()
-        del pl
+    for over, shapes in ((dict(), ((1, 64, 64, 64), (1, 96, 96, 96), (1, 8, 32, 32))),
+                         (dict(large_size=128, small_size=128, attention_resolutions="16"), ((1, 128, 128, 128),))):
+        fl = su.sr_model_and_diffusion_defaults()
+        fl.update(PUBLISHED)
+        fl.update(over)
+        model, _ = su.sr_create_model_and_diffusion(**fl)
+        model.conv_precision = precision
+        model.to("cuda").eval()          # (parameters are the initialiser's: the plan depends on shapes only)
+        eng = model.engine()
+        for shape in shapes:
+            pl = eng.plan(*shape)
+            for i, (tag, _) in pl.conv_meta.items():
+                fn, args = pl.steps[i]
+                if not tag.startswith("conv"):
+                    continue
+                d = args[0]._obj
+                _, _, split = H.conv_plan(d)
+                key = (tag, d.precision, d.in_mode, d.res_mode, d.act, d.io_dtype, split > 1)
+                found.setdefault(key, []).append(shape)
+            eng.plans.clear()
+            del pl
+            torch.cuda.empty_cache()
+        del model, eng
         torch.cuda.empty_cache()
     have = {c.key() for c in CASES}
     print("%s plan tuples (family, precision, in_mode, res_mode, act, io, split>1):" % precision)
