@@ -492,6 +492,35 @@ int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* 
                     "dpm_solver_step");
 }
 
+// ------------------------------------------------- uncertainty maps from K draws (added within ABI 13)
+int ddpm3d_draw_stitch(const float* samples, int K, int res, const double* window, int xs, int ys, int zs, int H,
+                       int W, int D, float* acc, float* wsum, void* stream) {
+    if (!samples || !window || !acc || !wsum)
+        return fail(DDPM3D_EINVAL, "draw_stitch: null pointer");
+    if (K < 1 || K > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "draw_stitch: K=%d draws (1..%d)", K, DDPM3D_MAX_DRAWS);
+    if (res < 1 || res > 1024 || H < 1 || W < 1 || D < 1)
+        return fail(DDPM3D_EINVAL, "draw_stitch: bad shape (res=%d, volume H=%d W=%d D=%d)", res, H, W, D);
+    if (xs < 0 || ys < 0 || zs < 0 || xs >= H || ys >= W || zs >= D)
+        return fail(DDPM3D_EINVAL, "draw_stitch: patch origin (%d, %d, %d) outside the %dx%dx%d volume", xs, ys, zs,
+                    H, W, D);
+    return launched(ddpm3d_launch_draw_stitch(samples, K, res, window, xs, ys, zs, H, W, D, acc, wsum,
+                                              (hipStream_t)stream),
+                    "draw_stitch");
+}
+
+int ddpm3d_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean, float* std,
+                        void* stream) {
+    if (!acc || !mean || !std) return fail(DDPM3D_EINVAL, "draw_moments: null pointer");
+    if (K < 2 || K > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "draw_moments: K=%d draws (2..%d)", K, DDPM3D_MAX_DRAWS);
+    // one thread per voxel in the unaligned form: the grid's x extent bounds the volume
+    if (voxels <= 0 || voxels > ((int64_t)0x7fffffff) * 256)
+        return fail(DDPM3D_EINVAL, "draw_moments: voxels=%lld", (long long)voxels);
+    return launched(ddpm3d_launch_draw_moments(acc, wsum, K, voxels, mean, std, (hipStream_t)stream),
+                    "draw_moments");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

@@ -58,3 +58,9 @@ hipError_t ddpm3d_launch_pool_act(const float* src, const float* A, const float*
 double ddpm3d_probe_flops_per_iter(int kind);
 hipError_t ddpm3d_launch_mfma_probe(int kind, int iters, int blocks, float* out, unsigned long long* clk,
                                     hipStream_t st);
+// uncertainty.hip: one patch origin's K draws into acc[K][H][W][D] / wsum[H][W][D] (the caller has checked that the
+// origin lies in the volume), and the per-voxel mean / sample std of K accumulators (wsum may be NULL)
+hipError_t ddpm3d_launch_draw_stitch(const float* samples, int K, int res, const double* window, int xs, int ys,
+                                     int zs, int H, int W, int D, float* acc, float* wsum, hipStream_t st);
+hipError_t ddpm3d_launch_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean,
+                                      float* std, hipStream_t st);

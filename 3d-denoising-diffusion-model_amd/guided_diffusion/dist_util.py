@@ -82,11 +82,22 @@ def partition(n_items, rank_=None, world=None):
     return [(r * world + rank_) if (r * world + rank_) < n_items else None for r in range(rounds)]
 
 
-def volume_generator(global_index, seed=10, device=None):
+# Seed offset between posterior draws of one volume.  2^24 > 1000003 keeps every (index, draw) pair apart for
+# index < 2^24 and draw < 256, and it does so in the low 32 bits too: the host generator (mt19937) keeps only
+# those, so a stride such as 2^40 would give every draw of a host-side run draw 0's stream.
+DRAW_SEED_STRIDE = 1 << 24
+MAX_DRAW = 255
+
+
+def volume_generator(global_index, seed=10, device=None, draw=0):
     """RNG for one volume, keyed by its global index: sampling volume i gives the
-    same result on 1, 2, 4 or 8 ranks."""
+    same result on 1, 2, 4 or 8 ranks.  `draw` (0..MAX_DRAW) selects one of several
+    independent posterior draws of the same volume (uncertainty maps): draw 0 is the
+    single-draw stream, draw d is seeded d * DRAW_SEED_STRIDE above it."""
+    if not 0 <= int(draw) <= MAX_DRAW:
+        raise ValueError("draw must be in 0..%d, got %s" % (MAX_DRAW, draw))
     g = torch.Generator(device=device if device is not None else dev())
-    g.manual_seed(int(seed) * 1000003 + int(global_index))
+    g.manual_seed(int(seed) * 1000003 + int(global_index) + int(draw) * DRAW_SEED_STRIDE)
     return g
 
 

@@ -19,7 +19,11 @@ with DPM-Solver++ instead and takes precedence over `--use_ddim`; pair it with
 `--timestep_respacing logsnrN`;
 ranks get an evenly padded work list (the reference hangs in all_gather on an
 uneven one); `--model_path ""` uses seeded synthetic weights (no checkpoint
-ships with the reference).
+ships with the reference); `--num_draws K` (K >= 2) samples every patch K times
+with independent noise and writes the per-voxel mean as `arr_0` and the sample
+std (ddof = 1) of the K stitched volumes as `std` (plus denoised_<name>_std.tif
+for .tif input): the uncertainty maps of README.md:44, which the reference
+script (one draw, seed 10) cannot produce.
 """
 
 import argparse
@@ -31,7 +35,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch as th
 
-from guided_diffusion import dist_util, logger, patches, synth
+from guided_diffusion import _hip, dist_util, logger, patches, synth, uncertainty
 from guided_diffusion.script_util import (
     add_dict_to_argparser,
     args_to_dict,
@@ -50,7 +54,9 @@ def create_argparser():
                     dist_backend="", share_gpu=False,
                     # one captured hipGraph per UNet forward / the library's own launch plan (both bit-identical
                     # to the default launch-by-launch replay of the Python plan)
-                    step_graph=False, native_plan=False)
+                    step_graph=False, native_plan=False,
+                    # posterior draws per patch (not in the reference): K >= 2 adds the per-voxel std map
+                    num_draws=1)
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
@@ -58,7 +64,10 @@ def create_argparser():
 
 
 def main(argv=None):
-    args = create_argparser().parse_args(argv)
+    parser = create_argparser()
+    args = parser.parse_args(argv)
+    if not 1 <= args.num_draws <= _hip.MAX_DRAWS:
+        parser.error("--num_draws must be in 1..%d (got %d)" % (_hip.MAX_DRAWS, args.num_draws))
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
     dev = dist_util.dev()
@@ -89,14 +98,10 @@ def main(argv=None):
     rank = dist_util.rank()
     bs = max(1, args.batch_size)
     n_batches = (len(grid) + bs - 1) // bs
+    sample_loop, extra = _sampler(args, diffusion)
+    if args.num_draws > 1:
+        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches)
     done = {}
-    if args.use_dpm_solver:
-        sample_loop = diffusion.dpm_solver_sample_loop
-        extra = dict(order=args.solver_order, stochastic=args.solver_stochastic)
-    elif args.use_ddim:
-        sample_loop, extra = diffusion.ddim_sample_loop, dict(eta=args.eta)
-    else:
-        sample_loop, extra = diffusion.p_sample_loop, {}
     for b in dist_util.partition(n_batches):
         block = th.zeros(bs, 1, res, res, res, device=dev)                  # padded so collectives stay aligned
         if b is not None:
@@ -130,11 +135,7 @@ def main(argv=None):
 
     out_path = None
     if rank == 0:
-        base = os.path.basename(args.base_samples)
-        for ext in (".tiff", ".tif", ".npz", ".npy"):
-            if base.lower().endswith(ext):
-                base = base[:-len(ext)]
-        out_path = os.path.join(logger.get_dir(), f"denoised_{base}.npz")
+        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
         logger.log(f"saving to {out_path}")
         np.savez(out_path, result)                                           # key 'arr_0', (H,W,Z) like the reference
         if args.base_samples.lower().endswith((".tif", ".tiff")):
@@ -142,6 +143,76 @@ def main(argv=None):
             tiff_path = out_path.replace(".npz", ".tif")
             tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))   # (H,W,Z) -> (Z,H,W), no scaling
             logger.log(f"Saved denoised TIFF: {tiff_path}")
+    dist_util.barrier()
+    logger.log("Full image denoising complete")
+    return out_path
+
+
+def _sampler(args, diffusion):
+    if args.use_dpm_solver:
+        return diffusion.dpm_solver_sample_loop, dict(order=args.solver_order, stochastic=args.solver_stochastic)
+    if args.use_ddim:
+        return diffusion.ddim_sample_loop, dict(eta=args.eta)
+    return diffusion.p_sample_loop, {}
+
+
+def _base_name(path):
+    base = os.path.basename(path)
+    for ext in (".tiff", ".tif", ".npz", ".npy"):
+        if base.lower().endswith(ext):
+            base = base[:-len(ext)]
+    return base
+
+
+def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches):
+    """--num_draws K >= 2: every forward batch is bs patches x K draws, patch-major (N = bs * K); the noise of draw d of
+    patch i comes from volume_generator(i, draw=d), so it depends on neither K, the batch size nor the world size.
+    Gathered rounds are stitched on rank 0's device in ascending patch order (DrawStitcher), then reduced to the
+    per-voxel mean and sample std."""
+    dev = dist_util.dev()
+    rank = dist_util.rank()
+    K, res = args.num_draws, args.large_size
+    stitcher = uncertainty.DrawStitcher(vol.shape, res, K, dev) if rank == 0 else None
+    for b in dist_util.partition(n_batches):
+        block = th.zeros(bs * K, 1, res, res, res, device=dev)               # padded so collectives stay aligned
+        if b is not None:
+            idx = list(range(b * bs, min((b + 1) * bs, len(grid))))
+            cond = th.from_numpy(low_res[idx]).to(dev).repeat_interleave(K, dim=0)
+            shape = tuple(cond.shape)
+            gens = [dist_util.volume_generator(i, seed=10, device=dev, draw=d) for i in idx for d in range(K)]
+
+            def draw(_k=None, _img=None):
+                return th.cat([th.randn(1, *shape[1:], device=dev, generator=g) for g in gens])
+
+            noise = draw()
+            logger.log(f"rank {rank}: patches {idx} x {K} draws shape={shape}")
+            block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
+                                               model_kwargs={"low_res": cond}, step_noise=draw, **extra)
+        for bb, blk in dist_util.gather_round(block, b):
+            if stitcher is None:
+                continue
+            blk = blk.to(dev)
+            for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
+                stitcher.add(i, blk[j * K:(j + 1) * K], grid[i])
+    out_path = None
+    if rank == 0:
+        logger.log(f"Reconstructing {K} draws with Hann window blending...")
+        mean, std, weight = stitcher.finish()
+        result, std_np = mean.cpu().numpy(), std.cpu().numpy()             # (H, W, Z)
+        covered = std[weight > 0]
+        logger.log(f"  Original std: {float(vol.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+        logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
+                   f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
+        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
+        logger.log(f"saving to {out_path}")
+        np.savez(out_path, result, std=std_np)                             # arr_0 = mean, std: both (H,W,Z)
+        if args.base_samples.lower().endswith((".tif", ".tiff")):
+            from guided_diffusion import tiff_io
+            tiff_path = out_path.replace(".npz", ".tif")
+            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))
+            std_path = out_path.replace(".npz", "_std.tif")
+            tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
+            logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path

@@ -539,6 +539,35 @@ int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* 
                            const float* x0_prev2, const float* noise, const float* coef,
                            const float* scoef, const int64_t* t_idx, int N, int voxels, int T,
                            int flags, int order, float* sample, float* pred_xstart, void* stream);
+
+/*
+ * Per-voxel uncertainty maps from K posterior draws of one volume (added within ABI 13; the reference's
+ * README.md:44 reports them, its scripts/test.py writes one draw only).  Draw d of the volume, V_d, is the
+ * Hann-weighted overlap-add of the d-th draw of every patch exactly as scripts/test.py:100-146 blends one draw
+ * (window :248-262); the maps are mean = (1/K) sum_d V_d and the sample std (ddof = 1) over d; a voxel whose weight
+ * sum is 0 gets 0 in both.  Every output element has one writer (no atomics): results are bit-repeatable.
+ *
+ * ddpm3d_draw_stitch adds one patch origin's draws into the K accumulators, scripts/test.py:141-142 as numpy
+ * evaluates them, bit for bit: acc = fl32(fl64(acc) + fl64(x) * w), wsum = fl32(fl64(wsum) + w).
+ *   samples  (K, 1, res, res, res) fp32 as the sampler returns them: NCDHW, x[d][z][h][w]; the kernel does the
+ *            reference's (Z, H, W) -> (H, W, Z) permute
+ *   window   (res, res, res) fp64, [h][w][z]: patches.hann_window_3d(res) (the reference's create_3d_hann_window)
+ *   xs, ys, zs  the patch origin in the volume (H, W, D axes); the patch is cropped at the far edges as the
+ *            reference crops it
+ *   acc      [K][H][W][D] fp32, wsum [H][W][D] fp32, both zeroed by the caller before the first origin
+ * Call it once per origin, in ascending patch order, so that the sums are the reference's.
+ * ddpm3d_draw_moments reads acc[K][voxels] and, when wsum is not NULL, divides each element by wsum[voxels]
+ * (np.divide, scripts/test.py:146: a correctly rounded fp32 division) before it reduces over d in fp64 (Welford);
+ * with wsum NULL it reduces a plain stack of K draws.  mean and std are [voxels] fp32.
+ * Both return DDPM3D_EINVAL before any launch for a NULL pointer (wsum of ddpm3d_draw_moments excepted), K above
+ * DDPM3D_MAX_DRAWS, K below 1 (stitch) or 2 (moments), voxels below 1, res outside 1..1024, an empty volume, or a
+ * patch origin outside the volume.
+ */
+#define DDPM3D_MAX_DRAWS 64
+int ddpm3d_draw_stitch(const float* samples, int K, int res, const double* window, int xs, int ys, int zs,
+                       int H, int W, int D, float* acc, float* wsum, void* stream);
+int ddpm3d_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean, float* std,
+                        void* stream);
 /*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
