@@ -521,6 +521,65 @@ int ddpm3d_draw_moments(const float* acc, const float* wsum, int K, int64_t voxe
                     "draw_moments");
 }
 
+// ------------------------------------------------- joint patch sampling (added within ABI 13)
+static int joint_check(const char* what, int B, int Dc, int H, int W, int res, const ddpm3d_joint_starts* s,
+                       bool covered) {
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "%s: B=%d canvases (1..%d)", what, B, DDPM3D_MAX_DRAWS);
+    if (res < 1 || res > 1024) return fail(DDPM3D_EINVAL, "%s: res=%d (1..1024)", what, res);
+    // the grids put depth on y and the draws (times the patches) on z; one plane, rounded up to whole workgroups
+    // of 256, is indexed in 32 bits
+    if (Dc < 1 || H < 1 || W < 1 || Dc > 65535 || H > 65535 || W > 65535 || (int64_t)H * W > 0x7fffffff - 256)
+        return fail(DDPM3D_EINVAL, "%s: bad canvas (Dc=%d H=%d W=%d; 1..65535 each, H * W <= 2^31 - 257)", what, Dc, H,
+                    W);
+    const struct { const char* name; int n; const int32_t* starts; int extent; } axes[3] = {
+        {"H", s->nx, s->xs, H}, {"W", s->ny, s->ys, W}, {"D", s->nz, s->zs, Dc}};
+    for (const auto& a : axes) {
+        if (a.n < 1 || a.n > DDPM3D_JOINT_MAX_STARTS)
+            return fail(DDPM3D_EINVAL, "%s: %d starts on axis %s (1..%d)", what, a.n, a.name, DDPM3D_JOINT_MAX_STARTS);
+        for (int i = 0; i < a.n; ++i)
+            if (a.starts[i] < 0 || a.starts[i] > a.extent - res)
+                return fail(DDPM3D_EINVAL, "%s: patch at %d on axis %s outside the canvas (starts 0..%d)", what,
+                            a.starts[i], a.name, a.extent - res);
+        if (!covered) continue;
+        // the union of [start, start + res) must hold every coordinate: sweep from 0, always taking the start that
+        // reaches furthest among those at or below the first uncovered coordinate
+        int reach = 0;
+        while (reach < a.extent) {
+            int next = reach;
+            for (int i = 0; i < a.n; ++i)
+                if (a.starts[i] <= reach && a.starts[i] + res > next) next = a.starts[i] + res;
+            if (next == reach)
+                return fail(DDPM3D_EINVAL, "%s: coordinate %d of axis %s is covered by no patch", what, reach, a.name);
+            reach = next;
+        }
+    }
+    return DDPM3D_OK;
+}
+
+int ddpm3d_joint_gather(const float* canvas, int B, int Dc, int H, int W, int res, const ddpm3d_joint_starts* starts,
+                        int first_patch, int n_patches, float* out, void* stream) {
+    if (!canvas || !starts || !out) return fail(DDPM3D_EINVAL, "joint_gather: null pointer");
+    const int rc = joint_check("joint_gather", B, Dc, H, W, res, starts, false);
+    if (rc != DDPM3D_OK) return rc;
+    const int P = starts->nx * starts->ny * starts->nz;
+    if (first_patch < 0 || n_patches < 1 || first_patch > P - n_patches)
+        return fail(DDPM3D_EINVAL, "joint_gather: patches %d..%d of %d", first_patch, first_patch + n_patches - 1, P);
+    return launched(ddpm3d_launch_joint_gather(canvas, B, Dc, H, W, res, *starts, first_patch, n_patches, out,
+                                               (hipStream_t)stream),
+                    "joint_gather");
+}
+
+int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, int res,
+                       const ddpm3d_joint_starts* starts, const double* tables, float* out_canvas, void* stream) {
+    if (!patch_values || !starts || !tables || !out_canvas) return fail(DDPM3D_EINVAL, "joint_blend: null pointer");
+    const int rc = joint_check("joint_blend", B, Dc, H, W, res, starts, true);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_joint_blend(patch_values, B, Dc, H, W, res, *starts, tables, out_canvas,
+                                              (hipStream_t)stream),
+                    "joint_blend");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

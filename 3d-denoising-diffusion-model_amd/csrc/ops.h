@@ -64,3 +64,11 @@ hipError_t ddpm3d_launch_draw_stitch(const float* samples, int K, int res, const
                                      int zs, int H, int W, int D, float* acc, float* wsum, hipStream_t st);
 hipError_t ddpm3d_launch_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean,
                                       float* std, hipStream_t st);
+// joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
+// patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
+struct ddpm3d_joint_starts;
+hipError_t ddpm3d_launch_joint_gather(const float* canvas, int B, int Dc, int H, int W, int res,
+                                      const ddpm3d_joint_starts& s, int first_patch, int n_patches, float* out,
+                                      hipStream_t st);
+hipError_t ddpm3d_launch_joint_blend(const float* patches, int B, int Dc, int H, int W, int res,
+                                     const ddpm3d_joint_starts& s, const double* tables, float* out, hipStream_t st);

@@ -81,6 +81,15 @@ class UnetDesc(C.Structure):
                 ("arithmetic", C.c_int32)]
 
 
+JOINT_MAX_STARTS = 8    # DDPM3D_JOINT_MAX_STARTS
+
+
+class JointStarts(C.Structure):
+    """struct ddpm3d_joint_starts"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("xs", C.c_int32 * JOINT_MAX_STARTS),
+                ("ys", C.c_int32 * JOINT_MAX_STARTS), ("zs", C.c_int32 * JOINT_MAX_STARTS)]
+
+
 LAYER_RES, LAYER_ATTN, LAYER_DOWNCONV, LAYER_UPCONV = 1, 2, 3, 4
 UPDOWN = {None: 0, "down": 1, "up": 2}
 
@@ -134,6 +143,10 @@ EXPORTS = {
     "ddpm3d_draw_stitch": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _fp, _fp, _fp]),
     "ddpm3d_draw_moments": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, _fp, _fp, _fp]),
+    "ddpm3d_joint_gather": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JointStarts),
+                                      C.c_int, C.c_int, _fp, _fp]),
+    "ddpm3d_joint_blend": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JointStarts), _fp,
+                                     _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

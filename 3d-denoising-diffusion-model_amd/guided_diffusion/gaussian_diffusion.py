@@ -256,7 +256,9 @@ class GaussianDiffusion:
         SpacedDiffusion, respace.py:123-128)."""
         return self._scale_timesteps(t)
 
-    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0):
+    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None):
+        """One fused reverse step.  `out`: (sample, pred_xstart) tensors of x's shape to write into (the joint loop's
+        patch buffers); fresh tensors otherwise."""
         lib = H.load()
         N = x.shape[0]
         vox = x[0].numel()
@@ -265,8 +267,11 @@ class GaussianDiffusion:
         H.require_device(x, "x")
         self._check_noise(noise, x)
         st = self._device_state(x.device)
-        sample = th.empty_like(x)
-        x0 = th.empty_like(x)
+        sample, x0 = out if out is not None else (th.empty_like(x), th.empty_like(x))
+        for name, o in (("out[0] (sample)", sample), ("out[1] (pred_xstart)", x0)):
+            H.require_device(o, name)
+            assert o.shape == x.shape and o.device == x.device, "%s: %s on %s for x %s on %s" % (
+                name, tuple(o.shape), o.device, tuple(x.shape), x.device)
         t = t.to(device=x.device, dtype=th.int64).contiguous()
         if kind == "ddpm":
             H.check(lib.ddpm3d_p_sample_step(H.ptr(model_output), H.ptr(x), H.ptr(noise), H.ptr(st["coef"]),
@@ -318,16 +323,18 @@ class GaussianDiffusion:
         """A loop's per-step network call, set up under no_grad on `device`: (t table [T][N] int64,
         call (x, i) -> model output at step index i).  With model_kwargs == {"low_res"} on a 5-D shape it
         takes the engine path: the x-independent timestep path (film rows) for the whole schedule once, then
-        one plan replay per step."""
+        one plan replay per step.  call(x, i, low_res) runs on another conditioning tensor of the same shape
+        (the joint loop: one table for all batches of a size)."""
         T = self.num_timesteps
         t_all = th.arange(T, device=device, dtype=th.int64)[:, None].repeat(1, shape[0]).contiguous()
         if not (hasattr(model, "engine") and set(model_kwargs) == {"low_res"} and len(shape) == 5):
-            return t_all, lambda img, i: self._call_model(model, img, t_all[i], model_kwargs)
+            return t_all, lambda img, i, lr=None: self._call_model(
+                model, img, t_all[i], model_kwargs if lr is None else dict(model_kwargs, low_res=lr))
         eng = model.engine()
         low_res = model_kwargs["low_res"].to(device).contiguous()
         t_model = self._model_timesteps(th.arange(T, device=device, dtype=th.int64))
         film = eng.film_rows(t_model.to(th.float32).contiguous())
-        return t_all, lambda img, i: eng.forward(img, low_res, film[i], 0)
+        return t_all, lambda img, i, lr=low_res: eng.forward(img, lr, film[i], 0)
 
     @staticmethod
     def _reject_hooks(denoised_fn, cond_fn):

@@ -1,0 +1,193 @@
+"""
+Joint patch sampling: one reverse-diffusion state for the whole volume.
+
+The reference samples every 96^3 patch on its own and Hann-blends the finished
+patches once (scripts/test.py:100-146).  Where patches overlap, that blend
+averages independent posterior draws, which shrinks their spread by
+sqrt(sum w_p^2) / sum w_p (down to 1/sqrt(8) where eight patches meet), so a
+per-voxel std map carries the imprint of the tiling.  Here the patches are
+sampled jointly instead: x_t and every step's noise are whole-volume canvases
+(patches.joint_geometry), each step cuts them into the overlapping patches
+(ddpm3d_joint_gather), runs the network and the existing fused step kernel on
+the patches, and blends the updated patches back with weights that sum to 1 at
+every voxel (ddpm3d_joint_blend).  Every patch sees the same x_t and the same
+noise in an overlap, and the noise is never averaged.  The forwards per volume
+are unchanged (patches x steps); DESIGN.md 3.7.
+
+Both kernels are HIP (csrc/joint.hip); there is no host fallback.
+"""
+
+import weakref
+
+import numpy as np
+import torch as th
+
+from . import _hip as H
+from . import dist_util
+
+
+_DEVICE_GEOMETRY = weakref.WeakKeyDictionary()       # JointGeometry -> {device: (starts, tables)}
+
+
+def _device_geometry(geom, device):
+    """(ddpm3d_joint_starts, the three tables back to back on `device`), built once per geometry and device."""
+    cache = _DEVICE_GEOMETRY.setdefault(geom, {})
+    key = str(device)
+    if key not in cache:
+        s = H.JointStarts()
+        for n, arr, starts in (("nx", s.xs, geom.x_starts), ("ny", s.ys, geom.y_starts), ("nz", s.zs, geom.z_starts)):
+            if len(starts) > H.JOINT_MAX_STARTS:
+                raise ValueError("at most %d patches per axis, got %d" % (H.JOINT_MAX_STARTS, len(starts)))
+            setattr(s, n, len(starts))
+            for i, v in enumerate(starts):
+                arr[i] = int(v)
+        tables = np.concatenate([np.ascontiguousarray(t, dtype=np.float64).ravel()
+                                 for t in (geom.a_x, geom.a_y, geom.a_z)])
+        cache[key] = (s, th.from_numpy(tables).to(device))
+    return cache[key]
+
+
+def gather(canvas, geom, first_patch=0, n_patches=None, out=None):
+    """(B, Dc, H, W) float32 canvases on the device -> (n_patches * B, 1, res, res, res) patches first_patch ..
+    first_patch + n_patches - 1 of the geometry, patch-major, draw-minor.  A copy: bit-exact."""
+    H.require_device(canvas, "canvas")
+    if canvas.dim() != 4 or tuple(canvas.shape[1:]) != tuple(geom.canvas):
+        raise ValueError("canvas of shape %s, expected (B, %d, %d, %d)"
+                         % ((tuple(canvas.shape),) + tuple(geom.canvas)))
+    B, r = int(canvas.shape[0]), geom.res
+    n = geom.n_patches - first_patch if n_patches is None else int(n_patches)
+    if out is None:
+        out = th.empty((max(n, 0) * B, 1, r, r, r), dtype=th.float32, device=canvas.device)
+    else:
+        H.require_device(out, "out")
+        if out.numel() != n * B * r ** 3:
+            raise ValueError("out holds %d elements, %d patches x %d draws need %d"
+                             % (out.numel(), n, B, n * B * r ** 3))
+    starts, _ = _device_geometry(geom, canvas.device)
+    Dc, Hh, W = geom.canvas
+    with th.cuda.device(canvas.device):
+        H.check(H.load().ddpm3d_joint_gather(H.ptr(canvas), B, Dc, Hh, W, r, starts, int(first_patch), n, H.ptr(out),
+                                             H.stream()))
+    return out
+
+
+def blend(patch_values, geom, num_draws=1, out=None):
+    """(P * B, 1, res, res, res) float32 patches (patch-major, draw-minor) -> (B, Dc, H, W) canvases with
+    patches.joint_blend's arithmetic, bit for bit."""
+    H.require_device(patch_values, "patch_values")
+    B, r = int(num_draws), geom.res
+    if patch_values.numel() != geom.n_patches * B * r ** 3:
+        raise ValueError("patches of shape %s, expected (%d, 1, %d, %d, %d)"
+                         % (tuple(patch_values.shape), geom.n_patches * B, r, r, r))
+    if out is None:
+        out = th.empty((B,) + tuple(geom.canvas), dtype=th.float32, device=patch_values.device)
+    else:
+        H.require_device(out, "out")
+        if tuple(out.shape) != (B,) + tuple(geom.canvas):
+            raise ValueError("out of shape %s, expected %s" % (tuple(out.shape), (B,) + tuple(geom.canvas)))
+    starts, tables = _device_geometry(geom, patch_values.device)
+    Dc, Hh, W = geom.canvas
+    with th.cuda.device(patch_values.device):
+        H.check(H.load().ddpm3d_joint_blend(H.ptr(patch_values), B, Dc, Hh, W, r, starts, H.ptr(tables), H.ptr(out),
+                                            H.stream()))
+    return out
+
+
+def _canvas_of(volume, geom, device):
+    """A (D, H, W) volume (numpy or tensor, D <= Dc) as one zero-extended (1, Dc, H, W) float32 canvas on `device`."""
+    vol = th.as_tensor(volume, dtype=th.float32)
+    Dc, Hh, W = geom.canvas
+    if vol.dim() != 3 or tuple(vol.shape[1:]) != (Hh, W) or vol.shape[0] > Dc:
+        raise ValueError("low_res volume of shape %s does not fit the canvas %s"
+                         % (tuple(vol.shape), tuple(geom.canvas)))
+    canvas = th.zeros((1, Dc, Hh, W), dtype=th.float32, device=device)
+    canvas[0, :vol.shape[0]] = vol.to(device)
+    return canvas
+
+
+def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm", num_draws=1, batch_size=1,
+                            noise=None, step_noise=None, clip_denoised=True, eta=0.0, device=None):
+    """Joint DDPM ("ddpm") or DDIM ("ddim", any eta) sampling of one volume; yields, per reverse step,
+    {"sample", "pred_xstart"}: (K, Dc, H, W) canvases on the device, K = num_draws.
+
+    low_res_volume  the (D, H, W) conditioning volume (zero-extended to the canvas here)
+    geom            patches.joint_geometry(volume.shape, res)
+    batch_size      patches per network call; a call's batch is batch_size patches x K draws, patch-major
+    noise           the (K, Dc, H, W) start canvas x_T; step_noise: the per-step noise canvases, a sequence in draw
+                    order or a callable (k, like) as in the independent loops.  Without them, draw d takes all its
+                    noise from dist_util.volume_generator(0, draw=d), one whole canvas at a time, so the result
+                    depends on neither the batch size nor the world size.
+    With several ranks, batch b runs on rank b mod W; the ranks exchange their updated patches once per round and
+    every rank blends all of them: all ranks hold the same canvas after every step, bit for bit."""
+    if kind not in ("ddpm", "ddim"):
+        raise ValueError("joint sampling implements the DDPM and DDIM steps, not %r (DPM-Solver++ keeps its history "
+                         "per patch and is not part of the joint loop)" % (kind,))
+    K, bs = int(num_draws), max(1, int(batch_size))
+    if not 1 <= K <= H.MAX_DRAWS:
+        raise ValueError("num_draws must be in 1..%d, got %d" % (H.MAX_DRAWS, K))
+    if device is None:
+        params = getattr(model, "parameters", None)
+        device = next(params()).device if params is not None else dist_util.dev()
+    device = th.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("sampling runs on HIP kernels only; got device %s" % device)
+    P, r = geom.n_patches, geom.res
+    cshape = (K,) + tuple(geom.canvas)
+    rounds = dist_util.partition((P + bs - 1) // bs)
+    world = dist_util.world_size()
+
+    def rows(b):                                  # batch b's rows of the (P * K) patch buffers
+        return b * bs * K, min((b + 1) * bs, P) * K
+
+    with th.no_grad(), th.cuda.device(device):
+        gens = [dist_util.volume_generator(0, seed=10, device=device, draw=d) for d in range(K)]
+
+        def draw():
+            return th.stack([th.randn(cshape[1:], device=device, generator=g) for g in gens])
+
+        img = noise if noise is not None else draw()
+        H.require_device(img, "noise")
+        if tuple(img.shape) != cshape:
+            raise ValueError("noise of shape %s, expected %s" % (tuple(img.shape), cshape))
+        low_res = gather(_canvas_of(low_res_volume, geom, device), geom).repeat_interleave(K, dim=0)
+        nets = {}                                 # one step table per batch size (there are at most two)
+        for b in rounds:
+            if b is not None:
+                lo, hi = rows(b)
+                if hi - lo not in nets:
+                    nets[hi - lo] = diffusion._step_model(model, (hi - lo, 1, r, r, r),
+                                                          {"low_res": low_res[lo:hi]}, device)
+        updated = th.empty((2, P * K, 1, r, r, r), dtype=th.float32, device=device)   # sample, pred_xstart
+        xg = th.empty((bs * K, 1, r, r, r), dtype=th.float32, device=device)
+        zg = th.empty_like(xg)
+        block = th.zeros((2, bs * K, 1, r, r, r), dtype=th.float32, device=device) if world > 1 else None
+
+    for k, i in enumerate(range(diffusion.num_timesteps - 1, -1, -1)):
+        with th.no_grad(), th.cuda.device(device):
+            z = draw() if step_noise is None else diffusion._draw_noise(step_noise, k, img)
+            diffusion._check_noise(z, img)
+            for b in rounds:
+                if b is not None:
+                    lo, hi = rows(b)
+                    t_all, net = nets[hi - lo]
+                    x, zb = xg[:hi - lo], zg[:hi - lo]
+                    gather(img, geom, lo // K, (hi - lo) // K, out=x)
+                    gather(z, geom, lo // K, (hi - lo) // K, out=zb)
+                    dst = updated[:, lo:hi] if world == 1 else block[:, :hi - lo]
+                    diffusion._update(kind, net(x, i, low_res[lo:hi]), x, t_all[i], zb, clip_denoised, eta,
+                                      out=(dst[0], dst[1]))
+                if world > 1:
+                    for bb, blk in dist_util.gather_round(block, b):
+                        lo, hi = rows(bb)
+                        updated[:, lo:hi].copy_(blk[:, :hi - lo])
+            out = {"sample": blend(updated[0], geom, K), "pred_xstart": blend(updated[1], geom, K)}
+        yield out
+        img = out["sample"]
+
+
+def sample_loop(diffusion, model, low_res_volume, geom, **kwargs):
+    """The final canvases, (K, Dc, H, W), of sample_loop_progressive."""
+    final = None
+    for final in sample_loop_progressive(diffusion, model, low_res_volume, geom, **kwargs):
+        pass
+    return final["sample"]

@@ -116,3 +116,94 @@ def load_volume(path):
     if vol.ndim != 3:
         raise ValueError("expected a (D,H,W) volume in %s, got %s" % (path, vol.shape))
     return vol.astype(np.float32)
+
+
+# ---------------------------------------------------------------- joint patch sampling
+class JointGeometry:
+    """Canvas, patch starts and per-axis blend tables of one volume (joint_geometry)."""
+
+    def __init__(self, canvas, res, x_starts, y_starts, z_starts, a_x, a_y, a_z):
+        self.canvas, self.res = canvas, res
+        self.x_starts, self.y_starts, self.z_starts = x_starts, y_starts, z_starts
+        self.a_x, self.a_y, self.a_z = a_x, a_y, a_z
+
+    @property
+    def n_patches(self):
+        return len(self.x_starts) * len(self.y_starts) * len(self.z_starts)
+
+    @property
+    def grid(self):
+        """[(x_start, y_start, z_start)] in patch_grid's order: p = (ix * ny + iy) * nz + iz."""
+        return [(xs, ys, zs) for xs in self.x_starts for ys in self.y_starts for zs in self.z_starts]
+
+
+def _axis_table(starts, extent, res, axis):
+    """a[i][c]: patch i's share of coordinate c on one axis.  The Hann window over the Hann sum where that sum is
+    positive; an equal share among the covering patches where it is 0 (np.hanning is 0 at both ends, so the
+    outermost coordinate of an axis has no Hann weight at all)."""
+    h = np.hanning(res)
+    hann = np.zeros((len(starts), extent), dtype=np.float64)
+    cover = np.zeros((len(starts), extent), dtype=bool)
+    for i, s in enumerate(starts):
+        if s < 0 or s >= extent:
+            raise ValueError("axis %s: patch start %d outside 0..%d" % (axis, s, extent - 1))
+        n = min(res, extent - s)
+        hann[i, s:s + n] = h[:n]
+        cover[i, s:s + n] = True
+    count = cover.sum(axis=0)
+    if (count == 0).any():
+        raise ValueError("axis %s: coordinate %d of %d is covered by no patch (starts %s, patch size %d)"
+                         % (axis, int(np.argmin(count > 0)), extent, list(starts), res))
+    total = hann.sum(axis=0)
+    live = total > 0
+    table = np.where(live, hann / np.where(live, total, 1.0), cover / count)
+    return table
+
+
+def joint_geometry(shape_dhw, res, num_xy=3):
+    """Geometry of joint patch sampling for a (D, H, W) volume: the canvas (max(D, res), H, W), patch_grid's
+    per-axis starts and the normalised blend weight as three fp64 tables,
+    nw_p(z, x, y) = a_x[ix][x] * a_y[iy][y] * a_z[iz][z], which sum to 1 over the patches at every canvas voxel."""
+    D, H, W = (int(v) for v in shape_dhw)
+    res = int(res)
+    if res < 1 or D < 1:
+        raise ValueError("joint_geometry: bad shape (D=%d, patch size %d)" % (D, res))
+    for axis, n in (("H", H), ("W", W)):
+        if n < res:
+            raise ValueError("axis %s: %d voxels is less than one patch of %d" % (axis, n, res))
+    Dc = max(D, res)
+    xs, ys, zs = xy_starts(H, res, num_xy), xy_starts(W, res, num_xy), z_starts(D, res)
+    return JointGeometry((Dc, H, W), res, xs, ys, zs, _axis_table(xs, H, res, "H"), _axis_table(ys, W, res, "W"),
+                         _axis_table(zs, Dc, res, "D"))
+
+
+def joint_gather(canvas, geom):
+    """(Dc, H, W) canvas -> (P, 1, res, res, res) patches in patch_grid's order (what ddpm3d_joint_gather copies)."""
+    canvas = np.asarray(canvas)
+    if canvas.shape != tuple(geom.canvas):
+        raise ValueError("canvas of shape %s, geometry expects %s" % (canvas.shape, tuple(geom.canvas)))
+    r = geom.res
+    out = np.zeros((geom.n_patches, 1, r, r, r), dtype=canvas.dtype)
+    for p, (xs, ys, zs) in enumerate(geom.grid):
+        out[p, 0] = canvas[zs:zs + r, xs:xs + r, ys:ys + r]
+    return out
+
+
+def joint_blend(patch_values, geom):
+    """(P, 1, res, res, res) float32 patches -> (Dc, H, W) float32 canvas: the normalised Hann blend of joint
+    sampling.  This is the arithmetic ddpm3d_joint_blend reproduces bit for bit: per voxel, over the covering
+    patches in ascending p, acc += float64(x_p) * ((a_x * a_y) * a_z) with the product and the sum rounded
+    separately, then one rounding to float32."""
+    patch_values = np.asarray(patch_values)
+    r = geom.res
+    if patch_values.shape != (geom.n_patches, 1, r, r, r):
+        raise ValueError("patches of shape %s, geometry expects %s"
+                         % (patch_values.shape, (geom.n_patches, 1, r, r, r)))
+    acc = np.zeros(geom.canvas, dtype=np.float64)
+    ny, nz = len(geom.y_starts), len(geom.z_starts)
+    for p, (xs, ys, zs) in enumerate(geom.grid):
+        ix, iy, iz = p // (ny * nz), (p // nz) % ny, p % nz
+        w = (geom.a_x[ix][None, xs:xs + r, None] * geom.a_y[iy][None, None, ys:ys + r]) \
+            * geom.a_z[iz][zs:zs + r, None, None]
+        acc[zs:zs + r, xs:xs + r, ys:ys + r] += patch_values[p, 0].astype(np.float64) * w
+    return acc.astype(np.float32)

@@ -23,7 +23,13 @@ ships with the reference); `--num_draws K` (K >= 2) samples every patch K times
 with independent noise and writes the per-voxel mean as `arr_0` and the sample
 std (ddof = 1) of the K stitched volumes as `std` (plus denoised_<name>_std.tif
 for .tif input): the uncertainty maps of README.md:44, which the reference
-script (one draw, seed 10) cannot produce.
+script (one draw, seed 10) cannot produce; `--joint_patches True` samples the
+patches jointly (guided_diffusion/joint.py): one state and one noise draw per
+voxel of the whole volume, blended after every reverse step, so that overlaps
+are not an average of independent draws (which lowers `std` there in the
+pattern of the patch grid).  DDPM and DDIM only.  Unlike the one-shot blend,
+whose Hann weights are 0 on the outermost planes of the volume (those voxels
+are written as 0), the joint path writes real values there.
 """
 
 import argparse
@@ -35,7 +41,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch as th
 
-from guided_diffusion import _hip, dist_util, logger, patches, synth, uncertainty
+from guided_diffusion import _hip, dist_util, joint, logger, patches, synth, uncertainty
 from guided_diffusion.script_util import (
     add_dict_to_argparser,
     args_to_dict,
@@ -56,7 +62,9 @@ def create_argparser():
                     # to the default launch-by-launch replay of the Python plan)
                     step_graph=False, native_plan=False,
                     # posterior draws per patch (not in the reference): K >= 2 adds the per-voxel std map
-                    num_draws=1)
+                    num_draws=1,
+                    # one state for the whole volume, blended after every step (not in the reference)
+                    joint_patches=False)
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
@@ -68,6 +76,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if not 1 <= args.num_draws <= _hip.MAX_DRAWS:
         parser.error("--num_draws must be in 1..%d (got %d)" % (_hip.MAX_DRAWS, args.num_draws))
+    if args.joint_patches and args.use_dpm_solver:
+        parser.error("--joint_patches True samples with DDPM or DDIM; it cannot be combined with "
+                     "--use_dpm_solver True")
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
     dev = dist_util.dev()
@@ -90,6 +101,8 @@ def main(argv=None):
     logger.log("loading data...")
     vol = patches.load_volume(args.base_samples)                 # (D, H, W)
     res = args.large_size
+    if args.joint_patches:
+        return _main_joint(args, model, diffusion, vol)
     low_res, grid = patches.split_volume(vol, res)               # (P, 1, Z, H, W)
     logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3")
 
@@ -213,6 +226,45 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             std_path = out_path.replace(".npz", "_std.tif")
             tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
+    dist_util.barrier()
+    logger.log("Full image denoising complete")
+    return out_path
+
+
+def _main_joint(args, model, diffusion, vol):
+    """--joint_patches True: every rank holds the whole canvas and runs its share of each step's forwards
+    (joint.sample_loop_progressive); rank 0 writes the canvas cropped to the volume, (H, W, Z) like the other paths.
+    With --num_draws K >= 2 the K canvases are reduced to the per-voxel mean and sample std."""
+    rank = dist_util.rank()
+    K, res = args.num_draws, args.large_size
+    geom = patches.joint_geometry(vol.shape, res)
+    logger.log(f"volume {vol.shape}: {geom.n_patches} patches of {res}^3, sampled jointly on a {geom.canvas} canvas")
+    sample = joint.sample_loop(diffusion, model, vol, geom, kind="ddim" if args.use_ddim else "ddpm", num_draws=K,
+                               batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
+                               device=dist_util.dev())
+    draws = sample[:, :vol.shape[0]].contiguous()                             # (K, D, H, W)
+    extra = {}
+    if K > 1:
+        mean, std = uncertainty.draw_moments(draws)
+        extra["std"] = std.permute(1, 2, 0).cpu().numpy()
+        logger.log(f"  Mean per-voxel std over {K} draws: {float(std.double().mean()):.6f}")
+    else:
+        mean = draws[0]
+    result = mean.permute(1, 2, 0).cpu().numpy()                              # (D, H, W) -> (H, W, Z)
+    logger.log(f"  Original std: {float(vol.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+    out_path = None
+    if rank == 0:
+        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
+        logger.log(f"saving to {out_path}")
+        np.savez(out_path, result, **extra)                                   # arr_0 [+ std], (H,W,Z)
+        if args.base_samples.lower().endswith((".tif", ".tiff")):
+            from guided_diffusion import tiff_io
+            tiff_path = out_path.replace(".npz", ".tif")
+            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))
+            if K > 1:
+                tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
+                                extra["std"].transpose(2, 0, 1).astype(np.float32))
+            logger.log(f"Saved denoised TIFF: {tiff_path}")
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path

@@ -569,6 +569,39 @@ int ddpm3d_draw_stitch(const float* samples, int K, int res, const double* windo
 int ddpm3d_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean, float* std,
                         void* stream);
 /*
+ * Joint patch sampling (added within ABI 13): one state per volume, cut into the overlapping patches before every
+ * network call and blended back after every reverse step, so that patches share x_t and the step's noise where they
+ * overlap (the one-shot blend of scripts/test.py:100-146 averages independent draws there and shrinks their spread).
+ * The canvas is the volume zero-extended to one patch along depth: canvas[b][z][x][y], B draws of (Dc, H, W) fp32,
+ * W innermost (the patches' own (Z, H, W) order).  Patch p = (ix * ny + iy) * nz + iz (the nesting of
+ * scripts/test.py:235-241) covers canvas[zs[iz] .. + res)[xs[ix] .. + res)[ys[iy] .. + res); patch tensors are
+ * (rows, 1, res, res, res) fp32 NCDHW with row = p * B + b.
+ *
+ * ddpm3d_joint_gather copies rows [first_patch * B, (first_patch + n_patches) * B) out of the canvases, bit for bit,
+ * into out[n_patches * B][res^3].  Every patch lies inside the canvas: 0 <= start <= extent - res on each axis.
+ * ddpm3d_joint_blend writes every canvas voxel from all nx * ny * nz patches:
+ *   out = fl32( sum over the covering patches in ascending p of fl64(x_p) * ((a_x[ix][x] * a_y[iy][y]) * a_z[iz][z]) )
+ * in fp64 with the product and the sum rounded separately (no FMA).  tables holds the three per-axis fp64 weight
+ * tables back to back on the device: a_x [nx][H], a_y [ny][W], a_z [nz][Dc]; the caller normalises them so that the
+ * weights of the covering patches sum to 1 at every voxel.  Each output element has one writer (no atomics).
+ * Both return DDPM3D_EINVAL before any launch for a NULL pointer, res outside 1..1024, an empty or oversized canvas
+ * (an axis above 65535, H * W above 2^31 - 257), an axis with no start or more than DDPM3D_JOINT_MAX_STARTS, a patch
+ * that leaves the canvas (start < 0 or start + res > extent), B outside 1..DDPM3D_MAX_DRAWS, a patch range outside
+ * 0..nx*ny*nz (gather) and an axis with a coordinate that no patch covers (blend).
+ */
+#define DDPM3D_JOINT_MAX_STARTS 8
+typedef struct ddpm3d_joint_starts {
+    int32_t nx, ny, nz;                       /* patches per axis (H, W, D)  */
+    int32_t xs[DDPM3D_JOINT_MAX_STARTS];      /* starts along H              */
+    int32_t ys[DDPM3D_JOINT_MAX_STARTS];      /* starts along W              */
+    int32_t zs[DDPM3D_JOINT_MAX_STARTS];      /* starts along D              */
+} ddpm3d_joint_starts;
+int ddpm3d_joint_gather(const float* canvas, int B, int Dc, int H, int W, int res,
+                        const ddpm3d_joint_starts* starts, int first_patch, int n_patches, float* out,
+                        void* stream);
+int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, int res,
+                       const ddpm3d_joint_starts* starts, const double* tables, float* out_canvas, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
