@@ -580,6 +580,61 @@ int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, i
                     "joint_blend");
 }
 
+// ------------------------------------------------- image-quality metrics (added within ABI 13)
+static const int64_t EM_MAX_VOXELS = (int64_t)1 << 40;
+static bool ssim_shape_ok(int D, int H, int W) {
+    return D >= 11 && H >= 11 && W >= 11 && D <= 65535 && H <= 65535 && W <= 65535 &&
+           (int64_t)H * W <= 0x7fffffff && (int64_t)D * H * W <= EM_MAX_VOXELS;
+}
+static int metric_ws_ok(const char* what, size_t need, const void* ws, size_t ws_bytes) {
+    if (!ws || ws_bytes < need || !aligned16(ws))
+        return fail(DDPM3D_EINVAL, "%s: needs %zu bytes of 16-byte aligned workspace (got %zu)", what, need,
+                    ws ? ws_bytes : (size_t)0);
+    return DDPM3D_OK;
+}
+
+size_t ddpm3d_error_moments_workspace_bytes(int B, int64_t voxels) {
+    if (B < 1 || B > DDPM3D_MAX_DRAWS || voxels <= 0 || voxels > EM_MAX_VOXELS) return 0;
+    return ddpm3d_em_workspace_bytes(B, voxels);
+}
+
+int ddpm3d_error_moments(const float* est, const float* target, const uint8_t* mask, const float* std, int B,
+                         int64_t voxels, void* ws, size_t ws_bytes, double* out, void* stream) {
+    if (!est || !target || !out) return fail(DDPM3D_EINVAL, "error_moments: null pointer");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "error_moments: B=%d estimates (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (voxels <= 0 || voxels > EM_MAX_VOXELS)
+        return fail(DDPM3D_EINVAL, "error_moments: voxels=%lld (1..2^40)", (long long)voxels);
+    const int rc = metric_ws_ok("error_moments", ddpm3d_em_workspace_bytes(B, voxels), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_error_moments(est, target, mask, std, B, voxels, (double*)ws, out,
+                                                (hipStream_t)stream),
+                    "error_moments");
+}
+
+size_t ddpm3d_ssim3d_workspace_bytes(int B, int D, int H, int W) {
+    if (B < 1 || B > DDPM3D_MAX_DRAWS || !ssim_shape_ok(D, H, W)) return 0;
+    return ddpm3d_ss_workspace_bytes(B, D, H, W);
+}
+
+int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, double C1,
+                  double C2, void* ws, size_t ws_bytes, float* map, double* out, void* stream) {
+    if (!est || !target || !out) return fail(DDPM3D_EINVAL, "ssim3d: null pointer");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "ssim3d: B=%d estimates (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (!ssim_shape_ok(D, H, W))
+        return fail(DDPM3D_EINVAL, "ssim3d: bad volume (D=%d H=%d W=%d; 11..65535 each, H * W <= 2^31 - 1, "
+                                   "D * H * W <= 2^40)", D, H, W);
+    // !(c >= 0) also catches NaN; the kernel evaluates S in fp32, so the constants must be finite there
+    if (!(C1 >= 0.0) || !(C2 >= 0.0) || C1 > 3.0e38 || C2 > 3.0e38)
+        return fail(DDPM3D_EINVAL, "ssim3d: C1=%g C2=%g must be finite and not negative", C1, C2);
+    const int rc = metric_ws_ok("ssim3d", ddpm3d_ss_workspace_bytes(B, D, H, W), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_ssim3d(est, target, mask, B, D, H, W, (float)C1, (float)C2, (double*)ws, map, out,
+                                         (hipStream_t)stream),
+                    "ssim3d");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

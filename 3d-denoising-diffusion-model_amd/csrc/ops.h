@@ -64,6 +64,14 @@ hipError_t ddpm3d_launch_draw_stitch(const float* samples, int K, int res, const
                                      int zs, int H, int W, int D, float* acc, float* wsum, hipStream_t st);
 hipError_t ddpm3d_launch_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean,
                                       float* std, hipStream_t st);
+// metrics.hip: error moments and 3-D SSIM of B estimates against one target (the caller has checked shapes and the
+// workspace; the *_workspace_bytes take valid shapes only)
+size_t ddpm3d_em_workspace_bytes(int B, int64_t voxels);
+hipError_t ddpm3d_launch_error_moments(const float* est, const float* target, const uint8_t* mask, const float* std,
+                                       int B, int64_t voxels, double* ws, double* out, hipStream_t st);
+size_t ddpm3d_ss_workspace_bytes(int B, int D, int H, int W);
+hipError_t ddpm3d_launch_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W,
+                                float C1, float C2, double* ws, float* map, double* out, hipStream_t st);
 // joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
 // patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
 struct ddpm3d_joint_starts;

@@ -81,6 +81,10 @@ class UnetDesc(C.Structure):
                 ("arithmetic", C.c_int32)]
 
 
+# DDPM3D_EM_*: columns of a ddpm3d_error_moments record
+(EM_N, EM_SUM_E, EM_SUM_ABS_E, EM_SUM_SQ_E, EM_SUM_Y, EM_SUM_SQ_Y, EM_MIN_Y, EM_MAX_Y, EM_COVER_1, EM_COVER_2,
+ EM_REC) = range(11)
+
 JOINT_MAX_STARTS = 8    # DDPM3D_JOINT_MAX_STARTS
 
 
@@ -147,6 +151,11 @@ EXPORTS = {
                                       C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_joint_blend": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JointStarts), _fp,
                                      _fp, _fp]),
+    "ddpm3d_error_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "ddpm3d_error_moments": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int64, _fp, C.c_size_t, _fp, _fp]),
+    "ddpm3d_ssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ddpm3d_ssim3d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _fp,
+                                C.c_size_t, _fp, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

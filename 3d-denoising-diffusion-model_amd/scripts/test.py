@@ -29,10 +29,18 @@ voxel of the whole volume, blended after every reverse step, so that overlaps
 are not an average of independent draws (which lowers `std` there in the
 pattern of the patch grid).  DDPM and DDIM only.  Unlike the one-shot blend,
 whose Hann weights are 0 on the outermost planes of the volume (those voxels
-are written as 0), the joint path writes real values there.
+are written as 0), the joint path writes real values there;
+`--target_samples full_dose.npz` (a volume of the input's shape) scores the
+written volume and the low-dose input itself against that target on the GPU
+(guided_diffusion/metrics.py: PSNR, NRMSE, MAE, bias, 3-D SSIM and, with
+`--num_draws`, the coverage of the std map) and writes metrics_<name>.json
+beside the .npz, which keeps its keys and contents; `--data_range` fixes L
+(default: the target's range), `--metrics_mask_threshold F` counts only
+voxels with target > F * max(target).
 """
 
 import argparse
+import json
 import os
 import sys
 
@@ -41,7 +49,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch as th
 
-from guided_diffusion import _hip, dist_util, joint, logger, patches, synth, uncertainty
+from guided_diffusion import _hip, dist_util, joint, logger, metrics, patches, synth, uncertainty
 from guided_diffusion.script_util import (
     add_dict_to_argparser,
     args_to_dict,
@@ -64,7 +72,9 @@ def create_argparser():
                     # posterior draws per patch (not in the reference): K >= 2 adds the per-voxel std map
                     num_draws=1,
                     # one state for the whole volume, blended after every step (not in the reference)
-                    joint_patches=False)
+                    joint_patches=False,
+                    # full-dose volume to score the result against (not in the reference); "" = no metrics
+                    target_samples="", data_range=0.0, metrics_mask_threshold=0.0)
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
@@ -79,6 +89,7 @@ def main(argv=None):
     if args.joint_patches and args.use_dpm_solver:
         parser.error("--joint_patches True samples with DDPM or DDIM; it cannot be combined with "
                      "--use_dpm_solver True")
+    vol, target = _load_target(parser, args)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
     dev = dist_util.dev()
@@ -99,10 +110,11 @@ def main(argv=None):
     model.eval()
 
     logger.log("loading data...")
-    vol = patches.load_volume(args.base_samples)                 # (D, H, W)
+    if vol is None:
+        vol = patches.load_volume(args.base_samples)             # (D, H, W)
     res = args.large_size
     if args.joint_patches:
-        return _main_joint(args, model, diffusion, vol)
+        return _main_joint(args, model, diffusion, vol, target)
     low_res, grid = patches.split_volume(vol, res)               # (P, 1, Z, H, W)
     logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3")
 
@@ -113,7 +125,7 @@ def main(argv=None):
     n_batches = (len(grid) + bs - 1) // bs
     sample_loop, extra = _sampler(args, diffusion)
     if args.num_draws > 1:
-        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches)
+        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target)
     done = {}
     for b in dist_util.partition(n_batches):
         block = th.zeros(bs, 1, res, res, res, device=dev)                  # padded so collectives stay aligned
@@ -156,9 +168,75 @@ def main(argv=None):
             tiff_path = out_path.replace(".npz", ".tif")
             tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))   # (H,W,Z) -> (Z,H,W), no scaling
             logger.log(f"Saved denoised TIFF: {tiff_path}")
+        _write_metrics(args, out_path, target, vol, result, weight=weight)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
+
+
+def _load_target(parser, args):
+    """--target_samples: (base volume, target), both (D, H, W), read and checked before the model is built or any
+    device call is made; (None, None) without the flag."""
+    if not args.target_samples:
+        return None, None
+    if args.metrics_mask_threshold < 0 or args.metrics_mask_threshold >= 1 or args.data_range < 0:
+        parser.error("--metrics_mask_threshold must be in [0, 1) and --data_range must not be negative")
+    for flag, path in (("--target_samples", args.target_samples), ("--base_samples", args.base_samples)):
+        if not os.path.isfile(path):
+            parser.error("%s: no such file: %r" % (flag, path))
+    vol = patches.load_volume(args.base_samples)
+    target = patches.load_volume(args.target_samples)
+    if target.shape != vol.shape:
+        parser.error("--target_samples: the target has shape %s, the base volume %s"
+                     % (tuple(target.shape), tuple(vol.shape)))
+    if min(vol.shape) < 2 * metrics.SSIM_RADIUS + 1:
+        parser.error("--target_samples: the 3-D SSIM needs every extent to be at least %d (volume %s)"
+                     % (2 * metrics.SSIM_RADIUS + 1, tuple(vol.shape)))
+    return vol, target
+
+
+def _write_metrics(args, out_path, target, vol, result, std=None, weight=None):
+    """Rank 0, after the .npz is written: scores the written volume `result` (and `std`, with --num_draws) and the
+    low-dose input `vol` against `target` on the device and writes metrics_<name>.json beside the .npz.  target and
+    vol are (D, H, W) host arrays; result, std and weight (the one-shot blend's Hann weight sum, whose zeros are not
+    counted) are (H, W, Z) host arrays or device tensors.  Nothing happens without --target_samples."""
+    if target is None:
+        return None
+    dev = dist_util.dev()
+
+    def hwz(a, permute=False):
+        t = th.as_tensor(a).to(device=dev, dtype=th.float32)
+        return (t.permute(1, 2, 0) if permute else t).contiguous()
+
+    tgt, inp, den = hwz(target, True), hwz(vol, True), hwz(result)
+    counted = None
+    if args.metrics_mask_threshold > 0:
+        counted = tgt > args.metrics_mask_threshold * tgt.max()
+    if weight is not None:
+        live = th.as_tensor(weight).to(dev) > 0
+        counted = live if counted is None else counted & live
+    mask = None if counted is None else counted.to(th.uint8).contiguous()
+    data_range = args.data_range if args.data_range > 0 else None
+    report = {
+        "denoised": metrics.evaluate(den, tgt, data_range=data_range, mask=mask,
+                                     std=None if std is None else hwz(std)),
+        "input": metrics.evaluate(inp, tgt, data_range=data_range, mask=mask),
+        "target": args.target_samples,
+        "mask_threshold": args.metrics_mask_threshold,
+    }
+    for name in ("input", "denoised"):
+        r = report[name]
+        logger.log("  %-8s vs target: PSNR %.3f dB  NRMSE %.5f  SSIM %.5f  MAE %.5g  bias %.5g  (L = %.6g, %d voxels)"
+                   % (name, r["psnr"], r["nrmse"], r["ssim"], r["mae"], r["bias"], r["data_range"], r["n_voxels"]))
+    if std is not None:
+        r = report["denoised"]
+        logger.log("  std map coverage: %.4f of the errors within 1 std, %.4f within 2"
+                   % (r["coverage_1"], r["coverage_2"]))
+    path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
+    with open(path, "w") as f:
+        json.dump(report, f, indent=2)
+    logger.log(f"saved metrics to {path}")
+    return path
 
 
 def _sampler(args, diffusion):
@@ -177,7 +255,7 @@ def _base_name(path):
     return base
 
 
-def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches):
+def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target=None):
     """--num_draws K >= 2: every forward batch is bs patches x K draws, patch-major (N = bs * K); the noise of draw d of
     patch i comes from volume_generator(i, draw=d), so it depends on neither K, the batch size nor the world size.
     Gathered rounds are stitched on rank 0's device in ascending patch order (DrawStitcher), then reduced to the
@@ -226,12 +304,13 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             std_path = out_path.replace(".npz", "_std.tif")
             tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
+        _write_metrics(args, out_path, target, vol, mean, std=std, weight=weight)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
 
 
-def _main_joint(args, model, diffusion, vol):
+def _main_joint(args, model, diffusion, vol, target=None):
     """--joint_patches True: every rank holds the whole canvas and runs its share of each step's forwards
     (joint.sample_loop_progressive); rank 0 writes the canvas cropped to the volume, (H, W, Z) like the other paths.
     With --num_draws K >= 2 the K canvases are reduced to the per-voxel mean and sample std."""
@@ -265,6 +344,7 @@ def _main_joint(args, model, diffusion, vol):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
+        _write_metrics(args, out_path, target, vol, result, std=extra.get("std"))
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path

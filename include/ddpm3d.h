@@ -602,6 +602,54 @@ int ddpm3d_joint_gather(const float* canvas, int B, int Dc, int H, int W, int re
 int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, int res,
                        const ddpm3d_joint_starts* starts, const double* tables, float* out_canvas, void* stream);
 /*
+ * Image-quality metrics of B estimates x_b against one full-dose target y (added within ABI 13; the reference has
+ * no metric code).  est is [B][voxels] fp32, target [voxels] fp32, mask an optional uint8 [voxels] (a voxel counts
+ * where mask != 0; NULL: every voxel counts), B in 1..DDPM3D_MAX_DRAWS.  Every workgroup writes one fp64 record to
+ * the caller's workspace and a second launch folds them in a fixed order: no atomics, the same bits on every run.
+ *
+ * ddpm3d_error_moments writes out[B][DDPM3D_EM_REC] doubles (device memory), sums over the counted voxels with
+ * every term formed and added in fp64, e = (double)x - (double)y:
+ *   N = count, SUM_E = sum e, SUM_ABS_E = sum |e|, SUM_SQ_E = sum e^2, SUM_Y = sum y, SUM_SQ_Y = sum y^2,
+ *   MIN_Y / MAX_Y = extremes of y (+inf / -inf when nothing counts), COVER_k = number of counted voxels with
+ *   |e| <= k * (double)std (k = 1, 2; 0 when std, an optional fp32 [voxels], is NULL).
+ * The host divides: mse = SUM_SQ_E / N, mae, bias, target_sq_mean = SUM_SQ_Y / N, psnr = 10 log10(L^2 / mse),
+ * nrmse = sqrt(mse / target_sq_mean), coverage_k = COVER_k / N.
+ *
+ * ddpm3d_ssim3d: Wang et al. 2004 as skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5,
+ * use_sample_covariance=False) evaluates it for 3-D input.  With the separable 11 x 11 x 11 Gaussian window
+ * (sigma 1.5, radius 5, taps normalised to sum 1): mu_x, mu_y, population variances s_x = E[x^2] - mu_x^2, s_y, s_xy,
+ *   S = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_x + s_y + C2)),  C1 = (0.01 L)^2, C2 = (0.03 L)^2,
+ * on the interior only (voxels at least 5 from every face: "valid" windows).  est is [B][D][H][W], W innermost,
+ * every extent >= 11.  map, when not NULL, receives S as [B][D-10][H-10][W-10] fp32; out[B][2] doubles receive
+ * {sum of S, count} over the interior voxels the mask counts (the window itself reads all voxels); ssim = sum /
+ * count.  One fused pass: fp32 filter arithmetic on values with a per-workgroup pivot taken off (no cancellation
+ * in E[x^2] - mu^2 when the data sit on an offset), the sum of S in fp64.
+ *
+ * ws: *_workspace_bytes(...) bytes, 16-byte aligned (0 is the answer for a shape the entry refuses).
+ * Both return DDPM3D_EINVAL before any launch for a NULL est, target, ws or out, B outside 1..DDPM3D_MAX_DRAWS,
+ * voxels outside 1..2^40, an extent outside 11..65535 or H * W above 2^31 - 1 (ssim3d), a workspace that is too
+ * small or misaligned, and a negative or non-finite C1 / C2.
+ */
+enum {
+    DDPM3D_EM_N = 0,
+    DDPM3D_EM_SUM_E = 1,
+    DDPM3D_EM_SUM_ABS_E = 2,
+    DDPM3D_EM_SUM_SQ_E = 3,
+    DDPM3D_EM_SUM_Y = 4,
+    DDPM3D_EM_SUM_SQ_Y = 5,
+    DDPM3D_EM_MIN_Y = 6,
+    DDPM3D_EM_MAX_Y = 7,
+    DDPM3D_EM_COVER_1 = 8,
+    DDPM3D_EM_COVER_2 = 9,
+    DDPM3D_EM_REC = 10          /* doubles per record */
+};
+size_t ddpm3d_error_moments_workspace_bytes(int B, int64_t voxels);
+int ddpm3d_error_moments(const float* est, const float* target, const uint8_t* mask, const float* std, int B,
+                         int64_t voxels, void* ws, size_t ws_bytes, double* out, void* stream);
+size_t ddpm3d_ssim3d_workspace_bytes(int B, int D, int H, int W);
+int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, double C1,
+                  double C2, void* ws, size_t ws_bytes, float* map, double* out, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
