@@ -57,6 +57,21 @@ int ddpm3d_pack_conv_weight(const float* w, int Cout, int Cin, int ksize, int pr
                     "pack_conv_weight");
 }
 
+size_t ddpm3d_packed_up_phase_bytes(int Cout, int Cin) {
+    if (Cout <= 0 || Cin <= 0 || !wz_layer_ok(Cout, Cin, 3)) return 0;
+    return ddpm3d_up_phase_bytes(Cout, Cin);
+}
+
+int ddpm3d_pack_up_phase_weight(const float* w, int Cout, int Cin, void* out, void* stream) {
+    if (!w || !out || Cout <= 0 || Cin <= 0)
+        return fail(DDPM3D_EINVAL, "pack_up_phase_weight: bad arguments (Cout=%d Cin=%d)", Cout, Cin);
+    if (!aligned16(out)) return fail(DDPM3D_EINVAL, "pack_up_phase_weight: w_packed must be 16-byte aligned");
+    if (!wz_layer_ok(Cout, Cin, 3))
+        return fail(DDPM3D_ENOSUP, "pack_up_phase_weight: needs Cout %% 128 == 0, Cin %% 16 == 0 (got Cout=%d Cin=%d)",
+                    Cout, Cin);
+    return launched(ddpm3d_launch_pack_up_phase(w, Cout, Cin, out, (hipStream_t)stream), "pack_up_phase_weight");
+}
+
 int ddpm3d_conv_stats_rows(int N, int D, int H, int W, int Cin, int Cout, int ksize, int precision) {
     if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !prec_ok(precision)) return 0;
     return ddpm3d_conv_cfg(N, D, H, W, Cin, Cout, ksize, precision).stats_rows;
@@ -138,6 +153,18 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
     k.stats_rows = c.stats_rows;
     k.reduce_vox = c.reduce_vox;
     k.hint = d->kernel_hint;
+    // DDPM3D_HINT_UP_PHASE: w_packed is the phase image; the phase form where the low-resolution grid tiles like the
+    // output grid, else the shipped path on the Winograd-D image the buffer starts with (hint bit dropped)
+    bool phase = false;
+    if (d->kernel_hint & DDPM3D_HINT_UP_PHASE) {
+        if (d->precision != DDPM3D_PREC_F16X3_WZ || d->in_mode != DDPM3D_IN_UP)
+            return fail(DDPM3D_EINVAL, "conv3d: DDPM3D_HINT_UP_PHASE needs precision F16X3_WZ and in_mode UP");
+        UpPhaseGeom g;
+        phase = ddpm3d_up_phase_geom(d->D, d->H, d->W, c, g) && d->res_mode != DDPM3D_RES_POOL;
+        if (!phase) k.hint &= ~DDPM3D_HINT_UP_PHASE;
+    }
+    const size_t w_front = phase ? ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision) : (size_t)0;
+    k.w = (const float*)((const char*)d->w_packed + w_front);
     k.io = d->io_dtype;
     if (d->io_dtype & ~(DDPM3D_IO_SRC0_BF16 | DDPM3D_IO_SRC1_BF16 | DDPM3D_IO_OUT_BF16 | DDPM3D_IO_RES_BF16 |
                         DDPM3D_IO_HALF_IS_F16))
@@ -167,7 +194,8 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
         const long long vox = (long long)d->N * d->D * Hs * Ws;
         const long long b0 = vox * d->C0 * ((d->io_dtype & DDPM3D_IO_SRC0_BF16) ? 2 : 4);
         const long long b1 = vox * d->C1 * ((d->io_dtype & DDPM3D_IO_SRC1_BF16) ? 2 : 4);
-        const size_t wb = ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision);
+        const size_t wb = phase ? ddpm3d_up_phase_body_bytes(d->Cout, d->Cin)
+                                : ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision);
         if (b0 >= 0xFFFFFFF0LL || b1 >= 0xFFFFFFF0LL || wb >= 0xFFFFFFF0ULL)
             return fail(DDPM3D_E2BIG, "conv3d: a source tensor or the weights exceed 4 GiB; split the batch");
         // the epilogue addresses one SAMPLE of the output (or residual) with 32-bit offsets
@@ -179,7 +207,9 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
                   : (d->kernel_hint & DDPM3D_HINT_WSTAT_OFF) ? 0
                                                              : ((long long)wb > b0 + b1 ? 1 : 0);
     }
-    if (c.PREC != DDPM3D_PREC_F32)  // output scales sit behind the f16 image
+    if (phase)
+        k.wscale = (const float*)((const char*)k.w + ddpm3d_up_phase_body_bytes(d->Cout, d->Cin));
+    else if (c.PREC != DDPM3D_PREC_F32)  // output scales sit behind the f16 image
         k.wscale = (const float*)((const char*)d->w_packed +
                                   ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision) -
                                   (size_t)ddpm3d_cout_pad(d->Cout) * 4);

@@ -508,6 +508,23 @@ hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvCfg& c, hipStream_t s
     // parameter).
     // f16x3: the issue order of a tap (conv3d_wz.h, IL): one order for every shape since r03
     // (profiles/r03_layer_ab_wz_issue_order.txt; r02 had picked between 0 and 1 by shape).
+    if (k.hint & DDPM3D_HINT_UP_PHASE) {
+        // an IN_UP conv as four 2x2 phase convs on the low-resolution source (conv3d_wz.h PHASE; api.hip keeps the bit
+        // only where ddpm3d_up_phase_geom holds): 4 phases x the low-resolution tiles = the grid the shape rule counted
+        UpPhaseGeom g;
+        if (c.PREC != DDPM3D_PREC_F16X3_WZ || !ddpm3d_up_phase_geom(k.D, k.H, k.W, c, g)) return hipErrorInvalidValue;
+        ConvK k2 = k;
+        k2.tilesX = g.tilesX; k2.tilesY = g.tilesY; k2.tilesZ = g.tilesZ;
+        const dim3 grid(4 * k.N * g.tilesZ * g.tilesY * g.tilesX, gy, k.ksplit);
+        constexpr size_t plds4 = (size_t)WzGeomT<4>::BUF + stamp_lds, plds84 = (size_t)WzGeomT<8, 4>::BUF + stamp_lds;
+        if (g.TX == 4)
+            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_UP, 4, 4, 4>), grid, dim3(256), plds4, st, k2);
+        else if (g.TY == 4)
+            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_UP, 4, 8, 4>), grid, dim3(256), plds84, st, k2);
+        else
+            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_UP, 4, 8, 8>), grid, dim3(256), lds, st, k2);
+        return hipGetLastError();
+    }
     if (c.TXL == 2) {
         // 4x4x8 tiles (the levels below 8x8: r03).  One issue order; the image is 56 KB
         constexpr size_t lds4 = (size_t)WzGeomT<4>::BUF + stamp_lds;

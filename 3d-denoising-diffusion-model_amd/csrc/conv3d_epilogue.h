@@ -214,15 +214,21 @@ __device__ __forceinline__ bool conv_epilogue_lean(const ConvK& p, const f32x16 
 }
 
 // KSPLIT: the caller knows this is a split launch (p.ksplit > 1): only the slab code is instantiated.
-template <int PREC, int WM, int MT, int TXL, int TYL, bool WIDE = false, bool ZPAIRS = false, bool KSPLIT = false>
+// PHASE (conv3d_wz.h, DDPM3D_HINT_UP_PHASE): the tile (z0, y0, x0) lies on the low-resolution grid of an IN_UP conv
+// and its row (y, x) is output voxel (2y + py, 2x + px) -- every offset below doubles in y and x; an up-sampled
+// residual (RES_UP) sits at the tile's own (y, x).  py_ / px_ are wave-uniform.
+template <int PREC, int WM, int MT, int TXL, int TYL, bool WIDE = false, bool ZPAIRS = false, bool KSPLIT = false,
+          bool PHASE = false>
 // pre_ws / pre_bias (pre = true): p.wscale[cout] and the lane's bias, loaded by the caller at kernel
 // START (conv3d_wz.h): at the epilogue's start they are a dependent global load -- ~2k cycles at the
 // head of a phase in which the wave issues no MFMA
 __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc)[MT], int n, int z0, int y0,
                                               int x0, int tile_in_n, int wm, int cout, int half, int ksplit_idx,
                                               float inv_act, bool pre = false, float pre_ws = 1.0f,
-                                              float pre_bias = 0.0f) {
+                                              float pre_bias = 0.0f, int py_ = 0, int px_ = 0) {
     constexpr int TX = 1 << TXL, TY = 1 << TYL;
+    constexpr int SH = PHASE ? 1 : 0;
+    const int py = PHASE ? py_ : 0, px = PHASE ? px_ : 0;
     const bool cvalid = cout < p.Cout;
     const size_t DHW = (size_t)p.D * p.H * p.W;
     // PREC 1/2: undo the operand scaling (exact: a power of two per cout)
@@ -238,7 +244,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
     {
         constexpr int TZ = WM * MT * 32 / (TX * TY);
         const bool split = KSPLIT || p.ksplit > 1;
-        const bool full = z0 + TZ <= p.D && y0 + TY <= p.H && x0 + TX <= p.W;
+        const bool full = z0 + TZ <= p.D && ((y0 + TY) << SH) <= p.H && ((x0 + TX) << SH) <= p.W;
         // residual of a split conv is the reduce kernel's business
         const int rm = split ? DDPM3D_RES_NONE : p.res_mode;
         // the residual tensor of the up / down ResBlocks is the block input at the other
@@ -250,7 +256,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
         const bool o16 = !split && (p.io & DDPM3D_IO_OUT_BF16), r16 = (p.io & DDPM3D_IO_RES_BF16) != 0;
         const bool f16 = (p.io & DDPM3D_IO_HALF_IS_F16) != 0;      // the 16-bit tensors hold IEEE f16, not bf16
         const unsigned eso = o16 ? 2u : 4u, esr = r16 ? 2u : 4u;
-        if (full && p.out_layout == DDPM3D_OUT_NDHWC && samp_r * 4 < 0xFFFFFFF0ull) {
+        if (full && p.out_layout == DDPM3D_OUT_NDHWC && samp_r * 4 < 0xFFFFFFF0ull && !(PHASE && rm == DDPM3D_RES_POOL)) {
             const size_t samp = DHW * p.Cout;                       // elements per sample (< 2^30, C ABI guard)
             const unsigned cstride = (unsigned)p.Cout * eso;        // bytes per voxel of the output
             const unsigned rstride = (unsigned)p.Cout * esr;        // ... of the residual
@@ -263,7 +269,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
                       : drsrc;
             // the lane's half adds 4 to the MFMA row: 4 voxels in x (8-wide tile) or one row in y (4-wide)
             const unsigned hx = (4 * half) & (TX - 1), hy = ((4 * half) >> TXL) & (TY - 1);
-            const unsigned vbase = (((unsigned)z0 * p.H + y0 + hy) * p.W + x0 + hx) * cstride + (unsigned)cout * eso;
+            // voxel offset of the lane's first row, and of tile position (tz, ty, tx) relative to it (wave-uniform)
+            const unsigned vox0 = ((unsigned)z0 * p.H + ((y0 + hy) << SH) + py) * p.W + ((x0 + hx) << SH) + px;
+            auto tvox = [&](int tz, int ty, int tx) { return (unsigned)((tz * p.H + (ty << SH)) * p.W + (tx << SH)); };
+            const unsigned vbase = vox0 * cstride + (unsigned)cout * eso;
             const unsigned voff = cvalid ? vbase : DDPM3D_OOB_OFFSET;   // out-of-range lanes: loads 0, stores dropped
             // Residual addressing, also "lane base + wave-uniform offset" (tiles start at even y0, x0):
             //   SAME  x[z][y][x]                      : the output's own offsets
@@ -271,8 +280,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
             //         4 voxels in x are 2 source voxels; in a 4-wide tile its one row in y shares the source row
             //   POOL  mean of x[z][2y+{0,1}][2x+{0,1}]: doubled offsets, four loads
             const unsigned rW = (unsigned)Wr, rH = (unsigned)Hr;
-            unsigned rbase = (((unsigned)z0 * p.H + y0 + hy) * p.W + x0 + hx) * rstride + (unsigned)cout * esr;
-            if (rm == DDPM3D_RES_UP)
+            unsigned rbase = vox0 * rstride + (unsigned)cout * esr;
+            if (PHASE && rm == DDPM3D_RES_UP)
+                rbase = (((unsigned)z0 * rH + y0 + hy) * rW + x0 + hx) * rstride + (unsigned)cout * esr;
+            else if (rm == DDPM3D_RES_UP)
                 rbase = (((unsigned)z0 * rH + (y0 >> 1)) * rW + (x0 >> 1) + (hx >> 1)) * rstride + (unsigned)cout * esr;
             else if (rm == DDPM3D_RES_POOL)
                 rbase = (((unsigned)z0 * rH + 2 * (y0 + hy)) * rW + 2 * (x0 + hx)) * rstride + (unsigned)cout * esr;
@@ -296,7 +307,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
             if (WIDE && (rm == DDPM3D_RES_NONE || rm == DDPM3D_RES_SAME) && (p.Cout & 3) == 0) {
                 const int li = threadIdx.x & 3;
                 const bool b0 = (li & 1) != 0, b1 = (li & 2) != 0;
-                const unsigned lane_vox = (((unsigned)z0 * p.H + y0 + hy) * p.W + x0 + hx + li);
+                const unsigned lane_vox = vox0 + ((unsigned)li << SH);
                 const unsigned cq = (unsigned)(cout & ~3);
                 const unsigned wv = cvalid ? lane_vox * cstride + cq * eso : DDPM3D_OOB_OFFSET;
                 const unsigned wr = cvalid ? lane_vox * rstride + cq * esr : DDPM3D_OOB_OFFSET;
@@ -310,7 +321,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
                         for (int g = 0; g < 4; ++g) {
                             const int m0 = (wm * MT + t) * 32 + 8 * g;
                             const int ty = (m0 >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m0), tx = m0 & (TX - 1);
-                            const unsigned so = (unsigned)((tz * p.H + ty) * p.W + tx) * rstride;
+                            const unsigned so = tvox(tz, ty, tx) * rstride;
                             if (r16) rq[g] = half4_expand(__builtin_amdgcn_raw_buffer_load_b64(rrsrc, wr, so, 0), f16);
                             else rq[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, wr, so, 0));
                         }
@@ -336,7 +347,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
                         }
                         const int m0 = (wm * MT + t) * 32 + 8 * g;
                         const int ty = (m0 >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m0), tx = m0 & (TX - 1);
-                        const unsigned so = (unsigned)((tz * p.H + ty) * p.W + tx) * cstride;
+                        const unsigned so = tvox(tz, ty, tx) * cstride;
                         // raw slab of a split launch (the reduce launch reads it): plain 16-byte stores (epi_store_b128)
                         if (split)
                             epi_store_b128(u32x4{__builtin_bit_cast(unsigned, a[0]), __builtin_bit_cast(unsigned, a[1]),
@@ -380,7 +391,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
                 for (int reg = 0; reg < 16; ++reg) {
                     const int m0 = (wm * MT + t) * 32 + (reg & 3) + 8 * (reg >> 2);
                     const int tx = m0 & (TX - 1), ty = (m0 >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m0);
-                    soff[reg] = (unsigned)((tz * p.H + ty) * p.W + tx) * cstride;
+                    soff[reg] = tvox(tz, ty, tx) * cstride;
                 }
                 float r[16];
                 if (rm == DDPM3D_RES_SAME) {
@@ -388,14 +399,14 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
                     for (int reg = 0; reg < 16; ++reg) {
                         const int m0 = (wm * MT + t) * 32 + (reg & 3) + 8 * (reg >> 2);
                         const int tx = m0 & (TX - 1), ty = (m0 >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m0);
-                        r[reg] = rload((unsigned)((tz * p.H + ty) * p.W + tx) * rstride);
+                        r[reg] = rload(tvox(tz, ty, tx) * rstride);
                     }
                 } else if (rm == DDPM3D_RES_UP) {
 #pragma unroll
                     for (int reg = 0; reg < 16; ++reg) {
                         const int m0 = (wm * MT + t) * 32 + (reg & 3) + 8 * (reg >> 2);
                         const int tx = m0 & (TX - 1), ty = (m0 >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m0);
-                        r[reg] = rload((unsigned)((tz * rH + (ty >> 1)) * rW + (tx >> 1)) * rstride);
+                        r[reg] = rload((unsigned)((tz * rH + (PHASE ? ty : ty >> 1)) * rW + (PHASE ? tx : tx >> 1)) * rstride);
                     }
                 } else if (rm == DDPM3D_RES_POOL) {
                     // AvgPool3d window order (h, w): ((r00 + r01) + r10) + r11, then * 1/4 (ddpm3d_residual)
@@ -448,7 +459,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
                 const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
                 const int m = (wm * MT + t) * 32 + row;
                 const int tx = m & (TX - 1), ty = (m >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m);
-                const int z = z0 + tz, y = y0 + ty, x = x0 + tx;
+                const int z = z0 + tz, y = ((y0 + ty) << SH) + py, x = ((x0 + tx) << SH) + px;
                 if (cvalid && z < p.D && y < p.H && x < p.W)
                     slab[(((size_t)z * p.H + y) * p.W + x) * p.Cout + cout] =
                         PREC != 0 ? acc[t][reg] * oscale : acc[t][reg];
@@ -468,7 +479,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, const f32x16 (&acc
             const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
             const int m = (wm * MT + t) * 32 + row;
             const int tx = m & (TX - 1), ty = (m >> TXL) & (TY - 1), tz = epi_tz<TXL, TYL, ZPAIRS>(m);
-            const int z = z0 + tz, y = y0 + ty, x = x0 + tx;
+            const int z = z0 + tz, y = ((y0 + ty) << SH) + py, x = ((x0 + tx) << SH) + px;
             const bool ok = cvalid && z < p.D && y < p.H && x < p.W;
             if (ok) {
                 float val = (PREC != 0 ? acc[t][reg] * oscale : acc[t][reg]) + bias;

@@ -175,6 +175,34 @@ static inline size_t ddpm3d_packed_bytes(int Cout, int Cin, int ksize, int prec)
     return prec != 0 ? body + (size_t)ddpm3d_cout_pad(Cout) * 4 : body;  // modes 1 and 2 share the image
 }
 
+// ---- DDPM3D_HINT_UP_PHASE: an IN_UP 3x3x3 conv as four 2x2 phase convs on the low-resolution source
+// (conv3d_wz.h PHASE).  The phase body of the image: 4 phases x 16 taps of the shipped per-tap layout.
+static inline size_t ddpm3d_up_phase_body_bytes(int Cout, int Cin) {
+    return (size_t)64 * ddpm3d_cin_pad(Cin) * ddpm3d_cout_pad(Cout) * 4;
+}
+// [F16X3_WZ image incl. its scales][phase body][CoutPad fp32 scales of the phase body]
+static inline size_t ddpm3d_up_phase_bytes(int Cout, int Cin) {
+    return ddpm3d_packed_bytes(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ) + ddpm3d_up_phase_body_bytes(Cout, Cin) +
+           (size_t)ddpm3d_cout_pad(Cout) * 4;
+}
+// Tile form on the LOW-resolution grid (H/2 x W/2), chosen like the launcher chooses the output grid's
+// (8x4x4 where H/2 % 8 == 0 and D % 4 == 0, else 8x8x2, 4x4x8 below 8x8), ragged edges included.  The form is
+// taken only where four phases x the low-resolution tiles are exactly the tiles the shape rule counted on
+// the output grid: statistics rows (one per workgroup), workspace and split then are what ddpm3d_conv_cfg
+// reports.  false = the shipped path.
+struct UpPhaseGeom { int TX, TY, tilesX, tilesY, tilesZ; };
+static inline bool ddpm3d_up_phase_geom(int D, int H, int W, const ConvCfg& c, UpPhaseGeom& g) {
+    if (((H | W) & 1) || c.KS != 3 || c.WN != 4 || c.MT != 4) return false;
+    const int Hl = H / 2, Wl = W / 2;
+    if (Hl >= 8 && Wl >= 8) { g.TX = 8; g.TY = (Hl % 8 == 0 && D % 4 == 0) ? 4 : 8; }
+    else { g.TX = 4; g.TY = 4; }
+    const int TZ = 128 / (g.TX * g.TY);
+    g.tilesX = (Wl + g.TX - 1) / g.TX;
+    g.tilesY = (Hl + g.TY - 1) / g.TY;
+    g.tilesZ = (D + TZ - 1) / TZ;
+    return 4LL * g.tilesX * g.tilesY * g.tilesZ == (long long)c.tilesX * c.tilesY * c.tilesZ;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: raise it once
 // per (kernel instantiation, device), not once per process (a process that drives two GPUs would
 // otherwise fail its first > 64 KB launch on the second one).  `done` = one flag word per kernel.

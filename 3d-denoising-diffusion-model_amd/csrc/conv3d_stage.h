@@ -23,7 +23,8 @@
 #include "conv3d_epilogue.h"
 
 // arithmetic of the staged operands: hi + lo f16 (three MFMAs per product), hi f16 only, bf16
-enum { WZ_F16X3 = 0, WZ_F16 = 1, WZ_BF16 = 2 };
+enum { WZ_F16X3 = 0, WZ_F16 = 1, WZ_BF16 = 2,
+       WZ_F16X3_UP = 3 };   // conv3d_wz.h only: the f16x3 arithmetic on the phase form of an up-sampled input
 
 // two fp32 -> packed f16 hi (RNE) and packed f16 lo = f16(s - hi); the subtraction is exact
 __device__ __forceinline__ void split_pair(float s0, float s1, unsigned& hi, unsigned& lo) {
@@ -78,12 +79,16 @@ struct StageLaneT {
 typedef StageLaneT<WzGeom> StageLane;
 
 // zb = the lowest input plane any item of this workgroup reads (clamped to 0)
-template <class G = WzGeom>
+// LOWRES (the phase form of an IN_UP conv, conv3d_wz.h PHASE): the tile (y0, x0) lies on the SOURCE grid
+// (H/2 x W/2) and is staged like an IN_SAME tile of that grid
+template <class G = WzGeom, bool LOWRES = false>
 __device__ __forceinline__ StageLaneT<G> stage_lane(const ConvK& p, int lt, int n, int y0, int x0, int zb, float scale) {
     StageLaneT<G> s;
     s.scale = scale;
-    const int up = p.in_mode == DDPM3D_IN_UP ? 1 : 0;
-    const int Hs = p.H >> up, Ws = p.W >> up;
+    const int up_mode = p.in_mode == DDPM3D_IN_UP ? 1 : 0;
+    const int Hs = p.H >> up_mode, Ws = p.W >> up_mode;
+    const int up = LOWRES ? 0 : up_mode;
+    const int Hb = LOWRES ? Hs : p.H, Wb = LOWRES ? Ws : p.W;     // the grid (y, x) walks
     s.q = lt & 3;
     s.zb = zb;
     s.es0 = (p.io & DDPM3D_IO_SRC0_BF16) ? 2u : 4u;
@@ -100,7 +105,7 @@ __device__ __forceinline__ StageLaneT<G> stage_lane(const ConvK& p, int lt, int 
         const int hyx = idx >> 2;
         const int hy = hyx / G::HX, hx = hyx - hy * G::HX;
         const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-        s.ok[i] = idx < G::HC && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        s.ok[i] = idx < G::HC && (unsigned)y < (unsigned)Hb && (unsigned)x < (unsigned)Wb;
         const unsigned vox = (unsigned)(((n * p.D + zb) * Hs + (y >> up)) * Ws + (x >> up));
         s.vo0[i] = s.ok[i] ? (vox * (unsigned)p.C0 + s.q * 4u) * s.es0 : DDPM3D_OOB_OFFSET;
         s.vo1[i] = s.ok[i] ? (vox * (unsigned)p.C1 + s.q * 4u) * s.es1 : DDPM3D_OOB_OFFSET;

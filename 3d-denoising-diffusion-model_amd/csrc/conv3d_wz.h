@@ -46,11 +46,23 @@
 // Tile forms (conv3d_stage.h WzGeomT): 8 x 8 x 2 (one z-pair), 8 x 4 x 4 (two; r03), 4 x 4 x 8 (four: the levels
 // below 8x8, which the direct kernel's 4x4 tiles ran at 1.5x the MFMAs; r03).  A 32-row MFMA tile is 32 positions of
 // one transformed plane -- half a pair, one pair or two pairs' worth; the tap loop below is the same code for all.
-template <int MODE, int IL = 0, int TX = 8, int TY = TX>
+//
+// PHASE (DDPM3D_HINT_UP_PHASE, f16x3 only): an IN_UP conv as four 2x2 phase convs on the low-resolution source.  On
+// the nearest-(1,2,2)-up-sampled plane the nine (dy, dx) taps of an output voxel of parity (py, px) meet 2x2 source
+// voxels (py = 0: source row i-1 | i, i; py = 1: i, i | i+1; the same along x), so a workgroup owns ONE phase of one
+// low-resolution tile: staged like an IN_SAME tile of the source grid (full 3x3 halo), 16 taps (j, a, b) per chunk
+// instead of 36 on the weights ops.hip summed per phase (pack_wz_up_kernel), tap (j, a, b) at LDS offset
+// (j RZ + (a + py) RY + (b + px) VS) 16 with the phase's share folded into arow[] once, and an epilogue that places
+// row (y, x) at output (2y + py, 2x + px).  The phase is wave-uniform (from the workgroup id).
+// (the phase form is MODE_ WZ_F16X3_UP of the one kernel, so that the shipped forms keep their code and their names)
+template <int MODE_, int IL = 0, int TX = 8, int TY = TX>
 __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
+    constexpr bool PHASE = MODE_ == WZ_F16X3_UP;
+    constexpr int MODE = PHASE ? (int)WZ_F16X3 : MODE_;     // the arithmetic
     typedef WzGeomT<TX, TY> G;
     constexpr bool X3 = MODE == WZ_F16X3;
-    constexpr int CK = DDPM3D_CONV_CK, NT = 36;
+    constexpr int CK = DDPM3D_CONV_CK, NT = PHASE ? 16 : 36;
+    constexpr int TPJ = NT / 4;     // taps per transformed plane j
     constexpr int TXL = TX == 8 ? 3 : 2, TYL = TY == 8 ? 3 : 2;
     constexpr int VS = G::VS, RY = G::RY, RZ = G::RZ;
 
@@ -70,7 +82,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
     const int tx_i = tile % p.tilesX; tile /= p.tilesX;
     const int ty_i = tile % p.tilesY; tile /= p.tilesY;
     const int tz_i = tile % p.tilesZ; tile /= p.tilesZ;
-    const int n = tile;
+    // PHASE: tiles count on the low-resolution grid; the phase sits above z, so that one XCD's run of consecutive
+    // workgroups meets one phase's quarter of the weights
+    const int ph = PHASE ? (tile & 3) : 0;
+    const int py = ph >> 1, px = ph & 1;
+    const int n = PHASE ? tile >> 2 : tile;
     const int x0 = tx_i * TX, y0 = ty_i * TY, z0 = tz_i * 2 * G::NZP;
 
     // GEMM rows of this wave, two 32-row MFMA tiles: row m = position m % RP of z-pair m / RP
@@ -80,6 +96,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
         const int m = t * 32 + (lane & 31);
         const int pos = m % G::RP;
         arow[t] = (m / G::RP) * G::PAIR + ((pos >> TXL) * RY + (pos & (TX - 1)) * VS + half) * 16;
+        if constexpr (PHASE) arow[t] += (py * RY + px * VS) * 16;
     }
 
     const int cout = wg.cy * 128 + wn * 32 + (lane & 31);
@@ -110,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
     ActScale asc = {1.0f, 1.0f};
     float bound_raw = 0.0f;
     if constexpr (MODE != WZ_BF16) bound_raw = act_scale_load(p, n);
-    StageLaneT<G> sl = stage_lane<G>(p, tid, n, y0, x0, max(z0 - 1, 0), 1.0f);
+    StageLaneT<G> sl = stage_lane<G, PHASE>(p, tid, n, y0, x0, max(z0 - 1, 0), 1.0f);
     stage_zero_border(sl, lds, 1, tid);
     StageRawT<G> raw;
     if (chunk_begin < chunk_end) stage_issue(p, sl, raw, n, z0, chunk_begin);
@@ -136,6 +153,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
     // the next chunk's raw loads are issued behind the chunk's LAST weight loads (vmcnt retires in order): at tap NT - R
     // in the one-MFMA forms; a deeper f16x3 ring stops loading earlier, and its staging loads still go out at tap NT - 3,
     // when ring slots have started to free up (the raw registers take their place)
+    // PHASE (16 taps): the same ring and the same rule -- the last weight loads go out at tap NT - R = 12, the staging
+    // loads behind them at tap 13; three taps (18 MFMAs per wave) and the barrier phase cover them as before
     constexpr int STAGE_TAP = X3 ? NT - 3 : NT - 8;
     for (int chunk = chunk_begin; chunk < chunk_end; ++chunk) {
         const bool more = chunk + 1 < chunk_end;
@@ -155,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
         // tap 28: no better; the A operands one tap ahead as below: two ahead -1.5 %, three -16 %).
         // The stream's byte offset is one running scalar
         if constexpr (IL == 3 || IL == 4 || IL == 6) __builtin_amdgcn_s_setprio(1);
-        unsigned woff = (unsigned)chunk * wchunk_stride;
+        unsigned woff = (unsigned)chunk * wchunk_stride + (PHASE ? (unsigned)ph * 16u * wtap_stride : 0u);
         auto bump = [&]() {
             woff += wtap_stride;
             asm volatile("" : "+s"(woff));
@@ -173,7 +192,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
         constexpr int AH = DDPM3D_WZ_A_AHEAD, AS = AH + 1;
         h8 af[AS][2][X3 ? 2 : 1];   // [slot][row tile][hi|lo]: A operands, read AH tap(s) ahead
         auto aread = [&](const int t1) {
-            const int off1 = ((t1 / 9) * RZ + ((t1 / 3) % 3) * RY + (t1 % 3) * VS) * 16;
+            const int off1 = PHASE ? ((t1 / 4) * RZ + ((t1 / 2) % 2) * RY + (t1 % 2) * VS) * 16
+                                   : ((t1 / 9) * RZ + ((t1 / 3) % 3) * RY + (t1 % 3) * VS) * 16;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 af[t1 % AS][t][0] = *reinterpret_cast<const h8*>(bufc + arow[t] + off1);
@@ -196,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
             if constexpr (!IL) __builtin_amdgcn_sched_barrier(0);   // prefetches issue BEFORE this tap's MFMAs
             // next chunk's raw loads: after the chunk's last weight loads (vmcnt retires in order)
             if (tap == STAGE_TAP && more) stage_issue(p, sl, raw, n, z0, chunk + 1);
-            const int j = tap / 9;
+            const int j = tap / TPJ;
             const h8 bhi = __builtin_bit_cast(h8, bq[tap % R][0]);
             // per accumulator the order stays lo*hi, hi*lo, hi*hi; the two row tiles alternate
             if (X3) {
@@ -260,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
         outv[t] = acc[0][t] + acc[1][t] + acc[2][t];
         outv[2 + t] = acc[1][t] - acc[2][t] - acc[3][t];
     }
-    const int tile_in_n = (tz_i * p.tilesY + ty_i) * p.tilesX + tx_i;
+    const int tile_in_n = ((ph * p.tilesZ + tz_i) * p.tilesY + ty_i) * p.tilesX + tx_i;
     #ifndef DDPM3D_WZ_WIDE_X3
 #define DDPM3D_WZ_WIDE_X3 0     // measurement: the 16-byte epilogue in the f16x3 form too
 #endif
@@ -280,14 +300,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
         if (LEAN && conv_epilogue_lean<1, 1, 4, 1, TXL, TYL, G::NZP != 1, true>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half,
                                                                                          wg.split, asc.inv, ws1, bs1)) {
         } else
-        conv_epilogue<1, 1, 4, TXL, TYL, true, G::NZP != 1, true>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
-                                                                 asc.inv, true, pre_ws, pre_bias);
+        conv_epilogue<1, 1, 4, TXL, TYL, true, G::NZP != 1, true, PHASE>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
+                                                                 asc.inv, true, pre_ws, pre_bias, py, px);
     } else if (LEAN &&
                conv_epilogue_lean<1, 1, 4, 1, TXL, TYL, G::NZP != 1, false>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
                                                                            asc.inv, ws1, bs1)) {
     } else
-    conv_epilogue<1, 1, 4, TXL, TYL, MODE != WZ_F16X3 || DDPM3D_WZ_WIDE_X3, G::NZP != 1>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
-                                                                 asc.inv, true, pre_ws, pre_bias);
+    conv_epilogue<1, 1, 4, TXL, TYL, MODE != WZ_F16X3 || DDPM3D_WZ_WIDE_X3, G::NZP != 1, false, PHASE>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
+                                                                 asc.inv, true, pre_ws, pre_bias, py, px);
 #ifdef DDPM3D_WZ_STAMPS
     WZ_STAMP(43);
     if (lane == 0) {

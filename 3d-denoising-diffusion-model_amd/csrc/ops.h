@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int prec, void* out, hipStream_t st);
+hipError_t ddpm3d_launch_pack_up_phase(const float* w, int Cout, int Cin, void* out, hipStream_t st);
 hipError_t ddpm3d_launch_gn_finalize(const double* st0, int C0, int rows0, const double* st1, int C1,
                                      int rows1, int N, int groups, double count, float eps,
                                      const float* gamma, const float* beta, const float* film,

@@ -137,6 +137,90 @@ __global__ void pack_wz_kernel(const float* __restrict__ w, const float* __restr
     }
 }
 
+// Phase weights of an IN_UP conv (DDPM3D_HINT_UP_PHASE, conv3d_wz.h PHASE): on the 2x nearest-up-sampled plane
+// the taps dy of an output row of parity py meet two source rows -- py = 0: {0} | {1, 2}, py = 1: {0, 1} | {2} --
+// and the same along x.  Phase tap t = j*4 + a*2 + b of phase ph = 2 py + px is the fp32 sum of the shipped
+// U_j[dy][dx] (wz_weight) over group a of py x group b of px, added in (dy, dx) row-major order.
+__device__ __forceinline__ float wz_up_weight(const float* __restrict__ w, size_t co_ci, int ph, int t) {
+    const int py = ph >> 1, px = ph & 1, j = t >> 2, a = (t >> 1) & 1, b = t & 1;
+    const int dy0 = a ? 1 + py : 0, dy1 = a ? 2 : py;
+    const int dx0 = b ? 1 + px : 0, dx1 = b ? 2 : px;
+    float s = 0.0f;
+    bool first = true;
+    for (int dy = dy0; dy <= dy1; ++dy)
+        for (int dx = dx0; dx <= dx1; ++dx) {
+            const float u = wz_weight(w, co_ci, j, dy * 3 + dx);
+            s = first ? u : s + u;
+            first = false;
+        }
+    return s;
+}
+
+// one scale per cout over all 64 phase taps (the rule of pack_wz_scale_kernel)
+__global__ __launch_bounds__(256) void pack_wz_up_scale_kernel(const float* __restrict__ w, int Cout, int Cin,
+                                                               float* __restrict__ wscale) {
+    const int co = blockIdx.x;
+    float m = 0.0f;
+    if (co < Cout)
+        for (int i = threadIdx.x; i < Cin * 64; i += 256) {
+            const int ci = i >> 6, pt = i & 63;
+            m = fmaxf(m, fabsf(wz_up_weight(w, (size_t)co * Cin + ci, pt >> 4, pt & 15)));
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        float s = 1.0f;
+        if (m > 0.0f && m < 3.0e38f) s = exp2f(floorf(log2f(DDPM3D_X3_W_TARGET / m)));
+        s = fminf(fmaxf(s, 1.0f / 16777216.0f), 16777216.0f);
+        wscale[co] = 1.0f / s;
+    }
+}
+
+// [phase][tap 16][ci/16][hi|lo][CoutPad][16 f16]: per (phase, tap) the layout of pack_wz_kernel
+__global__ void pack_wz_up_kernel(const float* __restrict__ w, const float* __restrict__ wscale, int Cout, int Cin,
+                                  int CoutPad, int CinPad, _Float16* __restrict__ out) {
+    const size_t total = (size_t)64 * CinPad * CoutPad;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const int jj = (int)(i & 15);
+        size_t r = i >> 4;
+        const int co = (int)(r % CoutPad); r /= CoutPad;
+        const int cb = (int)(r % (CinPad / 16));
+        const int pt = (int)(r / (CinPad / 16));     // phase * 16 + tap
+        const int ci = cb * 16 + jj;
+        float v = 0.0f;
+        if (co < Cout && ci < Cin)
+            v = wz_up_weight(w, (size_t)co * Cin + ci, pt >> 4, pt & 15) * (1.0f / wscale[co]);
+        const _Float16 hi = (_Float16)v;
+        const _Float16 lo = (_Float16)(v - (float)hi);
+        const size_t base = (((size_t)pt * (CinPad / 16) + cb) * 2) * CoutPad * 16;
+        out[base + (size_t)co * 16 + jj] = hi;
+        out[base + (size_t)CoutPad * 16 + (size_t)co * 16 + jj] = lo;
+    }
+}
+
+hipError_t ddpm3d_launch_pack_up_phase(const float* w, int Cout, int Cin, void* out, hipStream_t st) {
+    // the shipped Winograd-D image in front (the shapes that fall back run on it), the phase body behind it
+    hipError_t e = ddpm3d_launch_pack(w, Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ, out, st);
+    if (e != hipSuccess) return e;
+    const int CoutPad = ddpm3d_cout_pad(Cout), CinPad = ddpm3d_cin_pad(Cin);
+    char* body = reinterpret_cast<char*>(out) + ddpm3d_packed_bytes(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ);
+    const size_t total = (size_t)64 * CinPad * CoutPad;
+    float* wscale = reinterpret_cast<float*>(body + total * 4);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_wz_up_scale_kernel, dim3(CoutPad), dim3(256), 0, st, w, Cout, Cin, wscale);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pack_wz_up_kernel, dim3(blocks), dim3(256), 0, st, w, wscale, Cout, Cin, CoutPad, CinPad,
+                       (_Float16*)body);
+    return hipGetLastError();
+}
+
 hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int prec, void* out, hipStream_t st) {
     const int CoutPad = ddpm3d_cout_pad(Cout), CinPad = ddpm3d_cin_pad(Cin);
     const bool bf16 = prec == DDPM3D_PREC_BF16 || prec == DDPM3D_PREC_BF16_WZ;

@@ -132,8 +132,12 @@ struct Planner {
         ddpm3d_conv_desc d;
         memset(&d, 0, sizeof(d));
         const bool wz = pc.w_packed_wz && !a.planar && (a.in_mode == DDPM3D_IN_SAME || a.in_mode == DDPM3D_IN_UP);
-        d.precision = wz ? pc.precision_wz : pc.precision;
+        d.precision = wz ? (pc.precision_wz & ~DDPM3D_WZ_UP_PHASE_IMAGE) : pc.precision;
         d.w_packed = wz ? pc.w_packed_wz : pc.w_packed;
+        // a phase image (ddpm3d_pack_up_phase_weight) starts with the plain Winograd-D image: its IN_UP calls run the
+        // four-phase form where the library finds the shape fit (ddpm3d.h DDPM3D_HINT_UP_PHASE), the others as ever
+        if (wz && (pc.precision_wz & DDPM3D_WZ_UP_PHASE_IMAGE) && a.in_mode == DDPM3D_IN_UP)
+            d.kernel_hint = DDPM3D_HINT_UP_PHASE;
         d.bias = pc.bias;
         d.Cout = pc.Cout; d.ksize = pc.ksize;
         const Act* geo = a.out ? a.out : a.src0;

@@ -38,6 +38,10 @@ MAX_DRAWS = 64  # DDPM3D_MAX_DRAWS: draws per uncertainty map (ddpm3d_draw_stitc
 HINT_WSTAT_OFF, HINT_WSTAT_ON = 0x100, 0x200
 HINT_SPLITK_SHIFT = 16      # bits 16..21: forced split factor (measurement only, tools/splitk_sweep.py)
 HINT_WZ_ORDER_SHIFT = 12     # bits 12..14: tap issue order of the f16x3 Winograd-D kernel (A/B measurements)
+# w_packed is ddpm3d_pack_up_phase_weight's image: an IN_UP f16x3 Winograd-D conv runs as four 2x2 phase convs on
+# the low-resolution source (the one hint that selects a weight image and so changes rounding)
+HINT_UP_PHASE = 0x400
+WZ_UP_PHASE_IMAGE = 0x100    # flag in ddpm3d_conv_weights.precision_wz: w_packed_wz is that image
 
 _fp = C.c_void_p
 
@@ -103,6 +107,8 @@ EXPORTS = {
     "ddpm3d_last_error": (C.c_char_p, []),
     "ddpm3d_packed_weight_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ddpm3d_pack_conv_weight": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ddpm3d_packed_up_phase_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "ddpm3d_pack_up_phase_weight": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_conv_stats_rows": (C.c_int, [C.c_int] * 8),
     "ddpm3d_conv_workspace_bytes": (C.c_size_t, [C.c_int] * 8),
     "ddpm3d_conv3d": (C.c_int, [C.POINTER(ConvDesc), _fp]),

@@ -21,6 +21,7 @@ for every step of the schedule.
 import collections
 import ctypes as C
 import math
+import os
 
 import torch
 
@@ -46,11 +47,12 @@ class Act:
 
 
 class PackedConv:
-    __slots__ = ("w", "b", "Cout", "Cin", "k", "precision", "wz")
+    __slots__ = ("w", "b", "Cout", "Cin", "k", "precision", "wz", "up_phase")
 
     def __init__(self, weight, bias, precision, stream):
         lib = H.load()
         self.wz = None   # optional Winograd-along-depth packing of the same layer
+        self.up_phase = False   # w is ddpm3d_pack_up_phase_weight's image (pack_up_phase)
         Cout, Cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
         n = lib.ddpm3d_packed_weight_bytes(Cout, Cin, k, precision)
         if n == 0:
@@ -60,6 +62,18 @@ class PackedConv:
         H.check(lib.ddpm3d_pack_conv_weight(H.ptr(w32), Cout, Cin, k, precision, H.ptr(self.w), stream))
         self.b = bias.detach().float().contiguous()
         self.Cout, self.Cin, self.k, self.precision = Cout, Cin, k, precision
+
+    def pack_up_phase(self, weight, stream):
+        """Replace this f16x3 Winograd-D image by the phase image of the same weights (it starts with the same
+        Winograd-D image): the layer's IN_UP calls then carry HINT_UP_PHASE."""
+        lib = H.load()
+        n = lib.ddpm3d_packed_up_phase_bytes(self.Cout, self.Cin)
+        if n == 0:
+            raise RuntimeError("no phase image for a %dx%d conv" % (self.Cout, self.Cin))
+        w32 = weight.detach().float().contiguous()
+        self.w = torch.empty(n, dtype=torch.uint8, device=weight.device)
+        H.check(lib.ddpm3d_pack_up_phase_weight(H.ptr(w32), self.Cout, self.Cin, H.ptr(self.w), stream))
+        self.up_phase = True
 
 
 class UNetEngine:
@@ -117,6 +131,11 @@ class UNetEngine:
             params[base + ".weight"] = params[base + ".weight"][perm].contiguous()
             params[base + ".bias"] = params[base + ".bias"][perm].contiguous()
         self.p = params
+        # conv1 of the up-ResBlocks reads a nearest-up-sampled input: in the f16x3 mode it gets the phase image
+        # (four 2x2 phase convs on the low-resolution input, 16 taps instead of 36).  DDPM3D_UP_PHASE=0 keeps the
+        # plain Winograd-D image and with it the 36-tap path, in this plan and in the native one (A/B measurements).
+        self.up_phase = (winograd and precision == "f16x3" and os.environ.get("DDPM3D_UP_PHASE", "1") != "0")
+        up_conv1 = {e.prefix + ".in_layers.2" for e in topo.all_layers() if e.kind == "res" and e.updown == "up"}
         for name, t in params.items():
             if name.endswith(".weight") and t.dim() >= 3:
                 base = name[:-len(".weight")]
@@ -140,6 +159,8 @@ class UNetEngine:
                 if (prec in H.WINOGRAD_OF and self.winograd and w.shape[2] == 3 and w.shape[0] % 128 == 0
                         and w.shape[1] % 16 == 0):
                     self.conv[base].wz = PackedConv(w, params[base + ".bias"], H.WINOGRAD_OF[prec], st)
+                    if self.up_phase and base in up_conv1:
+                        self.conv[base].wz.pack_up_phase(w, st)
         # fuse every ResBlock's emb_layers Linear into one [total, ted] matrix
         ws, bs, self.film_off = [], [], {}
         off = 0
@@ -215,6 +236,8 @@ class UNetEngine:
             w.Cout, w.Cin, w.ksize, w.precision = pc.Cout, pc.Cin, pc.k, pc.precision
             if pc.wz is not None:
                 w.w_packed_wz, w.precision_wz = H.ptr(pc.wz.w), pc.wz.precision
+                if pc.wz.up_phase:
+                    w.precision_wz |= H.WZ_UP_PHASE_IMAGE
         return w
 
     def native_desc(self):
@@ -620,6 +643,8 @@ class _Plan(_PlanBase):
             d.in_bound_count, d.in_bound_stride = bound[2], bound[3]
         d.precision = pc_use.precision
         d.w_packed, d.bias = H.ptr(pc_use.w), H.ptr(pc.b)
+        if pc_use.up_phase and in_mode == H.IN_UP:
+            d.kernel_hint = H.HINT_UP_PHASE     # the library falls back by itself where the shape does not fit
         d.bias_stride_n = 0  # per-sample bias rows are patched in run()
         d.res_mode = res_mode
         if res is not None and res.C != pc.Cout:

@@ -124,7 +124,7 @@ typedef struct ddpm3d_conv_desc {
     size_t workspace_bytes;
     /* 0 = the library picks the workgroup order from the shape.  DDPM3D_HINT_* bits select among
      * launch orders of IDENTICAL arithmetic (bit-identical outputs); they exist for tests and A/B
-     * measurements and never change a result. */
+     * measurements and never change a result -- except DDPM3D_HINT_UP_PHASE, which names the weight image. */
     int32_t kernel_hint;
     /* Range of the convolution's INPUT as the matrix cores see it, for the split-f16 modes (every
      * precision but DDPM3D_PREC_F32, which ignores it; REQUIRED otherwise).  Sample n's entries
@@ -169,8 +169,20 @@ enum {
     /* bits 16..21: force the split factor over Cin of a conv with Cout > 64 (measurement only: size statistics
      * and workspace with ddpm3d_conv_plan on the same descriptor; 0 = the library's own choice) */
     DDPM3D_HINT_SPLITK_SHIFT = 16,
-    DDPM3D_HINT_SPLITK_MASK = 0x3F0000
+    DDPM3D_HINT_SPLITK_MASK = 0x3F0000,
+    /* The ONE hint that selects a weight image and therefore changes rounding: w_packed is the image of
+     * ddpm3d_pack_up_phase_weight (precision DDPM3D_PREC_F16X3_WZ, in_mode DDPM3D_IN_UP only; anything else
+     * is DDPM3D_EINVAL).  The conv then runs as four 2x2 phase convs on the low-resolution source wherever
+     * the low-resolution grid tiles like the output grid (same statistics rows, same workspace, same split,
+     * same kernel family name); other shapes run the unhinted path on the Winograd-D image that the same
+     * buffer starts with, bit for bit.  Results differ from the unhinted call in rounding only (the same
+     * products, with the weights of taps that meet the same source voxel summed in fp32 at pack time). */
+    DDPM3D_HINT_UP_PHASE = 0x400
 };
+
+/* flag in ddpm3d_conv_weights.precision_wz (the planner masks it off): w_packed_wz is the image of
+ * ddpm3d_pack_up_phase_weight; calls with in_mode DDPM3D_IN_UP get DDPM3D_HINT_UP_PHASE */
+#define DDPM3D_WZ_UP_PHASE_IMAGE 0x100
 
 int ddpm3d_abi_version(void);
 const char* ddpm3d_last_error(void);
@@ -215,6 +227,17 @@ size_t ddpm3d_packed_weight_bytes(int Cout, int Cin, int ksize, int precision);
 /* OIDHW (torch Conv3d.weight / Conv1d.weight with k=1) -> packed; device to device */
 int ddpm3d_pack_conv_weight(const float* w_oidhw, int Cout, int Cin, int ksize, int precision,
                             void* w_packed, void* stream);
+/* Phase image of a 3x3x3 conv that reads a nearest-(1,2,2)-up-sampled input (DDPM3D_HINT_UP_PHASE; ABI 13,
+ * additive).  On the up-sampled plane the nine (dy, dx) taps of an output voxel of parity (py, px) meet only
+ * 2x2 source voxels: py = 0 reads source row i-1 at dy = 0 and row i at dy = 1, 2; py = 1 reads row i at
+ * dy = 0, 1 and row i+1 at dy = 2; the same along x.  The image holds, behind the DDPM3D_PREC_F16X3_WZ image
+ * of the same weights (which serves the shapes that fall back), for each phase ph = 2 py + px the 16 taps
+ * (j, a, b) = the fp32 sum of the Winograd-D weights U_j[dy][dx] over the collapsing group, added in
+ * (dy, dx) row-major order; one power-of-two scale per cout over all 64 phase taps; then the f16 hi/lo split.
+ * Layout [phase][tap][ci/16][hi|lo][CoutPad][16 f16], then CoutPad fp32 output scales.
+ * Needs Cout % 128 == 0 and Cin % 16 == 0 (bytes query: 0 otherwise). */
+size_t ddpm3d_packed_up_phase_bytes(int Cout, int Cin);
+int ddpm3d_pack_up_phase_weight(const float* w_oidhw, int Cout, int Cin, void* w_packed, void* stream);
 
 /* rows per sample of the statistics buffer this conv writes, and the scratch
  * it needs (both depend on how the shape is tiled / split; `precision` = the DDPM3D_PREC_* of the call

@@ -34,8 +34,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--only64", action="store_true", help="only the full-resolution layers")
-    ap.add_argument("--what", default="order", choices=["order", "issue"],
-                    help="order: workgroup -> XCD orders; issue: issue orders of a tap (f16x3 Winograd-D kernel)")
+    ap.add_argument("--what", default="order", choices=["order", "issue", "phase"],
+                    help="order: workgroup -> XCD orders; issue: issue orders of a tap (f16x3 Winograd-D kernel); "
+                         "phase: the up-sampled-input convs on the 36-tap path against their four-phase form "
+                         "(HINT_UP_PHASE: NOT identical arithmetic, the same buffer holds both weight images)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model, _, _ = bench.build_model(bench.PUBLISHED, "250", dev)
@@ -53,7 +55,8 @@ def main():
     ap_what = a.what
     variants = {"order": [("default", 0), ("wstat_off", H.HINT_WSTAT_OFF), ("wstat_on", H.HINT_WSTAT_ON)],
                 # issue orders of a tap in the f16x3 Winograd-D kernel (conv3d_wz.h: IL)
-                "issue": [("default", 0)] + [("il%d" % il, (il + 1) << H.HINT_WZ_ORDER_SHIFT) for il in (0, 1, 2, 4)]}[ap_what]
+                "issue": [("default", 0)] + [("il%d" % il, (il + 1) << H.HINT_WZ_ORDER_SHIFT) for il in (0, 1, 2, 4)],
+                "phase": [("taps36", 0), ("phase16", H.HINT_UP_PHASE)]}[ap_what]
     seen = {}
     print("# published architecture, %dx1x%d^3, %s; ms per launch (median of %d rounds x %d launches)"
           % (B, S, a.precision, a.rounds, a.iters))
@@ -65,6 +68,10 @@ def main():
         d = plan.steps[i][1][0]._obj
         if a.only64 and d.H != S:
             continue
+        planned = d.kernel_hint       # the plan's own hint (HINT_UP_PHASE on the layers that carry the phase image)
+        if ap_what == "phase" and not planned & H.HINT_UP_PHASE:
+            continue
+        keep = 0 if ap_what == "phase" else planned
         key = (d.in_mode, d.Cin, d.Cout, d.D, d.H, d.W, d.res_mode)
         if key in seen:
             continue
@@ -73,7 +80,7 @@ def main():
         times = {n: [] for n, _ in variants}
         for _ in range(a.rounds):
             for n, hint in variants:
-                d.kernel_hint = hint
+                d.kernel_hint = hint | keep
                 H.check(lib.ddpm3d_conv3d(C.byref(d), st))     # warm
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -82,7 +89,7 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 times[n].append(e0.elapsed_time(e1) / a.iters)
-        d.kernel_hint = 0
+        d.kernel_hint = planned
         med = {n: sorted(v)[len(v) // 2] for n, v in times.items()}
         ws = lib.ddpm3d_conv_workspace_bytes(d.N, d.D, d.H, d.W, d.Cin, d.Cout, d.ksize, d.precision)
         split = ws // (d.N * d.D * d.H * d.W * d.Cout * 4) if ws else 1
@@ -90,6 +97,9 @@ def main():
         print("%-6s %-12s %-12s %2d | %s   best %s (%.0f TFLOP/s)" % (
             IN_MODES.get(d.in_mode, "?"), "%d->%d" % (d.Cin, d.Cout), "%dx%dx%d" % (d.D, d.H, d.W), split,
             "  ".join("%9.4f" % med[n] for n, _ in variants), best, fl / med[best] / 1e9))
+        if ap_what == "phase":      # every round, so that the spread shows beside the difference
+            for n, _ in variants:
+                print("#   %-8s rounds: %s" % (n, "  ".join("%.4f" % v for v in times[n])))
 
 
 if __name__ == "__main__":
