@@ -610,6 +610,82 @@ int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, i
                     "joint_blend");
 }
 
+// ------------------------------------------------- sliding-window tiling (added within ABI 13)
+static int tiling_check(const char* what, int B, int Dc, int H, int W, int res, const ddpm3d_tiling* t, bool blend,
+                        int64_t* patches) {
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "%s: B=%d canvases (1..%d)", what, B, DDPM3D_MAX_DRAWS);
+    if (res < 1 || res > 1024) return fail(DDPM3D_EINVAL, "%s: res=%d (1..1024)", what, res);
+    if (Dc < 1 || H < 1 || W < 1 || Dc > 65535 || H > 65535 || W > 65535 || (int64_t)H * W > 0x7fffffff - 256)
+        return fail(DDPM3D_EINVAL, "%s: bad canvas (Dc=%d H=%d W=%d; 1..65535 each, H * W <= 2^31 - 257)", what, Dc, H,
+                    W);
+    if (!t->d_starts || (blend && (!t->d_cover || !t->d_tables)))
+        return fail(DDPM3D_EINVAL, "%s: null device table in the tiling descriptor", what);
+    if (blend && ((reinterpret_cast<uintptr_t>(t->d_cover) | reinterpret_cast<uintptr_t>(t->d_tables)) & 7))
+        return fail(DDPM3D_EINVAL, "%s: d_cover and d_tables must be 8-byte aligned", what);
+    const struct { const char* name; int extent; } axes[3] = {{"H", H}, {"W", W}, {"D", Dc}};
+    int64_t P = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int n = t->n[a], extent = axes[a].extent;
+        const int32_t* s = t->starts[a];
+        // a patch covers at least one coordinate of its own, so an axis holds at most `extent` ascending starts
+        if (n < 1 || n > extent || !s)
+            return fail(DDPM3D_EINVAL, "%s: %d starts on axis %s (1..%d, not NULL)", what, n, axes[a].name, extent);
+        for (int i = 0; i < n; ++i) {
+            if (s[i] < 0 || s[i] > extent - res)
+                return fail(DDPM3D_EINVAL, "%s: patch at %d on axis %s outside the canvas (starts 0..%d)", what, s[i],
+                            axes[a].name, extent - res);
+            if (i && s[i] <= s[i - 1])
+                return fail(DDPM3D_EINVAL, "%s: starts on axis %s do not ascend (%d after %d)", what, axes[a].name,
+                            s[i], s[i - 1]);
+        }
+        if (blend) {
+            // ascending starts: the union of [start, start + res) is the axis iff it begins at 0, ends at the extent
+            // and no neighbour starts beyond its predecessor's end
+            int gap = s[0] > 0 ? 0 : -1;
+            for (int i = 1; i < n && gap < 0; ++i)
+                if (s[i] > s[i - 1] + res) gap = s[i - 1] + res;
+            if (gap < 0 && s[n - 1] + res < extent) gap = s[n - 1] + res;
+            if (gap >= 0)
+                return fail(DDPM3D_EINVAL, "%s: coordinate %d of axis %s is covered by no patch", what, gap,
+                            axes[a].name);
+        }
+        P *= n;                                   // at most 65535^3 < 2^48
+    }
+    // rows are indexed in 32 bits inside the kernels, elements in 64
+    const int64_t rows = P * B, r3 = (int64_t)res * res * res;
+    if (rows > 0x7fffffff || rows > ((int64_t)1 << 61) / r3)
+        return fail(DDPM3D_EINVAL, "%s: %lld patches x %d canvases of %d^3 are too many rows", what, (long long)P, B,
+                    res);
+    *patches = P;
+    return DDPM3D_OK;
+}
+
+int ddpm3d_tiles_gather(const float* canvas, int B, int Dc, int H, int W, int res, const ddpm3d_tiling* tiling,
+                        int first_patch, int n_patches, float* out, void* stream) {
+    if (!canvas || !tiling || !out) return fail(DDPM3D_EINVAL, "tiles_gather: null pointer");
+    int64_t P = 0;
+    const int rc = tiling_check("tiles_gather", B, Dc, H, W, res, tiling, false, &P);
+    if (rc != DDPM3D_OK) return rc;
+    if (first_patch < 0 || n_patches < 1 || first_patch > P - n_patches)
+        return fail(DDPM3D_EINVAL, "tiles_gather: patches %d..%lld of %lld", first_patch,
+                    (long long)first_patch + n_patches - 1, (long long)P);
+    return launched(ddpm3d_launch_tiles_gather(canvas, B, Dc, H, W, res, *tiling, first_patch, n_patches, out,
+                                               (hipStream_t)stream),
+                    "tiles_gather");
+}
+
+int ddpm3d_tiles_blend(const float* patch_values, int B, int Dc, int H, int W, int res, const ddpm3d_tiling* tiling,
+                       float* out_canvas, void* stream) {
+    if (!patch_values || !tiling || !out_canvas) return fail(DDPM3D_EINVAL, "tiles_blend: null pointer");
+    int64_t P = 0;
+    const int rc = tiling_check("tiles_blend", B, Dc, H, W, res, tiling, true, &P);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_tiles_blend(patch_values, B, Dc, H, W, res, *tiling, out_canvas,
+                                              (hipStream_t)stream),
+                    "tiles_blend");
+}
+
 // ------------------------------------------------- image-quality metrics (added within ABI 13)
 static const int64_t EM_MAX_VOXELS = (int64_t)1 << 40;
 static bool ssim_shape_ok(int D, int H, int W) {

@@ -81,3 +81,10 @@ hipError_t ddpm3d_launch_joint_gather(const float* canvas, int B, int Dc, int H,
                                       hipStream_t st);
 hipError_t ddpm3d_launch_joint_blend(const float* patches, int B, int Dc, int H, int W, int res,
                                      const ddpm3d_joint_starts& s, const double* tables, float* out, hipStream_t st);
+// tiling.hip: the same two operations for any number of starts per axis (tables in device memory)
+struct ddpm3d_tiling;
+hipError_t ddpm3d_launch_tiles_gather(const float* canvas, int B, int Dc, int H, int W, int res,
+                                      const ddpm3d_tiling& t, int first_patch, int n_patches, float* out,
+                                      hipStream_t st);
+hipError_t ddpm3d_launch_tiles_blend(const float* patches, int B, int Dc, int H, int W, int res,
+                                     const ddpm3d_tiling& t, float* out, hipStream_t st);

@@ -98,6 +98,13 @@ class JointStarts(C.Structure):
                 ("ys", C.c_int32 * JOINT_MAX_STARTS), ("zs", C.c_int32 * JOINT_MAX_STARTS)]
 
 
+class Tiling(C.Structure):
+    """struct ddpm3d_tiling: host starts per axis (H, W, D) and the device copies of the starts, the per-coordinate
+    {first covering patch, count} lookup and the three fp64 weight tables"""
+    _fields_ = [("n", C.c_int32 * 3), ("starts", C.POINTER(C.c_int32) * 3), ("d_starts", C.c_void_p),
+                ("d_cover", C.c_void_p), ("d_tables", C.c_void_p)]
+
+
 LAYER_RES, LAYER_ATTN, LAYER_DOWNCONV, LAYER_UPCONV = 1, 2, 3, 4
 UPDOWN = {None: 0, "down": 1, "up": 2}
 
@@ -157,6 +164,9 @@ EXPORTS = {
                                       C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_joint_blend": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JointStarts), _fp,
                                      _fp, _fp]),
+    "ddpm3d_tiles_gather": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Tiling), C.c_int,
+                                      C.c_int, _fp, _fp]),
+    "ddpm3d_tiles_blend": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Tiling), _fp, _fp]),
     "ddpm3d_error_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "ddpm3d_error_moments": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int64, _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_ssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

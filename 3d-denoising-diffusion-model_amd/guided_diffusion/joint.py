@@ -14,9 +14,14 @@ every voxel (ddpm3d_joint_blend).  Every patch sees the same x_t and the same
 noise in an overlap, and the noise is never averaged.  The forwards per volume
 are unchanged (patches x steps); DESIGN.md 3.7.
 
-Both kernels are HIP (csrc/joint.hip); there is no host fallback.
+Both kernels are HIP (csrc/joint.hip); there is no host fallback.  A sliding
+geometry (patches.joint_geometry(..., min_overlap=N): any volume size, any
+number of patches per axis) takes the same two steps through
+ddpm3d_tiles_gather / ddpm3d_tiles_blend (csrc/tiling.hip), which keep the
+starts in device memory and visit only the patches that cover a voxel.
 """
 
+import ctypes
 import weakref
 
 import numpy as np
@@ -24,6 +29,8 @@ import torch as th
 
 from . import _hip as H
 from . import dist_util
+from . import logger
+from . import patches
 
 
 _DEVICE_GEOMETRY = weakref.WeakKeyDictionary()       # JointGeometry -> {device: (starts, tables)}
@@ -47,6 +54,29 @@ def _device_geometry(geom, device):
     return cache[key]
 
 
+def _device_tiling(geom, device):
+    """ddpm3d_tiling of a sliding geometry on `device`: the host starts, their device copy, the per-coordinate
+    {first covering patch, count} lookup (patches.axis_cover) and the three weight tables.  Built once per geometry
+    and device; the cache entry keeps the arrays the descriptor points into alive."""
+    cache = _DEVICE_GEOMETRY.setdefault(geom, {})
+    key = "tiling:" + str(device)
+    if key not in cache:
+        Dc, Hh, W = geom.canvas
+        axes = ((geom.x_starts, Hh), (geom.y_starts, W), (geom.z_starts, Dc))
+        host = [np.ascontiguousarray(starts, dtype=np.int32) for starts, _ in axes]
+        cover = np.concatenate([patches.axis_cover(starts, extent, geom.res) for starts, extent in axes])
+        tables = np.concatenate([np.ascontiguousarray(t, dtype=np.float64).ravel()
+                                 for t in (geom.a_x, geom.a_y, geom.a_z)])
+        dev = [th.from_numpy(a).to(device) for a in (np.concatenate(host), np.ascontiguousarray(cover), tables)]
+        t = H.Tiling()
+        for a, arr in enumerate(host):
+            t.n[a] = len(arr)
+            t.starts[a] = arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        t.d_starts, t.d_cover, t.d_tables = (d.data_ptr() for d in dev)
+        cache[key] = (t, host, dev)
+    return cache[key][0]
+
+
 def gather(canvas, geom, first_patch=0, n_patches=None, out=None):
     """(B, Dc, H, W) float32 canvases on the device -> (n_patches * B, 1, res, res, res) patches first_patch ..
     first_patch + n_patches - 1 of the geometry, patch-major, draw-minor.  A copy: bit-exact."""
@@ -63,8 +93,13 @@ def gather(canvas, geom, first_patch=0, n_patches=None, out=None):
         if out.numel() != n * B * r ** 3:
             raise ValueError("out holds %d elements, %d patches x %d draws need %d"
                              % (out.numel(), n, B, n * B * r ** 3))
-    starts, _ = _device_geometry(geom, canvas.device)
     Dc, Hh, W = geom.canvas
+    if geom.min_overlap is not None:
+        with th.cuda.device(canvas.device):
+            H.check(H.load().ddpm3d_tiles_gather(H.ptr(canvas), B, Dc, Hh, W, r, _device_tiling(geom, canvas.device),
+                                                 int(first_patch), n, H.ptr(out), H.stream()))
+        return out
+    starts, _ = _device_geometry(geom, canvas.device)
     with th.cuda.device(canvas.device):
         H.check(H.load().ddpm3d_joint_gather(H.ptr(canvas), B, Dc, Hh, W, r, starts, int(first_patch), n, H.ptr(out),
                                              H.stream()))
@@ -85,8 +120,13 @@ def blend(patch_values, geom, num_draws=1, out=None):
         H.require_device(out, "out")
         if tuple(out.shape) != (B,) + tuple(geom.canvas):
             raise ValueError("out of shape %s, expected %s" % (tuple(out.shape), (B,) + tuple(geom.canvas)))
-    starts, tables = _device_geometry(geom, patch_values.device)
     Dc, Hh, W = geom.canvas
+    if geom.min_overlap is not None:
+        with th.cuda.device(patch_values.device):
+            H.check(H.load().ddpm3d_tiles_blend(H.ptr(patch_values), B, Dc, Hh, W, r,
+                                                _device_tiling(geom, patch_values.device), H.ptr(out), H.stream()))
+        return out
+    starts, tables = _device_geometry(geom, patch_values.device)
     with th.cuda.device(patch_values.device):
         H.check(H.load().ddpm3d_joint_blend(H.ptr(patch_values), B, Dc, Hh, W, r, starts, H.ptr(tables), H.ptr(out),
                                             H.stream()))
@@ -94,14 +134,19 @@ def blend(patch_values, geom, num_draws=1, out=None):
 
 
 def _canvas_of(volume, geom, device):
-    """A (D, H, W) volume (numpy or tensor, D <= Dc) as one zero-extended (1, Dc, H, W) float32 canvas on `device`."""
+    """A (D, H, W) volume (numpy or tensor, D <= Dc) as one zero-extended (1, Dc, H, W) float32 canvas on `device`.
+    A sliding geometry's canvas extends H and W to one patch as well."""
     vol = th.as_tensor(volume, dtype=th.float32)
     Dc, Hh, W = geom.canvas
-    if vol.dim() != 3 or tuple(vol.shape[1:]) != (Hh, W) or vol.shape[0] > Dc:
+    if geom.min_overlap is not None:
+        fits = vol.dim() == 3 and all(v <= c for v, c in zip(vol.shape, geom.canvas))
+    else:
+        fits = vol.dim() == 3 and tuple(vol.shape[1:]) == (Hh, W) and vol.shape[0] <= Dc
+    if not fits:
         raise ValueError("low_res volume of shape %s does not fit the canvas %s"
                          % (tuple(vol.shape), tuple(geom.canvas)))
     canvas = th.zeros((1, Dc, Hh, W), dtype=th.float32, device=device)
-    canvas[0, :vol.shape[0]] = vol.to(device)
+    canvas[0, :vol.shape[0], :vol.shape[1], :vol.shape[2]] = vol.to(device)
     return canvas
 
 
@@ -149,17 +194,37 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
         H.require_device(img, "noise")
         if tuple(img.shape) != cshape:
             raise ValueError("noise of shape %s, expected %s" % (tuple(img.shape), cshape))
-        low_res = gather(_canvas_of(low_res_volume, geom, device), geom).repeat_interleave(K, dim=0)
+        xg = th.empty((bs * K, 1, r, r, r), dtype=th.float32, device=device)
+        zg = th.empty_like(xg)
+        sliding = geom.min_overlap is not None
+        if sliding:
+            # any number of patches: the conditioning patches are cut per batch, not held for the whole volume
+            low_canvas = _canvas_of(low_res_volume, geom, device)
+            lrg, lr1 = th.empty_like(xg), (th.empty((bs, 1, r, r, r), dtype=th.float32, device=device) if K > 1
+                                           else None)
+            logger.log("joint sampling: %d patches x %d draws, %.2f GB for the updated patches of a step"
+                       % (P, K, 2 * P * K * r ** 3 * 4 / 1e9))
+
+            def cond(lo, hi):
+                n = (hi - lo) // K
+                if K == 1:
+                    return gather(low_canvas, geom, lo, n, out=lrg[:n])
+                gather(low_canvas, geom, lo // K, n, out=lr1[:n])
+                lrg[:hi - lo].view(n, K, -1).copy_(lr1[:n].view(n, 1, -1).expand(n, K, -1))
+                return lrg[:hi - lo]
+        else:
+            low_res = gather(_canvas_of(low_res_volume, geom, device), geom).repeat_interleave(K, dim=0)
+
+            def cond(lo, hi):
+                return low_res[lo:hi]
         nets = {}                                 # one step table per batch size (there are at most two)
         for b in rounds:
             if b is not None:
                 lo, hi = rows(b)
                 if hi - lo not in nets:
-                    nets[hi - lo] = diffusion._step_model(model, (hi - lo, 1, r, r, r),
-                                                          {"low_res": low_res[lo:hi]}, device)
+                    nets[hi - lo] = diffusion._step_model(model, (hi - lo, 1, r, r, r), {"low_res": cond(lo, hi)},
+                                                          device)
         updated = th.empty((2, P * K, 1, r, r, r), dtype=th.float32, device=device)   # sample, pred_xstart
-        xg = th.empty((bs * K, 1, r, r, r), dtype=th.float32, device=device)
-        zg = th.empty_like(xg)
         block = th.zeros((2, bs * K, 1, r, r, r), dtype=th.float32, device=device) if world > 1 else None
 
     for k, i in enumerate(range(diffusion.num_timesteps - 1, -1, -1)):
@@ -174,7 +239,7 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                     gather(img, geom, lo // K, (hi - lo) // K, out=x)
                     gather(z, geom, lo // K, (hi - lo) // K, out=zb)
                     dst = updated[:, lo:hi] if world == 1 else block[:, :hi - lo]
-                    diffusion._update(kind, net(x, i, low_res[lo:hi]), x, t_all[i], zb, clip_denoised, eta,
+                    diffusion._update(kind, net(x, i, cond(lo, hi)), x, t_all[i], zb, clip_denoised, eta,
                                       out=(dst[0], dst[1]))
                 if world > 1:
                     for bb, blk in dist_util.gather_round(block, b):

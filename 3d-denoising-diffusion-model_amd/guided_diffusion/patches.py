@@ -48,6 +48,46 @@ def patch_grid(shape_dhw, resolution, num_xy=3):
             for ys in xy_starts(W, resolution, num_xy) for zs in z_starts(D, resolution)]
 
 
+def sliding_starts(extent, res, min_overlap):
+    """Gap-free patch starts along one axis of any length: [0] when one (zero-padded) patch holds
+    the axis, otherwise the fewest evenly spread starts, first 0 and last extent - res, whose neighbours overlap by
+    at least min_overlap.  min_overlap is in 2..res - 1: np.hanning is 0 at both ends of a patch, so an overlap of
+    0 or 1 can leave planes inside the volume without any weight."""
+    extent, res, min_overlap = int(extent), int(res), int(min_overlap)
+    if extent < 1 or res < 1:
+        raise ValueError("sliding_starts: bad axis (extent %d, patch size %d)" % (extent, res))
+    if not 2 <= min_overlap <= res - 1:
+        raise ValueError("sliding_starts: the overlap must be in 2..%d (patch size %d), got %d"
+                         % (res - 1, res, min_overlap))
+    if extent <= res:
+        return [0]
+    span, stride = extent - res, res - min_overlap
+    n = (span + stride - 1) // stride + 1
+    return [(i * span) // (n - 1) for i in range(n)]
+
+
+def sliding_grid(shape_dhw, res, min_overlap):
+    """[(x_start, y_start, z_start)] of the sliding tiling, in patch_grid's nesting order (x, y, z)."""
+    D, H, W = shape_dhw
+    return [(xs, ys, zs) for xs in sliding_starts(H, res, min_overlap)
+            for ys in sliding_starts(W, res, min_overlap) for zs in sliding_starts(D, res, min_overlap)]
+
+
+def grid_gaps(shape_dhw, res, num_xy=3):
+    """Coordinates per axis {"D": n, "H": n, "W": n} that no patch of patch_grid covers (all 0: the fixed grid
+    tiles the volume).  A voxel is written by the one-shot stitcher only if all three of its coordinates are
+    covered."""
+    D, H, W = (int(v) for v in shape_dhw)
+    gaps = {}
+    for axis, extent, starts in (("D", D, z_starts(D, res)), ("H", H, xy_starts(H, res, num_xy)),
+                                 ("W", W, xy_starts(W, res, num_xy))):
+        cover = np.zeros(extent, dtype=bool)
+        for s in starts:
+            cover[max(s, 0):max(s + res, 0)] = True
+        gaps[axis] = int((~cover).sum())
+    return gaps
+
+
 def split_volume(vol, resolution, num_xy=3):
     """(D,H,W) volume -> (P, 1, Z, H, W) float32 zero-padded patches + the grid.
     (The reference routes through an (H,W,Z) transpose and back; the result is the
@@ -122,8 +162,9 @@ def load_volume(path):
 class JointGeometry:
     """Canvas, patch starts and per-axis blend tables of one volume (joint_geometry)."""
 
-    def __init__(self, canvas, res, x_starts, y_starts, z_starts, a_x, a_y, a_z):
+    def __init__(self, canvas, res, x_starts, y_starts, z_starts, a_x, a_y, a_z, min_overlap=None):
         self.canvas, self.res = canvas, res
+        self.min_overlap = min_overlap            # None: patch_grid's fixed grid; an integer: the sliding grid
         self.x_starts, self.y_starts, self.z_starts = x_starts, y_starts, z_starts
         self.a_x, self.a_y, self.a_z = a_x, a_y, a_z
 
@@ -160,12 +201,35 @@ def _axis_table(starts, extent, res, axis):
     return table
 
 
-def joint_geometry(shape_dhw, res, num_xy=3):
+def axis_cover(starts, extent, res):
+    """(extent, 2) int32: per coordinate of one axis, {index of the first covering patch, number of covering
+    patches}.  Ascending starts make the covering patches of a coordinate one run of indices (ddpm3d_tiling.d_cover:
+    what ddpm3d_tiles_blend walks instead of all patches)."""
+    starts = np.asarray(starts, dtype=np.int64)
+    if starts.ndim != 1 or len(starts) < 1 or (np.diff(starts) <= 0).any():
+        raise ValueError("axis_cover: starts must ascend, got %s" % (list(starts),))
+    c = np.arange(extent)
+    first = np.searchsorted(starts, c - res, side="right")       # first i with starts[i] + res > c
+    end = np.searchsorted(starts, c, side="right")               # first i with starts[i] > c
+    return np.stack([first, end - first], axis=1).astype(np.int32)
+
+
+def joint_geometry(shape_dhw, res, num_xy=3, min_overlap=None):
     """Geometry of joint patch sampling for a (D, H, W) volume: the canvas (max(D, res), H, W), patch_grid's
     per-axis starts and the normalised blend weight as three fp64 tables,
-    nw_p(z, x, y) = a_x[ix][x] * a_y[iy][y] * a_z[iz][z], which sum to 1 over the patches at every canvas voxel."""
+    nw_p(z, x, y) = a_x[ix][x] * a_y[iy][y] * a_z[iz][z], which sum to 1 over the patches at every canvas voxel.
+    With min_overlap (an integer in 2..res - 1) the starts are sliding_starts' on all three axes, for a volume of
+    any size, and the canvas is max(extent, res) on every axis (num_xy is not used)."""
     D, H, W = (int(v) for v in shape_dhw)
     res = int(res)
+    if min_overlap is not None:
+        if res < 1 or min(D, H, W) < 1:
+            raise ValueError("joint_geometry: bad shape (D=%d H=%d W=%d, patch size %d)" % (D, H, W, res))
+        canvas = tuple(max(n, res) for n in (D, H, W))
+        xs, ys, zs = (sliding_starts(n, res, min_overlap) for n in (H, W, D))
+        return JointGeometry(canvas, res, xs, ys, zs, _axis_table(xs, canvas[1], res, "H"),
+                             _axis_table(ys, canvas[2], res, "W"), _axis_table(zs, canvas[0], res, "D"),
+                             min_overlap=int(min_overlap))
     if res < 1 or D < 1:
         raise ValueError("joint_geometry: bad shape (D=%d, patch size %d)" % (D, res))
     for axis, n in (("H", H), ("W", W)):

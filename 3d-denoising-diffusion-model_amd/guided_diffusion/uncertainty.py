@@ -37,24 +37,31 @@ def draw_moments(draws):
     return mean, std
 
 
-class DrawStitcher:
-    """K full-volume accumulators and one weight sum on the device, (K + 1) * H * W * D * 4 bytes.
+class VolumeStitcher:
+    """K >= 1 full-volume accumulators and one weight sum on the device, (K + 1) * H * W * D * 4 bytes: the one-shot
+    Hann blend of patches.stitch_patches, patch by patch as the patches arrive, so that no rank holds all patches.
 
     add(global_index, samples_kcdhw, origin) blends one patch origin's K draws, as the sampler returns them
-    ((K, 1, res, res, res) NCDHW float32), at origin = (x_start, y_start, z_start) of patches.patch_grid;
+    ((K, 1, res, res, res) NCDHW float32), at origin = (x_start, y_start, z_start) of the patch grid;
     patches must come in ascending global index (the order patches.stitch_patches sums in).
-    finish() -> (mean, std, weight), each (H, W, D) float32 on the device (the reference's (H, W, Z) layout);
-    voxels of weight 0 are 0 in mean and std."""
+    finish() (K >= 2) -> (mean, std, weight), each (H, W, D) float32 on the device (the reference's (H, W, Z)
+    layout); voxels of weight 0 are 0 in mean and std.
+    finish_single() (K = 1) -> (volume, weight), (H, W, D) float32 host arrays: patches.stitch_patches' result bit
+    for bit.  The sums are the device's; the one division per voxel is numpy's on the host, as in stitch_patches."""
+
+    _MIN_DRAWS = 1
 
     def __init__(self, shape_dhw, resolution, num_draws, device):
-        _check_draws(num_draws, "DrawStitcher")
+        if not (isinstance(num_draws, int) and self._MIN_DRAWS <= num_draws <= H.MAX_DRAWS):
+            raise ValueError("%s: needs %d..%d draws, got %r"
+                             % (type(self).__name__, self._MIN_DRAWS, H.MAX_DRAWS, num_draws))
         D, Hh, W = (int(v) for v in shape_dhw)
         self.shape_hwd = (Hh, W, D)
         self.res = int(resolution)
         self.K = int(num_draws)
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("DrawStitcher runs on HIP kernels only (got device %s)" % self.device)
+            raise RuntimeError("%s runs on HIP kernels only (got device %s)" % (type(self).__name__, self.device))
         self.acc = torch.zeros((self.K,) + self.shape_hwd, dtype=torch.float32, device=self.device)
         self.wsum = torch.zeros(self.shape_hwd, dtype=torch.float32, device=self.device)
         self.window = torch.from_numpy(np.ascontiguousarray(patches.hann_window_3d(self.res))).to(self.device)
@@ -62,12 +69,12 @@ class DrawStitcher:
 
     def add(self, global_index, samples_kcdhw, origin):
         if global_index <= self._last:
-            raise ValueError("DrawStitcher.add: patch %d after patch %d -- patches must come in ascending order"
-                             % (global_index, self._last))
+            raise ValueError("%s.add: patch %d after patch %d -- patches must come in ascending order"
+                             % (type(self).__name__, global_index, self._last))
         r = self.res
         if tuple(samples_kcdhw.shape) != (self.K, 1, r, r, r):
-            raise ValueError("DrawStitcher.add: samples of shape %s, expected %s"
-                             % (tuple(samples_kcdhw.shape), (self.K, 1, r, r, r)))
+            raise ValueError("%s.add: samples of shape %s, expected %s"
+                             % (type(self).__name__, tuple(samples_kcdhw.shape), (self.K, 1, r, r, r)))
         H.require_device(samples_kcdhw, "samples")
         xs, ys, zs = (int(v) for v in origin)
         Hh, W, D = self.shape_hwd
@@ -77,9 +84,23 @@ class DrawStitcher:
         self._last = global_index
 
     def finish(self):
+        _check_draws(self.K, type(self).__name__ + ".finish")
         mean = torch.empty(self.shape_hwd, dtype=torch.float32, device=self.device)
         std = torch.empty_like(mean)
         with torch.cuda.device(self.device):
             H.check(H.load().ddpm3d_draw_moments(H.ptr(self.acc), H.ptr(self.wsum), self.K, mean.numel(), H.ptr(mean),
                                                  H.ptr(std), H.stream()))
         return mean, std, self.wsum
+
+    def finish_single(self):
+        if self.K != 1:
+            raise ValueError("%s.finish_single: one draw only, this stitcher holds %d (use finish())"
+                             % (type(self).__name__, self.K))
+        acc, wsum = self.acc[0].cpu().numpy(), self.wsum.cpu().numpy()
+        return np.divide(acc, wsum, out=acc.copy(), where=wsum > 0), wsum
+
+
+class DrawStitcher(VolumeStitcher):
+    """VolumeStitcher for the uncertainty maps: K >= 2 draws."""
+
+    _MIN_DRAWS = 2

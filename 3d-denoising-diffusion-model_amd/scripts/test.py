@@ -12,7 +12,17 @@ results with a 3-D Hann window.
 
 Differences from the reference script, all on the host side: `.npz`/`.npy`
 inputs are accepted besides `.tif` (README.md:67 asks users to edit the loader;
-scripts/test.py:187 rejects them); volumes need not be 200x200; `--use_ddim`
+scripts/test.py:187 rejects them); volumes need not be 200x200, but the default
+tiling is the reference's fixed grid of 3 x 3 x (1 | 2) patches, which covers a
+volume only up to 3 x 3 x 2 patch sizes (H, W, D): beyond that it leaves gaps
+(written as 0, with one warning in the log), and `--patch_overlap N` (N in
+2..patch size - 1) tiles a volume of any size without gaps instead, with as many
+evenly spread patches per axis as it takes for neighbours to overlap by at
+least N voxels (patches.sliding_starts; 44 extends the reference's grid for
+200 x 200 volumes).  With it the volume is uploaded once, every batch's
+conditioning patches are cut on the device and finished patches are blended on
+rank 0's device as they arrive, for all of the one-shot path, `--num_draws` and
+`--joint_patches`; `--use_ddim`
 is honoured (the reference parses it but always runs DDPM, scripts/test.py:63);
 `--use_dpm_solver True` (with `--solver_order`, `--solver_stochastic`) samples
 with DPM-Solver++ instead and takes precedence over `--use_ddim`; pair it with
@@ -73,6 +83,9 @@ def create_argparser():
                     num_draws=1,
                     # one state for the whole volume, blended after every step (not in the reference)
                     joint_patches=False,
+                    # minimum overlap of neighbouring patches of the gap-free sliding grid (not in the reference);
+                    # -1 = the reference's fixed 3 x 3 x (1 | 2) grid
+                    patch_overlap=-1,
                     # full-dose volume to score the result against (not in the reference); "" = no metrics
                     target_samples="", data_range=0.0, metrics_mask_threshold=0.0)
     defaults.update(sr_model_and_diffusion_defaults())
@@ -89,6 +102,9 @@ def main(argv=None):
     if args.joint_patches and args.use_dpm_solver:
         parser.error("--joint_patches True samples with DDPM or DDIM; it cannot be combined with "
                      "--use_dpm_solver True")
+    if args.patch_overlap != -1 and not 2 <= args.patch_overlap <= args.large_size - 1:
+        parser.error("--patch_overlap must be in 2..%d for patches of %d (got %d); -1 keeps the fixed 3 x 3 x (1 | 2) "
+                     "grid" % (args.large_size - 1, args.large_size, args.patch_overlap))
     vol, target = _load_target(parser, args)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
@@ -115,8 +131,15 @@ def main(argv=None):
     res = args.large_size
     if args.joint_patches:
         return _main_joint(args, model, diffusion, vol, target)
+    if args.patch_overlap >= 0:
+        return _main_sliding(args, model, diffusion, vol, target)
     low_res, grid = patches.split_volume(vol, res)               # (P, 1, Z, H, W)
     logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3")
+    gaps = patches.grid_gaps(vol.shape, res)
+    if any(gaps.values()):
+        logger.log("WARNING: the fixed 3 x 3 x (1 | 2) grid does not cover this volume (coordinates without a patch: "
+                   + ", ".join("%d of %d along %s" % (gaps[a], n, a) for a, n in zip("DHW", vol.shape) if gaps[a])
+                   + "); those voxels are written as 0.  --patch_overlap N tiles a volume of any size without gaps.")
 
     # Work units are batches of --batch_size patches; batch b goes to rank b mod W
     # (scripts/test.py:243 with batch_size 1), every rank runs the same number of rounds.
@@ -310,18 +333,88 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
     return out_path
 
 
+def _main_sliding(args, model, diffusion, vol, target=None):
+    """--patch_overlap N: the one-shot path (and --num_draws K) on the gap-free sliding grid.  The volume is uploaded
+    once as a zero-extended canvas; every batch's conditioning patches are cut from it on the device
+    (ddpm3d_tiles_gather); gathered rounds are blended on rank 0's device in ascending patch order as they arrive
+    (uncertainty.VolumeStitcher: patches.stitch_patches' arithmetic), so no rank holds all patches.  Noise is keyed
+    by the global patch index (and draw), as in the default path."""
+    dev = dist_util.dev()
+    rank = dist_util.rank()
+    K, res, bs = args.num_draws, args.large_size, max(1, args.batch_size)
+    geom = patches.joint_geometry(vol.shape, res, min_overlap=args.patch_overlap)
+    grid = geom.grid
+    logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3 ({len(geom.x_starts)} x {len(geom.y_starts)} x "
+               f"{len(geom.z_starts)} along H, W, D; neighbours overlap by at least {args.patch_overlap})")
+    sample_loop, extra = _sampler(args, diffusion)
+    canvas = joint._canvas_of(vol, geom, dev)
+    stitcher = uncertainty.VolumeStitcher(vol.shape, res, K, dev) if rank == 0 else None
+    for b in dist_util.partition((len(grid) + bs - 1) // bs):
+        block = th.zeros(bs * K, 1, res, res, res, device=dev)               # padded so collectives stay aligned
+        if b is not None:
+            idx = list(range(b * bs, min((b + 1) * bs, len(grid))))
+            cond = joint.gather(canvas, geom, idx[0], len(idx))
+            if K > 1:
+                cond = cond.repeat_interleave(K, dim=0)
+            shape = tuple(cond.shape)
+            gens = [dist_util.volume_generator(i, seed=10, device=dev, draw=d) for i in idx for d in range(K)]
+
+            def draw(_k=None, _img=None):
+                return th.cat([th.randn(1, *shape[1:], device=dev, generator=g) for g in gens])
+
+            noise = draw()
+            logger.log(f"rank {rank}: patches {idx[0]}..{idx[-1]} x {K} draws shape={shape}")
+            block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
+                                               model_kwargs={"low_res": cond}, step_noise=draw, **extra)
+        for bb, blk in dist_util.gather_round(block, b):
+            if stitcher is None:
+                continue
+            blk = blk.to(dev)
+            for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
+                stitcher.add(i, blk[j * K:(j + 1) * K], grid[i])
+    out_path = None
+    if rank == 0:
+        logger.log("Reconstructing full image with Hann window blending...")
+        extra_out, std = {}, None
+        if K > 1:
+            mean, std, weight = stitcher.finish()
+            result = mean.cpu().numpy()                                    # (H, W, Z)
+            extra_out["std"] = std.cpu().numpy()
+            covered = std[weight > 0]
+            logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
+                       f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
+        else:
+            result, weight = stitcher.finish_single()
+        logger.log(f"  Original std: {float(vol.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
+        logger.log(f"saving to {out_path}")
+        np.savez(out_path, result, **extra_out)                            # arr_0 [+ std], (H,W,Z)
+        if args.base_samples.lower().endswith((".tif", ".tiff")):
+            from guided_diffusion import tiff_io
+            tiff_path = out_path.replace(".npz", ".tif")
+            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))
+            if K > 1:
+                tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
+                                extra_out["std"].transpose(2, 0, 1).astype(np.float32))
+            logger.log(f"Saved denoised TIFF: {tiff_path}")
+        _write_metrics(args, out_path, target, vol, result, std=std, weight=weight)
+    dist_util.barrier()
+    logger.log("Full image denoising complete")
+    return out_path
+
+
 def _main_joint(args, model, diffusion, vol, target=None):
     """--joint_patches True: every rank holds the whole canvas and runs its share of each step's forwards
     (joint.sample_loop_progressive); rank 0 writes the canvas cropped to the volume, (H, W, Z) like the other paths.
     With --num_draws K >= 2 the K canvases are reduced to the per-voxel mean and sample std."""
     rank = dist_util.rank()
     K, res = args.num_draws, args.large_size
-    geom = patches.joint_geometry(vol.shape, res)
+    geom = patches.joint_geometry(vol.shape, res, min_overlap=args.patch_overlap if args.patch_overlap >= 0 else None)
     logger.log(f"volume {vol.shape}: {geom.n_patches} patches of {res}^3, sampled jointly on a {geom.canvas} canvas")
     sample = joint.sample_loop(diffusion, model, vol, geom, kind="ddim" if args.use_ddim else "ddpm", num_draws=K,
                                batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
                                device=dist_util.dev())
-    draws = sample[:, :vol.shape[0]].contiguous()                             # (K, D, H, W)
+    draws = sample[:, :vol.shape[0], :vol.shape[1], :vol.shape[2]].contiguous()     # (K, D, H, W)
     extra = {}
     if K > 1:
         mean, std = uncertainty.draw_moments(draws)

@@ -625,6 +625,39 @@ int ddpm3d_joint_gather(const float* canvas, int B, int Dc, int H, int W, int re
 int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, int res,
                        const ddpm3d_joint_starts* starts, const double* tables, float* out_canvas, void* stream);
 /*
+ * Sliding-window tiling (added within ABI 13): the two joint entries without DDPM3D_JOINT_MAX_STARTS, for volumes of
+ * any size.  Canvas, patch order (p = (ix * ny + iy) * nz + iz), row order (row = p * B + b) and arithmetic are those
+ * of ddpm3d_joint_gather / ddpm3d_joint_blend, bit for bit; the starts and the lookup that replaces the walk over all
+ * nx * ny * nz patches live in device memory, described by ddpm3d_tiling:
+ *   n[a], starts[a]  patches along H, W, D (a = 0, 1, 2) and their starts, HOST memory, strictly ascending; read and
+ *              checked on every call, never by the device
+ *   d_starts   DEVICE int32: the same starts, xs then ys then zs (n[0] + n[1] + n[2] values)
+ *   d_cover    DEVICE int32 pairs, 8-byte aligned: per coordinate {index of the first covering patch, number of
+ *              covering patches} for H, then W, then Dc coordinates (ascending starts make the covering patches of a
+ *              coordinate one run of indices); built by the caller once per geometry.  Only ddpm3d_tiles_blend reads
+ *              it (and d_tables); both may be NULL for ddpm3d_tiles_gather
+ *   d_tables   DEVICE fp64: the weight tables of ddpm3d_joint_blend, a_x [nx][H], a_y [ny][W], a_z [nz][Dc]
+ * ddpm3d_tiles_gather copies rows [first_patch * B, (first_patch + n_patches) * B) into out[n_patches * B][res^3];
+ * ddpm3d_tiles_blend writes every canvas voxel from its covering patches only.  Both use 16-byte accesses when W,
+ * res and every y start are multiples of 4 and both tensors are 16-byte aligned, and split their work into launches
+ * of at most 65535 rows.  One writer per element, no atomics.
+ * Both return DDPM3D_EINVAL before any launch for a NULL pointer, res outside 1..1024, an empty or oversized canvas
+ * (an axis above 65535, H * W above 2^31 - 257), an axis without a start, starts that do not ascend, a patch that
+ * leaves the canvas, a coordinate that no patch covers (blend), B outside 1..DDPM3D_MAX_DRAWS, a patch range outside
+ * 0..nx*ny*nz (gather), and nx * ny * nz * B rows above 2^31 - 1 or of more than 2^61 elements.
+ */
+typedef struct ddpm3d_tiling {
+    int32_t n[3];
+    const int32_t* starts[3];
+    const int32_t* d_starts;
+    const int32_t* d_cover;
+    const double* d_tables;
+} ddpm3d_tiling;
+int ddpm3d_tiles_gather(const float* canvas, int B, int Dc, int H, int W, int res, const ddpm3d_tiling* tiling,
+                        int first_patch, int n_patches, float* out, void* stream);
+int ddpm3d_tiles_blend(const float* patch_values, int B, int Dc, int H, int W, int res,
+                       const ddpm3d_tiling* tiling, float* out_canvas, void* stream);
+/*
  * Image-quality metrics of B estimates x_b against one full-dose target y (added within ABI 13; the reference has
  * no metric code).  est is [B][voxels] fp32, target [voxels] fp32, mask an optional uint8 [voxels] (a voxel counts
  * where mask != 0; NULL: every voxel counts), B in 1..DDPM3D_MAX_DRAWS.  Every workgroup writes one fp64 record to
