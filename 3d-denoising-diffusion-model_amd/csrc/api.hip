@@ -741,6 +741,57 @@ int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, in
                     "ssim3d");
 }
 
+// ------------------------------------------------- per-region moments (added within ABI 13)
+// Checks the host side of a region index; *chunks receives the number of chunks all regions are cut into.
+static int roi_index_check(int B, const ddpm3d_roi_index* ix, int64_t* chunks) {
+    if (!ix || !ix->offsets || !ix->d_offsets || !ix->d_chunks || !ix->d_index)
+        return fail(DDPM3D_EINVAL, "roi_moments: null pointer in the region index");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "roi_moments: B=%d estimates (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (ix->regions < 1 || ix->regions > DDPM3D_ROI_MAX_REGIONS)
+        return fail(DDPM3D_EINVAL, "roi_moments: %d regions (1..%d)", ix->regions, DDPM3D_ROI_MAX_REGIONS);
+    if (ix->entries < 0 || ix->entries > EM_MAX_VOXELS)
+        return fail(DDPM3D_EINVAL, "roi_moments: entries=%lld (0..2^40)", (long long)ix->entries);
+    if (ix->offsets[0] != 0)
+        return fail(DDPM3D_EINVAL, "roi_moments: offsets[0]=%lld, not 0", (long long)ix->offsets[0]);
+    int64_t n = 0;
+    for (int r = 0; r < ix->regions; ++r) {
+        const int64_t len = ix->offsets[r + 1] - ix->offsets[r];
+        if (len < 0 || ix->offsets[r + 1] > ix->entries)
+            return fail(DDPM3D_EINVAL, "roi_moments: offsets[%d]=%lld after %lld (non-decreasing, at most entries=%lld)",
+                        r + 1, (long long)ix->offsets[r + 1], (long long)ix->offsets[r], (long long)ix->entries);
+        n += (len + DDPM3D_ROI_CHUNK - 1) / DDPM3D_ROI_CHUNK;
+    }
+    if (ix->offsets[ix->regions] != ix->entries)
+        return fail(DDPM3D_EINVAL, "roi_moments: offsets end at %lld, not at entries=%lld",
+                    (long long)ix->offsets[ix->regions], (long long)ix->entries);
+    *chunks = n;                                  // at most 2^40 / 4096 + 4096: a grid's x extent
+    return DDPM3D_OK;
+}
+static size_t roi_ws_bytes(int B, int64_t chunks) {
+    return (size_t)B * (size_t)(chunks > 0 ? chunks : 1) * DDPM3D_ROI_REC * sizeof(double);
+}
+
+size_t ddpm3d_roi_moments_workspace_bytes(int B, const ddpm3d_roi_index* index) {
+    int64_t chunks = 0;
+    return roi_index_check(B, index, &chunks) == DDPM3D_OK ? roi_ws_bytes(B, chunks) : 0;
+}
+
+int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t voxels, const ddpm3d_roi_index* index,
+                       void* ws, size_t ws_bytes, double* out, void* stream) {
+    if (!est || !out) return fail(DDPM3D_EINVAL, "roi_moments: null pointer");
+    if (voxels <= 0 || voxels > EM_MAX_VOXELS)
+        return fail(DDPM3D_EINVAL, "roi_moments: voxels=%lld (1..2^40)", (long long)voxels);
+    int64_t chunks = 0;
+    int rc = roi_index_check(B, index, &chunks);
+    if (rc != DDPM3D_OK) return rc;
+    rc = metric_ws_ok("roi_moments", roi_ws_bytes(B, chunks), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_roi_moments(est, target, B, voxels, *index, chunks, (double*)ws, out,
+                                              (hipStream_t)stream),
+                    "roi_moments");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

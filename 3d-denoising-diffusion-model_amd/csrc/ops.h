@@ -73,6 +73,12 @@ hipError_t ddpm3d_launch_error_moments(const float* est, const float* target, co
 size_t ddpm3d_ss_workspace_bytes(int B, int D, int H, int W);
 hipError_t ddpm3d_launch_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W,
                                 float C1, float C2, double* ws, float* map, double* out, hipStream_t st);
+// roi.hip: per-region moments over a region index cut into `chunks` chunks in all (the caller has checked the
+// descriptor's host side and the workspace)
+struct ddpm3d_roi_index;
+hipError_t ddpm3d_launch_roi_moments(const float* est, const float* target, int B, int64_t voxels,
+                                     const ddpm3d_roi_index& ix, int64_t chunks, double* ws, double* out,
+                                     hipStream_t st);
 // joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
 // patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
 struct ddpm3d_joint_starts;

@@ -89,6 +89,10 @@ class UnetDesc(C.Structure):
 (EM_N, EM_SUM_E, EM_SUM_ABS_E, EM_SUM_SQ_E, EM_SUM_Y, EM_SUM_SQ_Y, EM_MIN_Y, EM_MAX_Y, EM_COVER_1, EM_COVER_2,
  EM_REC) = range(11)
 
+# DDPM3D_ROI_*: columns of a ddpm3d_roi_moments record, and the limits of a region index
+(ROI_N, ROI_SUM_X, ROI_SUM_SQ_X, ROI_MIN_X, ROI_MAX_X, ROI_SUM_E, ROI_SUM_ABS_E, ROI_SUM_SQ_E, ROI_REC) = range(9)
+ROI_MAX_REGIONS, ROI_CHUNK = 4096, 4096
+
 JOINT_MAX_STARTS = 8    # DDPM3D_JOINT_MAX_STARTS
 
 
@@ -103,6 +107,13 @@ class Tiling(C.Structure):
     {first covering patch, count} lookup and the three fp64 weight tables"""
     _fields_ = [("n", C.c_int32 * 3), ("starts", C.POINTER(C.c_int32) * 3), ("d_starts", C.c_void_p),
                 ("d_cover", C.c_void_p), ("d_tables", C.c_void_p)]
+
+
+class RoiIndex(C.Structure):
+    """struct ddpm3d_roi_index: R regions over `entries` sorted flat voxel indices in CSR form; host offsets and the
+    device copies of the offsets, the per-region first-chunk prefix and the index itself"""
+    _fields_ = [("regions", C.c_int32), ("entries", C.c_int64), ("offsets", C.POINTER(C.c_int64)),
+                ("d_offsets", C.c_void_p), ("d_chunks", C.c_void_p), ("d_index", C.c_void_p)]
 
 
 LAYER_RES, LAYER_ATTN, LAYER_DOWNCONV, LAYER_UPCONV = 1, 2, 3, 4
@@ -172,6 +183,8 @@ EXPORTS = {
     "ddpm3d_ssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "ddpm3d_ssim3d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _fp,
                                 C.c_size_t, _fp, _fp, _fp]),
+    "ddpm3d_roi_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(RoiIndex)]),
+    "ddpm3d_roi_moments": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.POINTER(RoiIndex), _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

@@ -7,8 +7,14 @@ metrics are one pass of a HIP kernel (csrc/metrics.hip, ddpm3d_error_moments / d
 against one shared target, and only the K small records come back, in one copy.  There is no host fallback.
 
 All of it is isotropic: (D, H, W) canvases and the inference script's (H, W, Z) volumes alike.
+
+Per-region (lesion / organ) statistics: roi_index turns a label volume into a region index on the
+device, roi_moments is one launch of ddpm3d_roi_moments (csrc/roi.hip) over it, roi_figures turns the records into
+SUVmean / SUVmax bias, contrast recovery, CNR, CoV and the spread of a region mean over draws, roi_report puts them
+together.
 """
 
+import ctypes
 import math
 
 import torch
@@ -163,3 +169,169 @@ def evaluate(estimate, target, data_range=None, mask=None, std=None):
     if std is not None:
         res["coverage_1"], res["coverage_2"] = m["coverage_1"], m["coverage_2"]
     return res
+
+
+# ----------------------------------------------------------------- per-region statistics
+class RoiIndex:
+    """A labelled volume as a region index (roi_index): `labels` (ascending positive ints), `counts` and host
+    `offsets` per region, the sorted flat voxel indices on the device, and the ddpm3d_roi_index descriptor."""
+
+    def __init__(self, shape, labels, counts, index):
+        self.shape = tuple(int(v) for v in shape)
+        self.voxels = int(math.prod(self.shape))
+        self.labels = [int(v) for v in labels]
+        self.counts = [int(v) for v in counts]
+        self.index = index                                        # device int64 [entries]
+        self.device = index.device
+        offsets = [0]
+        for n in self.counts:
+            offsets.append(offsets[-1] + n)
+        chunks = [0]
+        for n in self.counts:
+            chunks.append(chunks[-1] + (n + H.ROI_CHUNK - 1) // H.ROI_CHUNK)
+        self.offsets = offsets
+        self._host = (ctypes.c_int64 * len(offsets))(*offsets)
+        self._dev = torch.tensor([offsets, chunks], dtype=torch.int64).to(self.device)
+        self.desc = H.RoiIndex(len(self.labels), offsets[-1], self._host, H.ptr(self._dev[0]), H.ptr(self._dev[1]),
+                               H.ptr(index))
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def roi_index(labels, keep=None):
+    """The region index of a device integer tensor (D, H, W): 0 is unlabelled, every distinct positive value is a
+    region, in ascending order; voxels with keep == 0 (an optional uint8 tensor of the same shape) are dropped.
+    Built on the device with torch ops, once, and reused for every estimate."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
+        raise RuntimeError("labels must live on the GPU: this package runs on HIP kernels only "
+                           "(got %s)" % getattr(labels, "device", type(labels)))
+    if labels.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64) or labels.dim() != 3:
+        raise ValueError("roi_index: labels must be an integer tensor (D, H, W), got %s of shape %s"
+                         % (labels.dtype, tuple(labels.shape)))
+    flat = labels.reshape(-1)
+    if keep is not None:
+        if not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.dtype == torch.uint8
+                and tuple(keep.shape) == tuple(labels.shape)):
+            raise ValueError("roi_index: keep must be a device uint8 tensor of the labels' shape %s"
+                             % (tuple(labels.shape),))
+        flat = torch.where(keep.reshape(-1) != 0, flat, torch.zeros_like(flat))
+    with torch.cuda.device(labels.device):
+        if int(flat.min()) < 0:
+            raise ValueError("roi_index: negative labels")
+        at = torch.nonzero(flat).squeeze(1)                        # ascending flat indices, int64
+        if at.numel() == 0:
+            raise ValueError("roi_index: no labelled voxel")
+        values, order = torch.sort(flat[at].to(torch.int64), stable=True)
+        found, counts = torch.unique_consecutive(values, return_counts=True)
+        if found.numel() > H.ROI_MAX_REGIONS:
+            raise ValueError("roi_index: %d regions (at most %d)" % (found.numel(), H.ROI_MAX_REGIONS))
+        return RoiIndex(labels.shape, found.tolist(), counts.tolist(), at[order].contiguous())
+
+
+def roi_moments(estimate, index, target=None):
+    """ddpm3d_roi_moments of a (D, H, W) or (K, D, H, W) estimate over a region index: one launch, one
+    device-to-host copy.  -> the R records of the regions, each a list of H.ROI_REC floats (columns H.ROI_*; the
+    three error columns are 0 without a target); a list of K such lists for a (K, D, H, W) estimate."""
+    H.require_device(estimate, "estimate")
+    if estimate.dim() not in (3, 4) or tuple(estimate.shape[-3:]) != index.shape or estimate.device != index.device:
+        raise ValueError("roi_moments: estimate of shape %s on %s against an index of a %s volume on %s"
+                         % (tuple(estimate.shape), estimate.device, index.shape, index.device))
+    if target is not None:
+        H.require_device(target, "target")
+        if tuple(target.shape) != index.shape or target.device != index.device:
+            raise ValueError("roi_moments: target of shape %s, index of a %s volume" % (tuple(target.shape),
+                                                                                      index.shape))
+    K = int(estimate.shape[0]) if estimate.dim() == 4 else 1
+    if not 1 <= K <= H.MAX_DRAWS:
+        raise ValueError("roi_moments: %d estimates (1..%d)" % (K, H.MAX_DRAWS))
+    lib = H.load()
+    need = lib.ddpm3d_roi_moments_workspace_bytes(K, index.desc)
+    with torch.cuda.device(index.device):
+        ws = torch.empty(max(need, 16) // 8, dtype=torch.float64, device=index.device)
+        out = torch.empty((K, len(index), H.ROI_REC), dtype=torch.float64, device=index.device)
+        H.check(lib.ddpm3d_roi_moments(H.ptr(estimate), H.ptr(target), K, index.voxels, index.desc, H.ptr(ws),
+                                       ws.numel() * 8, H.ptr(out), H.stream()))
+        rec = out.cpu().tolist()                       # the one device-to-host copy (it waits for the stream)
+    return rec if estimate.dim() == 4 else rec[0]
+
+
+def _ratio(a, b):
+    return None if a is None or b is None or b == 0 else a / b
+
+
+def _region(rec):
+    """n, mean, std (population), min, max, cov of one record"""
+    n = int(rec[H.ROI_N])
+    mean = _ratio(rec[H.ROI_SUM_X], n)
+    std = None if mean is None else math.sqrt(max(rec[H.ROI_SUM_SQ_X] / n - mean * mean, 0.0))
+    return {"n": n, "mean": mean, "std": std, "min": rec[H.ROI_MIN_X] if n else None,
+            "max": rec[H.ROI_MAX_X] if n else None, "cov": _ratio(std, mean)}
+
+
+def roi_figures(records, target_records=None, labels=None, background=None, draw_records=None):
+    """Records to figures, on the host: {label: figures} for the R records of one estimate (roi_moments' return).
+    Per region n, mean, std (population), min, max, cov = std / mean.  With target_records, the target's own records
+    (roi_moments(target, index)) beside records taken against that target: mean_bias, mean_bias_rel, max_bias_rel,
+    rmse, mae.  With a background label g, for every other region contrast = mean_r / mean_g - 1, cnr =
+    (mean_r - mean_g) / std_g and, with target_records, crc = contrast / the target's contrast.  With draw_records
+    (K >= 2 lists of R records): draw_means, mean_std (sample std of the K region means, ddof = 1) and, with
+    target_records, mean_z = (mean of the draw means - target mean) / mean_std.  A figure whose denominator is 0 is
+    None.  labels default to 0..R-1."""
+    R = len(records)
+    labels = list(range(R)) if labels is None else [int(v) for v in labels]
+    if len(labels) != R or (target_records is not None and len(target_records) != R):
+        raise ValueError("roi_figures: %d records, %d labels, %s target records"
+                         % (R, len(labels), None if target_records is None else len(target_records)))
+    if draw_records is not None and (len(draw_records) < 2 or any(len(d) != R for d in draw_records)):
+        raise ValueError("roi_figures: draw_records must be K >= 2 lists of %d records" % R)
+    if background is not None and background not in labels:
+        raise ValueError("roi_figures: background label %r is not a region (%s)" % (background, labels))
+    figs = [_region(r) for r in records]
+    tfigs = None if target_records is None else [_region(r) for r in target_records]
+    g = None if background is None else labels.index(background)
+    out = {}
+    for i, (label, rec, f) in enumerate(zip(labels, records, figs)):
+        n = f["n"]
+        if tfigs is not None:
+            t = tfigs[i]
+            f["mean_bias"] = None if f["mean"] is None or t["mean"] is None else f["mean"] - t["mean"]
+            f["mean_bias_rel"] = _ratio(f["mean_bias"], t["mean"])
+            f["max_bias_rel"] = None if not n or t["max"] is None else _ratio(f["max"] - t["max"], t["max"])
+            f["rmse"] = math.sqrt(rec[H.ROI_SUM_SQ_E] / n) if n else None
+            f["mae"] = _ratio(rec[H.ROI_SUM_ABS_E], n)
+        if g is not None and i != g:
+            bg = figs[g]
+            ratio = _ratio(f["mean"], bg["mean"])
+            f["contrast"] = None if ratio is None else ratio - 1.0
+            if tfigs is not None:
+                tr = _ratio(tfigs[i]["mean"], tfigs[g]["mean"])
+                f["crc"] = _ratio(f["contrast"], None if tr is None else tr - 1.0)
+            f["cnr"] = None if f["mean"] is None or bg["mean"] is None else _ratio(f["mean"] - bg["mean"], bg["std"])
+        if draw_records is not None:
+            means = [_ratio(d[i][H.ROI_SUM_X], int(d[i][H.ROI_N])) for d in draw_records]
+            f["draw_means"] = means
+            f["mean_std"] = f["mean_z"] = None
+            if n:
+                K = len(means)
+                centre = math.fsum(means) / K
+                f["mean_std"] = math.sqrt(math.fsum((m - centre) ** 2 for m in means) / (K - 1))
+                if tfigs is not None:
+                    f["mean_z"] = _ratio(centre - tfigs[i]["mean"], f["mean_std"])
+        out[label] = f
+    return out
+
+
+def roi_report(estimate, target, index, labels=None, background=None, draws=None):
+    """Region figures of one (D, H, W) estimate against the target: {label: {"n", "target": the target's own n,
+    mean, std, min, max, cov, "estimate": roi_figures of the estimate}}.  labels names the regions (default: the
+    index's own labels); draws is a (K, D, H, W) device tensor of K >= 2 posterior draws or their K lists of records
+    (roi_moments of each draw).  The target's own statistics come from one roi_moments(target, index) call."""
+    labels = index.labels if labels is None else labels
+    trec = roi_moments(target, index)
+    if isinstance(draws, torch.Tensor):
+        draws = roi_moments(draws, index)
+    est = roi_figures(roi_moments(estimate, index, target=target), target_records=trec, labels=labels,
+                      background=background, draw_records=draws)
+    tgt = roi_figures(trec, labels=labels)
+    return {label: {"n": tgt[label]["n"], "target": tgt[label], "estimate": est[label]} for label in labels}

@@ -138,6 +138,11 @@ def load_volume(path):
     """Input volume as (D,H,W) float32.  .npz ('arr_0' or the first array) and .npy
     besides the reference's .tif/.tiff (tiff_io: tifffile when importable, else its own reader; scripts/test.py
     reads tif only, README.md:67 tells users to edit the loader for other formats)."""
+    return _read_array(path).astype(np.float32)
+
+
+def _read_array(path):
+    """the (D,H,W) array of a volume file in the dtype it was stored in"""
     low = path.lower()
     if low.endswith(".npz"):
         with np.load(path, allow_pickle=False) as z:
@@ -155,7 +160,18 @@ def load_volume(path):
         vol = vol[0]
     if vol.ndim != 3:
         raise ValueError("expected a (D,H,W) volume in %s, got %s" % (path, vol.shape))
-    return vol.astype(np.float32)
+    return vol
+
+
+def load_labels(path):
+    """Region labels as (D,H,W) int32 from the file types load_volume reads: 0 is unlabelled, every positive value
+    names a region.  Values that are not integers, are negative or do not fit int32 are refused."""
+    vol = _read_array(path)
+    if vol.dtype.kind not in "iuf" or not np.all(np.isfinite(vol)) or np.any(vol != np.floor(vol)):
+        raise ValueError("labels in %s are not integers (%s)" % (path, vol.dtype))
+    if vol.size and (vol.min() < 0 or vol.max() > np.iinfo(np.int32).max):
+        raise ValueError("labels in %s must lie in 0..2^31 - 1 (found %s..%s)" % (path, vol.min(), vol.max()))
+    return vol.astype(np.int32)
 
 
 # ---------------------------------------------------------------- joint patch sampling (DESIGN.md 3.7)

@@ -92,6 +92,11 @@ class VolumeStitcher:
                                                  H.ptr(std), H.stream()))
         return mean, std, self.wsum
 
+    def draw(self, k):
+        """Stitched draw k as finish() averages it: acc[k] / wsum in fp32, 0 where the weight is 0; (H, W, D) on the
+        device, one temporary volume."""
+        return torch.where(self.wsum > 0, self.acc[k] / self.wsum, torch.zeros_like(self.wsum))
+
     def finish_single(self):
         if self.K != 1:
             raise ValueError("%s.finish_single: one draw only, this stitcher holds %d (use finish())"

@@ -46,7 +46,13 @@ written volume and the low-dose input itself against that target on the GPU
 `--num_draws`, the coverage of the std map) and writes metrics_<name>.json
 beside the .npz, which keeps its keys and contents; `--data_range` fixes L
 (default: the target's range), `--metrics_mask_threshold F` counts only
-voxels with target > F * max(target).
+voxels with target > F * max(target); `--roi_labels labels.npz` (an integer
+volume of the input's shape, 0 = unlabelled; needs `--target_samples`) adds
+per-region statistics of the target, the input and the written volume
+(guided_diffusion/metrics.py roi_report: mean, max, CoV, bias, and with
+`--roi_background LABEL` contrast recovery and contrast-to-noise against that
+region; with `--num_draws` the spread of every region mean over the draws)
+under the key "roi" of metrics_<name>.json.
 """
 
 import argparse
@@ -87,7 +93,10 @@ def create_argparser():
                     # -1 = the reference's fixed 3 x 3 x (1 | 2) grid
                     patch_overlap=-1,
                     # full-dose volume to score the result against (not in the reference); "" = no metrics
-                    target_samples="", data_range=0.0, metrics_mask_threshold=0.0)
+                    target_samples="", data_range=0.0, metrics_mask_threshold=0.0,
+                    # integer label volume for per-region statistics and the reference region of contrast and CNR
+                    # (not in the reference); "" = no region statistics, -1 = no reference region
+                    roi_labels="", roi_background=-1)
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
@@ -106,6 +115,7 @@ def main(argv=None):
         parser.error("--patch_overlap must be in 2..%d for patches of %d (got %d); -1 keeps the fixed 3 x 3 x (1 | 2) "
                      "grid" % (args.large_size - 1, args.large_size, args.patch_overlap))
     vol, target = _load_target(parser, args)
+    roi = _load_roi(parser, args, vol)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
     dev = dist_util.dev()
@@ -130,9 +140,9 @@ def main(argv=None):
         vol = patches.load_volume(args.base_samples)             # (D, H, W)
     res = args.large_size
     if args.joint_patches:
-        return _main_joint(args, model, diffusion, vol, target)
+        return _main_joint(args, model, diffusion, vol, target, roi)
     if args.patch_overlap >= 0:
-        return _main_sliding(args, model, diffusion, vol, target)
+        return _main_sliding(args, model, diffusion, vol, target, roi)
     low_res, grid = patches.split_volume(vol, res)               # (P, 1, Z, H, W)
     logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3")
     gaps = patches.grid_gaps(vol.shape, res)
@@ -148,7 +158,7 @@ def main(argv=None):
     n_batches = (len(grid) + bs - 1) // bs
     sample_loop, extra = _sampler(args, diffusion)
     if args.num_draws > 1:
-        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target)
+        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target, roi)
     done = {}
     for b in dist_util.partition(n_batches):
         block = th.zeros(bs, 1, res, res, res, device=dev)                  # padded so collectives stay aligned
@@ -191,7 +201,7 @@ def main(argv=None):
             tiff_path = out_path.replace(".npz", ".tif")
             tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))   # (H,W,Z) -> (Z,H,W), no scaling
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        _write_metrics(args, out_path, target, vol, result, weight=weight)
+        _write_metrics(args, out_path, target, vol, result, weight=weight, roi=roi)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
@@ -218,11 +228,69 @@ def _load_target(parser, args):
     return vol, target
 
 
-def _write_metrics(args, out_path, target, vol, result, std=None, weight=None):
+def _load_roi(parser, args, vol):
+    """--roi_labels: the (D, H, W) int32 label volume, read and checked before the model is built or any device call
+    is made; None without the flag."""
+    if not args.roi_labels:
+        return None
+    if not args.target_samples:
+        parser.error("--roi_labels needs --target_samples: regions are scored against the full-dose target")
+    if not os.path.isfile(args.roi_labels):
+        parser.error("--roi_labels: no such file: %r" % args.roi_labels)
+    try:
+        labels = patches.load_labels(args.roi_labels)
+    except ValueError as e:
+        parser.error("--roi_labels: %s" % e)
+    if labels.shape != vol.shape:
+        parser.error("--roi_labels: the labels have shape %s, the base volume %s"
+                     % (tuple(labels.shape), tuple(vol.shape)))
+    found = np.unique(labels)
+    found = found[found > 0]
+    if found.size == 0:
+        parser.error("--roi_labels: no voxel carries a positive label")
+    if found.size > _hip.ROI_MAX_REGIONS:
+        parser.error("--roi_labels: %d labels (at most %d)" % (found.size, _hip.ROI_MAX_REGIONS))
+    if args.roi_background != -1 and (args.roi_background <= 0 or args.roi_background not in found):
+        parser.error("--roi_background: %d is not a positive label of --roi_labels" % args.roi_background)
+    return labels
+
+
+def _roi_block(args, roi, tgt, inp, den, keep, draws):
+    """The "roi" entry of the metrics file: per-region figures of target, input and written volume, all (H, W, Z) on
+    the device; keep drops the voxels the blend left at 0; draws yields the K stitched draws one volume at a time,
+    of which only the small records are kept."""
+    labels = th.from_numpy(roi).to(tgt.device).permute(1, 2, 0).contiguous()         # (D, H, W) -> (H, W, Z)
+    index = metrics.roi_index(labels, keep=keep)
+    background = args.roi_background if args.roi_background > 0 else None
+    if background is not None and background not in index.labels:
+        logger.log("  WARNING: --roi_background %d has no voxel of non-zero blend weight: no contrast figures"
+                   % background)
+        background = None
+    records = None if draws is None else [metrics.roi_moments(d, index) for d in draws]
+    den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records)
+    inp_rep = metrics.roi_report(inp, tgt, index, background=background)
+    regions = {str(label): {"n": den_rep[label]["n"], "target": den_rep[label]["target"],
+                            "input": inp_rep[label]["estimate"], "denoised": den_rep[label]["estimate"]}
+               for label in index.labels}
+    show = lambda v: "n/a" if v is None else "%.5g" % v
+    for label in index.labels[:20]:
+        r = regions[str(label)]
+        logger.log("  region %d (%d voxels): mean %s target, %s input, %s denoised; max %s / %s / %s%s"
+                   % (label, r["n"], show(r["target"]["mean"]), show(r["input"]["mean"]), show(r["denoised"]["mean"]),
+                      show(r["target"]["max"]), show(r["input"]["max"]), show(r["denoised"]["max"]),
+                      "; mean over draws +- %s" % show(r["denoised"]["mean_std"]) if records else ""))
+    if len(index.labels) > 20:
+        logger.log("  (%d more regions in the metrics file)" % (len(index.labels) - 20))
+    return {"labels": args.roi_labels, "background": background, "regions": regions}
+
+
+def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, roi=None, draws=None):
     """Rank 0, after the .npz is written: scores the written volume `result` (and `std`, with --num_draws) and the
     low-dose input `vol` against `target` on the device and writes metrics_<name>.json beside the .npz.  target and
     vol are (D, H, W) host arrays; result, std and weight (the one-shot blend's Hann weight sum, whose zeros are not
-    counted) are (H, W, Z) host arrays or device tensors.  Nothing happens without --target_samples."""
+    counted) are (H, W, Z) host arrays or device tensors.  With --roi_labels (roi, (D, H, W) int32) the file gains the
+    "roi" entry; draws then yields the K draws of --num_draws as (H, W, Z) device tensors.  Nothing happens without
+    --target_samples."""
     if target is None:
         return None
     dev = dist_util.dev()
@@ -255,6 +323,9 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None):
         r = report["denoised"]
         logger.log("  std map coverage: %.4f of the errors within 1 std, %.4f within 2"
                    % (r["coverage_1"], r["coverage_2"]))
+    if roi is not None:
+        keep = None if weight is None else live.to(th.uint8).contiguous()
+        report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws)
     path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
     with open(path, "w") as f:
         json.dump(report, f, indent=2)
@@ -278,7 +349,7 @@ def _base_name(path):
     return base
 
 
-def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target=None):
+def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target=None, roi=None):
     """--num_draws K >= 2: every forward batch is bs patches x K draws, patch-major (N = bs * K); the noise of draw d of
     patch i comes from volume_generator(i, draw=d), so it depends on neither K, the batch size nor the world size.
     Gathered rounds are stitched on rank 0's device in ascending patch order (DrawStitcher), then reduced to the
@@ -327,13 +398,14 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             std_path = out_path.replace(".npz", "_std.tif")
             tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
-        _write_metrics(args, out_path, target, vol, mean, std=std, weight=weight)
+        _write_metrics(args, out_path, target, vol, mean, std=std, weight=weight, roi=roi,
+                       draws=(stitcher.draw(k) for k in range(K)))
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
 
 
-def _main_sliding(args, model, diffusion, vol, target=None):
+def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
     """--patch_overlap N: the one-shot path (and --num_draws K) on the gap-free sliding grid.  The volume is uploaded
     once as a zero-extended canvas; every batch's conditioning patches are cut from it on the device
     (ddpm3d_tiles_gather); gathered rounds are blended on rank 0's device in ascending patch order as they arrive
@@ -397,13 +469,14 @@ def _main_sliding(args, model, diffusion, vol, target=None):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra_out["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        _write_metrics(args, out_path, target, vol, result, std=std, weight=weight)
+        _write_metrics(args, out_path, target, vol, result, std=std, weight=weight, roi=roi,
+                       draws=(stitcher.draw(k) for k in range(K)) if K > 1 else None)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
 
 
-def _main_joint(args, model, diffusion, vol, target=None):
+def _main_joint(args, model, diffusion, vol, target=None, roi=None):
     """--joint_patches True: every rank holds the whole canvas and runs its share of each step's forwards
     (joint.sample_loop_progressive); rank 0 writes the canvas cropped to the volume, (H, W, Z) like the other paths.
     With --num_draws K >= 2 the K canvases are reduced to the per-voxel mean and sample std."""
@@ -437,7 +510,8 @@ def _main_joint(args, model, diffusion, vol, target=None):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        _write_metrics(args, out_path, target, vol, result, std=extra.get("std"))
+        _write_metrics(args, out_path, target, vol, result, std=extra.get("std"), roi=roi,
+                       draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path

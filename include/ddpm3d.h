@@ -706,6 +706,56 @@ size_t ddpm3d_ssim3d_workspace_bytes(int B, int D, int H, int W);
 int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, double C1,
                   double C2, void* ws, size_t ws_bytes, float* map, double* out, void* stream);
 /*
+ * Per-region (lesion / organ) moments of B estimates over a region index (added within ABI 13; the reference has no
+ * metric code).  A labelled volume reaches the library as a sorted index list in CSR form, ddpm3d_roi_index, never
+ * as a dense label volume:
+ *   regions    R in 1..DDPM3D_ROI_MAX_REGIONS
+ *   entries    length of the index, 0..2^40
+ *   offsets    HOST int64 [R + 1]: region r owns index[offsets[r] .. offsets[r + 1]); offsets[0] = 0, non-decreasing,
+ *              offsets[R] = entries (an empty region is legal); read and checked on every call, never by the device
+ *   d_offsets  DEVICE int64 [R + 1]: the same values
+ *   d_chunks   DEVICE int64 [R + 1]: d_chunks[r] = sum over r' < r of ceil((offsets[r' + 1] - offsets[r']) /
+ *              DDPM3D_ROI_CHUNK), the first chunk of region r; built by the caller once per index
+ *   d_index    DEVICE int64 [entries]: flat voxel indices, ascending within a region.  Every value must lie in
+ *              [0, voxels): the producer guarantees it (the library cannot read device memory on the host)
+ * ddpm3d_roi_moments: est is [B][voxels] fp32, B in 1..DDPM3D_MAX_DRAWS; target is [voxels] fp32 or NULL.  It writes
+ * out[B][R][DDPM3D_ROI_REC] doubles (device memory), sums over the region's entries with every term formed and added
+ * in fp64 without contraction, e = (double)x - (double)y:
+ *   N = count, SUM_X = sum x, SUM_SQ_X = sum x^2, MIN_X / MAX_X = extremes of x (+inf / -inf for an empty region),
+ *   SUM_E = sum e, SUM_ABS_E = sum |e|, SUM_SQ_E = sum e^2 (all three 0 without a target).
+ * Region r's entries are cut into consecutive chunks of DDPM3D_ROI_CHUNK starting at its first entry; one workgroup
+ * per (chunk, estimate) writes one record to the workspace and a second launch folds each (estimate, region)'s
+ * records in a fixed order: no atomics, the same bits on every run, and row b does not depend on B.
+ * ws: ddpm3d_roi_moments_workspace_bytes(B, index) bytes, 16-byte aligned (0 is the answer for what the entry
+ * refuses).  Returns DDPM3D_EINVAL before any launch for a NULL est, out, ws, index or any of its pointers, B outside
+ * 1..DDPM3D_MAX_DRAWS, R outside 1..DDPM3D_ROI_MAX_REGIONS, voxels or entries outside 1..2^40 / 0..2^40, offsets
+ * that do not start at 0, decrease or end elsewhere than entries, and a workspace that is too small or misaligned.
+ */
+#define DDPM3D_ROI_MAX_REGIONS 4096
+#define DDPM3D_ROI_CHUNK 4096
+enum {
+    DDPM3D_ROI_N = 0,
+    DDPM3D_ROI_SUM_X = 1,
+    DDPM3D_ROI_SUM_SQ_X = 2,
+    DDPM3D_ROI_MIN_X = 3,
+    DDPM3D_ROI_MAX_X = 4,
+    DDPM3D_ROI_SUM_E = 5,
+    DDPM3D_ROI_SUM_ABS_E = 6,
+    DDPM3D_ROI_SUM_SQ_E = 7,
+    DDPM3D_ROI_REC = 8          /* doubles per record */
+};
+typedef struct ddpm3d_roi_index {
+    int32_t regions;
+    int64_t entries;
+    const int64_t* offsets;
+    const int64_t* d_offsets;
+    const int64_t* d_chunks;
+    const int64_t* d_index;
+} ddpm3d_roi_index;
+size_t ddpm3d_roi_moments_workspace_bytes(int B, const ddpm3d_roi_index* index);
+int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t voxels, const ddpm3d_roi_index* index,
+                       void* ws, size_t ws_bytes, double* out, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
