@@ -245,6 +245,90 @@ int ddpm3d_conv3d(const ddpm3d_conv_desc* d, void* stream) {
     return launched(ddpm3d_launch_splitk_reduce(k, (hipStream_t)stream), "conv3d split-K reduce");
 }
 
+// ---- ddpm3d_conv3d_skip: out = conv2(act(A h + B)) + skip(x) + biases, the tail of a ResBlock whose skip connection is a
+// 1x1 conv (unet.py:173-186, :256).  Validation shared by the entry and its query: fills the skip conv's own descriptor
+// (the two-step form's first call), conv2's launch record with the sk_* fields, and says whether the fused form runs.
+static int base_prec(int p) {
+    return p == DDPM3D_PREC_F16X3_WZ ? DDPM3D_PREC_F16X3 : p == DDPM3D_PREC_F16_WZ ? DDPM3D_PREC_F16
+         : p == DDPM3D_PREC_BF16_WZ ? DDPM3D_PREC_BF16 : p;
+}
+static int skip_prepare(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk, ddpm3d_conv_desc& sd, ConvK& k, ConvCfg& c,
+                        bool& fused, bool for_launch) {
+    fused = false;
+    if (!d || !sk) return fail(DDPM3D_EINVAL, "conv3d_skip: null descriptor");
+    if (d->res_mode != DDPM3D_RES_NONE || d->res)
+        return fail(DDPM3D_EINVAL, "conv3d_skip: conv2 carries no residual of its own (the skip conv is its residual)");
+    if (d->out_layout != DDPM3D_OUT_NDHWC) return fail(DDPM3D_EINVAL, "conv3d_skip: NDHWC output only");
+    if (d->ksize != 3) return fail(DDPM3D_EINVAL, "conv3d_skip: conv2 is a 3x3x3 conv (ksize %d)", d->ksize);
+    if (sk->C0 <= 0 || sk->C1 < 0) return fail(DDPM3D_EINVAL, "conv3d_skip: C0=%d C1=%d", sk->C0, sk->C1);
+    if (sk->io_dtype & ~(DDPM3D_IO_SRC0_BF16 | DDPM3D_IO_SRC1_BF16))
+        return fail(DDPM3D_EINVAL, "conv3d_skip: skip io_dtype names sources only (%#x)", sk->io_dtype);
+    memset(&sd, 0, sizeof(sd));
+    sd.N = d->N; sd.D = d->D; sd.H = d->H; sd.W = d->W;
+    sd.C0 = sk->C0; sd.C1 = sk->C1; sd.Cin = sk->C0 + sk->C1; sd.Cout = d->Cout;
+    sd.ksize = 1; sd.in_mode = DDPM3D_IN_SAME;
+    sd.src0 = sk->src0; sd.src1 = sk->src1;
+    sd.act = DDPM3D_ACT_NONE; sd.precision = base_prec(d->precision);
+    sd.w_packed = sk->w_packed; sd.bias = sk->bias;
+    sd.res_mode = DDPM3D_RES_NONE;
+    sd.out = d->out; sd.out_layout = DDPM3D_OUT_NDHWC;
+    sd.workspace = d->workspace; sd.workspace_bytes = d->workspace_bytes;
+    sd.in_bound = sk->in_bound; sd.in_bound_count = sk->in_bound_count; sd.in_bound_stride = sk->in_bound_stride;
+    sd.io_dtype = sk->io_dtype | (d->io_dtype & (DDPM3D_IO_OUT_BF16 | DDPM3D_IO_HALF_IS_F16));
+    ConvK ks;
+    ConvCfg cs;
+    int route_s = ROUTE_GENERAL, route = ROUTE_GENERAL;
+    int ok = conv_prepare(&sd, ks, cs, route_s, false);
+    if (ok != DDPM3D_OK) return ok;
+    if (for_launch && (!sk->src0 || !sk->w_packed || !sk->bias)) return fail(DDPM3D_EINVAL, "conv3d_skip: null buffer");
+    // the fused form: f16x3 Winograd-D conv2 on a plain fp32 input, the default issue order; a skip conv that conv1x1.hip
+    // would take (whole 32-channel blocks), fp32 tensors throughout; and the level is one the measured rule admits
+    const int cand = d->precision == DDPM3D_PREC_F16X3_WZ && d->in_mode == DDPM3D_IN_SAME && d->io_dtype == 0 &&
+                     sk->io_dtype == 0 && !(d->kernel_hint & (DDPM3D_HINT_UP_PHASE | DDPM3D_HINT_WZ_ORDER_MASK)) &&
+                     route_s == ROUTE_PW && aligned16(sk->bias);
+    ok = conv_prepare(d, k, c, route, for_launch && cand);
+    if (ok != DDPM3D_OK) return ok;
+    fused = cand && route == ROUTE_GENERAL && ddpm3d_skip_fuse_rule(d->N, d->D, d->H, d->W, sd.Cin, d->Cout, c);
+    if (!fused) return DDPM3D_OK;
+    k.sk_src0 = sk->src0; k.sk_src1 = sk->src1; k.sk_C0 = sk->C0; k.sk_C1 = sk->C1;
+    k.sk_src0_bytes = ks.src0_bytes; k.sk_src1_bytes = ks.src1_bytes;
+    k.sk_w = ks.w; k.sk_w_bytes = ks.w_bytes; k.sk_wscale = ks.wscale;
+    k.sk_bias = sk->bias;
+    k.sk_bound = sk->in_bound; k.sk_bound_count = sk->in_bound_count; k.sk_bound_stride = sk->in_bound_stride;
+    k.sk_blocks_per_split = (sd.Cin / 32 + c.S - 1) / c.S;
+    return DDPM3D_OK;
+}
+
+int ddpm3d_conv3d_skip(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk, void* stream) {
+    ddpm3d_conv_desc sd;
+    ConvK k;
+    ConvCfg c;
+    bool fused = false;
+    const int ok = skip_prepare(d, sk, sd, k, c, fused, true);
+    if (ok != DDPM3D_OK) return ok;
+    if (fused) {
+        const int rc = launched(ddpm3d_launch_conv(k, c, (hipStream_t)stream), "conv3d_skip");
+        if (rc != DDPM3D_OK || c.S == 1) return rc;
+        return launched(ddpm3d_launch_splitk_reduce(k, (hipStream_t)stream), "conv3d_skip split-K reduce");
+    }
+    // today's two steps: the 1x1 conv into out, then conv2 with out as its same-shape residual
+    const int rc = ddpm3d_conv3d(&sd, stream);
+    if (rc != DDPM3D_OK) return rc;
+    ddpm3d_conv_desc d2 = *d;
+    d2.res = d->out;
+    d2.res_mode = DDPM3D_RES_SAME;
+    if (d->io_dtype & DDPM3D_IO_OUT_BF16) d2.io_dtype |= DDPM3D_IO_RES_BF16;
+    return ddpm3d_conv3d(&d2, stream);
+}
+
+int ddpm3d_conv_skip_fused(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk) {
+    ddpm3d_conv_desc sd;
+    ConvK k;
+    ConvCfg c;
+    bool fused = false;
+    return skip_prepare(d, sk, sd, k, c, fused, false) == DDPM3D_OK && fused ? 1 : 0;
+}
+
 int ddpm3d_conv_plan(const ddpm3d_conv_desc* d, int* stats_rows, size_t* workspace_bytes, int* split) {
     ConvK k;
     ConvCfg c;

@@ -332,7 +332,8 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvK p) 
     const size_t v1 = min(v0 + (size_t)p.reduce_vox, DHW);
     const size_t slab_stride = (size_t)p.N * DHW * p.Cout;
     for (int cout = threadIdx.x; cout < p.Cout; cout += 256) {
-        const float bias = p.bias[(size_t)n * p.bias_stride_n + cout];
+        float bias = p.bias[(size_t)n * p.bias_stride_n + cout];
+        if (p.sk_bias != nullptr) bias += p.sk_bias[cout];     // ddpm3d_conv3d_skip: b_conv2 + b_skip, one add
         GnAcc gs;
         gs.init(0.0f);
         float cnt = 0.0f;
@@ -383,7 +384,8 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_v4_kernel(const ConvK 
 #pragma unroll
         for (int c = 0; c < 4; ++c) gs[c].init(0.0f);
         if (qok) {
-            const f32x4 bias = *reinterpret_cast<const f32x4*>(p.bias + (size_t)n * p.bias_stride_n + q * 4);
+            f32x4 bias = *reinterpret_cast<const f32x4*>(p.bias + (size_t)n * p.bias_stride_n + q * 4);
+            if (p.sk_bias != nullptr) bias += *reinterpret_cast<const f32x4*>(p.sk_bias + q * 4);   // ddpm3d_conv3d_skip
 #pragma unroll
             for (int i = 0; i < RV / 4; ++i) {
                 const size_t v = v0 + vl + 4 * i;
@@ -485,6 +487,9 @@ hipError_t ddpm3d_launch_conv(const ConvK& k, const ConvCfg& c, hipStream_t st) 
 // Winograd-D forms of the f16x3 / f16 / bf16 3x3x3 conv, an object of their own (conv3d_p3.o;
 // eligibility is checked by the C ABI)
 #include "conv3d_wz.h"
+#ifndef DDPM3D_WZ_T84
+#define DDPM3D_WZ_T84 1     // measurement builds: 0 = 8x8x2 tiles wherever 8x4x4 ones would be taken
+#endif
 hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvCfg& c, hipStream_t st) {
     const int gy = k.CoutPad / 128;
     const int gx = k.N * k.tilesZ * k.tilesY * k.tilesX;
@@ -508,6 +513,22 @@ hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvCfg& c, hipStream_t s
     // parameter).
     // f16x3: the issue order of a tap (conv3d_wz.h, IL): one order for every shape since r03
     // (profiles/r03_layer_ab_wz_issue_order.txt; r02 had picked between 0 and 1 by shape).
+    if (k.sk_w != nullptr) {
+        // ddpm3d_conv3d_skip's fused form (conv3d_wz.h SKIP; api.hip has checked the arithmetic, the input mode and the
+        // hints): the tile forms and the grids of the plain f16x3 launches below
+        if (c.PREC != DDPM3D_PREC_F16X3_WZ) return hipErrorInvalidValue;
+        constexpr size_t slds4 = (size_t)WzGeomT<4>::BUF + stamp_lds, slds84 = (size_t)WzGeomT<8, 4>::BUF + stamp_lds;
+        if (c.TXL == 2)
+            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_SKIP, 4, 4>), dim3(gx, gy, k.ksplit), dim3(256), slds4, st, k);
+        else if (DDPM3D_WZ_T84 && k.H % 8 == 0 && k.D % 4 == 0) {
+            ConvK k2 = k;
+            k2.tilesY = 2 * k.tilesY;
+            k2.tilesZ = k.tilesZ / 2;
+            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_SKIP, 4, 8, 4>), dim3(gx, gy, k.ksplit), dim3(256), slds84, st, k2);
+        } else
+            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_SKIP, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds, st, k);
+        return hipGetLastError();
+    }
     if (k.hint & DDPM3D_HINT_UP_PHASE) {
         // an IN_UP conv as four 2x2 phase convs on the low-resolution source (conv3d_wz.h PHASE; api.hip keeps the bit
         // only where ddpm3d_up_phase_geom holds): 4 phases x the low-resolution tiles = the grid the shape rule counted
@@ -536,9 +557,6 @@ hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvCfg& c, hipStream_t s
             hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 4, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds4, st, k);
         return hipGetLastError();
     }
-#ifndef DDPM3D_WZ_T84
-#define DDPM3D_WZ_T84 1
-#endif
     // 8x4x4 tiles (two z-pairs per workgroup; r03) where they tile the volume like the 8x8x2 grid the shape rule
     // counted (H % 8 == 0, D % 4 == 0: same number of tiles, so statistics rows and workspace are unchanged); the
     // default issue order only

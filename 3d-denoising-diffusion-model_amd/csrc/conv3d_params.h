@@ -38,6 +38,19 @@ struct ConvK {
     int reduce_vox;  // voxels per statistics row of the split-K reduce
     int hint;        // ddpm3d_conv_desc.kernel_hint
     int io;          // ddpm3d_conv_desc.io_dtype (DDPM3D_IO_* bits)
+    // ---- ddpm3d_conv3d_skip's fused form (conv3d_wz.h SKIP; sk_w == NULL everywhere else): the ResBlock's 1x1 skip conv
+    // on the raw block input x = [sk_src0 | sk_src1] (fp32 NDHWC, the output's grid), accumulated behind the output
+    // transform.  The reduce launch of a split conv adds sk_bias to the bias.
+    const float* sk_src0;
+    const float* sk_src1;
+    const float* sk_w;        // ddpm3d_pack_conv_weight's 1x1 image (precision F16X3), unchanged
+    const float* sk_wscale;   // its per-cout 1 / weight scale
+    const float* sk_bias;     // [Cout]
+    const float* sk_bound;    // in_bound of x
+    int sk_bound_count, sk_bound_stride;
+    unsigned sk_w_bytes, sk_src0_bytes, sk_src1_bytes;
+    int sk_C0, sk_C1;
+    int sk_blocks_per_split;  // 32-channel blocks of x dealt to each split: ceil(blocks / ksplit)
 };
 
 struct ConvCfg {
@@ -163,6 +176,19 @@ static inline ConvCfg ddpm3d_conv_cfg(int N, int D, int H, int W, int Cin, int C
         c.reduce_vox /= 2;
     ddpm3d_conv_cfg_split(c, best, N, D, H, W, Cout);
     return c;
+}
+
+// ---- ddpm3d_conv3d_skip: which ResBlocks run their 1x1 skip conv inside conv2's launch (conv3d_wz.h SKIP), keyed on
+// the shape alone.  c = conv2's configuration (split included), Cx = channels of the block input.  The form EXISTS
+// where api.hip says (f16x3 Winograd-D conv2, a skip conv of whole 32-channel blocks, fp32 tensors); this rule keeps
+// it to the levels the layer A/B found faster in every round (tools/layer_ab.py --what skip).  Measured
+// (profiles/r06_layer_ab_skip_fuse_f16x3.txt, the published network's fourteen distinct tails at 1 x 64^3, 7 rounds):
+// fused was faster in EVERY round on every one of them -- unsplit 64^3 and 64x32x32 (-11 %, -9 %), and every split
+// level from 64x16x16 down to 64x4x4 (-10 ... -29 %) -- so no shape is excluded.  Until a measurement excludes one this
+// is a hook that admits everything: the arguments are what a refit would key on, and none is read today.
+static inline bool ddpm3d_skip_fuse_rule(int N, int D, int H, int W, int Cx, int Cout, const ConvCfg& c) {
+    (void)N; (void)D; (void)H; (void)W; (void)Cx; (void)Cout; (void)c;
+    return true;
 }
 
 // bytes of the packed weight image: fp32 [tap][ci/8][CoutPad][8] for PREC 0;

@@ -24,7 +24,8 @@
 
 // arithmetic of the staged operands: hi + lo f16 (three MFMAs per product), hi f16 only, bf16
 enum { WZ_F16X3 = 0, WZ_F16 = 1, WZ_BF16 = 2,
-       WZ_F16X3_UP = 3 };   // conv3d_wz.h only: the f16x3 arithmetic on the phase form of an up-sampled input
+       WZ_F16X3_UP = 3,     // conv3d_wz.h only: the f16x3 arithmetic on the phase form of an up-sampled input
+       WZ_F16X3_SKIP = 4 }; // conv3d_wz.h only: the f16x3 arithmetic + the ResBlock's 1x1 skip conv behind the output transform
 
 // two fp32 -> packed f16 hi (RNE) and packed f16 lo = f16(s - hi); the subtraction is exact
 __device__ __forceinline__ void split_pair(float s0, float s1, unsigned& hi, unsigned& lo) {

@@ -55,10 +55,20 @@
 // (j RZ + (a + py) RY + (b + px) VS) 16 with the phase's share folded into arow[] once, and an epilogue that places
 // row (y, x) at output (2y + py, 2x + px).  The phase is wave-uniform (from the workgroup id).
 // (the phase form is MODE_ WZ_F16X3_UP of the one kernel, so that the shipped forms keep their code and their names)
+//
+// SKIP (MODE_ WZ_F16X3_SKIP, ddpm3d_conv3d_skip, f16x3 only): conv2 of a ResBlock whose skip connection is a 1x1 conv on
+// the raw block input x.  Behind the output transform the four outv accumulators of a wave are plain conv outputs of
+// the tile's 128 voxels x the wave's 32 couts, in units of S_h s_conv2[c]; they are brought to the skip conv's units
+// S_x s_skip[c] (a power of two per lane: exact) and the 1x1 conv is accumulated onto them as GEMM work: x is staged
+// through the LDS image (free after the last tap) in blocks of 32 channels -- the tile's own voxels, no halo, no
+// transform, raw fp32 times S_x, the same hi/lo split -- with rows in the order of outv (epi_tz), against B fragments
+// read from the unchanged 1x1 image (the per-tap layout of the 3x3x3 image, one tap).  One epilogue, one bias
+// b_conv2 + b_skip, no residual read.  A split launch deals the x blocks to its splits like the chunks.
 template <int MODE_, int IL = 0, int TX = 8, int TY = TX>
 __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
     constexpr bool PHASE = MODE_ == WZ_F16X3_UP;
-    constexpr int MODE = PHASE ? (int)WZ_F16X3 : MODE_;     // the arithmetic
+    constexpr bool SKIP = MODE_ == WZ_F16X3_SKIP;
+    constexpr int MODE = (PHASE || SKIP) ? (int)WZ_F16X3 : MODE_;     // the arithmetic
     typedef WzGeomT<TX, TY> G;
     constexpr bool X3 = MODE == WZ_F16X3;
     constexpr int CK = DDPM3D_CONV_CK, NT = PHASE ? 16 : 36;
@@ -127,12 +137,18 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
     ActScale asc = {1.0f, 1.0f};
     float bound_raw = 0.0f;
     if constexpr (MODE != WZ_BF16) bound_raw = act_scale_load(p, n);
+    // SKIP: the bound of x beside it; its scale is wave-uniform (scalar registers for the kernel's life)
+    float sk_bound_raw = 0.0f;
+    ActScale ax = {1.0f, 1.0f};
+    if constexpr (SKIP)
+        if (lane < p.sk_bound_count) sk_bound_raw = p.sk_bound[((size_t)n * p.sk_bound_count + lane) * p.sk_bound_stride];
     StageLaneT<G> sl = stage_lane<G, PHASE>(p, tid, n, y0, x0, max(z0 - 1, 0), 1.0f);
     stage_zero_border(sl, lds, 1, tid);
     StageRawT<G> raw;
     if (chunk_begin < chunk_end) stage_issue(p, sl, raw, n, z0, chunk_begin);
     if constexpr (MODE != WZ_BF16) {
         asc = act_scale_finish(bound_raw, 2.0f);   // the input transform adds two planes
+        if constexpr (SKIP) ax = act_scale_finish(sk_bound_raw, 1.0f);   // (here: its lane shuffles share the indices)
         stage_lane_scale(p, sl, asc.s);
     }
     WZ_STAMP(1);
@@ -281,6 +297,116 @@ __global__ __launch_bounds__(256, 2) void conv3d_wz_kernel(const ConvK p) {
         outv[2 + t] = acc[1][t] - acc[2][t] - acc[3][t];
     }
     const int tile_in_n = ((ph * p.tilesZ + tz_i) * p.tilesY + ty_i) * p.tilesX + tx_i;
+    if constexpr (SKIP) {
+        const int tid_ = tid;
+        // ---- (b) x through LDS (its first loads go out before (a) below), 32 channels (two chunks) a block: [chunk][row m = u*32 + r][80 B: hi 32 | lo 32 | pad]
+        // -- the voxel stride of the halo image, so that a wave's A read meets the banks as a tap's does.
+        // Thread = channel quad xq of rows (tid >> 3) + 32 i; rows outside the volume read zeros.
+        constexpr int XB = 32, XROW = VS * 16, XCH = 128 * XROW;
+        static_assert(2 * XCH <= G::BUF, "an x block fits the tile's image");
+        const int nxb = (p.sk_C0 + p.sk_C1) / XB;
+        const int xb_begin = wg.split * p.sk_blocks_per_split;
+        const int xb_end = min(nxb, xb_begin + p.sk_blocks_per_split);
+        // (the thread id made opaque HERE: the staging addresses below are launch-invariant, and hoisted above the tap
+        // loop they are a dozen registers more at its point of highest pressure -- the 4x4x8 and 8x8x2 forms spilled)
+        int tid = tid_;
+        asm volatile("" : "+v"(tid));
+        const int lane = tid & 63, half = lane >> 5;
+        const int xq = tid & 7;
+        unsigned xv0[4], xv1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = (tid >> 3) + 32 * i;
+            const int z = z0 + epi_tz<TXL, TYL, G::NZP != 1>(m), y = y0 + ((m >> TXL) & (TY - 1)), x = x0 + (m & (TX - 1));
+            const bool inb = z < p.D && y < p.H && x < p.W;
+            const unsigned vox = (unsigned)(((n * p.D + z) * p.H + y) * p.W + x);
+            xv0[i] = inb ? (vox * (unsigned)p.sk_C0 + xq * 4u) * 4u : DDPM3D_OOB_OFFSET;
+            xv1[i] = inb ? (vox * (unsigned)p.sk_C1 + xq * 4u) * 4u : DDPM3D_OOB_OFFSET;
+        }
+        const int xl = ((xq >> 2) * 128 + (tid >> 3)) * XROW + (xq & 3) * 8;
+        const int xa = ((lane & 31) * VS + half) * 16;
+        // every issue is unconditional (a block past the split's range loads through a zero-length descriptor: zeros,
+        // no traffic), so that the compiler's vmcnt stays a count (conv1x1.hip)
+        auto x_issue = [&](const int b, u32x4 (&xr)[4]) {
+            const bool valid = b < xb_end;
+            const int c0 = b * XB;
+            const bool from0 = c0 < p.sk_C0;
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(from0 ? p.sk_src0 : p.sk_src1,
+                                                        valid ? (from0 ? p.sk_src0_bytes : p.sk_src1_bytes) : 0u);
+            const unsigned soff = valid ? (unsigned)(from0 ? c0 : c0 - p.sk_C0) * 4u : 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xr[i] = buffer_load16(rs, from0 ? xv0[i] : xv1[i], soff);
+        };
+        auto w_issue = [&](const int b, u32x4 (&wq)[2][2]) {
+            const bool valid = b < xb_end;
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(p.sk_w, valid ? p.sk_w_bytes : 0u);
+            const unsigned soff = valid ? (unsigned)(2 * b) * wchunk_stride : 0u;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                wq[c][0] = buffer_load16(rs, wlane, soff + c * wchunk_stride);
+                wq[c][1] = buffer_load16(rs, wlane, soff + c * wchunk_stride + wpart);
+            }
+        };
+        u32x4 xr[4], wa[2][2], wb[2][2];
+        x_issue(xb_begin, xr);
+        w_issue(xb_begin, wa);
+        // the 1x1 image's scale and its bias: requested HERE, behind the first block's loads (at kernel start they
+        // are two more registers live through the tap loop, whose 4x4x8 form stands at 256)
+        const int coutk = wg.cy * 128 + (tid >> 6) * 32 + (lane & 31);     // = cout, from the opaque thread id
+        const float sk_ws = coutk < p.Cout ? p.sk_wscale[coutk] : 1.0f;
+        const float sk_bias = coutk < p.Cout ? p.sk_bias[coutk] : 0.0f;
+        // ---- (a) conv2's accumulators in the skip conv's units: rho = (S_x s_skip) / (S_h s_conv2), a power of two
+        const float rho = (ax.s * asc.inv) * (pre_ws / sk_ws);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) outv[u][i] *= rho;
+        // one block: the staged x of block b against the weights wq; x of block b + 1 and its weights wn are requested
+        // in front of the MFMAs
+        auto x_block = [&](const int b, u32x4 (&xr)[4], u32x4 (&wq)[2][2], u32x4 (&wn)[2][2]) {
+            __syncthreads();    // the image's (the previous block's) last readers are through
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f32x4 v = __builtin_bit_cast(f32x4, xr[i]);
+                unsigned h0, h1, l0, l1;
+                split_pair(v[0] * ax.s, v[1] * ax.s, h0, l0);
+                split_pair(v[2] * ax.s, v[3] * ax.s, h1, l1);
+                unsigned char* row = lds + xl + i * 32 * XROW;
+                *reinterpret_cast<u32x2*>(row) = u32x2{h0, h1};
+                *reinterpret_cast<u32x2*>(row + 32) = u32x2{l0, l1};
+            }
+            x_issue(b + 1, xr);
+            w_issue(b + 1, wn);
+            __syncthreads();
+            // ---- (c) per chunk and row tile: lo*hi, hi*lo, hi*hi (the tap loop's order)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const h8 bhi = __builtin_bit_cast(h8, wq[c][0]), blo = __builtin_bit_cast(h8, wq[c][1]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const unsigned char* a = lds + c * XCH + u * 32 * XROW + xa;
+                    const h8 ahi = *reinterpret_cast<const h8*>(a), alo = *reinterpret_cast<const h8*>(a + 32);
+                    outv[u] = mfma16<false>(alo, bhi, outv[u]);
+                    outv[u] = mfma16<false>(ahi, blo, outv[u]);
+                    outv[u] = mfma16<false>(ahi, bhi, outv[u]);
+                }
+            }
+        };
+        // two blocks a turn (the weight registers swap roles); an odd range multiplies one block of zeros
+        for (int b = xb_begin; b < xb_end; b += 2) {
+            x_block(b, xr, wa, wb);
+            x_block(b + 1, xr, wb, wa);
+        }
+        // ---- (d) the shipped epilogue in the skip conv's units, one bias, no residual
+        const float bias2 = pre_bias + sk_bias;
+        if (p.ksplit > 1)
+            conv_epilogue<1, 1, 4, TXL, TYL, true, G::NZP != 1, true, false>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
+                                                                     ax.inv, true, sk_ws, bias2, 0, 0);
+        else
+            conv_epilogue<1, 1, 4, TXL, TYL, false, G::NZP != 1, false, false>(p, outv, n, z0, y0, x0, tile_in_n, 0, cout, half, wg.split,
+                                                                     ax.inv, true, sk_ws, bias2, 0, 0);
+        return;
+    }
     #ifndef DDPM3D_WZ_WIDE_X3
 #define DDPM3D_WZ_WIDE_X3 0     // measurement: the 16-byte epilogue in the f16x3 form too
 #endif

@@ -31,6 +31,7 @@ enum StepKind { S_CONV, S_FINALIZE, S_ABSMAX, S_PAD, S_POOL, S_ATTN };
 struct Step {
     int kind;
     ddpm3d_conv_desc conv;                       // S_CONV
+    ddpm3d_conv_skip skip; bool has_skip;        // S_CONV: the ResBlock tail as one ddpm3d_conv3d_skip call
     // S_FINALIZE
     size_t st0, st1; int C0, rows0, C1, rows1; double count; const float *gamma, *beta; int film, film_off;
     size_t A, B, bound; bool has_ab;
@@ -127,12 +128,19 @@ struct Planner {
         bool ncdhw_out = false;                    // the network's last conv: out pointer patched per call
         size_t bound = 0; int bound_first = 0, bound_count = 0, bound_stride = 0; bool has_bound = false;
         int film_off = 0;
+        // the ResBlock tail as ONE ddpm3d_conv3d_skip step where the library takes its fused form: the 1x1 conv, its
+        // sources and the first entry of their bound (count / stride as `bound`); *fused = false, and nothing
+        // planned, where it does not
+        const ddpm3d_conv_weights* skip_w = nullptr;
+        const Act* x0 = nullptr; const Act* x1 = nullptr;
+        size_t xbound = 0; int xbound_first = 0; bool has_xbound = false;
+        bool* fused = nullptr;
     };
     bool conv_step(const ddpm3d_conv_weights& pc, ConvArgs a, int* step_index = nullptr) {
         ddpm3d_conv_desc d;
         memset(&d, 0, sizeof(d));
         const bool wz = pc.w_packed_wz && !a.planar && (a.in_mode == DDPM3D_IN_SAME || a.in_mode == DDPM3D_IN_UP);
-        d.precision = wz ? (pc.precision_wz & ~DDPM3D_WZ_UP_PHASE_IMAGE) : pc.precision;
+        d.precision = wz ? (pc.precision_wz & ~DDPM3D_WZ_UP_PHASE_IMAGE) : (pc.precision & ~DDPM3D_SKIP_TWO_CALLS);
         d.w_packed = wz ? pc.w_packed_wz : pc.w_packed;
         // a phase image (ddpm3d_pack_up_phase_weight) starts with the plain Winograd-D image: its IN_UP calls run the
         // four-phase form where the library finds the shape fit (ddpm3d.h DDPM3D_HINT_UP_PHASE), the others as ever
@@ -172,6 +180,22 @@ struct Planner {
             d.in_bound = (const float*)at(a.bound) + a.bound_first;
             d.in_bound_count = a.bound_count; d.in_bound_stride = a.bound_stride;
         }
+        ddpm3d_conv_skip sk;
+        memset(&sk, 0, sizeof(sk));
+        if (a.skip_w) {
+            sk.src0 = (const float*)at(a.x0->off); sk.C0 = a.x0->C;
+            if (a.x1) { sk.src1 = (const float*)at(a.x1->off); sk.C1 = a.x1->C; }
+            sk.w_packed = a.skip_w->w_packed; sk.bias = a.skip_w->bias;
+            if (a.x0->esize == 2) sk.io_dtype |= DDPM3D_IO_SRC0_BF16;
+            if (a.x1 && a.x1->esize == 2) sk.io_dtype |= DDPM3D_IO_SRC1_BF16;
+            if (scaled) {
+                if (!a.has_xbound) return fail("skip conv without an input bound");
+                sk.in_bound = (const float*)at(a.xbound) + a.xbound_first;
+                sk.in_bound_count = a.bound_count; sk.in_bound_stride = a.bound_stride;
+            }
+            *a.fused = ddpm3d_conv_skip_fused(&d, &sk) != 0;
+            if (!*a.fused) return true;
+        }
         // how the library itself will run this descriptor: statistics rows, split-K scratch (needs real-looking
         // pointers only where the validation looks at them: none while sizing)
         int rows = 0, split = 1;
@@ -189,6 +213,8 @@ struct Planner {
         memset(&st, 0, sizeof(st));
         st.kind = S_CONV;
         st.conv = d;
+        st.skip = sk;
+        st.has_skip = a.skip_w != nullptr;
         if (a.bias_per_n) { bias_steps.push_back((int)steps.size()); bias_offs.push_back(a.film_off); }
         if (step_index) *step_index = (int)steps.size();
         steps.push_back(st);
@@ -240,7 +266,22 @@ struct Planner {
         c2.bound = bnd2; c2.bound_count = 32; c2.bound_stride = 2; c2.has_bound = has2;
         if (e.skip.w_packed) {
             if (e.updown != DDPM3D_UPDOWN_NONE) return fail("up/down ResBlock with a channel change is not in the reference");
-            ConvArgs cs;        // y = skip(x) on the RAW block input (its range: entry 1 of the same finalize)
+            // y = skip(x) on the RAW block input (its range: entry 1 of the same finalize) -- in ONE step where the
+            // library runs the 1x1 conv inside conv2's launch (ddpm3d_conv3d_skip), else -- or where the description
+            // carries DDPM3D_SKIP_TWO_CALLS -- as two
+            bool fused = false;
+            if (!(e.skip.precision & DDPM3D_SKIP_TWO_CALLS)) {
+                ConvArgs cf = c2;
+                cf.skip_w = &e.skip; cf.x0 = s0; cf.x1 = s1;
+                cf.xbound = bnd1; cf.xbound_first = 1; cf.has_xbound = has1; cf.fused = &fused;
+                if (!conv_step(e.conv2, cf)) return false;
+            }
+            if (fused) {
+                release(h1);
+                *y_out = y;
+                return true;
+            }
+            ConvArgs cs;
             cs.src0 = s0; cs.src1 = s1; cs.out = &y; cs.want_stats = false;
             cs.bound = bnd1; cs.bound_first = 1; cs.bound_count = 32; cs.bound_stride = 2; cs.has_bound = has1;
             if (!conv_step(e.skip, cs)) return false;
@@ -466,7 +507,9 @@ int ddpm3d_unet_forward(ddpm3d_unet_plan* pl, const float* x, const float* low_r
     for (const Step& s : pl->steps) {
         int rc = DDPM3D_OK;
         switch (s.kind) {
-            case S_CONV: rc = ddpm3d_conv3d(&s.conv, stream); break;
+            case S_CONV:
+                rc = s.has_skip ? ddpm3d_conv3d_skip(&s.conv, &s.skip, stream) : ddpm3d_conv3d(&s.conv, stream);
+                break;
             case S_FINALIZE:
                 rc = ddpm3d_gn_finalize((const double*)(b + s.st0), s.C0, s.rows0, s.C1 ? (const double*)(b + s.st1) : nullptr,
                                         s.C1, s.rows1, pl->N, 32, s.count, 1e-5f, s.gamma, s.beta,

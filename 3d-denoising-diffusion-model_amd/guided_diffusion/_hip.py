@@ -42,6 +42,7 @@ HINT_WZ_ORDER_SHIFT = 12     # bits 12..14: tap issue order of the f16x3 Winogra
 # the low-resolution source (the one hint that selects a weight image and so changes rounding)
 HINT_UP_PHASE = 0x400
 WZ_UP_PHASE_IMAGE = 0x100    # flag in ddpm3d_conv_weights.precision_wz: w_packed_wz is that image
+SKIP_TWO_CALLS = 0x100       # flag in ddpm3d_conv_weights.precision of a skip conv: never plan ddpm3d_conv3d_skip
 
 _fp = C.c_void_p
 
@@ -59,6 +60,13 @@ class ConvDesc(C.Structure):
         ("kernel_hint", C.c_int32), ("in_bound_count", C.c_int32), ("in_bound", _fp),
         ("in_bound_stride", C.c_int32), ("io_dtype", C.c_int32),
     ]
+
+
+class ConvSkip(C.Structure):
+    """struct ddpm3d_conv_skip: the ResBlock's 1x1 skip conv of ddpm3d_conv3d_skip"""
+    _fields_ = [("src0", _fp), ("src1", _fp), ("C0", C.c_int32), ("C1", C.c_int32), ("w_packed", _fp), ("bias", _fp),
+                ("in_bound", _fp), ("in_bound_count", C.c_int32), ("in_bound_stride", C.c_int32),
+                ("io_dtype", C.c_int32)]
 
 
 class ConvWeights(C.Structure):
@@ -132,6 +140,8 @@ EXPORTS = {
     "ddpm3d_conv3d": (C.c_int, [C.POINTER(ConvDesc), _fp]),
     "ddpm3d_conv_kernel_family": (C.c_int, [C.POINTER(ConvDesc), C.c_char_p, C.c_int]),
     "ddpm3d_conv_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "ddpm3d_conv3d_skip": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvSkip), _fp]),
+    "ddpm3d_conv_skip_fused": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvSkip)]),
     "ddpm3d_unet_plan_bytes": (C.c_size_t, [C.POINTER(UnetDesc), C.c_int, C.c_int, C.c_int, C.c_int]),
     "ddpm3d_unet_plan_create": (C.c_int, [C.POINTER(UnetDesc), C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t,
                                           C.POINTER(_fp)]),

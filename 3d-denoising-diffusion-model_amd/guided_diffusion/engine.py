@@ -135,6 +135,9 @@ class UNetEngine:
         # (four 2x2 phase convs on the low-resolution input, 16 taps instead of 36).  DDPM3D_UP_PHASE=0 keeps the
         # plain Winograd-D image and with it the 36-tap path, in this plan and in the native one (A/B measurements).
         self.up_phase = (winograd and precision == "f16x3" and os.environ.get("DDPM3D_UP_PHASE", "1") != "0")
+        # DDPM3D_SKIP_FUSE=0: both planners keep the two shipped steps for the tail of a ResBlock with a 1x1 skip conv,
+        # also where ddpm3d_conv3d_skip would run it as one launch (A/B runs)
+        self.skip_fuse = os.environ.get("DDPM3D_SKIP_FUSE", "1") != "0"
         up_conv1 = {e.prefix + ".in_layers.2" for e in topo.all_layers() if e.kind == "res" and e.updown == "up"}
         for name, t in params.items():
             if name.endswith(".weight") and t.dim() >= 3:
@@ -258,6 +261,8 @@ class UNetEngine:
                 L.conv1 = self._conv_weights(self.conv[e.prefix + ".in_layers.2"])
                 L.conv2 = self._conv_weights(self.conv[e.prefix + ".out_layers.3"])
                 L.skip = self._conv_weights(self.conv.get(e.prefix + ".skip_connection"))
+                if L.skip.w_packed and not self.skip_fuse:
+                    L.skip.precision |= H.SKIP_TWO_CALLS
             elif e.kind == "attn":
                 L.kind = H.LAYER_ATTN
                 L.norm1_gamma, L.norm1_beta = H.ptr(p[e.prefix + ".norm.weight"]), H.ptr(p[e.prefix + ".norm.bias"])
@@ -587,8 +592,10 @@ class _Plan(_PlanBase):
 
     def conv_step(self, pc, srcs, out, aff=None, act=H.ACT_NONE, in_mode=H.IN_SAME, res=None,
                   res_mode=H.RES_NONE, planar=False, out_tensor=None, out_layout=H.OUT_NDHWC,
-                  bias_per_n=False, want_stats=True, bound=None):
-        """bound = (tensor, first entry, entries per sample, stride): ddpm3d_conv_desc.in_bound"""
+                  bias_per_n=False, want_stats=True, bound=None, skip=None):
+        """bound = (tensor, first entry, entries per sample, stride): ddpm3d_conv_desc.in_bound
+        skip = (1x1 PackedConv, its sources, their bound): the ResBlock tail as ONE ddpm3d_conv3d_skip step where the
+        library takes its fused form; returns None, with nothing enqueued, where it does not"""
         N = self.N
         d = H.ConvDesc()
         lib = self.eng.lib
@@ -652,6 +659,20 @@ class _Plan(_PlanBase):
             # read out of bounds
             raise RuntimeError("residual has %d channels, the conv writes %d" % (res.C, pc.Cout))
         d.res = H.ptr(res.buf) if res is not None else 0
+        sk = None
+        if skip is not None:
+            spc, xs, xb = skip
+            sk = H.ConvSkip()
+            sk.src0, sk.C0 = H.ptr(xs[0].buf), xs[0].C
+            if len(xs) > 1:
+                sk.src1, sk.C1 = H.ptr(xs[1].buf), xs[1].C
+            sk.w_packed, sk.bias = H.ptr(spc.w), H.ptr(spc.b)
+            sk.io_dtype = (H.IO_SRC0_BF16 if xs[0].half else 0) | (H.IO_SRC1_BF16 if len(xs) > 1 and xs[1].half else 0)
+            if self.scaled:
+                sk.in_bound = xb[0].data_ptr() + 4 * xb[1]
+                sk.in_bound_count, sk.in_bound_stride = xb[2], xb[3]
+            if not lib.ddpm3d_conv_skip_fused(C.byref(d), C.byref(sk)):
+                return None
         # how the library will run this descriptor: statistics rows, split-K scratch
         rows, need, _ = H.conv_plan(d)
         if out is not None and want_stats:
@@ -670,6 +691,13 @@ class _Plan(_PlanBase):
         name = C.create_string_buffer(64)
         H.check(lib.ddpm3d_conv_kernel_family(C.byref(d), name, 64))
         tag = name.value.decode()
+        if sk is not None:
+            # conv2's family; the FLOPs of both convs
+            flops += 2.0 * N * d.D * d.H * d.W * pc.Cout * (sk.C0 + sk.C1)
+            self.keep.append(sk)
+            self.conv_meta[len(self.steps)] = (tag, flops)
+            self.steps.append((lib.ddpm3d_conv3d_skip, [C.byref(d), C.byref(sk), 0]))
+            return d
         self.conv_meta[len(self.steps)] = (tag, flops)
         self.steps.append((self.eng.lib.ddpm3d_conv3d, [C.byref(d), 0]))
         return d
@@ -784,9 +812,16 @@ class _Plan(_PlanBase):
                 raise RuntimeError("up/down ResBlock with a channel change is not in the reference")
             # y = skip(x) on the RAW block input (its range: entry 1 of the same finalize), then
             # accumulated into
-            self.conv_step(skip, srcs, y, want_stats=False, bound=(bnd1, 1, 32, 2))
-            self.conv_step(c2, [h1], y, aff=(A2, B2), act=H.ACT_SILU, res=y, res_mode=H.RES_SAME,
-                           bound=(bnd2, 0, 32, 2))
+            # -- in ONE step where the library runs the 1x1 conv inside conv2's launch (ddpm3d_conv3d_skip;
+            # Engine.skip_fuse off: never, for A/B runs), else as two
+            fused = None
+            if eng.skip_fuse:
+                fused = self.conv_step(c2, [h1], y, aff=(A2, B2), act=H.ACT_SILU, bound=(bnd2, 0, 32, 2),
+                                       skip=(skip, srcs, (bnd1, 1, 32, 2)))
+            if fused is None:
+                self.conv_step(skip, srcs, y, want_stats=False, bound=(bnd1, 1, 32, 2))
+                self.conv_step(c2, [h1], y, aff=(A2, B2), act=H.ACT_SILU, res=y, res_mode=H.RES_SAME,
+                               bound=(bnd2, 0, 32, 2))
         else:
             if len(srcs) > 1:
                 # Identity skip over the decoder's virtual concat [h, skip] (2*inch == outch, e.g. a

@@ -183,6 +183,9 @@ enum {
 /* flag in ddpm3d_conv_weights.precision_wz (the planner masks it off): w_packed_wz is the image of
  * ddpm3d_pack_up_phase_weight; calls with in_mode DDPM3D_IN_UP get DDPM3D_HINT_UP_PHASE */
 #define DDPM3D_WZ_UP_PHASE_IMAGE 0x100
+/* flag in ddpm3d_conv_weights.precision of a ResBlock's `skip` conv (the planner masks it off): plan the block's tail
+ * as its two ddpm3d_conv3d calls even where ddpm3d_conv3d_skip would run fused (A/B runs; added within ABI 13) */
+#define DDPM3D_SKIP_TWO_CALLS 0x100
 
 int ddpm3d_abi_version(void);
 const char* ddpm3d_last_error(void);
@@ -255,6 +258,39 @@ int ddpm3d_conv_kernel_family(const ddpm3d_conv_desc* desc, char* name, int name
  * and the split factor over Cin.  Any out pointer may be NULL.  Validates like ddpm3d_conv_kernel_family;
  * launches nothing (ABI 12). */
 int ddpm3d_conv_plan(const ddpm3d_conv_desc* desc, int* stats_rows, size_t* workspace_bytes, int* split);
+
+/* ---- The tail of a ResBlock whose skip connection is a 1x1 conv, as one call (ABI 13, additive) --------------------
+ * out = conv2(act(A h + B)) + skip(x) + b_conv2 + b_skip                  (unet.py:173-186, :256)
+ * `conv2` is the 3x3x3 conv's descriptor as ddpm3d_conv3d takes it, with res_mode DDPM3D_RES_NONE and NDHWC output;
+ * `skip` names the 1x1 conv on the raw block input x = [src0 | src1] (NDHWC on conv2's output grid, C0 + C1 channels;
+ * w_packed = ddpm3d_pack_conv_weight's ksize-1 image in the direct form of conv2's arithmetic -- F16X3 for F16X3_WZ,
+ * F16 for F16_WZ, BF16 for BF16_WZ, else conv2's own --, bias [Cout], in_bound* = the range of x as
+ * ddpm3d_conv_desc.in_bound describes it; io_dtype: DDPM3D_IO_SRC0_BF16 / _SRC1_BF16 for 16-bit sources, of conv2's
+ * 16-bit type).
+ * Where the library takes the FUSED form -- conv2 in DDPM3D_PREC_F16X3_WZ on an fp32 DDPM3D_IN_SAME input, fp32 tensors
+ * throughout, C0 and C1 multiples of 32, Cout a multiple of 128, a level its measured rule admits -- the 1x1 products are
+ * accumulated onto conv2's accumulators inside conv2's launch (behind the Winograd-D output transform, in the skip
+ * conv's power-of-two units) and one epilogue adds b_conv2 + b_skip: one launch, plus conv2's reduce launch where
+ * conv2 is split.  Statistics rows, workspace bytes and the split factor are exactly what ddpm3d_conv_plan reports
+ * for `conv2`.  The products and operand roundings are those of the two separate calls; their fp32 sums are ordered
+ * differently, so the result agrees with the two calls to fp32 rounding, not bit for bit.
+ * Everywhere else the entry issues the two calls itself -- the 1x1 conv into `out`, then conv2 with res = out,
+ * DDPM3D_RES_SAME -- bit for bit what the caller's own two calls give; `conv2->workspace` must then also cover the
+ * 1x1 conv's need (ddpm3d_conv_workspace_bytes of its shape).  The choice is the library's; ddpm3d_conv_skip_fused
+ * returns it (1 fused, 0 two calls or an invalid pair) without launching.  No allocation, no synchronisation. */
+typedef struct ddpm3d_conv_skip {
+    const float* src0;
+    const float* src1;      /* NULL when C1 == 0 */
+    int32_t C0, C1;
+    const void* w_packed;
+    const float* bias;
+    const float* in_bound;
+    int32_t in_bound_count;
+    int32_t in_bound_stride;
+    int32_t io_dtype;
+} ddpm3d_conv_skip;
+int ddpm3d_conv3d_skip(const ddpm3d_conv_desc* conv2, const ddpm3d_conv_skip* skip, void* stream);
+int ddpm3d_conv_skip_fused(const ddpm3d_conv_desc* conv2, const ddpm3d_conv_skip* skip);
 
 /*
  * ---- The whole network (ABI 12; SURVEY 8b's `unet_forward(handle, ...)` granularity) ----------------------------

@@ -5,6 +5,11 @@ A/B of kernel forms / launch orders of identical arithmetic, layer by layer, in 
 architecture, variants interleaved over --rounds rounds.
 
     python tools/layer_ab.py [--size 64] [--precision f16x3] [--only64] > gpurun_out/layer_ab.txt
+
+--what skip: the ResBlock tails with a 1x1 skip conv that the plan runs fused (ddpm3d_conv3d_skip), each against its
+two shipped launches -- the 1x1 conv (+ reduce) into out, then conv2 (+ reduce) with out as its residual -- on the
+plan's own buffers.  NOT identical arithmetic (the fp32 sums are ordered differently).  The table fixes the routing
+rule (conv3d_params.h ddpm3d_skip_fuse_rule): a level is admitted only if fused was faster in every round.
 """
 
 import argparse
@@ -34,7 +39,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--only64", action="store_true", help="only the full-resolution layers")
-    ap.add_argument("--what", default="order", choices=["order", "issue", "phase"],
+    ap.add_argument("--what", default="order", choices=["order", "issue", "phase", "skip"],
                     help="order: workgroup -> XCD orders; issue: issue orders of a tap (f16x3 Winograd-D kernel); "
                          "phase: the up-sampled-input convs on the 36-tap path against their four-phase form "
                          "(HINT_UP_PHASE: NOT identical arithmetic, the same buffer holds both weight images)")
@@ -53,6 +58,8 @@ def main():
     torch.cuda.synchronize()
     plan = model.engine().plan(B, S, S, S)
     ap_what = a.what
+    if ap_what == "skip":
+        return skip_ab(a, lib, plan, B, S)
     variants = {"order": [("default", 0), ("wstat_off", H.HINT_WSTAT_OFF), ("wstat_on", H.HINT_WSTAT_ON)],
                 # issue orders of a tap in the f16x3 Winograd-D kernel (conv3d_wz.h: IL)
                 "issue": [("default", 0)] + [("il%d" % il, (il + 1) << H.HINT_WZ_ORDER_SHIFT) for il in (0, 1, 2, 4)],
@@ -100,6 +107,67 @@ def main():
         if ap_what == "phase":      # every round, so that the spread shows beside the difference
             for n, _ in variants:
                 print("#   %-8s rounds: %s" % (n, "  ".join("%.4f" % v for v in times[n])))
+
+
+def skip_ab(a, lib, plan, B, S):
+    """fused ResBlock tails against their two shipped launches, every round printed"""
+    print("# published architecture, %dx1x%d^3, %s; ms per ResBlock tail (median of %d rounds x %d launches)"
+          % (B, S, a.precision, a.rounds, a.iters))
+    print("%-12s %-12s %2s %2s | %9s  %9s   %s" % ("Cx->Cout", "DxHxW", "S", "n", "two_calls", "fused", "verdict"))
+    seen, total = {}, {"two_calls": 0.0, "fused": 0.0}
+    tails = [(args[0]._obj, args[1]._obj) for fn, args in plan.steps if fn is lib.ddpm3d_conv3d_skip]
+    for d, sk in tails:
+        key = (sk.C0, sk.C1, d.Cout, d.D, d.H, d.W)
+        seen[key] = seen.get(key, 0) + 1
+    done = set()
+    st = H.stream()
+    for d, sk in tails:
+        key = (sk.C0, sk.C1, d.Cout, d.D, d.H, d.W)
+        if key in done:
+            continue
+        done.add(key)
+        d1 = H.ConvDesc()
+        d1.N, d1.D, d1.H, d1.W, d1.Cin, d1.Cout, d1.ksize, d1.in_mode = d.N, d.D, d.H, d.W, sk.C0 + sk.C1, d.Cout, 1, H.IN_SAME
+        d1.src0, d1.src1, d1.C0, d1.C1 = sk.src0, sk.src1, sk.C0, sk.C1
+        d1.precision, d1.w_packed, d1.bias = H.PREC_F16X3, sk.w_packed, sk.bias
+        d1.out, d1.out_layout = d.out, H.OUT_NDHWC
+        d1.in_bound, d1.in_bound_count, d1.in_bound_stride = sk.in_bound, sk.in_bound_count, sk.in_bound_stride
+        d1.workspace, d1.workspace_bytes = d.workspace, d.workspace_bytes
+        if H.conv_plan(d1)[1] > (d.workspace_bytes or 0):
+            print("# %s: the 1x1 conv's workspace exceeds the plan's; skipped" % (key,))
+            continue
+        d2 = H.ConvDesc.from_buffer_copy(d)
+        d2.res, d2.res_mode = d.out, H.RES_SAME
+
+        def two_calls():
+            H.check(lib.ddpm3d_conv3d(C.byref(d1), st))
+            H.check(lib.ddpm3d_conv3d(C.byref(d2), st))
+
+        def fused():
+            H.check(lib.ddpm3d_conv3d_skip(C.byref(d), C.byref(sk), st))
+
+        variants = [("two_calls", two_calls), ("fused", fused)]
+        times = {n: [] for n, _ in variants}
+        for _ in range(a.rounds):
+            for n, fn in variants:
+                fn()        # warm
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _k in range(a.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[n].append(e0.elapsed_time(e1) / a.iters)
+        med = {n: sorted(v)[len(v) // 2] for n, v in times.items()}
+        every = all(f < t for f, t in zip(times["fused"], times["two_calls"]))
+        for n in total:
+            total[n] += med[n] * seen[key]
+        print("%-12s %-12s %2d %2d | %9.4f  %9.4f   %s" % (
+            "%d+%d->%d" % (sk.C0, sk.C1, d.Cout), "%dx%dx%d" % (d.D, d.H, d.W), H.conv_plan(d)[2], seen[key],
+            med["two_calls"], med["fused"], "fused in every round" if every else "NOT in every round"))
+        for n, _ in variants:
+            print("#   %-9s rounds: %s" % (n, "  ".join("%.4f" % v for v in times[n])))
+    print("# per forward (medians x occurrences): two_calls %.4f ms, fused %.4f ms" % (total["two_calls"], total["fused"]))
 
 
 if __name__ == "__main__":
