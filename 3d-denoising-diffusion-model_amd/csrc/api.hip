@@ -876,6 +876,31 @@ int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t vox
                     "roi_moments");
 }
 
+// ------------------------------------------------- connected components (added within ABI 13)
+static bool ccl_shape_ok(int D, int H, int W) {
+    return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H <= 0x7fffffff && (int64_t)D * H * W <= 0x7fffffff;
+}
+
+size_t ddpm3d_label_components_workspace_bytes(int D, int H, int W) {
+    return ccl_shape_ok(D, H, W) ? ddpm3d_ccl_workspace_bytes(D, H, W) : 0;
+}
+
+int ddpm3d_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity, int D, int H,
+                            int W, int32_t* roots, void* ws, size_t ws_bytes, int32_t* status, void* stream) {
+    if (!vol || !roots || !status) return fail(DDPM3D_EINVAL, "label_components: null pointer");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(DDPM3D_EINVAL, "label_components: connectivity %d (6, 18 or 26)", connectivity);
+    if (!ccl_shape_ok(D, H, W))
+        return fail(DDPM3D_EINVAL, "label_components: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= "
+                                   "2^31 - 1)", D, H, W);
+    if (threshold != threshold) return fail(DDPM3D_EINVAL, "label_components: the threshold is NaN");
+    const int rc = metric_ws_ok("label_components", ddpm3d_ccl_workspace_bytes(D, H, W), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_label_components(vol, keep, threshold, connectivity, D, H, W, roots, ws, status,
+                                                   (hipStream_t)stream),
+                    "label_components");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

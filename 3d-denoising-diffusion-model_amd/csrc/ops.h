@@ -79,6 +79,12 @@ struct ddpm3d_roi_index;
 hipError_t ddpm3d_launch_roi_moments(const float* est, const float* target, int B, int64_t voxels,
                                      const ddpm3d_roi_index& ix, int64_t chunks, double* ws, double* out,
                                      hipStream_t st);
+// ccl.hip: connected components of vol > threshold (the caller has checked the shape, the connectivity and the
+// workspace; the workspace query takes valid shapes only)
+size_t ddpm3d_ccl_workspace_bytes(int D, int H, int W);
+hipError_t ddpm3d_launch_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity,
+                                          int D, int H, int W, int32_t* roots, void* ws, int32_t* status,
+                                          hipStream_t st);
 // joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
 // patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
 struct ddpm3d_joint_starts;

@@ -12,6 +12,10 @@ Per-region (lesion / organ) statistics: roi_index turns a label
 device, roi_moments is one launch of ddpm3d_roi_moments (csrc/roi.hip) over it, roi_figures turns the records into
 SUVmean / SUVmax bias, contrast recovery, CNR, CoV and the spread of a region mean over draws, roi_report puts them
 together.
+
+Lesion segmentation: label_components thresholds a volume and labels its connected components with
+ddpm3d_label_components (csrc/ccl.hip), segment drops the specks, detection compares two segmentations (lesions
+found and missed, false positives).  Their labels feed roi_index.
 """
 
 import ctypes
@@ -335,3 +339,113 @@ def roi_report(estimate, target, index, labels=None, background=None, draws=None
                       background=background, draw_records=draws)
     tgt = roi_figures(trec, labels=labels)
     return {label: {"n": tgt[label]["n"], "target": tgt[label], "estimate": est[label]} for label in labels}
+
+
+# ----------------------------------------------------------------- lesion segmentation
+def _check_labels(labels, what):
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
+        raise RuntimeError("%s must live on the GPU: this package runs on HIP kernels only "
+                           "(got %s)" % (what, getattr(labels, "device", type(labels))))
+    if labels.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64) or labels.dim() != 3:
+        raise ValueError("%s must be an integer tensor (D, H, W), got %s of shape %s"
+                         % (what, labels.dtype, tuple(labels.shape)))
+
+
+def label_components(volume, threshold, connectivity=26, keep=None):
+    """Connected components of volume > threshold (and keep != 0, an optional device uint8 tensor of the same shape)
+    of a device float32 (D, H, W) tensor, connectivity 6, 18 or 26: one call of ddpm3d_label_components
+    (csrc/ccl.hip), then the roots are ranked with torch ops.  -> (labels, n): int32 (D, H, W) on the device, 0 for
+    background and 1..n in raster order of each component's first voxel (scipy.ndimage.label's numbering)."""
+    H.require_device(volume, "volume")
+    if volume.dim() != 3:
+        raise ValueError("label_components: volume of shape %s (want (D, H, W))" % (tuple(volume.shape),))
+    if connectivity not in (6, 18, 26):
+        raise ValueError("label_components: connectivity %r (6, 18 or 26)" % (connectivity,))
+    threshold = float(threshold)
+    if math.isnan(threshold):
+        raise ValueError("label_components: the threshold is NaN")
+    if keep is not None and not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.dtype == torch.uint8
+                                 and keep.is_contiguous() and tuple(keep.shape) == tuple(volume.shape)
+                                 and keep.device == volume.device):
+        raise ValueError("label_components: keep must be a contiguous device uint8 tensor of the volume's shape %s"
+                         % (tuple(volume.shape),))
+    D, Hh, W = (int(v) for v in volume.shape)
+    if volume.numel() == 0 or volume.numel() > 2 ** 31 - 1:
+        raise ValueError("label_components: %d voxels (1..2^31 - 1)" % volume.numel())
+    lib = H.load()
+    need = lib.ddpm3d_label_components_workspace_bytes(D, Hh, W)
+    with torch.cuda.device(volume.device):
+        ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=volume.device)
+        roots = torch.empty((D, Hh, W), dtype=torch.int32, device=volume.device)
+        status = torch.empty(2, dtype=torch.int32, device=volume.device)
+        H.check(lib.ddpm3d_label_components(H.ptr(volume), H.ptr(keep), threshold, connectivity, D, Hh, W,
+                                            H.ptr(roots), H.ptr(ws), ws.numel() * 4, H.ptr(status), H.stream()))
+        flat = roots.reshape(-1)
+        is_root = flat == torch.arange(flat.numel(), dtype=torch.int32, device=volume.device)
+        rank = torch.cumsum(is_root, 0, dtype=torch.int32)         # rank[root] = its 1-based number, in raster order
+        labels = torch.where(flat >= 0, rank.index_select(0, flat.clamp(min=0)), torch.zeros_like(flat))
+        labels = labels.reshape(D, Hh, W)
+        overrun, n = status.cpu().tolist()                         # the one device-to-host copy
+    if overrun:
+        raise RuntimeError("label_components: a device loop hit its iteration cap; the labels are not valid")
+    return labels, int(n)
+
+
+def segment(volume, threshold, connectivity=26, min_voxels=1, keep=None):
+    """label_components with the components of fewer than min_voxels voxels set to 0 and the rest renumbered 1..n in
+    raster order of their first voxel; torch ops on the device.  -> (labels int32 (D, H, W) on the device, n)."""
+    if int(min_voxels) != min_voxels or min_voxels < 1:
+        raise ValueError("segment: min_voxels must be an integer of at least 1 (got %r)" % (min_voxels,))
+    labels, n = label_components(volume, threshold, connectivity=connectivity, keep=keep)
+    if min_voxels == 1 or n == 0:
+        return labels, n
+    with torch.cuda.device(volume.device):
+        # sizes by sorting the foreground's labels, not by bincount: a histogram's atomics would all land on one word
+        # for the background and for a component of millions of voxels
+        flat = labels.reshape(-1)
+        _, counts = torch.unique_consecutive(torch.sort(flat[flat > 0]).values, return_counts=True)   # numbers 1..n
+        kept = counts >= int(min_voxels)
+        remap = torch.zeros(n + 1, dtype=torch.int32, device=volume.device)   # old number -> new number, 0 = dropped
+        remap[1:] = torch.cumsum(kept, 0) * kept
+        return remap.index_select(0, flat).reshape(labels.shape), int(kept.sum())
+
+
+def detection(target_labels, estimate_labels):
+    """Lesion detectability of an estimate's segmentation against the target's, both device integer label volumes
+    (D, H, W) as segment returns them (0 = background; target numbers in 1..DDPM3D_ROI_MAX_REGIONS, estimate numbers
+    1..n all in use, any n).  A target region is found iff at least one of its voxels is foreground in the estimate;
+    an estimate component is a false positive iff none of its voxels is foreground in the target.  torch ops only and
+    one device-to-host copy.  -> {"n_target", "n_estimate", "found": [bool per target region], "overlap": [voxels of
+    the region that are foreground in the estimate], "n_found", "n_missed", "false_positives", "sensitivity":
+    n_found / n_target, None without a target region}."""
+    _check_labels(target_labels, "target_labels")
+    _check_labels(estimate_labels, "estimate_labels")
+    if tuple(target_labels.shape) != tuple(estimate_labels.shape) or target_labels.device != estimate_labels.device:
+        raise ValueError("detection: target labels of shape %s on %s, estimate labels of shape %s on %s"
+                         % (tuple(target_labels.shape), target_labels.device, tuple(estimate_labels.shape),
+                            estimate_labels.device))
+    cap, spread = H.ROI_MAX_REGIONS, 4096
+    with torch.cuda.device(target_labels.device):
+        t = target_labels.reshape(-1).long()
+        e = estimate_labels.reshape(-1).long()
+        both = (t > 0) & (e > 0)
+        # overlap[r], r in 1..cap (cap + 1 collects any larger number): voxels of both go to their region's bin, all
+        # others add 0 to one of `spread` spare bins, so that no single word takes every atomic
+        spare = cap + 2 + (torch.arange(t.numel(), device=t.device) & (spread - 1))
+        overlap = torch.zeros(cap + 2 + spread, dtype=torch.int64, device=t.device)
+        overlap.scatter_add_(0, torch.where(both, t.clamp(max=cap + 1), spare), both.long())
+        # hit[c] = 1 for every estimate component c with a voxel in the target's foreground (plain stores of one
+        # value; slot 0 takes the rest)
+        hit = torch.zeros(t.numel() + 1, dtype=torch.uint8, device=t.device)
+        hit.scatter_(0, torch.where(both, e, torch.zeros_like(e)), 1)
+        head = torch.stack([t.max(), e.max(), hit[1:].sum(dtype=torch.int64)])
+        rec = torch.cat([head, overlap[1:cap + 1]]).cpu().tolist()  # the one device-to-host copy
+    n_target, n_estimate, n_hit = (int(v) for v in rec[:3])
+    if n_target > cap:
+        raise ValueError("detection: %d target regions (at most %d)" % (n_target, cap))
+    over = [int(v) for v in rec[3:3 + n_target]]
+    found = [v > 0 for v in over]
+    n_found = sum(found)
+    return {"n_target": n_target, "n_estimate": n_estimate, "found": found, "overlap": over, "n_found": n_found,
+            "n_missed": n_target - n_found, "false_positives": n_estimate - n_hit,
+            "sensitivity": n_found / n_target if n_target else None}

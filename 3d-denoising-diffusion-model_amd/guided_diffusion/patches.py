@@ -134,6 +134,18 @@ def stitch_patches(patches_hwz, grid, shape_dhw, resolution):
     return np.divide(acc, wsum, out=acc.copy(), where=wsum > 0), wsum
 
 
+def blend_cover(grid, shape_dhw, resolution):
+    """(H,W,Z) bool: the voxels to which stitch_patches gives a weight above 0 (some patch covers them away from its
+    own outermost planes, where the Hann window is 0), known from the grid alone, before any patch is sampled."""
+    D, H, W = shape_dhw
+    cover = np.zeros((H, W, D), dtype=bool)
+    live = hann_window_3d(resolution) > 0
+    for xs, ys, zs in grid:
+        xe, ye, ze = min(xs + resolution, H), min(ys + resolution, W), min(zs + resolution, D)
+        cover[xs:xe, ys:ye, zs:ze] |= live[:xe - xs, :ye - ys, :ze - zs]
+    return cover
+
+
 def load_volume(path):
     """Input volume as (D,H,W) float32.  .npz ('arr_0' or the first array) and .npy
     besides the reference's .tif/.tiff (tiff_io: tifffile when importable, else its own reader; scripts/test.py

@@ -52,7 +52,17 @@ per-region statistics of the target, the input and the written volume
 (guided_diffusion/metrics.py roi_report: mean, max, CoV, bias, and with
 `--roi_background LABEL` contrast recovery and contrast-to-noise against that
 region; with `--num_draws` the spread of every region mean over the draws)
-under the key "roi" of metrics_<name>.json.
+under the key "roi" of metrics_<name>.json; `--roi_threshold F` (absolute, in
+the target's units, e.g. SUV 2.5) or `--roi_threshold_frac F` (a fraction of
+the target's maximum) makes the labels instead of reading them: the target's
+voxels above the threshold, grouped into connected components on the GPU
+(`--roi_connectivity 6|18|26`, components of fewer than `--roi_min_voxels`
+voxels dropped; guided_diffusion/metrics.py segment).  The target is segmented
+before the first sampling step and the labels are written as
+roi_labels_<name>.npz, which `--roi_labels` reads back; the "roi" entry is built
+from them as from a file and also carries "detection": which of the target's
+lesions are still there in the input and in the denoised volume (and in every
+draw), and how many hot spots either has that the target has not.
 """
 
 import argparse
@@ -96,10 +106,15 @@ def create_argparser():
                     target_samples="", data_range=0.0, metrics_mask_threshold=0.0,
                     # integer label volume for per-region statistics and the reference region of contrast and CNR
                     # (not in the reference); "" = no region statistics, -1 = no reference region
-                    roi_labels="", roi_background=-1)
+                    roi_labels="", roi_background=-1,
+                    # lesion labels made from the target instead (not in the reference): connected components of the
+                    # voxels above --roi_threshold / --roi_threshold_frac, specks below roi_min_voxels dropped
+                    roi_connectivity=26, roi_min_voxels=1)
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
+    parser.add_argument("--roi_threshold", type=float, default=None)          # absolute, in the target's units
+    parser.add_argument("--roi_threshold_frac", type=float, default=None)     # in (0, 1), of the target's maximum
     return parser
 
 
@@ -114,6 +129,7 @@ def main(argv=None):
     if args.patch_overlap != -1 and not 2 <= args.patch_overlap <= args.large_size - 1:
         parser.error("--patch_overlap must be in 2..%d for patches of %d (got %d); -1 keeps the fixed 3 x 3 x (1 | 2) "
                      "grid" % (args.large_size - 1, args.large_size, args.patch_overlap))
+    _check_segmentation(parser, args)
     vol, target = _load_target(parser, args)
     roi = _load_roi(parser, args, vol)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
@@ -139,6 +155,8 @@ def main(argv=None):
     if vol is None:
         vol = patches.load_volume(args.base_samples)             # (D, H, W)
     res = args.large_size
+    if _segmenting(args):
+        roi = _segment_target(parser, args, vol, target)
     if args.joint_patches:
         return _main_joint(args, model, diffusion, vol, target, roi)
     if args.patch_overlap >= 0:
@@ -255,18 +273,112 @@ def _load_roi(parser, args, vol):
     return labels
 
 
-def _roi_block(args, roi, tgt, inp, den, keep, draws):
+def _segmenting(args):
+    return args.roi_threshold is not None or args.roi_threshold_frac is not None
+
+
+def _check_segmentation(parser, args):
+    """--roi_threshold / --roi_threshold_frac and their options, checked before any file is read"""
+    if args.roi_connectivity not in (6, 18, 26):
+        parser.error("--roi_connectivity must be 6, 18 or 26 (got %d)" % args.roi_connectivity)
+    if args.roi_min_voxels < 1:
+        parser.error("--roi_min_voxels must be at least 1 (got %d)" % args.roi_min_voxels)
+    if not _segmenting(args):
+        return
+    if args.roi_threshold is not None and args.roi_threshold_frac is not None:
+        parser.error("--roi_threshold and --roi_threshold_frac cannot be combined: give one threshold")
+    flag = "--roi_threshold" if args.roi_threshold is not None else "--roi_threshold_frac"
+    if args.roi_labels or args.roi_background != -1:
+        parser.error("%s makes the labels itself: it cannot be combined with --roi_labels or --roi_background" % flag)
+    if not args.target_samples:
+        parser.error("%s needs --target_samples: the full-dose target is what gets segmented" % flag)
+    if args.roi_threshold is not None and not np.isfinite(args.roi_threshold):
+        parser.error("--roi_threshold must be a finite number (got %r)" % args.roi_threshold)
+    if args.roi_threshold_frac is not None and not 0.0 < args.roi_threshold_frac < 1.0:
+        parser.error("--roi_threshold_frac must lie in (0, 1) (got %r)" % args.roi_threshold_frac)
+
+
+def _segment_target(parser, args, vol, target):
+    """--roi_threshold / --roi_threshold_frac: the target's lesion labels, made once on the device before the first
+    sampling step so that a threshold that cannot be used stops the run now.  -> {"labels": int32 (H, W, Z) on the
+    device, "n", "keep": uint8 (H, W, Z) or None, "threshold": the absolute threshold as applied (fp32),
+    "connectivity", "min_voxels"}.  keep holds the voxels the one-shot blend will give a weight above 0, known from
+    the grid alone (the joint path writes every voxel)."""
+    dev = dist_util.dev()
+    res = args.large_size
+    keep = None
+    if not args.joint_patches:
+        grid = (patches.sliding_grid(vol.shape, res, args.patch_overlap) if args.patch_overlap >= 0
+                else patches.patch_grid(vol.shape, res))
+        keep = th.from_numpy(patches.blend_cover(grid, vol.shape, res).astype(np.uint8)).to(dev).contiguous()
+    if args.roi_threshold is not None:
+        threshold = float(np.float32(args.roi_threshold))
+    else:
+        threshold = float(np.float32(args.roi_threshold_frac * float(target.max())))
+    tgt = th.from_numpy(target).to(dev).permute(1, 2, 0).contiguous()                 # (D, H, W) -> (H, W, Z)
+    labels, n = metrics.segment(tgt, threshold, connectivity=args.roi_connectivity, min_voxels=args.roi_min_voxels,
+                                keep=keep)
+    if n == 0:
+        parser.error("the target has no region of at least %d voxels above the threshold %g (its maximum is %g): "
+                     "lower the threshold or --roi_min_voxels" % (args.roi_min_voxels, threshold, float(target.max())))
+    if n > _hip.ROI_MAX_REGIONS:
+        parser.error("the target has %d regions above the threshold %g (at most %d): raise --roi_min_voxels to drop "
+                     "the specks, or raise the threshold" % (n, threshold, _hip.ROI_MAX_REGIONS))
+    logger.log(f"target segmented at {threshold:g} (connectivity {args.roi_connectivity}, at least "
+               f"{args.roi_min_voxels} voxels): {n} regions")
+    return {"labels": labels, "n": n, "keep": keep, "threshold": threshold, "connectivity": args.roi_connectivity,
+            "min_voxels": args.roi_min_voxels}
+
+
+def _detection_block(seg, regions, inp, den, draw_found):
+    """"detection" of the "roi" entry: the target's lesions against the input's and the denoised volume's own
+    segmentation at the same threshold; every region gains "found" and "overlap" under "input" and "denoised"."""
+    out = {}
+    for name, x in (("input", inp), ("denoised", den)):
+        est, _ = metrics.segment(x, seg["threshold"], connectivity=seg["connectivity"], min_voxels=seg["min_voxels"],
+                                 keep=seg["keep"])
+        out[name] = d = metrics.detection(seg["labels"], est)
+        for r in range(seg["n"]):
+            regions[str(r + 1)][name]["found"] = d["found"][r]
+            regions[str(r + 1)][name]["overlap"] = d["overlap"][r]
+    if draw_found is not None:
+        out["denoised"]["draws"] = draw_found
+    logger.log("  lesions: %d in the target; input finds %d, misses %d, %d false positives; denoised finds %d, "
+               "misses %d, %d false positives"
+               % (seg["n"], out["input"]["n_found"], out["input"]["n_missed"], out["input"]["false_positives"],
+                  out["denoised"]["n_found"], out["denoised"]["n_missed"], out["denoised"]["false_positives"]))
+    return out
+
+
+def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None):
     """The "roi" entry of the metrics file: per-region figures of target, input and written volume, all (H, W, Z) on
     the device; keep drops the voxels the blend left at 0; draws yields the K stitched draws one volume at a time,
-    of which only the small records are kept."""
-    labels = th.from_numpy(roi).to(tgt.device).permute(1, 2, 0).contiguous()         # (D, H, W) -> (H, W, Z)
+    of which only the small records are kept.  roi is the (D, H, W) label volume of --roi_labels or _segment_target's
+    dict, whose labels are written beside out_path first."""
+    seg = roi if isinstance(roi, dict) else None
+    if seg is not None:
+        labels, keep = seg["labels"], seg["keep"]
+        labels_path = os.path.join(os.path.dirname(out_path), "roi_labels_%s.npz" % _base_name(args.base_samples))
+        np.savez(labels_path, labels.permute(2, 0, 1).cpu().numpy())                 # (H, W, Z) -> (D, H, W), int32
+        logger.log(f"saved lesion labels to {labels_path}")
+    else:
+        labels = th.from_numpy(roi).to(tgt.device).permute(1, 2, 0).contiguous()     # (D, H, W) -> (H, W, Z)
     index = metrics.roi_index(labels, keep=keep)
     background = args.roi_background if args.roi_background > 0 else None
     if background is not None and background not in index.labels:
         logger.log("  WARNING: --roi_background %d has no voxel of non-zero blend weight: no contrast figures"
                    % background)
         background = None
-    records = None if draws is None else [metrics.roi_moments(d, index) for d in draws]
+    records = draw_found = None
+    if draws is not None:
+        records, draw_found = [], []
+        for d in draws:
+            records.append(metrics.roi_moments(d, index))
+            if seg is not None:
+                est, _ = metrics.segment(d, seg["threshold"], connectivity=seg["connectivity"],
+                                         min_voxels=seg["min_voxels"], keep=keep)
+                found = metrics.detection(labels, est)
+                draw_found.append({"n_found": found["n_found"], "false_positives": found["false_positives"]})
     den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records)
     inp_rep = metrics.roi_report(inp, tgt, index, background=background)
     regions = {str(label): {"n": den_rep[label]["n"], "target": den_rep[label]["target"],
@@ -281,7 +393,11 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws):
                       "; mean over draws +- %s" % show(r["denoised"]["mean_std"]) if records else ""))
     if len(index.labels) > 20:
         logger.log("  (%d more regions in the metrics file)" % (len(index.labels) - 20))
-    return {"labels": args.roi_labels, "background": background, "regions": regions}
+    if seg is None:
+        return {"labels": args.roi_labels, "background": background, "regions": regions}
+    return {"labels": labels_path, "background": None, "threshold": seg["threshold"],
+            "connectivity": seg["connectivity"], "min_voxels": seg["min_voxels"], "regions": regions,
+            "detection": _detection_block(seg, regions, inp, den, draw_found)}
 
 
 def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, roi=None, draws=None):
@@ -325,7 +441,7 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
                    % (r["coverage_1"], r["coverage_2"]))
     if roi is not None:
         keep = None if weight is None else live.to(th.uint8).contiguous()
-        report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws)
+        report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=out_path)
     path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
     with open(path, "w") as f:
         json.dump(report, f, indent=2)

@@ -792,6 +792,35 @@ size_t ddpm3d_roi_moments_workspace_bytes(int B, const ddpm3d_roi_index* index);
 int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t voxels, const ddpm3d_roi_index* index,
                        void* ws, size_t ws_bytes, double* out, void* stream);
 /*
+ * Connected-component labelling of a thresholded volume (added within ABI 13; the reference has no such code): the
+ * mechanical lesion definition of PET, "voxels above an SUV threshold, grouped into connected components", whose
+ * labels feed the region index above.
+ *   vol           [D][H][W] fp32, W innermost
+ *   keep          [D][H][W] uint8 or NULL
+ *   foreground    vol > threshold (so NaN is background) and, with keep, keep != 0
+ *   connectivity  6 (faces), 18 (faces + edges) or 26 (faces + edges + corners)
+ *   roots         [D][H][W] int32 out: roots[v] = the flat index of the lowest-index voxel of v's component, -1 for
+ *                 background.  One right answer: the same bits on every run, whatever order the atomics resolve in.
+ *                 Ranking the roots (roots[v] == v) in ascending order numbers the components in raster order of
+ *                 their first voxel, which is scipy.ndimage.label's numbering.
+ *   status        DEVICE int32[2] out: {a device loop hit its iteration cap (always 0; anything else means the result
+ *                 must not be used), the number of roots}.  The kernels write both words; no need to clear them.
+ * Four launches on `stream`: a workgroup per brick of DDPM3D_CCL_TILE_D x _H x _W voxels labels it in LDS; foreground
+ * voxels on a brick's low faces unite the trees across brick borders (atomicMin on root slots only); every voxel
+ * looks its root up; one workgroup folds per-workgroup root counts and cap flags from the workspace into status.  No
+ * workgroup waits for another.
+ * ws: ddpm3d_label_components_workspace_bytes(D, H, W) bytes, 16-byte aligned; its contents before the call do not
+ * matter (0 is the answer for a shape the entry refuses).  Returns DDPM3D_EINVAL before any launch for a NULL vol,
+ * roots, status or ws, a connectivity other than 6 / 18 / 26, an extent below 1, D * H * W above 2^31 - 1 (labels are
+ * 32-bit), a NaN threshold, and a workspace that is too small or misaligned.
+ */
+#define DDPM3D_CCL_TILE_D 8
+#define DDPM3D_CCL_TILE_H 8
+#define DDPM3D_CCL_TILE_W 64
+size_t ddpm3d_label_components_workspace_bytes(int D, int H, int W);
+int ddpm3d_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity, int D, int H,
+                            int W, int32_t* roots, void* ws, size_t ws_bytes, int32_t* status, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
