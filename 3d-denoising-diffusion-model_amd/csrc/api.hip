@@ -901,6 +901,33 @@ int ddpm3d_label_components(const float* vol, const uint8_t* keep, float thresho
                     "label_components");
 }
 
+// ------------------------------------------------- sphere-mean map for SUVpeak (added within ABI 13)
+int ddpm3d_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int H, int W, int r0, int r1,
+                       const int32_t* half_w, float* out, void* stream) {
+    const int R = DDPM3D_PEAK_MAX_RADIUS;
+    if (!vol || !out || !half_w) return fail(DDPM3D_EINVAL, "sphere_mean: null pointer");
+    if (vol == out) return fail(DDPM3D_EINVAL, "sphere_mean: out must not be vol (every voxel is read by its neighbours)");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "sphere_mean: B=%d volumes (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (D < 1 || H < 1 || W < 1 || (int64_t)D * H > 0x7fffffff || (int64_t)D * H * W > 0x7fffffff)
+        return fail(DDPM3D_EINVAL, "sphere_mean: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)",
+                    D, H, W);
+    if (r0 < 0 || r0 > R || r1 < 0 || r1 > R)
+        return fail(DDPM3D_EINVAL, "sphere_mean: radii r0=%d r1=%d (0..%d)", r0, r1, R);
+    const int n0 = 2 * r0 + 1, n1 = 2 * r1 + 1;
+    for (int i = 0; i < n0 * n1; ++i)
+        if (half_w[i] < -1 || half_w[i] > R)
+            return fail(DDPM3D_EINVAL, "sphere_mean: half_w[%d][%d]=%d (-1..%d)", i / n1, i % n1, half_w[i], R);
+    if (half_w[r0 * n1 + r1] < 0) return fail(DDPM3D_EINVAL, "sphere_mean: the centre row half_w[%d][%d] is absent", r0, r1);
+    for (int i = 0; i < n0; ++i)
+        for (int j = 0; j < n1; ++j)
+            if (half_w[i * n1 + j] != half_w[(n0 - 1 - i) * n1 + j] || half_w[i * n1 + j] != half_w[i * n1 + n1 - 1 - j])
+                return fail(DDPM3D_EINVAL, "sphere_mean: half_w is not symmetric under dz -> -dz and dy -> -dy (at [%d][%d])",
+                            i, j);
+    return launched(ddpm3d_launch_sphere_mean(vol, keep, B, D, H, W, r0, r1, half_w, out, (hipStream_t)stream),
+                    "sphere_mean");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

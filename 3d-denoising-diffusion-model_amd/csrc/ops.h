@@ -85,6 +85,12 @@ size_t ddpm3d_ccl_workspace_bytes(int D, int H, int W);
 hipError_t ddpm3d_launch_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity,
                                           int D, int H, int W, int32_t* roots, void* ws, int32_t* status,
                                           hipStream_t st);
+// peak.hip: the sphere-mean map of B volumes (the caller has checked the shape, the radii and the table, whose
+// entries lie in -1..DDPM3D_PEAK_MAX_RADIUS)
+hipError_t ddpm3d_launch_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int H, int W, int r0, int r1,
+                                     const int32_t* half_w, float* out, hipStream_t st);
+// the tile (TD, TH; TW = 64) and the LDS bytes that launch uses for radii (r0, r1, rw) with or without keep
+void ddpm3d_sphere_mean_tile(int r0, int r1, int rw, bool keep, int* TD, int* TH, size_t* lds_bytes);
 // joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
 // patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
 struct ddpm3d_joint_starts;

@@ -101,6 +101,7 @@ class UnetDesc(C.Structure):
 (ROI_N, ROI_SUM_X, ROI_SUM_SQ_X, ROI_MIN_X, ROI_MAX_X, ROI_SUM_E, ROI_SUM_ABS_E, ROI_SUM_SQ_E, ROI_REC) = range(9)
 ROI_MAX_REGIONS, ROI_CHUNK = 4096, 4096
 CCL_TILE = (8, 8, 64)   # DDPM3D_CCL_TILE_D / _H / _W: the brick one workgroup of ddpm3d_label_components labels in LDS
+PEAK_MAX_RADIUS = 8     # DDPM3D_PEAK_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_sphere_mean's footprint
 
 JOINT_MAX_STARTS = 8    # DDPM3D_JOINT_MAX_STARTS
 
@@ -199,6 +200,8 @@ EXPORTS = {
     "ddpm3d_label_components_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ddpm3d_label_components": (C.c_int, [_fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp,
                                           C.c_size_t, _fp, _fp]),
+    "ddpm3d_sphere_mean": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(C.c_int32), _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

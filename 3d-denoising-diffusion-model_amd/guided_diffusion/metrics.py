@@ -16,6 +16,10 @@ together.
 Lesion segmentation: label_components thresholds a volume and labels its connected components with
 ddpm3d_label_components (csrc/ccl.hip), segment drops the specks, detection compares two segmentations (lesions
 found and missed, false positives).  Their labels feed roi_index.
+
+SUVpeak, MTV and TLG: sphere_footprint turns a voxel spacing into PERCIST's 1 cm^3 sphere in run
+form, sphere_mean is one launch of ddpm3d_sphere_mean (csrc/peak.hip) that writes the sphere mean around every voxel,
+roi_peak is roi_moments' MAX_X of that map; with a spacing roi_figures adds volume_ml and tlg, roi_report the peaks.
 """
 
 import ctypes
@@ -273,7 +277,8 @@ def _region(rec):
             "max": rec[H.ROI_MAX_X] if n else None, "cov": _ratio(std, mean)}
 
 
-def roi_figures(records, target_records=None, labels=None, background=None, draw_records=None):
+def roi_figures(records, target_records=None, labels=None, background=None, draw_records=None, *, spacing=None,
+                peaks=None, target_peaks=None, draw_peaks=None):
     """Records to figures, on the host: {label: figures} for the R records of one estimate (roi_moments' return).
     Per region n, mean, std (population), min, max, cov = std / mean.  With target_records, the target's own records
     (roi_moments(target, index)) beside records taken against that target: mean_bias, mean_bias_rel, max_bias_rel,
@@ -281,7 +286,11 @@ def roi_figures(records, target_records=None, labels=None, background=None, draw
     (mean_r - mean_g) / std_g and, with target_records, crc = contrast / the target's contrast.  With draw_records
     (K >= 2 lists of R records): draw_means, mean_std (sample std of the K region means, ddof = 1) and, with
     target_records, mean_z = (mean of the draw means - target mean) / mean_std.  A figure whose denominator is 0 is
-    None.  labels default to 0..R-1."""
+    None.  labels default to 0..R-1.  The keyword-only arguments add figures and change none: spacing (mm per voxel,
+    three numbers): volume_ml = n s0 s1 s2 / 1000 (the MTV of a lesion), tlg = volume_ml * mean and, with
+    target_records, tlg_bias_rel; peaks (R values, roi_peak's return): peak and, with target_peaks, peak_bias_rel =
+    (peak - target peak) / target peak; draw_peaks (K >= 2 lists of R values): draw_peaks and peak_std (sample std,
+    ddof = 1)."""
     R = len(records)
     labels = list(range(R)) if labels is None else [int(v) for v in labels]
     if len(labels) != R or (target_records is not None and len(target_records) != R):
@@ -291,6 +300,11 @@ def roi_figures(records, target_records=None, labels=None, background=None, draw
         raise ValueError("roi_figures: draw_records must be K >= 2 lists of %d records" % R)
     if background is not None and background not in labels:
         raise ValueError("roi_figures: background label %r is not a region (%s)" % (background, labels))
+    if any(p is not None and len(p) != R for p in (peaks, target_peaks)):
+        raise ValueError("roi_figures: peaks and target_peaks must hold %d values" % R)
+    if draw_peaks is not None and (len(draw_peaks) < 2 or any(len(d) != R for d in draw_peaks)):
+        raise ValueError("roi_figures: draw_peaks must be K >= 2 lists of %d values" % R)
+    voxel_ml = None if spacing is None else math.prod(_check_spacing(spacing, "roi_figures")) / 1000.0
     figs = [_region(r) for r in records]
     tfigs = None if target_records is None else [_region(r) for r in target_records]
     g = None if background is None else labels.index(background)
@@ -322,23 +336,160 @@ def roi_figures(records, target_records=None, labels=None, background=None, draw
                 f["mean_std"] = math.sqrt(math.fsum((m - centre) ** 2 for m in means) / (K - 1))
                 if tfigs is not None:
                     f["mean_z"] = _ratio(centre - tfigs[i]["mean"], f["mean_std"])
+        if voxel_ml is not None:
+            f["volume_ml"] = n * voxel_ml
+            f["tlg"] = None if f["mean"] is None else f["volume_ml"] * f["mean"]
+            if tfigs is not None:
+                t = tfigs[i]
+                t_tlg = None if t["mean"] is None else t["n"] * voxel_ml * t["mean"]
+                f["tlg_bias_rel"] = None if f["tlg"] is None or t_tlg is None else _ratio(f["tlg"] - t_tlg, t_tlg)
+        if peaks is not None:
+            f["peak"] = peaks[i] if n else None
+            if target_peaks is not None:
+                tp = target_peaks[i] if n else None
+                f["peak_bias_rel"] = None if tp is None else _ratio(f["peak"] - tp, tp)
+        if draw_peaks is not None:
+            f["draw_peaks"] = [d[i] if n else None for d in draw_peaks]
+            f["peak_std"] = None
+            if n:
+                K = len(draw_peaks)
+                centre = math.fsum(f["draw_peaks"]) / K
+                f["peak_std"] = math.sqrt(math.fsum((v - centre) ** 2 for v in f["draw_peaks"]) / (K - 1))
         out[label] = f
     return out
 
 
-def roi_report(estimate, target, index, labels=None, background=None, draws=None):
+def roi_report(estimate, target, index, labels=None, background=None, draws=None, *, spacing=None, volume_mm3=None,
+               keep=None, draw_peaks=None, footprint=None, target_peaks=None):
     """Region figures of one (D, H, W) estimate against the target: {label: {"n", "target": the target's own n,
     mean, std, min, max, cov, "estimate": roi_figures of the estimate}}.  labels names the regions (default: the
     index's own labels); draws is a (K, D, H, W) device tensor of K >= 2 posterior draws or their K lists of records
-    (roi_moments of each draw).  The target's own statistics come from one roi_moments(target, index) call."""
+    (roi_moments of each draw).  The target's own statistics come from one roi_moments(target, index) call.
+    With spacing (mm per voxel along the tensors' three axes) both blocks gain volume_ml, tlg and peak (roi_peak over
+    the sphere of volume_mm3, default 1000; keep as in sphere_mean) and the estimate tlg_bias_rel and peak_bias_rel;
+    draws given as a tensor, or draw_peaks (K lists of roi_peak's values, for draws given as records), add draw_peaks
+    and peak_std.  A caller that reports several estimates against one target passes the footprint it already has
+    (sphere_footprint of the same spacing; volume_mm3 is then not given) and the target's peaks (roi_peak(target,
+    ...)) so that neither is computed again."""
     labels = index.labels if labels is None else labels
+    if spacing is None and not (volume_mm3 is None and keep is None and draw_peaks is None and footprint is None
+                                and target_peaks is None):
+        raise ValueError("roi_report: volume_mm3, keep, draw_peaks, footprint and target_peaks need a spacing")
+    more, tmore = {}, {}
+    if spacing is not None:
+        if footprint is None:
+            footprint = sphere_footprint(spacing, 1000.0 if volume_mm3 is None else volume_mm3)
+        elif volume_mm3 is not None or footprint.spacing != _check_spacing(spacing, "roi_report"):
+            raise ValueError("roi_report: the footprint given is its own volume_mm3 and must be of the spacing %r"
+                             % (spacing,))
+        tpeaks = roi_peak(target, index, footprint, keep=keep) if target_peaks is None else target_peaks
+        if draw_peaks is None and isinstance(draws, torch.Tensor):
+            draw_peaks = roi_peak(draws, index, footprint, keep=keep)
+        tmore = dict(spacing=spacing, peaks=tpeaks)
+        more = dict(spacing=spacing, peaks=roi_peak(estimate, index, footprint, keep=keep), target_peaks=tpeaks,
+                    draw_peaks=draw_peaks)
     trec = roi_moments(target, index)
     if isinstance(draws, torch.Tensor):
         draws = roi_moments(draws, index)
     est = roi_figures(roi_moments(estimate, index, target=target), target_records=trec, labels=labels,
-                      background=background, draw_records=draws)
-    tgt = roi_figures(trec, labels=labels)
+                      background=background, draw_records=draws, **more)
+    tgt = roi_figures(trec, labels=labels, **tmore)
     return {label: {"n": tgt[label]["n"], "target": tgt[label], "estimate": est[label]} for label in labels}
+
+
+# ----------------------------------------------------------------- SUVpeak, MTV, TLG (DESIGN.md 3.12)
+def _check_spacing(spacing, what):
+    try:
+        values = [float(v) for v in spacing]
+    except (TypeError, ValueError):
+        values = []
+    if len(values) != 3 or not all(math.isfinite(v) and v > 0 for v in values):
+        raise ValueError("%s: the voxel spacing must be three positive finite numbers, in mm (got %r)"
+                         % (what, spacing))
+    return tuple(values)
+
+
+class SphereFootprint:
+    """sphere_footprint's return: `spacing` and `volume_mm3` as given, `radius_mm`, the per-axis `radii` (r0, r1, r2)
+    in voxels, `half_w`, a (2 r0 + 1) x (2 r1 + 1) tuple of tuples (-1: the row is absent, w: it covers dx in -w..w)
+    and the tap count `taps`."""
+
+    def __init__(self, spacing, volume_mm3, radius_mm, radii, half_w):
+        self.spacing, self.volume_mm3, self.radius_mm, self.radii = spacing, volume_mm3, radius_mm, radii
+        self.half_w = tuple(tuple(row) for row in half_w)
+        self.taps = sum(2 * w + 1 for row in self.half_w for w in row if w >= 0)
+        flat = [w for row in self.half_w for w in row]
+        self.table = (ctypes.c_int32 * len(flat))(*flat)            # what ddpm3d_sphere_mean reads, on the host
+
+
+def sphere_footprint(spacing, volume_mm3=1000.0):
+    """The binary sphere of volume_mm3 (PERCIST's SUVpeak: 1 cm^3) on a grid of `spacing` = (s0, s1, s2) mm per voxel,
+    in the axis order of the tensor it will be applied to.  r = (3 V / 4 pi)^(1/3) in fp64 (6.2035 mm for 1000);
+    offset (dz, dy, dx) belongs iff (dz s0)^2 + (dy s1)^2 + (dx s2)^2 <= r^2: the voxel centre decides, no partial
+    volumes.  A spacing coarser than r on every axis gives the single voxel (the peak is then the maximum).  Refuses a
+    spacing that is not three positive finite numbers, a volume that is not positive and finite, and a radius above
+    DDPM3D_PEAK_MAX_RADIUS voxels on any axis.  Host arithmetic only.  -> SphereFootprint"""
+    s = _check_spacing(spacing, "sphere_footprint")
+    try:
+        volume = math.nan if isinstance(volume_mm3, (bool, str)) else float(volume_mm3)
+    except (TypeError, ValueError):
+        volume = math.nan
+    if not (math.isfinite(volume) and volume > 0):
+        raise ValueError("sphere_footprint: the volume must be a positive finite number of mm^3 (got %r)"
+                         % (volume_mm3,))
+    volume_mm3 = volume
+    r = (3.0 * volume / (4.0 * math.pi)) ** (1.0 / 3.0)
+    if any(r / v >= H.PEAK_MAX_RADIUS + 1 for v in s):
+        raise ValueError("sphere_footprint: a sphere of %g mm^3 (radius %.4f mm) spans more than %d voxels from its "
+                         "centre at a spacing of %s mm: the radius is limited to DDPM3D_PEAK_MAX_RADIUS = %d voxels "
+                         "per axis" % (volume_mm3, r, H.PEAK_MAX_RADIUS, s, H.PEAK_MAX_RADIUS))
+    inside = lambda dz, dy, dx: (dz * s[0]) ** 2 + (dy * s[1]) ** 2 + (dx * s[2]) ** 2 <= r * r
+    reach = lambda axis: max(d for d in range(H.PEAK_MAX_RADIUS + 1) if inside(*[d if a == axis else 0 for a in range(3)]))
+    r0, r1, r2 = reach(0), reach(1), reach(2)
+    half_w = [[max((dx for dx in range(r2 + 1) if inside(dz, dy, dx)), default=-1) for dy in range(-r1, r1 + 1)]
+              for dz in range(-r0, r0 + 1)]
+    return SphereFootprint(s, float(volume_mm3), r, (r0, r1, r2), half_w)
+
+
+def sphere_mean(volume, footprint, keep=None):
+    """The mean over the footprint around every voxel of a device float32 (D, H, W) or (K, D, H, W) tensor: one call
+    of ddpm3d_sphere_mean (csrc/peak.hip), no host copy.  Only the footprint voxels inside the volume and, with keep
+    (a device uint8 tensor (D, H, W), shared by the K volumes), with keep != 0 are counted; a voxel none of whose
+    footprint counts gets 0.  keep does not blank the voxel itself.  -> a tensor of the volume's shape."""
+    H.require_device(volume, "volume")
+    if volume.dim() not in (3, 4):
+        raise ValueError("sphere_mean: volume of shape %s (want (D, H, W) or (K, D, H, W))" % (tuple(volume.shape),))
+    if not isinstance(footprint, SphereFootprint):
+        raise ValueError("sphere_mean: footprint must be sphere_footprint's return (got %r)" % (footprint,))
+    shape = tuple(int(v) for v in volume.shape[-3:])
+    if keep is not None and not (isinstance(keep, torch.Tensor) and keep.is_cuda and keep.dtype == torch.uint8
+                                 and keep.is_contiguous() and tuple(keep.shape) == shape
+                                 and keep.device == volume.device):
+        raise ValueError("sphere_mean: keep must be a contiguous device uint8 tensor of the volume's shape %s"
+                         % (shape,))
+    K = int(volume.shape[0]) if volume.dim() == 4 else 1
+    if not 1 <= K <= H.MAX_DRAWS:
+        raise ValueError("sphere_mean: %d volumes (1..%d)" % (K, H.MAX_DRAWS))
+    voxels = shape[0] * shape[1] * shape[2]
+    if voxels == 0 or voxels > 2 ** 31 - 1:
+        raise ValueError("sphere_mean: %d voxels (1..2^31 - 1)" % voxels)
+    lib = H.load()
+    with torch.cuda.device(volume.device):
+        out = torch.empty_like(volume)
+        H.check(lib.ddpm3d_sphere_mean(H.ptr(volume), H.ptr(keep), K, shape[0], shape[1], shape[2],
+                                       footprint.radii[0], footprint.radii[1], footprint.table, H.ptr(out),
+                                       H.stream()))
+    return out
+
+
+def roi_peak(volume, index, footprint, keep=None):
+    """SUVpeak of every region of the index: the largest sphere mean centred on a voxel of the region, i.e. column
+    MAX_X of roi_moments(sphere_mean(volume, footprint, keep), index).  -> a list of R floats for a (D, H, W) volume,
+    K such lists for a (K, D, H, W) stack."""
+    rec = roi_moments(sphere_mean(volume, footprint, keep=keep), index)
+    if volume.dim() == 4:
+        return [[r[H.ROI_MAX_X] for r in draw] for draw in rec]
+    return [r[H.ROI_MAX_X] for r in rec]
 
 
 # ----------------------------------------------------------------- lesion segmentation (DESIGN.md 3.11)

@@ -62,7 +62,14 @@ before the first sampling step and the labels are written as
 roi_labels_<name>.npz, which `--roi_labels` reads back; the "roi" entry is built
 from them as from a file and also carries "detection": which of the target's
 lesions are still there in the input and in the denoised volume (and in every
-draw), and how many hot spots either has that the target has not.
+draw), and how many hot spots either has that the target has not;
+`--voxel_spacing S0 S1 S2` (mm per voxel along the input file's axes (D, H, W);
+needs `--target_samples` and `--roi_labels` or a `--roi_threshold`) adds to
+every region's target, input and denoised figures its volume in ml (the MTV of
+a lesion), its TLG = volume x mean and its SUVpeak: the largest mean of a 1 cm^3
+sphere centred on a voxel of the region (guided_diffusion/metrics.py
+sphere_mean, roi_peak), with their relative bias against the target and, with
+`--num_draws`, the spread of the peak over the draws.
 """
 
 import argparse
@@ -115,6 +122,8 @@ def create_argparser():
     add_dict_to_argparser(parser, defaults)
     parser.add_argument("--roi_threshold", type=float, default=None)          # absolute, in the target's units
     parser.add_argument("--roi_threshold_frac", type=float, default=None)     # in (0, 1), of the target's maximum
+    # mm per voxel along the input file's (D, H, W): adds SUVpeak, volume in ml and TLG to every region
+    parser.add_argument("--voxel_spacing", type=float, nargs="+", default=None, metavar="MM")
     return parser
 
 
@@ -130,6 +139,7 @@ def main(argv=None):
         parser.error("--patch_overlap must be in 2..%d for patches of %d (got %d); -1 keeps the fixed 3 x 3 x (1 | 2) "
                      "grid" % (args.large_size - 1, args.large_size, args.patch_overlap))
     _check_segmentation(parser, args)
+    args.peak = _check_spacing(parser, args)
     vol, target = _load_target(parser, args)
     roi = _load_roi(parser, args, vol)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
@@ -298,6 +308,28 @@ def _check_segmentation(parser, args):
         parser.error("--roi_threshold_frac must lie in (0, 1) (got %r)" % args.roi_threshold_frac)
 
 
+def _check_spacing(parser, args):
+    """--voxel_spacing, checked before any file is read: None without the flag, else {"spacing": the three values
+    permuted along with the volumes, (D, H, W) -> (H, W, Z), "footprint": PERCIST's 1 cm^3 sphere on that grid}"""
+    if args.voxel_spacing is None:
+        return None
+    if len(args.voxel_spacing) != 3:
+        parser.error("--voxel_spacing takes three numbers, mm per voxel along (D, H, W) (got %d)"
+                     % len(args.voxel_spacing))
+    if not all(np.isfinite(v) and v > 0 for v in args.voxel_spacing):
+        parser.error("--voxel_spacing must be three positive finite numbers (got %s)" % (args.voxel_spacing,))
+    if not args.target_samples:
+        parser.error("--voxel_spacing needs --target_samples: its figures are taken per region against the target")
+    if not (args.roi_labels or _segmenting(args)):
+        parser.error("--voxel_spacing needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
+    s0, s1, s2 = args.voxel_spacing
+    try:
+        footprint = metrics.sphere_footprint((s1, s2, s0))
+    except ValueError as e:
+        parser.error("--voxel_spacing: %s" % e)
+    return {"spacing": (s1, s2, s0), "footprint": footprint}
+
+
 def _segment_target(parser, args, vol, target):
     """--roi_threshold / --roi_threshold_frac: the target's lesion labels, made once on the device before the first
     sampling step so that a threshold that cannot be used stops the run now.  -> {"labels": int32 (H, W, Z) on the
@@ -369,35 +401,51 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None):
         logger.log("  WARNING: --roi_background %d has no voxel of non-zero blend weight: no contrast figures"
                    % background)
         background = None
+    peak = getattr(args, "peak", None)
+    more = {}
+    if peak is not None:                       # the footprint and the target's peaks once, for both reports
+        more = {"spacing": peak["spacing"], "keep": keep, "footprint": peak["footprint"],
+                "target_peaks": metrics.roi_peak(tgt, index, peak["footprint"], keep=keep)}
     records = draw_found = None
     if draws is not None:
         records, draw_found = [], []
+        if peak is not None:
+            more["draw_peaks"] = []
         for d in draws:
             records.append(metrics.roi_moments(d, index))
+            if peak is not None:
+                more["draw_peaks"].append(metrics.roi_peak(d, index, peak["footprint"], keep=keep))
             if seg is not None:
                 est, _ = metrics.segment(d, seg["threshold"], connectivity=seg["connectivity"],
                                          min_voxels=seg["min_voxels"], keep=keep)
                 found = metrics.detection(labels, est)
                 draw_found.append({"n_found": found["n_found"], "false_positives": found["false_positives"]})
-    den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records)
-    inp_rep = metrics.roi_report(inp, tgt, index, background=background)
+    den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records, **more)
+    inp_rep = metrics.roi_report(inp, tgt, index, background=background,
+                                 **{k: v for k, v in more.items() if k != "draw_peaks"})
     regions = {str(label): {"n": den_rep[label]["n"], "target": den_rep[label]["target"],
                             "input": inp_rep[label]["estimate"], "denoised": den_rep[label]["estimate"]}
                for label in index.labels}
     show = lambda v: "n/a" if v is None else "%.5g" % v
     for label in index.labels[:20]:
         r = regions[str(label)]
-        logger.log("  region %d (%d voxels): mean %s target, %s input, %s denoised; max %s / %s / %s%s"
+        logger.log("  region %d (%d voxels): mean %s target, %s input, %s denoised; max %s / %s / %s%s%s"
                    % (label, r["n"], show(r["target"]["mean"]), show(r["input"]["mean"]), show(r["denoised"]["mean"]),
                       show(r["target"]["max"]), show(r["input"]["max"]), show(r["denoised"]["max"]),
-                      "; mean over draws +- %s" % show(r["denoised"]["mean_std"]) if records else ""))
+                      "; mean over draws +- %s" % show(r["denoised"]["mean_std"]) if records else "",
+                      "; peak %s / %s / %s" % (show(r["target"]["peak"]), show(r["input"]["peak"]),
+                                               show(r["denoised"]["peak"])) if peak is not None else ""))
     if len(index.labels) > 20:
         logger.log("  (%d more regions in the metrics file)" % (len(index.labels) - 20))
+    spaced = {}
+    if peak is not None:
+        spaced = {"voxel_spacing": list(args.voxel_spacing), "peak_volume_mm3": peak["footprint"].volume_mm3,
+                  "peak_taps": peak["footprint"].taps}
     if seg is None:
-        return {"labels": args.roi_labels, "background": background, "regions": regions}
+        return {"labels": args.roi_labels, "background": background, "regions": regions, **spaced}
     return {"labels": labels_path, "background": None, "threshold": seg["threshold"],
             "connectivity": seg["connectivity"], "min_voxels": seg["min_voxels"], "regions": regions,
-            "detection": _detection_block(seg, regions, inp, den, draw_found)}
+            "detection": _detection_block(seg, regions, inp, den, draw_found), **spaced}
 
 
 def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, roi=None, draws=None):

@@ -821,6 +821,32 @@ size_t ddpm3d_label_components_workspace_bytes(int D, int H, int W);
 int ddpm3d_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity, int D, int H,
                             int W, int32_t* roots, void* ws, size_t ws_bytes, int32_t* status, void* stream);
 /*
+ * Sphere-mean map for SUVpeak (added within ABI 13; the reference has no metric code).  PERCIST 1.0 (Wahl et al.,
+ * J Nucl Med 2009; 50 Suppl 1: 122S) defines SUVpeak as the mean of a 1 cm^3 spherical region centred on the hottest
+ * part of the lesion: here, the largest sphere mean whose centre is a voxel of the lesion, i.e. ddpm3d_roi_moments'
+ * MAX_X of the map this entry writes.  The sphere is a binary footprint decided by the voxel centre (no partial
+ * volumes): offset (dz, dy, dx) belongs to it iff (dz s0)^2 + (dy s1)^2 + (dx s2)^2 <= r^2, r = (3 V / 4 pi)^(1/3)
+ * (6.2035 mm for V = 1000 mm^3), s the voxel spacing in mm.  It reaches the library in run form:
+ *   r0, r1    radii along D and H in voxels, 0..DDPM3D_PEAK_MAX_RADIUS
+ *   half_w    HOST int32 [2 r0 + 1][2 r1 + 1]: -1 = row (dz, dy) is absent, w = it covers dx in -w..w
+ *             (w <= DDPM3D_PEAK_MAX_RADIUS).  Read during the call only: the values travel in the kernel arguments.
+ *   vol, out  [B][D][H][W] fp32, W innermost, B in 1..DDPM3D_MAX_DRAWS; keep [D][H][W] uint8 or NULL, shared by all B
+ *   out[b][v] = (sum of vol[b][u] over the n footprint voxels u around v that lie inside the volume and, with keep,
+ *             have keep[u] != 0) / n, and 0.0f where n = 0.  keep does not blank v itself: a voxel with keep == 0
+ *             still gets the mean of its kept neighbours.
+ * One launch: a workgroup stages its output tile plus halo in LDS (zeros outside the volume and where keep == 0) and
+ * sums the row runs from there in a fixed order, in fp32:
+ *   |out - m| <= (n + 2) 2^-24 (sum |x_i| / n),  m the exact mean over the n counted taps
+ * (n - 1 additions, the division, the final rounding).  No atomics: the same bits on every run, and row b does not
+ * depend on B.  Returns DDPM3D_EINVAL before any launch for a NULL vol, out or half_w, vol == out, B outside
+ * 1..DDPM3D_MAX_DRAWS, an extent below 1 or D * H * W above 2^31 - 1, r0 or r1 outside 0..DDPM3D_PEAK_MAX_RADIUS, a
+ * half_w entry outside -1..DDPM3D_PEAK_MAX_RADIUS, an absent centre row (half_w[r0][r1] < 0) and a table that is not
+ * symmetric under dz -> -dz and dy -> -dy.
+ */
+#define DDPM3D_PEAK_MAX_RADIUS 8
+int ddpm3d_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int H, int W, int r0, int r1,
+                       const int32_t* half_w, float* out, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
