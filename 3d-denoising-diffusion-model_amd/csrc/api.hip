@@ -928,6 +928,69 @@ int ddpm3d_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int 
                     "sphere_mean");
 }
 
+// ------------------------------------------------- baseline denoisers (added within ABI 13)
+static bool baseline_shape_ok(int D, int H, int W) {
+    return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H <= 0x7fffffff && (int64_t)D * H * W <= 0x7fffffff;
+}
+
+size_t ddpm3d_gauss_smooth_workspace_bytes(int D, int H, int W) {
+    return baseline_shape_ok(D, H, W) ? (((size_t)D * H * W * sizeof(float) + 15) & ~(size_t)15) : 0;
+}
+
+int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, int r2, const float* taps0,
+                        const float* taps1, const float* taps2, float* out, void* ws, size_t ws_bytes, void* stream) {
+    const int R = DDPM3D_SMOOTH_MAX_RADIUS;
+    if (!vol || !out || !taps0 || !taps1 || !taps2) return fail(DDPM3D_EINVAL, "gauss_smooth: null pointer");
+    if (vol == out) return fail(DDPM3D_EINVAL, "gauss_smooth: out must not be vol (every voxel is read by its neighbours)");
+    if (!baseline_shape_ok(D, H, W))
+        return fail(DDPM3D_EINVAL, "gauss_smooth: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)",
+                    D, H, W);
+    const int radii[3] = {r0, r1, r2};
+    const float* taps[3] = {taps0, taps1, taps2};
+    for (int a = 0; a < 3; ++a) {
+        if (radii[a] < 0 || radii[a] > R)
+            return fail(DDPM3D_EINVAL, "gauss_smooth: radii r0=%d r1=%d r2=%d (0..%d)", r0, r1, r2, R);
+        const int n = 2 * radii[a] + 1;
+        for (int j = 0; j < n; ++j) {
+            const float t = taps[a][j];
+            if (!(t > 0.0f) || t > 3.402823466e38f)
+                return fail(DDPM3D_EINVAL, "gauss_smooth: taps%d[%d]=%g (positive and finite)", a, j, (double)t);
+            if (t != taps[a][n - 1 - j])
+                return fail(DDPM3D_EINVAL, "gauss_smooth: taps%d is not symmetric (at [%d])", a, j);
+        }
+    }
+    const int rc = metric_ws_ok("gauss_smooth", ddpm3d_gauss_smooth_workspace_bytes(D, H, W), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    if (ws == (const void*)vol || ws == (void*)out)
+        return fail(DDPM3D_EINVAL, "gauss_smooth: the workspace must be neither vol nor out");
+    return launched(ddpm3d_launch_gauss_smooth(vol, D, H, W, radii, taps, out, (float*)ws, (hipStream_t)stream),
+                    "gauss_smooth");
+}
+
+int ddpm3d_nlm(const float* vol, int D, int H, int W, int s0, int s1, int s2, int p0, int p1, int p2, float h,
+               float sigma, float* out, void* stream) {
+    const int S = DDPM3D_NLM_MAX_SEARCH, P = DDPM3D_NLM_MAX_PATCH;
+    if (!vol || !out) return fail(DDPM3D_EINVAL, "nlm: null pointer");
+    if (vol == out) return fail(DDPM3D_EINVAL, "nlm: out must not be vol (every voxel is read by its neighbours)");
+    if (!baseline_shape_ok(D, H, W))
+        return fail(DDPM3D_EINVAL, "nlm: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)", D, H, W);
+    if (s0 < 0 || s0 > S || s1 < 0 || s1 > S || s2 < 0 || s2 > S)
+        return fail(DDPM3D_EINVAL, "nlm: search radii s0=%d s1=%d s2=%d (0..%d)", s0, s1, s2, S);
+    if (p0 < 0 || p0 > P || p1 < 0 || p1 > P || p2 < 0 || p2 > P)
+        return fail(DDPM3D_EINVAL, "nlm: patch radii p0=%d p1=%d p2=%d (0..%d)", p0, p1, p2, P);
+    if (!(h > 0.0f) || h > 3.402823466e38f) return fail(DDPM3D_EINVAL, "nlm: h=%g (positive and finite)", (double)h);
+    if (!(sigma >= 0.0f) || sigma > 3.402823466e38f)
+        return fail(DDPM3D_EINVAL, "nlm: sigma=%g (0 or more, finite)", (double)sigma);
+    // the two constants of the exponent, formed in fp64 and rounded once each
+    const double n_p = (double)(2 * p0 + 1) * (2 * p1 + 1) * (2 * p2 + 1);
+    const double k1 = 1.0 / (n_p * (double)h * (double)h), k2 = 2.0 * (double)sigma * (double)sigma / ((double)h * (double)h);
+    if (k1 > 3.402823466e38 || k2 > 3.402823466e38)
+        return fail(DDPM3D_EINVAL, "nlm: h=%g is too small: 1 / (n_p h^2) = %g and 2 sigma^2 / h^2 = %g must be finite "
+                                   "in fp32", (double)h, k1, k2);
+    const int search[3] = {s0, s1, s2}, patch[3] = {p0, p1, p2};
+    return launched(ddpm3d_launch_nlm(vol, D, H, W, search, patch, (float)k1, (float)k2, out, (hipStream_t)stream), "nlm");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

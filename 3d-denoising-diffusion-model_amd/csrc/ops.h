@@ -91,6 +91,16 @@ hipError_t ddpm3d_launch_sphere_mean(const float* vol, const uint8_t* keep, int 
                                      const int32_t* half_w, float* out, hipStream_t st);
 // the tile (TD, TH; TW = 64) and the LDS bytes that launch uses for radii (r0, r1, rw) with or without keep
 void ddpm3d_sphere_mean_tile(int r0, int r1, int rw, bool keep, int* TD, int* TH, size_t* lds_bytes);
+// smooth.hip: the separable Gaussian of one volume, passes along W, H, D (the caller has checked the shape, the radii
+// (D, H, W order, 0..DDPM3D_SMOOTH_MAX_RADIUS), the three host tap tables and the workspace of one volume)
+hipError_t ddpm3d_launch_gauss_smooth(const float* vol, int D, int H, int W, const int* radii, const float* const* taps,
+                                      float* out, float* ws, hipStream_t st);
+// nlm.hip: non-local means of one volume (the caller has checked the shape and the radii); the weight of a candidate
+// is exp(-max(fma(sum of squared patch differences, k1, -k2), 0)), k1 = 1 / (n_p h^2), k2 = 2 sigma^2 / h^2
+hipError_t ddpm3d_launch_nlm(const float* vol, int D, int H, int W, const int* search, const int* patch, float k1,
+                             float k2, float* out, hipStream_t st);
+// the tile (TD, TH; TW = 64) and the LDS bytes that launch uses for halos (R0, R1, R2), R_a = s_a + p_a
+void ddpm3d_nlm_tile(int R0, int R1, int R2, int* TD, int* TH, size_t* lds_bytes);
 // joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
 // patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
 struct ddpm3d_joint_starts;

@@ -102,6 +102,9 @@ class UnetDesc(C.Structure):
 ROI_MAX_REGIONS, ROI_CHUNK = 4096, 4096
 CCL_TILE = (8, 8, 64)   # DDPM3D_CCL_TILE_D / _H / _W: the brick one workgroup of ddpm3d_label_components labels in LDS
 PEAK_MAX_RADIUS = 8     # DDPM3D_PEAK_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_sphere_mean's footprint
+SMOOTH_MAX_RADIUS = 16  # DDPM3D_SMOOTH_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_gauss_smooth's taps
+NLM_MAX_SEARCH, NLM_MAX_PATCH = 5, 2    # DDPM3D_NLM_MAX_SEARCH / _PATCH: ddpm3d_nlm's largest window radii per axis
+NLM_CUTOFF = 80.0       # DDPM3D_NLM_CUTOFF: beyond this exponent a candidate's weight is exactly 0
 
 JOINT_MAX_STARTS = 8    # DDPM3D_JOINT_MAX_STARTS
 
@@ -202,6 +205,9 @@ EXPORTS = {
                                           C.c_size_t, _fp, _fp]),
     "ddpm3d_sphere_mean": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(C.c_int32), _fp, _fp]),
+    "ddpm3d_gauss_smooth_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ddpm3d_gauss_smooth": (C.c_int, [_fp] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 3 + [_fp, _fp, C.c_size_t, _fp]),
+    "ddpm3d_nlm": (C.c_int, [_fp] + [C.c_int] * 9 + [C.c_float, C.c_float, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

@@ -20,6 +20,10 @@ found and missed, false positives).  Their labels feed roi_index.
 SUVpeak, MTV and TLG: sphere_footprint turns a voxel spacing into PERCIST's 1 cm^3 sphere in run
 form, sphere_mean is one launch of ddpm3d_sphere_mean (csrc/peak.hip) that writes the sphere mean around every voxel,
 roi_peak is roi_moments' MAX_X of that map; with a spacing roi_figures adds volume_ml and tlg, roi_report the peaks.
+
+Baseline denoisers, to score beside the written volume: gaussian_taps turns a FWHM in mm and a voxel
+spacing into the taps of the clinic's Gaussian post-filter, gaussian_smooth applies them with ddpm3d_gauss_smooth
+(csrc/smooth.hip), nlm is non-local means in one launch of ddpm3d_nlm (csrc/nlm.hip).
 """
 
 import ctypes
@@ -490,6 +494,138 @@ def roi_peak(volume, index, footprint, keep=None):
     if volume.dim() == 4:
         return [[r[H.ROI_MAX_X] for r in draw] for draw in rec]
     return [r[H.ROI_MAX_X] for r in rec]
+
+
+# ----------------------------------------------------------------- baseline denoisers
+FWHM_PER_SIGMA = 2.0 * math.sqrt(2.0 * math.log(2.0))
+
+
+class GaussianTaps:
+    """gaussian_taps' return: `fwhm_mm` (three values) and `spacing` as given, the per-axis `sigma_voxels`, `radii`
+    and `taps`: three tuples of 2 r + 1 fp32 values, exp(-j^2 / 2 sigma^2) for j = -r..r."""
+
+    def __init__(self, fwhm_mm, spacing, sigma_voxels, radii, taps):
+        self.fwhm_mm, self.spacing, self.sigma_voxels, self.radii = fwhm_mm, spacing, sigma_voxels, radii
+        self.taps = tuple(tuple(t) for t in taps)
+        self.tables = tuple((ctypes.c_float * len(t))(*t) for t in self.taps)   # what ddpm3d_gauss_smooth reads
+
+
+def _positive(value, what):
+    try:
+        v = math.nan if isinstance(value, (bool, str)) else float(value)
+    except (TypeError, ValueError):
+        v = math.nan
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError("%s must be a positive finite number (got %r)" % (what, value))
+    return v
+
+
+def gaussian_taps(fwhm_mm, spacing, truncate=3.0):
+    """The taps of a Gaussian post-filter of `fwhm_mm` (one number or three, in mm) on a grid of `spacing` mm per
+    voxel, in the axis order of the tensor: per axis sigma = fwhm / (2 sqrt(2 ln 2)) / spacing voxels and the radius
+    int(truncate sigma + 0.5), scipy.ndimage.gaussian_filter's rule, so that away from the faces gaussian_smooth
+    equals scipy.ndimage.gaussian_filter(x, sigma, truncate=truncate).  The taps are formed in fp64 and rounded to
+    fp32.  Refuses a radius above DDPM3D_SMOOTH_MAX_RADIUS voxels and names the axis.  Host arithmetic only.
+    -> GaussianTaps"""
+    s = _check_spacing(spacing, "gaussian_taps")
+    if isinstance(fwhm_mm, (list, tuple)):
+        if len(fwhm_mm) != 3:
+            raise ValueError("gaussian_taps: the FWHM is one number or three, in mm (got %r)" % (fwhm_mm,))
+        fwhm = tuple(_positive(f, "gaussian_taps: the FWHM") for f in fwhm_mm)
+    else:
+        fwhm = (_positive(fwhm_mm, "gaussian_taps: the FWHM"),) * 3
+    truncate = _positive(truncate, "gaussian_taps: truncate")
+    sigma = tuple(f / FWHM_PER_SIGMA / v for f, v in zip(fwhm, s))
+    radii = tuple(int(truncate * sg + 0.5) for sg in sigma)
+    for axis, r in enumerate(radii):
+        if r > H.SMOOTH_MAX_RADIUS:
+            raise ValueError("gaussian_taps: a FWHM of %g mm at a spacing of %g mm needs a radius of %d voxels along "
+                             "axis %d: the radius is limited to DDPM3D_SMOOTH_MAX_RADIUS = %d voxels per axis"
+                             % (fwhm[axis], s[axis], r, axis, H.SMOOTH_MAX_RADIUS))
+    as_fp32 = lambda v: ctypes.c_float(v).value
+    taps = [[as_fp32(math.exp(-0.5 * j * j / (sg * sg))) for j in range(-r, r + 1)] for sg, r in zip(sigma, radii)]
+    for axis, t in enumerate(taps):
+        if not all(v > 0 for v in t):
+            raise ValueError("gaussian_taps: a tap along axis %d underflows fp32 (truncate = %g)" % (axis, truncate))
+    return GaussianTaps(fwhm, s, sigma, radii, taps)
+
+
+def _one_volume(volume, what):
+    H.require_device(volume, "volume")
+    if volume.dim() != 3:
+        raise ValueError("%s: volume of shape %s (want (D, H, W))" % (what, tuple(volume.shape)))
+    shape = tuple(int(v) for v in volume.shape)
+    voxels = shape[0] * shape[1] * shape[2]
+    if voxels == 0 or voxels > 2 ** 31 - 1:
+        raise ValueError("%s: %d voxels (1..2^31 - 1)" % (what, voxels))
+    return shape
+
+
+def gaussian_smooth(volume, taps):
+    """The separable Gaussian of a device float32 (D, H, W) tensor with gaussian_taps' taps: ddpm3d_gauss_smooth
+    (csrc/smooth.hip), no host copy.  Taps beyond a face do not count and the rest are renormalised.  -> a device
+    tensor of the volume's shape."""
+    if not isinstance(taps, GaussianTaps):
+        raise ValueError("gaussian_smooth: taps must be gaussian_taps' return (got %r)" % (taps,))
+    shape = _one_volume(volume, "gaussian_smooth")
+    lib = H.load()
+    with torch.cuda.device(volume.device):
+        out = torch.empty_like(volume)
+        need = lib.ddpm3d_gauss_smooth_workspace_bytes(*shape)
+        ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=volume.device)
+        H.check(lib.ddpm3d_gauss_smooth(H.ptr(volume), shape[0], shape[1], shape[2], taps.radii[0], taps.radii[1],
+                                        taps.radii[2], taps.tables[0], taps.tables[1], taps.tables[2], H.ptr(out),
+                                        H.ptr(ws), ws.numel() * 4, H.stream()))
+    return out
+
+
+def _radii(value, limit, what):
+    """an int for all three axes, or three ints, each in 0..limit"""
+    values = [value] * 3 if isinstance(value, int) and not isinstance(value, bool) else value
+    try:
+        values = tuple(values)
+    except TypeError:
+        values = ()
+    if len(values) != 3 or not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v <= limit for v in values):
+        raise ValueError("%s must be an int or three ints in 0..%d (got %r)" % (what, limit, value))
+    return values
+
+
+def nlm_check(h, search=(3, 3, 3), patch=(1, 1, 1), sigma=0.0):
+    """nlm's refusals of its parameters, on the host.  -> (h, search, patch, sigma) as nlm passes them on"""
+    search = _radii(search, H.NLM_MAX_SEARCH, "nlm: the search radius")
+    patch = _radii(patch, H.NLM_MAX_PATCH, "nlm: the patch radius")
+    h = ctypes.c_float(_positive(h, "nlm: h")).value
+    try:
+        sigma = math.nan if isinstance(sigma, (bool, str)) else float(sigma)
+    except (TypeError, ValueError):
+        sigma = math.nan
+    if not (math.isfinite(sigma) and sigma >= 0):
+        raise ValueError("nlm: sigma must be a finite number, 0 or more (got %r)" % (sigma,))
+    sigma = ctypes.c_float(sigma).value
+    fp32_max = 3.4028234663852886e38
+    n_p = (2 * patch[0] + 1) * (2 * patch[1] + 1) * (2 * patch[2] + 1)
+    if h == 0 or math.isinf(h) or math.isinf(sigma):
+        raise ValueError("nlm: h and sigma must be finite in fp32, h above 0 (got %r, %r)" % (h, sigma))
+    if 1.0 / n_p / h / h > fp32_max or 2.0 * (sigma / h) ** 2 > fp32_max:
+        raise ValueError("nlm: h = %r is too small: 1 / (n_p h^2) and 2 sigma^2 / h^2 must be finite in fp32" % (h,))
+    return h, search, patch, sigma
+
+
+def nlm(volume, h, search=(3, 3, 3), patch=(1, 1, 1), sigma=0.0):
+    """Non-local means of a device float32 (D, H, W) tensor: ddpm3d_nlm (csrc/nlm.hip), one launch, no host copy.
+    Every voxel becomes the weighted mean of the voxels within `search` (radii per axis, or one int for all) that lie
+    inside the volume, with the weight exp(-max(d2 - 2 sigma^2, 0) / h^2) of the mean squared difference d2 of the
+    patches of radius `patch` around the two (replicate padding), exactly 0 beyond an exponent of 80, and 1 for the
+    voxel itself.  -> a device tensor of the volume's shape."""
+    h, search, patch, sigma = nlm_check(h, search, patch, sigma)
+    shape = _one_volume(volume, "nlm")
+    lib = H.load()
+    with torch.cuda.device(volume.device):
+        out = torch.empty_like(volume)
+        H.check(lib.ddpm3d_nlm(H.ptr(volume), shape[0], shape[1], shape[2], search[0], search[1], search[2],
+                               patch[0], patch[1], patch[2], h, sigma, H.ptr(out), H.stream()))
+    return out
 
 
 # ----------------------------------------------------------------- lesion segmentation (DESIGN.md 3.11)

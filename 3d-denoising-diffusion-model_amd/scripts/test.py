@@ -69,7 +69,16 @@ every region's target, input and denoised figures its volume in ml (the MTV of
 a lesion), its TLG = volume x mean and its SUVpeak: the largest mean of a 1 cm^3
 sphere centred on a voxel of the region (guided_diffusion/metrics.py
 sphere_mean, roi_peak), with their relative bias against the target and, with
-`--num_draws`, the spread of the peak over the draws.
+`--num_draws`, the spread of the peak over the draws;
+`--baseline_gaussian_fwhm MM` (needs `--target_samples` and `--voxel_spacing`,
+which then needs no regions) and `--baseline_nlm_h H` (needs
+`--target_samples`; `--baseline_nlm_search N`, default 3, `--baseline_nlm_patch
+N`, default 1, `--baseline_nlm_sigma S`, default 0) filter the low-dose input
+once on the GPU with the clinic's Gaussian post-filter of that FWHM and with
+non-local means (guided_diffusion/metrics.py gaussian_smooth, nlm) and score
+the two like the input and the written volume: the entry "baselines" of
+metrics_<name>.json and, with regions, "gaussian" and "nlm" beside "input" in
+every region.  The filtered volumes are not written.
 """
 
 import argparse
@@ -124,6 +133,13 @@ def create_argparser():
     parser.add_argument("--roi_threshold_frac", type=float, default=None)     # in (0, 1), of the target's maximum
     # mm per voxel along the input file's (D, H, W): adds SUVpeak, volume in ml and TLG to every region
     parser.add_argument("--voxel_spacing", type=float, nargs="+", default=None, metavar="MM")
+    # baseline denoisers of the input, scored beside it: a Gaussian post-filter of this FWHM in mm, and non-local
+    # means with this h (in the volume's units), these window radii in voxels and this noise std
+    parser.add_argument("--baseline_gaussian_fwhm", type=float, default=None, metavar="MM")
+    parser.add_argument("--baseline_nlm_h", type=float, default=None, metavar="H")
+    parser.add_argument("--baseline_nlm_search", type=int, default=3, metavar="N")
+    parser.add_argument("--baseline_nlm_patch", type=int, default=1, metavar="N")
+    parser.add_argument("--baseline_nlm_sigma", type=float, default=0.0, metavar="S")
     return parser
 
 
@@ -140,6 +156,7 @@ def main(argv=None):
                      "grid" % (args.large_size - 1, args.large_size, args.patch_overlap))
     _check_segmentation(parser, args)
     args.peak = _check_spacing(parser, args)
+    args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
     roi = _load_roi(parser, args, vol)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
@@ -321,6 +338,8 @@ def _check_spacing(parser, args):
     if not args.target_samples:
         parser.error("--voxel_spacing needs --target_samples: its figures are taken per region against the target")
     if not (args.roi_labels or _segmenting(args)):
+        if args.baseline_gaussian_fwhm is not None:
+            return None                        # the spacing serves the Gaussian baseline alone
         parser.error("--voxel_spacing needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
     s0, s1, s2 = args.voxel_spacing
     try:
@@ -328,6 +347,62 @@ def _check_spacing(parser, args):
     except ValueError as e:
         parser.error("--voxel_spacing: %s" % e)
     return {"spacing": (s1, s2, s0), "footprint": footprint}
+
+
+def _check_baselines(parser, args):
+    """--baseline_gaussian_fwhm / --baseline_nlm_h and their options, checked before any file is read (and after
+    --voxel_spacing): None without either flag, else {"gaussian": the taps on the volumes' (H, W, Z) grid, "nlm":
+    {"h", "search", "patch", "sigma"}} with the entries of the flags given"""
+    out = {}
+    if args.baseline_gaussian_fwhm is not None:
+        fwhm = args.baseline_gaussian_fwhm
+        if not (np.isfinite(fwhm) and fwhm > 0):
+            parser.error("--baseline_gaussian_fwhm must be a positive finite number of mm (got %r)" % fwhm)
+        if not args.target_samples:
+            parser.error("--baseline_gaussian_fwhm needs --target_samples: baselines are scored against the target")
+        if args.voxel_spacing is None:
+            parser.error("--baseline_gaussian_fwhm needs --voxel_spacing: the FWHM is in mm")
+        s0, s1, s2 = args.voxel_spacing
+        try:
+            out["gaussian"] = metrics.gaussian_taps(fwhm, (s1, s2, s0))     # (D, H, W) -> (H, W, Z)
+        except ValueError as e:
+            parser.error("--baseline_gaussian_fwhm: %s" % e)
+    if args.baseline_nlm_h is not None:
+        h = args.baseline_nlm_h
+        if not (np.isfinite(h) and h > 0):
+            parser.error("--baseline_nlm_h must be a positive finite number (got %r)" % h)
+        if not args.target_samples:
+            parser.error("--baseline_nlm_h needs --target_samples: baselines are scored against the target")
+        if not 0 <= args.baseline_nlm_search <= _hip.NLM_MAX_SEARCH:
+            parser.error("--baseline_nlm_search must be in 0..%d (got %d)" % (_hip.NLM_MAX_SEARCH, args.baseline_nlm_search))
+        if not 0 <= args.baseline_nlm_patch <= _hip.NLM_MAX_PATCH:
+            parser.error("--baseline_nlm_patch must be in 0..%d (got %d)" % (_hip.NLM_MAX_PATCH, args.baseline_nlm_patch))
+        try:
+            h, search, patch, sigma = metrics.nlm_check(h, args.baseline_nlm_search, args.baseline_nlm_patch,
+                                                        args.baseline_nlm_sigma)
+        except ValueError as e:
+            parser.error("--baseline_nlm_h / --baseline_nlm_sigma: %s" % e)
+        out["nlm"] = {"h": h, "search": search, "patch": patch, "sigma": sigma}
+    return out or None
+
+
+def _baseline_volumes(args, inp):
+    """The input filtered once per baseline flag, on the device: {name: ((H, W, Z) tensor, its parameters as the
+    metrics file states them)}, "gaussian" before "nlm".  The Gaussian's per-axis figures are listed along the input
+    file's (D, H, W), like --voxel_spacing."""
+    base = getattr(args, "baselines", None) or {}
+    out = {}
+    if "gaussian" in base:
+        g = base["gaussian"]
+        file_order = lambda v: [v[2], v[0], v[1]]                            # (H, W, Z) -> (D, H, W)
+        out["gaussian"] = (metrics.gaussian_smooth(inp, g),
+                           {"fwhm_mm": args.baseline_gaussian_fwhm, "sigma_voxels": file_order(g.sigma_voxels),
+                            "radii": file_order(g.radii)})
+    if "nlm" in base:
+        n = base["nlm"]
+        out["nlm"] = (metrics.nlm(inp, n["h"], search=n["search"], patch=n["patch"], sigma=n["sigma"]),
+                      {"h": n["h"], "sigma": n["sigma"], "search": list(n["search"]), "patch": list(n["patch"])})
+    return out
 
 
 def _segment_target(parser, args, vol, target):
@@ -382,9 +457,9 @@ def _detection_block(seg, regions, inp, den, draw_found):
     return out
 
 
-def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None):
+def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=None):
     """The "roi" entry of the metrics file: per-region figures of target, input and written volume, all (H, W, Z) on
-    the device; keep drops the voxels the blend left at 0; draws yields the K stitched draws one volume at a time,
+    the device, and of the `baselines` ({name: volume}), which get no detection figures; keep drops the voxels the blend left at 0; draws yields the K stitched draws one volume at a time,
     of which only the small records are kept.  roi is the (D, H, W) label volume of --roi_labels or _segment_target's
     dict, whose labels are written beside out_path first."""
     seg = roi if isinstance(roi, dict) else None
@@ -423,8 +498,13 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None):
     den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records, **more)
     inp_rep = metrics.roi_report(inp, tgt, index, background=background,
                                  **{k: v for k, v in more.items() if k != "draw_peaks"})
+    base_rep = {name: metrics.roi_report(x, tgt, index, background=background,
+                                         **{k: v for k, v in more.items() if k != "draw_peaks"})
+                for name, x in (baselines or {}).items()}
     regions = {str(label): {"n": den_rep[label]["n"], "target": den_rep[label]["target"],
-                            "input": inp_rep[label]["estimate"], "denoised": den_rep[label]["estimate"]}
+                            "input": inp_rep[label]["estimate"],
+                            **{name: rep[label]["estimate"] for name, rep in base_rep.items()},
+                            "denoised": den_rep[label]["estimate"]}
                for label in index.labels}
     show = lambda v: "n/a" if v is None else "%.5g" % v
     for label in index.labels[:20]:
@@ -487,9 +567,17 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
         r = report["denoised"]
         logger.log("  std map coverage: %.4f of the errors within 1 std, %.4f within 2"
                    % (r["coverage_1"], r["coverage_2"]))
+    filtered = _baseline_volumes(args, inp)
+    if filtered:
+        report["baselines"] = {}
+    for name, (x, params) in filtered.items():
+        report["baselines"][name] = r = {**params, **metrics.evaluate(x, tgt, data_range=data_range, mask=mask)}
+        logger.log("  %-8s vs target: PSNR %.3f dB  NRMSE %.5f  SSIM %.5f  MAE %.5g  bias %.5g  (L = %.6g, %d voxels)"
+                   % (name, r["psnr"], r["nrmse"], r["ssim"], r["mae"], r["bias"], r["data_range"], r["n_voxels"]))
     if roi is not None:
         keep = None if weight is None else live.to(th.uint8).contiguous()
-        report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=out_path)
+        report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=out_path,
+                                   baselines={name: x for name, (x, _) in filtered.items()})
     path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
     with open(path, "w") as f:
         json.dump(report, f, indent=2)

@@ -847,6 +847,59 @@ int ddpm3d_label_components(const float* vol, const uint8_t* keep, float thresho
 int ddpm3d_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int H, int W, int r0, int r1,
                        const int32_t* half_w, float* out, void* stream);
 /*
+ * Baseline denoisers (added within ABI 13; the reference has no such code): what a denoised volume is compared with.
+ * Both take one [D][H][W] fp32 volume, W innermost, no batch and no keep mask, only enqueue, use no atomics and sum in
+ * a fixed order: the same bits on every run.  u = 2^-24 below.
+ *
+ * ddpm3d_gauss_smooth: the separable Gaussian post-filter of the clinic.  taps_a is a HOST fp32 array of 2 r_a + 1
+ * symmetric, positive, finite weights (read during the call only: they travel in the kernel arguments), r_a in
+ * 0..DDPM3D_SMOOTH_MAX_RADIUS.  Per axis
+ *   y[i] = sum_j t[j] x[i + j] / sum_j t[j]   over the j in -r..r with i + j inside the volume
+ * (taps beyond a face do not count and the rest are renormalised: ddpm3d_sphere_mean's rule), along W, then H, then D.
+ * One launch per axis with r_a > 0 (a pass with r_a = 0 is the identity and is not launched; with none, out is a copy
+ * of vol), chained through ws so that vol is only read: 8 bytes of traffic per voxel and pass.  Per pass, against fp64
+ * arithmetic on the same fp32 taps, with n the counted taps (n roundings of the fma chain, the divisor, the division):
+ *   |y - m| <= (n + 2) u (sum t |x| / sum t)
+ * and over the three passes, with c_a = n_a + 2 (n_a depends only on the voxel's coordinate along a), m the exact
+ * filter of vol and M the exact filter of |vol|:
+ *   |out - m| <= ((1 + c_0 u)(1 + c_1 u)(1 + c_2 u) - 1) M
+ * ws: ddpm3d_gauss_smooth_workspace_bytes(D, H, W) bytes (one volume), 16-byte aligned, neither vol nor out; 0 is the
+ * answer for a shape the entry refuses.
+ *
+ * ddpm3d_nlm: non-local means (Buades, Coll, Morel 2005), the classical baseline of the PET denoising literature:
+ *   out[v]  = sum_s w(v, s) x[v + s] / sum_s w(v, s)    s over the box |s_a| <= s_a, only v + s inside the volume
+ *   d2(v,s) = (1 / n_p) sum_p (x[c(v + p)] - x[c(v + s + p)])^2    p over the box |p_a| <= p_a, n_p its size, c clamps
+ *             a coordinate into the volume (replicate padding, for patch taps only)
+ *   a       = max(d2 - 2 sigma^2, 0) / h^2,   w = exp(-a) if a <= DDPM3D_NLM_CUTOFF, else exactly 0;   w(v, 0) = 1
+ * so the divisor is at least 1.  s_a in 0..DDPM3D_NLM_MAX_SEARCH, p_a in 0..DDPM3D_NLM_MAX_PATCH, h > 0, sigma >= 0,
+ * both finite, and 1 / (n_p h^2) and 2 sigma^2 / h^2 finite in fp32.  One launch: a workgroup stages its output tile
+ * plus a halo of s_a + p_a per side in LDS (the tile is chosen on the host against the radii) and works from there, in
+ * fp32: the squares of a patch are added in the order (py, px, pz) ascending, a = max(fma(sum, k1, -k2), 0) with the
+ * two constants rounded once from fp64, the candidates in raster order of s (the numerator by fma, the divisor as a
+ * compensated sum whose two words enter one fp64 division), whatever the tile.  With N_s the candidates inside the
+ * volume, E = 2 (expf is within 1 ulp = 2 u) and the yardstick's m and w in fp64:
+ *   |out - m| <= c u (sum w |x| / sum w),   c = 2 ((80 + 2 sigma^2 / h^2) (n_p + 4) + E) + N_s + 2
+ * (n_p + 4: the relative error of the exponent's argument before the shift by 2 sigma^2 / h^2, which is at most 80
+ * plus that shift; twice, for the numerator and the divisor; N_s roundings of the numerator and the final one, the
+ * divisor and the division adding terms of order u^2 only).  A candidate whose a lies within (n_p + 4) u of the cutoff, relatively, may go
+ * either way: it adds at most e^-79.9 (|x[v + s]| + |m|) / sum w.  With sigma = 0 this is the form
+ * c = 2 (80 (n_p + 4) + E) + N_s + 2.
+ *
+ * Both return DDPM3D_EINVAL before any launch for a NULL pointer, vol == out, an extent below 1 or D * H * W above
+ * 2^31 - 1, a radius outside its range; the Gaussian also for a tap that is not positive and finite, a tap table that
+ * is not symmetric and a workspace that is NULL, too small, misaligned or one of the volumes; NLM for a bad h or
+ * sigma.
+ */
+#define DDPM3D_SMOOTH_MAX_RADIUS 16
+#define DDPM3D_NLM_MAX_SEARCH 5
+#define DDPM3D_NLM_MAX_PATCH 2
+#define DDPM3D_NLM_CUTOFF 80.0f
+size_t ddpm3d_gauss_smooth_workspace_bytes(int D, int H, int W);
+int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, int r2, const float* taps0,
+                        const float* taps1, const float* taps2, float* out, void* ws, size_t ws_bytes, void* stream);
+int ddpm3d_nlm(const float* vol, int D, int H, int W, int s0, int s1, int s2, int p0, int p1, int p2, float h,
+               float sigma, float* out, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
