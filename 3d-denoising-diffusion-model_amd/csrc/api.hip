@@ -825,6 +825,52 @@ int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, in
                     "ssim3d");
 }
 
+// ------------------------------------------------- multi-scale SSIM (added within ABI 13)
+int ddpm3d_pool2(const float* vol, const uint8_t* mask, int B, int D, int H, int W, float* out, uint8_t* mask_out,
+                 void* stream) {
+    if (!vol || !out) return fail(DDPM3D_EINVAL, "pool2: null pointer");
+    if ((mask == nullptr) != (mask_out == nullptr))
+        return fail(DDPM3D_EINVAL, "pool2: mask and mask_out must both be given or both be NULL");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "pool2: B=%d volumes (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (D < 2 || H < 2 || W < 2 || D > 65535 || H > 65535 || W > 65535 || (int64_t)H * W > 0x7fffffff ||
+        (int64_t)D * H * W > EM_MAX_VOXELS)
+        return fail(DDPM3D_EINVAL, "pool2: bad volume (D=%d H=%d W=%d; 2..65535 each, H * W <= 2^31 - 1, "
+                                   "D * H * W <= 2^40)", D, H, W);
+    return launched(ddpm3d_launch_pool2(vol, mask, B, D, H, W, out, mask_out, (hipStream_t)stream), "pool2");
+}
+
+static bool msssim_shape_ok(int D, int H, int W, int scales) {
+    if (scales < 1 || scales > DDPM3D_MSSSIM_MAX_SCALES || !ssim_shape_ok(D, H, W)) return false;
+    return (D >> (scales - 1)) >= 11 && (H >> (scales - 1)) >= 11 && (W >> (scales - 1)) >= 11;
+}
+
+size_t ddpm3d_msssim3d_workspace_bytes(int B, int D, int H, int W, int scales) {
+    if (B < 1 || B > DDPM3D_MAX_DRAWS || !msssim_shape_ok(D, H, W, scales)) return 0;
+    return ddpm3d_ms_workspace_bytes(B, D, H, W, scales);
+}
+
+int ddpm3d_msssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, int scales,
+                    double C1, double C2, void* ws, size_t ws_bytes, double* out, void* stream) {
+    if (!est || !target || !out) return fail(DDPM3D_EINVAL, "msssim3d: null pointer");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "msssim3d: B=%d estimates (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (scales < 1 || scales > DDPM3D_MSSSIM_MAX_SCALES)
+        return fail(DDPM3D_EINVAL, "msssim3d: scales=%d (1..%d)", scales, DDPM3D_MSSSIM_MAX_SCALES);
+    if (!msssim_shape_ok(D, H, W, scales))
+        return fail(DDPM3D_EINVAL, "msssim3d: bad volume for %d scales (D=%d H=%d W=%d; each at most 65535 and at "
+                                   "least 11 after %d halvings, H * W <= 2^31 - 1, D * H * W <= 2^40)", scales, D, H, W,
+                    scales - 1);
+    // !(c >= 0) also catches NaN; the kernel evaluates S in fp32, so the constants must be finite there
+    if (!(C1 >= 0.0) || !(C2 >= 0.0) || C1 > 3.0e38 || C2 > 3.0e38)
+        return fail(DDPM3D_EINVAL, "msssim3d: C1=%g C2=%g must be finite and not negative", C1, C2);
+    const int rc = metric_ws_ok("msssim3d", ddpm3d_ms_workspace_bytes(B, D, H, W, scales), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_msssim3d(est, target, mask, B, D, H, W, scales, (float)C1, (float)C2, ws, out,
+                                           (hipStream_t)stream),
+                    "msssim3d");
+}
+
 // ------------------------------------------------- per-region moments (added within ABI 13)
 // Checks the host side of a region index; *chunks receives the number of chunks all regions are cut into.
 static int roi_index_check(int B, const ddpm3d_roi_index* ix, int64_t* chunks) {

@@ -73,6 +73,14 @@ hipError_t ddpm3d_launch_error_moments(const float* est, const float* target, co
 size_t ddpm3d_ss_workspace_bytes(int B, int D, int H, int W);
 hipError_t ddpm3d_launch_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W,
                                 float C1, float C2, double* ws, float* map, double* out, hipStream_t st);
+// msssim.hip: 2 x 2 x 2 mean pooling of B volumes (and of one mask, by the 4-of-8 rule), and the multi-scale SSIM of B
+// estimates against one target: per scale the SSIM parts launch and its fold into out[B][scales][3], then the pools
+// into ws (the caller has checked the shapes, that every extent >> (scales - 1) is at least 11, and the workspace)
+hipError_t ddpm3d_launch_pool2(const float* vol, const uint8_t* mask, int B, int D, int H, int W, float* out,
+                               uint8_t* mask_out, hipStream_t st);
+size_t ddpm3d_ms_workspace_bytes(int B, int D, int H, int W, int scales);
+hipError_t ddpm3d_launch_msssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H,
+                                  int W, int scales, float C1, float C2, void* ws, double* out, hipStream_t st);
 // roi.hip: per-region moments over a region index cut into `chunks` chunks in all (the caller has checked the
 // descriptor's host side and the workspace)
 struct ddpm3d_roi_index;

@@ -97,6 +97,8 @@ class UnetDesc(C.Structure):
 (EM_N, EM_SUM_E, EM_SUM_ABS_E, EM_SUM_SQ_E, EM_SUM_Y, EM_SUM_SQ_Y, EM_MIN_Y, EM_MAX_Y, EM_COVER_1, EM_COVER_2,
  EM_REC) = range(11)
 
+MSSSIM_MAX_SCALES = 5   # DDPM3D_MSSSIM_MAX_SCALES: scales of ddpm3d_msssim3d
+
 # DDPM3D_ROI_*: columns of a ddpm3d_roi_moments record, and the limits of a region index
 (ROI_N, ROI_SUM_X, ROI_SUM_SQ_X, ROI_MIN_X, ROI_MAX_X, ROI_SUM_E, ROI_SUM_ABS_E, ROI_SUM_SQ_E, ROI_REC) = range(9)
 ROI_MAX_REGIONS, ROI_CHUNK = 4096, 4096
@@ -198,6 +200,10 @@ EXPORTS = {
     "ddpm3d_ssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "ddpm3d_ssim3d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _fp,
                                 C.c_size_t, _fp, _fp, _fp]),
+    "ddpm3d_pool2": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "ddpm3d_msssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "ddpm3d_msssim3d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                  _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_roi_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(RoiIndex)]),
     "ddpm3d_roi_moments": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.POINTER(RoiIndex), _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_label_components_workspace_bytes": (C.c_size_t, [C.c_int] * 3),

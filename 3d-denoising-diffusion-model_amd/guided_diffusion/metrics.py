@@ -24,6 +24,10 @@ roi_peak is roi_moments' MAX_X of that map; with a spacing roi_figures adds volu
 Baseline denoisers, to score beside the written volume: gaussian_taps turns a FWHM in mm and a voxel
 spacing into the taps of the clinic's Gaussian post-filter, gaussian_smooth applies them with ddpm3d_gauss_smooth
 (csrc/smooth.hip), nlm is non-local means in one launch of ddpm3d_nlm (csrc/nlm.hip).
+
+Multi-scale SSIM: pool2 is the 2 x 2 x 2 mean pooling of ddpm3d_pool2, msssim3d one call of
+ddpm3d_msssim3d (csrc/msssim.hip) over up to five scales and the product of the per-scale means on the host;
+evaluate(..., msssim_scales=M) adds it to the figures.
 """
 
 import ctypes
@@ -156,10 +160,120 @@ def ssim3d(estimate, target, data_range, mask=None, full=False):
     return (mean, smap) if full else mean
 
 
-def evaluate(estimate, target, data_range=None, mask=None, std=None):
+# ----------------------------------------------------------------- multi-scale SSIM
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli, Bovik 2003, scales 0..4
+
+
+def _check_scales(scales, what):
+    if isinstance(scales, bool) or not isinstance(scales, int) or not 1 <= scales <= H.MSSSIM_MAX_SCALES:
+        raise ValueError("%s: scales must be an int in 1..%d (got %r)" % (what, H.MSSSIM_MAX_SCALES, scales))
+    return scales
+
+
+def msssim_weights(scales):
+    """The default exponents of msssim3d: the first `scales` of MSSSIM_WEIGHTS divided by their sum (the published
+    weights for 5 scales, (1.0,) for one).  -> a tuple of floats"""
+    w = MSSSIM_WEIGHTS[:_check_scales(scales, "msssim_weights")]
+    total = math.fsum(w)
+    return tuple(v / total for v in w)
+
+
+def msssim_max_scales(shape):
+    """The most scales a volume of this shape allows: every extent >> (M - 1) must be at least 11; 0 if none."""
+    n = 2 * SSIM_RADIUS + 1
+    return max([m for m in range(1, H.MSSSIM_MAX_SCALES + 1) if min(int(v) for v in shape) >> (m - 1) >= n],
+               default=0)
+
+
+def pool2(volume, mask=None):
+    """2 x 2 x 2 mean pooling of a device float32 (D, H, W) or (K, D, H, W) tensor: one call of ddpm3d_pool2
+    (csrc/msssim.hip), no host copy.  The extents halve (an odd trailing plane, row or column is dropped); the eight
+    values are summed in fp32 in one fixed order.  With mask (a device uint8 (D, H, W) tensor shared by the K
+    volumes) also the pooled mask: 1 where at least 4 of the 8 inputs are non-zero.  -> pooled, or (pooled, mask)."""
+    H.require_device(volume, "volume")
+    if volume.dim() not in (3, 4):
+        raise ValueError("pool2: volume of shape %s (want (D, H, W) or (K, D, H, W))" % (tuple(volume.shape),))
+    D, Hh, W = (int(v) for v in volume.shape[-3:])
+    if min(D, Hh, W) < 2:
+        raise ValueError("pool2: every extent must be at least 2 (got %s)" % ((D, Hh, W),))
+    K = int(volume.shape[0]) if volume.dim() == 4 else 1
+    if not 1 <= K <= H.MAX_DRAWS:
+        raise ValueError("pool2: %d volumes (1..%d)" % (K, H.MAX_DRAWS))
+    if mask is not None and not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.uint8
+                                 and mask.is_contiguous() and tuple(mask.shape) == (D, Hh, W)
+                                 and mask.device == volume.device):
+        raise ValueError("pool2: mask must be a contiguous device uint8 tensor of the volume's shape %s"
+                         % ((D, Hh, W),))
+    lib = H.load()
+    with torch.cuda.device(volume.device):
+        out = torch.empty(tuple(volume.shape[:-3]) + (D // 2, Hh // 2, W // 2), dtype=torch.float32,
+                          device=volume.device)
+        mask_out = None if mask is None else torch.empty((D // 2, Hh // 2, W // 2), dtype=torch.uint8,
+                                                         device=volume.device)
+        H.check(lib.ddpm3d_pool2(H.ptr(volume), H.ptr(mask), K, D, Hh, W, H.ptr(out), H.ptr(mask_out), H.stream()))
+    return out if mask is None else (out, mask_out)
+
+
+def msssim3d(estimate, target, data_range, scales, weights=None, mask=None, parts=False):
+    """Multi-scale structural similarity (include/ddpm3d.h has the definition): the product over the scales
+    j < scales - 1 of max(CS_j, 0) ** w_j, times max(S_last, 0) ** w_last, where scale j + 1 is scale j pooled by
+    2 x 2 x 2 means (estimate, target and mask alike), CS_j and S_j are the means of the contrast-structure term and
+    of the SSIM over the interior voxels that scale's mask counts, and w = weights, default msssim_weights(scales).
+    A mean that is not positive makes the result 0.0.  One call of ddpm3d_msssim3d and one device-to-host copy.
+    scales = 1 is ssim3d.  -> float (list of K for a (K, D, H, W) estimate); with parts=True also {"cs": the
+    scales - 1 values CS_j, "ssim": S_last} (a list of K such dicts)."""
+    K, batched = _stack(estimate, target, "msssim3d")
+    _check_mask(mask, target, "msssim3d")
+    if not (isinstance(data_range, (int, float)) and math.isfinite(data_range) and data_range > 0):
+        raise ValueError("msssim3d: data_range must be a positive finite number (got %r)" % (data_range,))
+    M = _check_scales(scales, "msssim3d")
+    D, Hh, W = (int(v) for v in target.shape)
+    most = msssim_max_scales((D, Hh, W))
+    if M > most:
+        raise ValueError("msssim3d: a volume of %s is too small for %d scales: every extent must be at least %d after "
+                         "%d halvings; it allows at most %d" % ((D, Hh, W), M, 2 * SSIM_RADIUS + 1, M - 1, most))
+    if weights is None:
+        w = msssim_weights(M)
+    else:
+        try:
+            w = tuple(math.nan if isinstance(v, (bool, str)) else float(v) for v in weights)
+        except (TypeError, ValueError):
+            w = ()
+        if len(w) != M or not all(math.isfinite(v) and v >= 0 for v in w):
+            raise ValueError("msssim3d: weights must be %d finite numbers, none negative (got %r)" % (M, weights))
+    lib = H.load()
+    need = lib.ddpm3d_msssim3d_workspace_bytes(K, D, Hh, W, M)
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    with torch.cuda.device(target.device):
+        ws = torch.empty(max(need, 16) // 8, dtype=torch.float64, device=target.device)
+        out = torch.empty((K, M, 3), dtype=torch.float64, device=target.device)
+        H.check(lib.ddpm3d_msssim3d(H.ptr(estimate), H.ptr(target), H.ptr(mask), K, D, Hh, W, M, c1, c2, H.ptr(ws),
+                                    ws.numel() * 8, H.ptr(out), H.stream()))
+        rec = out.cpu().tolist()                       # the one device-to-host copy (it waits for the stream)
+    values, details = [], []
+    for r in rec:
+        for j, (_, _, n) in enumerate(r):
+            if n == 0:
+                raise ValueError("msssim3d: the mask counts no interior voxel at scale %d" % j)
+        cs = [r[j][1] / r[j][2] for j in range(M - 1)]
+        last = r[M - 1][0] / r[M - 1][2]
+        terms = cs + [last]
+        value = 0.0 if any(not t > 0 for t in terms) else math.prod(t ** e for t, e in zip(terms, w))
+        values.append(value)
+        details.append({"cs": cs, "ssim": last})
+    if not batched:
+        values, details = values[0], details[0]
+    return (values, details) if parts else values
+
+
+def evaluate(estimate, target, data_range=None, mask=None, std=None, msssim_scales=0):
     """All figures of one estimate (or K of them) against the target: psnr, nrmse, mae, bias, ssim, data_range,
-    n_voxels and, with `std`, coverage_1 / coverage_2.  data_range None: max - min of the target over the counted
-    voxels.  Python floats, or lists of K; data_range and n_voxels are the same for every estimate."""
+    n_voxels and, with `std`, coverage_1 / coverage_2; msssim_scales M > 0 adds msssim = msssim3d over M scales with
+    the default weights.  data_range None: max - min of the target over the counted voxels.  Python floats, or lists
+    of K; data_range and n_voxels are the same for every estimate."""
+    if isinstance(msssim_scales, bool) or not isinstance(msssim_scales, int) or msssim_scales < 0:
+        raise ValueError("evaluate: msssim_scales must be an int, 0 (none) or 1..%d (got %r)"
+                         % (H.MSSSIM_MAX_SCALES, msssim_scales))
     m = error_moments(estimate, target, mask=mask, std=std)
     batched = isinstance(m["n"], list)
     first = (lambda v: v[0]) if batched else (lambda v: v)
@@ -180,6 +294,8 @@ def evaluate(estimate, target, data_range=None, mask=None, std=None):
     }
     if std is not None:
         res["coverage_1"], res["coverage_2"] = m["coverage_1"], m["coverage_2"]
+    if msssim_scales:
+        res["msssim"] = msssim3d(estimate, target, data_range, msssim_scales, mask=mask)
     return res
 
 

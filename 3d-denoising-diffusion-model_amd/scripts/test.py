@@ -78,7 +78,12 @@ once on the GPU with the clinic's Gaussian post-filter of that FWHM and with
 non-local means (guided_diffusion/metrics.py gaussian_smooth, nlm) and score
 the two like the input and the written volume: the entry "baselines" of
 metrics_<name>.json and, with regions, "gaussian" and "nlm" beside "input" in
-every region.  The filtered volumes are not written.
+every region.  The filtered volumes are not written;
+`--msssim_scales N` (1..5; needs `--target_samples` and every extent to be at
+least 11 after N - 1 halvings) adds "msssim", the multi-scale SSIM over N
+scales (guided_diffusion/metrics.py msssim3d), to the "denoised", "input" and
+baseline rows of metrics_<name>.json, and "msssim_scales" and
+"msssim_weights" beside them.
 """
 
 import argparse
@@ -120,6 +125,8 @@ def create_argparser():
                     patch_overlap=-1,
                     # full-dose volume to score the result against (not in the reference); "" = no metrics
                     target_samples="", data_range=0.0, metrics_mask_threshold=0.0,
+                    # scales of the multi-scale SSIM added to every metric row (not in the reference); 0 = none
+                    msssim_scales=0,
                     # integer label volume for per-region statistics and the reference region of contrast and CNR
                     # (not in the reference); "" = no region statistics, -1 = no reference region
                     roi_labels="", roi_background=-1,
@@ -255,7 +262,12 @@ def main(argv=None):
 def _load_target(parser, args):
     """--target_samples: (base volume, target), both (D, H, W), read and checked before the model is built or any
     device call is made; (None, None) without the flag."""
+    if not 0 <= args.msssim_scales <= _hip.MSSSIM_MAX_SCALES:
+        parser.error("--msssim_scales must be in 0..%d (got %d)" % (_hip.MSSSIM_MAX_SCALES, args.msssim_scales))
     if not args.target_samples:
+        if args.msssim_scales:
+            parser.error("--msssim_scales needs --target_samples: the multi-scale SSIM is taken against the "
+                         "full-dose target")
         return None, None
     if args.metrics_mask_threshold < 0 or args.metrics_mask_threshold >= 1 or args.data_range < 0:
         parser.error("--metrics_mask_threshold must be in [0, 1) and --data_range must not be negative")
@@ -270,6 +282,11 @@ def _load_target(parser, args):
     if min(vol.shape) < 2 * metrics.SSIM_RADIUS + 1:
         parser.error("--target_samples: the 3-D SSIM needs every extent to be at least %d (volume %s)"
                      % (2 * metrics.SSIM_RADIUS + 1, tuple(vol.shape)))
+    if args.msssim_scales > metrics.msssim_max_scales(vol.shape):
+        parser.error("--msssim_scales: a volume of %s is too small for %d scales (every extent must be at least %d "
+                     "after %d halvings); it allows at most %d"
+                     % (tuple(vol.shape), args.msssim_scales, 2 * metrics.SSIM_RADIUS + 1, args.msssim_scales - 1,
+                        metrics.msssim_max_scales(vol.shape)))
     return vol, target
 
 
@@ -552,17 +569,27 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
         counted = live if counted is None else counted & live
     mask = None if counted is None else counted.to(th.uint8).contiguous()
     data_range = args.data_range if args.data_range > 0 else None
+    more = {"msssim_scales": args.msssim_scales} if args.msssim_scales else {}
+
+    def log_msssim(name, r):
+        if more:
+            logger.log("  %-8s vs target: MS-SSIM %.5f over %d scales" % (name, r["msssim"], args.msssim_scales))
+
     report = {
         "denoised": metrics.evaluate(den, tgt, data_range=data_range, mask=mask,
-                                     std=None if std is None else hwz(std)),
-        "input": metrics.evaluate(inp, tgt, data_range=data_range, mask=mask),
+                                     std=None if std is None else hwz(std), **more),
+        "input": metrics.evaluate(inp, tgt, data_range=data_range, mask=mask, **more),
         "target": args.target_samples,
         "mask_threshold": args.metrics_mask_threshold,
     }
+    if more:
+        report["msssim_scales"] = args.msssim_scales
+        report["msssim_weights"] = list(metrics.msssim_weights(args.msssim_scales))
     for name in ("input", "denoised"):
         r = report[name]
         logger.log("  %-8s vs target: PSNR %.3f dB  NRMSE %.5f  SSIM %.5f  MAE %.5g  bias %.5g  (L = %.6g, %d voxels)"
                    % (name, r["psnr"], r["nrmse"], r["ssim"], r["mae"], r["bias"], r["data_range"], r["n_voxels"]))
+        log_msssim(name, r)
     if std is not None:
         r = report["denoised"]
         logger.log("  std map coverage: %.4f of the errors within 1 std, %.4f within 2"
@@ -571,9 +598,11 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
     if filtered:
         report["baselines"] = {}
     for name, (x, params) in filtered.items():
-        report["baselines"][name] = r = {**params, **metrics.evaluate(x, tgt, data_range=data_range, mask=mask)}
+        report["baselines"][name] = r = {**params,
+                                         **metrics.evaluate(x, tgt, data_range=data_range, mask=mask, **more)}
         logger.log("  %-8s vs target: PSNR %.3f dB  NRMSE %.5f  SSIM %.5f  MAE %.5g  bias %.5g  (L = %.6g, %d voxels)"
                    % (name, r["psnr"], r["nrmse"], r["ssim"], r["mae"], r["bias"], r["data_range"], r["n_voxels"]))
+        log_msssim(name, r)
     if roi is not None:
         keep = None if weight is None else live.to(th.uint8).contiguous()
         report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=out_path,

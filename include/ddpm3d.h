@@ -742,6 +742,44 @@ size_t ddpm3d_ssim3d_workspace_bytes(int B, int D, int H, int W);
 int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, double C1,
                   double C2, void* ws, size_t ws_bytes, float* map, double* out, void* stream);
 /*
+ * Multi-scale 3-D SSIM (added within ABI 13; the reference has no metric code): Wang, Simoncelli, Bovik 2003,
+ * extended to 3-D as ddpm3d_ssim3d extends SSIM.  Scales j = 0..M-1, M in 1..DDPM3D_MSSSIM_MAX_SCALES.
+ *
+ * ddpm3d_pool2: scale j + 1 is scale j pooled by 2 x 2 x 2 means.  vol is [B][D][H][W] fp32, out [B][D/2][H/2][W/2]:
+ *   out(d, h, w) = (((v000 + v001) + (v010 + v011)) + ((v100 + v101) + (v110 + v111))) * 0.125f,
+ *   v_dz,dy,dx = vol(2d + dz, 2h + dy, 2w + dx), summed in fp32 in exactly this order.  The extent is n / 2 per axis
+ * (integer division): an odd trailing plane, row or column is dropped.  mask, an optional uint8 [D][H][W] shared by
+ * the B volumes, is pooled into mask_out [D/2][H/2][W/2]: a pooled voxel counts (1) iff at least 4 of its 8 inputs
+ * count (are != 0), else 0; mask and mask_out are both given or both NULL.  One streaming pass, every input read
+ * once (8-byte loads where W is even and vol is 8-byte aligned, 4-byte loads otherwise: the same bits).
+ *
+ * ddpm3d_msssim3d: est is [B][D][H][W], target [D][H][W], mask as for ddpm3d_ssim3d.  The estimates, the target and
+ * the mask are pooled the same way from scale to scale.  At every scale, with the window, the interior and the mask
+ * rule of ddpm3d_ssim3d and the same C1, C2, out[B][scales][3] doubles (device memory) receive over the interior
+ * voxels the scale's mask counts
+ *   {sum of S, sum of CS, count},  CS = (2 s_xy + C2) / (s_x + s_y + C2),
+ * S by exactly ddpm3d_ssim3d's arithmetic: scale 0's {sum of S, count} are ddpm3d_ssim3d's out bit for bit.  The host
+ * divides and combines, in fp64, with S_j = sum S / count, CS_j = sum CS / count:
+ *   MS-SSIM = prod_{j < M-1} max(CS_j, 0)^w_j * max(S_{M-1}, 0)^w_{M-1}   (0 when a mean is <= 0, never NaN);
+ * the default weights are the first M of (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) divided by their sum, so that M = 5
+ * gives the published weights and M = 1 plain SSIM.  Every extent must satisfy extent >> (M - 1) >= 11.  Per scale
+ * one SSIM launch, its fold and, below the last scale, the pools of estimates, target and mask into ws: enqueue-only
+ * (no allocation, no synchronisation, capturable in a graph), no floating-point atomics, the same bits on every run.
+ *
+ * ws: ddpm3d_msssim3d_workspace_bytes(...) bytes, 16-byte aligned; the query returns 0 for a shape the entry refuses
+ * and never shrinks when an extent grows.  Both entries return DDPM3D_EINVAL before any launch for a NULL vol / out /
+ * est / target / ws, mask and mask_out not both set or both NULL (pool2), B outside 1..DDPM3D_MAX_DRAWS, an extent
+ * below 2 (pool2) or above 65535, H * W above 2^31 - 1 or D * H * W above 2^40, scales outside
+ * 1..DDPM3D_MSSSIM_MAX_SCALES, an extent with extent >> (scales - 1) < 11, a workspace that is too small or
+ * misaligned, and a negative or non-finite C1 / C2.
+ */
+#define DDPM3D_MSSSIM_MAX_SCALES 5
+int ddpm3d_pool2(const float* vol, const uint8_t* mask, int B, int D, int H, int W, float* out, uint8_t* mask_out,
+                 void* stream);
+size_t ddpm3d_msssim3d_workspace_bytes(int B, int D, int H, int W, int scales);
+int ddpm3d_msssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, int scales,
+                    double C1, double C2, void* ws, size_t ws_bytes, double* out, void* stream);
+/*
  * Per-region (lesion / organ) moments of B estimates over a region index (added within ABI 13; the reference has no
  * metric code).  A labelled volume reaches the library as a sorted index list in CSR form, ddpm3d_roi_index, never
  * as a dense label volume:
