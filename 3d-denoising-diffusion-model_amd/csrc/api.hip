@@ -825,6 +825,36 @@ int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, in
                     "ssim3d");
 }
 
+// ------------------------------------------------- per-step convergence trace (added within ABI 13)
+static bool trace_shape_ok(int B, int64_t voxels) {
+    return B >= 1 && B <= DDPM3D_TRACE_MAX_BATCH && voxels >= 1 && voxels <= EM_MAX_VOXELS;
+}
+
+size_t ddpm3d_trace_moments_workspace_bytes(int B, int64_t voxels) {
+    if (!trace_shape_ok(B, voxels)) return 0;
+    return ddpm3d_tr_workspace_bytes(B, voxels);
+}
+
+int ddpm3d_trace_moments(const float* est, const float* prev, const float* target, const float* weight, int B,
+                         int64_t voxels, int64_t target_stride, int64_t weight_stride, void* ws, size_t ws_bytes,
+                         double* out, void* stream) {
+    if (!est || !out) return fail(DDPM3D_EINVAL, "trace_moments: null pointer");
+    if (B < 1 || B > DDPM3D_TRACE_MAX_BATCH)
+        return fail(DDPM3D_EINVAL, "trace_moments: B=%d estimates (1..%d)", B, DDPM3D_TRACE_MAX_BATCH);
+    if (voxels <= 0 || voxels > EM_MAX_VOXELS)
+        return fail(DDPM3D_EINVAL, "trace_moments: voxels=%lld (1..2^40)", (long long)voxels);
+    if ((target_stride != 0 && target_stride != voxels) || (weight_stride != 0 && weight_stride != voxels))
+        return fail(DDPM3D_EINVAL, "trace_moments: target_stride=%lld weight_stride=%lld (each 0, shared, or %lld)",
+                    (long long)target_stride, (long long)weight_stride, (long long)voxels);
+    if ((!target && target_stride != 0) || (!weight && weight_stride != 0))
+        return fail(DDPM3D_EINVAL, "trace_moments: a NULL target / weight takes stride 0");
+    const int rc = metric_ws_ok("trace_moments", ddpm3d_tr_workspace_bytes(B, voxels), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_trace_moments(est, prev, target, weight, B, voxels, target_stride, weight_stride,
+                                                (double*)ws, out, (hipStream_t)stream),
+                    "trace_moments");
+}
+
 // ------------------------------------------------- multi-scale SSIM (added within ABI 13)
 int ddpm3d_pool2(const float* vol, const uint8_t* mask, int B, int D, int H, int W, float* out, uint8_t* mask_out,
                  void* stream) {

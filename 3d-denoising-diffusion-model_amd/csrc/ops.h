@@ -73,6 +73,12 @@ hipError_t ddpm3d_launch_error_moments(const float* est, const float* target, co
 size_t ddpm3d_ss_workspace_bytes(int B, int D, int H, int W);
 hipError_t ddpm3d_launch_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W,
                                 float C1, float C2, double* ws, float* map, double* out, hipStream_t st);
+// trace.hip: weighted moments of B estimates against their targets and the previous estimates (the caller has checked
+// the pointers, the strides (0 or voxels) and the workspace; the workspace query takes valid shapes only)
+size_t ddpm3d_tr_workspace_bytes(int B, int64_t voxels);
+hipError_t ddpm3d_launch_trace_moments(const float* est, const float* prev, const float* target, const float* weight,
+                                       int B, int64_t voxels, int64_t target_stride, int64_t weight_stride, double* ws,
+                                       double* out, hipStream_t st);
 // msssim.hip: 2 x 2 x 2 mean pooling of B volumes (and of one mask, by the 4-of-8 rule), and the multi-scale SSIM of B
 // estimates against one target: per scale the SSIM parts launch and its fold into out[B][scales][3], then the pools
 // into ws (the caller has checked the shapes, that every extent >> (scales - 1) is at least 11, and the workspace)

@@ -97,6 +97,11 @@ class UnetDesc(C.Structure):
 (EM_N, EM_SUM_E, EM_SUM_ABS_E, EM_SUM_SQ_E, EM_SUM_Y, EM_SUM_SQ_Y, EM_MIN_Y, EM_MAX_Y, EM_COVER_1, EM_COVER_2,
  EM_REC) = range(11)
 
+# DDPM3D_TR_*: columns of a ddpm3d_trace_moments record
+(TR_W, TR_N, TR_SUM_E, TR_SUM_ABS_E, TR_SUM_SQ_E, TR_SUM_SQ_Y, TR_SUM_X, TR_SUM_SQ_X, TR_SUM_SQ_D, TR_CLIPPED,
+ TR_REC) = range(11)
+TRACE_MAX_BATCH = 4096  # DDPM3D_TRACE_MAX_BATCH: estimates per ddpm3d_trace_moments call
+
 MSSSIM_MAX_SCALES = 5   # DDPM3D_MSSSIM_MAX_SCALES: scales of ddpm3d_msssim3d
 
 # DDPM3D_ROI_*: columns of a ddpm3d_roi_moments record, and the limits of a region index
@@ -200,6 +205,9 @@ EXPORTS = {
     "ddpm3d_ssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "ddpm3d_ssim3d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _fp,
                                 C.c_size_t, _fp, _fp, _fp]),
+    "ddpm3d_trace_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "ddpm3d_trace_moments": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_size_t,
+                                       _fp, _fp]),
     "ddpm3d_pool2": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
     "ddpm3d_msssim3d_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "ddpm3d_msssim3d": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,

@@ -362,8 +362,16 @@ class GaussianDiffusion:
         return self._update("ddim", out, x, t, noise, clip_denoised, eta)
 
     # ------------------------------------------------------------------ loops
+    def _trace_step(self, trace, res, prev, i):
+        """Row of a metrics.StepTrace for the step at index i: this step's pred_xstart against the previous one (one
+        launch pair, nothing waits); -> the tensor the next step passes as prev"""
+        if trace is not None:
+            tmap = getattr(self, "timestep_map", None)
+            trace.add(res["pred_xstart"], prev, i if tmap is None else tmap[i], self.num_timesteps)
+        return res["pred_xstart"]
+
     def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-              progress, eta, step_noise):
+              progress, eta, step_noise, trace=None):
         self._reject_hooks(denoised_fn, cond_fn)
         if device is None:
             device = next(model.parameters()).device
@@ -380,45 +388,50 @@ class GaussianDiffusion:
         # leaves nothing changed.
         with th.no_grad(), th.cuda.device(device):
             t_all, net = self._step_model(model, shape, model_kwargs or {}, device)
+        prev = None                     # the previous step's pred_xstart, kept for `trace` only
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
                 out = net(img, i)
                 z = self._draw_noise(step_noise, k, img)
                 res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta)
+                if trace is not None:
+                    prev = self._trace_step(trace, res, prev, i)
             yield res
             img = res["sample"]
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, progress=False,
-                                  step_noise=None):
+                                  step_noise=None, trace=None):
         """gaussian_diffusion.py:487-535.  `step_noise` (extension): a sequence of
-        T tensors used instead of randn_like, in draw order, for parity runs."""
+        T tensors used instead of randn_like, in draw order, for parity runs.  `trace` (extension, on every loop): a
+        metrics.StepTrace that receives one record per step and sample of that step's pred_xstart (one reduction
+        per step, nothing waits for the device); None launches nothing more."""
         yield from self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, 0.0, step_noise)
+                              device, progress, 0.0, step_noise, trace)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, progress=False, step_noise=None):
+                      model_kwargs=None, device=None, progress=False, step_noise=None, trace=None):
         """gaussian_diffusion.py:441-485."""
         final = None
         for final in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
-                                                    model_kwargs, device, progress, step_noise):
+                                                    model_kwargs, device, progress, step_noise, trace):
             pass
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None):
+                                     step_noise=None, trace=None):
         """gaussian_diffusion.py:659-707."""
         yield from self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, eta, step_noise)
+                              device, progress, eta, step_noise, trace)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                         model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None):
+                         model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, trace=None):
         """gaussian_diffusion.py:625-657."""
         final = None
         for final in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
                                                        cond_fn, model_kwargs, device, progress, eta,
-                                                       step_noise):
+                                                       step_noise, trace):
             pass
         return final["sample"]
 
@@ -625,7 +638,8 @@ class GaussianDiffusion:
             return self._reverse_step(out, x, t, flags)
 
     def ddim_reverse_sample_loop_progressive(self, model, x_start, clip_denoised=True, denoised_fn=None,
-                                             model_kwargs=None, device=None, progress=False, eta=0.0):
+                                             model_kwargs=None, device=None, progress=False, eta=0.0,
+                                             trace=None):
         """DDIM inversion (extension; the reference has the step, :587-623, but no loop): starting from
         x = x_start, x <- ddim_reverse_sample(x, t=k)["sample"] for k = 0 ... T-1, yielding each step's dict.
         Draws no noise.  With model_kwargs == {"low_res"} on a 5-D input it takes the samplers' engine path: the
@@ -643,19 +657,22 @@ class GaussianDiffusion:
         with th.no_grad(), th.cuda.device(device):
             img = x_start.to(device)
             t_all, net = self._step_model(model, x_start.shape, model_kwargs or {}, device)
+        prev = None
         for i in indices:
             with th.no_grad(), th.cuda.device(device):
                 res = self._reverse_step(net(img, i), img, t_all[i], flags)
+                if trace is not None:
+                    prev = self._trace_step(trace, res, prev, i)
             yield res
             img = res["sample"]
 
     def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None,
-                                 device=None, progress=False, eta=0.0):
+                                 device=None, progress=False, eta=0.0, trace=None):
         """DDIM inversion (extension): x_T from a clean x_start, the last sample of
         ddim_reverse_sample_loop_progressive."""
         final = None
         for final in self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised, denoised_fn,
-                                                               model_kwargs, device, progress, eta):
+                                                               model_kwargs, device, progress, eta, trace):
             pass
         return final["sample"]
 
@@ -677,7 +694,7 @@ class GaussianDiffusion:
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                            cond_fn=None, model_kwargs=None, device=None, progress=False, order=2,
-                                           stochastic=False, step_noise=None):
+                                           stochastic=False, step_noise=None, trace=None):
         """DPM-Solver++ multistep sampling (extension; Lu et al. 2022, arXiv:2211.01095), yielding
         {"sample", "pred_xstart"} per step as ddim_sample_loop_progressive does.  Step k leaves index
         s = T - 1 - k at order min(order, k + 1); the last step returns its pred_xstart.  The weights are
@@ -699,10 +716,10 @@ class GaussianDiffusion:
         assert isinstance(shape, (tuple, list))
         flags = self._flags(clip_denoised)
         return self._solver_loop(model, shape, noise, flags, model_kwargs or {}, device, progress, order,
-                                 stochastic, step_noise)
+                                 stochastic, step_noise, trace)
 
     def _solver_loop(self, model, shape, noise, flags, model_kwargs, device, progress, order, stochastic,
-                     step_noise):
+                     step_noise, trace=None):
         indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
         # as in _loop: grad mode and the current device change around each step's compute only
         with th.no_grad(), th.cuda.device(device):
@@ -717,17 +734,19 @@ class GaussianDiffusion:
                 p = 1 if i == 0 else min(order, k + 1)
                 res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z,
                                         t_all[i], flags, order, stochastic, p)
+                if trace is not None:       # prev is the newest entry of the solver's own history
+                    self._trace_step(trace, res, hist[0] if hist else None, i)
             yield res
             img = res["sample"]
             hist = [res["pred_xstart"]] + hist[:1]
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, order=2, stochastic=False,
-                               step_noise=None):
+                               step_noise=None, trace=None):
         """DPM-Solver++ multistep sampling (extension): the last sample of dpm_solver_sample_loop_progressive."""
         final = None
         for final in self.dpm_solver_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
                                                              cond_fn, model_kwargs, device, progress, order,
-                                                             stochastic, step_noise):
+                                                             stochastic, step_noise, trace):
             pass
         return final["sample"]

@@ -151,7 +151,7 @@ def _canvas_of(volume, geom, device):
 
 
 def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm", num_draws=1, batch_size=1,
-                            noise=None, step_noise=None, clip_denoised=True, eta=0.0, device=None):
+                            noise=None, step_noise=None, clip_denoised=True, eta=0.0, device=None, trace=None):
     """Joint DDPM ("ddpm") or DDIM ("ddim", any eta) sampling of one volume; yields, per reverse step,
     {"sample", "pred_xstart"}: (K, Dc, H, W) canvases on the device, K = num_draws.
 
@@ -162,6 +162,8 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                     order or a callable (k, like) as in the independent loops.  Without them, draw d takes all its
                     noise from dist_util.volume_generator(0, draw=d), one whole canvas at a time, so the result
                     depends on neither the batch size nor the world size.
+    trace           a metrics.StepTrace: every step's blended pred_xstart canvases are its estimates, so its target
+                    and weight are (Dc, H, W) or (K, Dc, H, W) canvases (weight 0 outside the volume)
     With several ranks, batch b runs on rank b mod W; the ranks exchange their updated patches once per round and
     every rank blends all of them: all ranks hold the same canvas after every step, bit for bit."""
     if kind not in ("ddpm", "ddim"):
@@ -226,6 +228,7 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                                                           device)
         updated = th.empty((2, P * K, 1, r, r, r), dtype=th.float32, device=device)   # sample, pred_xstart
         block = th.zeros((2, bs * K, 1, r, r, r), dtype=th.float32, device=device) if world > 1 else None
+    prev = None
 
     for k, i in enumerate(range(diffusion.num_timesteps - 1, -1, -1)):
         with th.no_grad(), th.cuda.device(device):
@@ -246,6 +249,8 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                         lo, hi = rows(bb)
                         updated[:, lo:hi].copy_(blk[:, :hi - lo])
             out = {"sample": blend(updated[0], geom, K), "pred_xstart": blend(updated[1], geom, K)}
+            if trace is not None:
+                prev = diffusion._trace_step(trace, out, prev, i)
         yield out
         img = out["sample"]
 

@@ -28,11 +28,18 @@ spacing into the taps of the clinic's Gaussian post-filter, gaussian_smooth appl
 Multi-scale SSIM: pool2 is the 2 x 2 x 2 mean pooling of ddpm3d_pool2, msssim3d one call of
 ddpm3d_msssim3d (csrc/msssim.hip) over up to five scales and the product of the per-scale means on the host;
 evaluate(..., msssim_scales=M) adds it to the figures.
+
+Per-step convergence trace: a StepTrace handed to a sampling loop as trace= records, per reverse
+step and sample, the weighted moments of that step's pred_xstart against a target and against the previous step's
+pred_xstart, one call of ddpm3d_trace_moments (csrc/trace.hip) per step and no host synchronisation before
+records(); trace_figures turns pooled records into PSNR, NRMSE, MAE, bias, mean, std, delta_rms and clipped per step
+on the host.
 """
 
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _hip as H
@@ -297,6 +304,126 @@ def evaluate(estimate, target, data_range=None, mask=None, std=None, msssim_scal
     if msssim_scales:
         res["msssim"] = msssim3d(estimate, target, data_range, msssim_scales, mask=mask)
     return res
+
+
+# ----------------------------------------------------------------- per-step convergence trace
+class StepTrace:
+    """The trace= argument of a sampling loop: per reverse step k and sample b, one ddpm3d_trace_moments record of
+    that step's pred_xstart x (include/ddpm3d.h has the columns): its weighted moments against `target`, against the
+    previous step's pred_xstart and on its own.
+
+    target, weight  optional device float32 tensors of the loop's x shape (every sample has its own target and
+                    weights) or of one sample's shape (shared by all samples).  Only voxels with weight > 0 count;
+                    no weight counts every voxel with weight 1.
+    The first step allocates a (T, N, REC) float64 table and the workspace on x's device; every step writes row k with
+    one call.  Nothing waits for the device until records().  `t` lists the original timestep of each row.  One
+    StepTrace serves one run of one loop."""
+
+    def __init__(self, target=None, weight=None):
+        for name, v in (("target", target), ("weight", weight)):
+            if v is not None:
+                H.require_device(v, name)
+        self.target, self.weight = target, weight
+        self.t = []
+        self._table = self._ws = None
+
+    def _stride(self, v, est, name):
+        if v is None:
+            return 0
+        if v.device != est.device:
+            raise ValueError("StepTrace: %s on %s, the loop's x on %s" % (name, v.device, est.device))
+        if tuple(v.shape) == tuple(est.shape):
+            return est[0].numel()
+        if tuple(v.shape) == tuple(est.shape[1:]):
+            return 0
+        raise ValueError("StepTrace: %s of shape %s; the loop's x has shape %s (want that, or one sample's %s)"
+                         % (name, tuple(v.shape), tuple(est.shape), tuple(est.shape[1:])))
+
+    def add(self, est, prev, t, steps):
+        """Called by the loops: row len(self.t) of `steps` <- the records of est (N, ...) against prev (the previous
+        step's est, None on the first step); t is the step's original timestep.  Enqueue-only."""
+        H.require_device(est, "pred_xstart")
+        N, voxels = int(est.shape[0]), est[0].numel()
+        k = len(self.t)
+        lib = H.load()
+        if self._table is None:
+            if not 1 <= N <= H.TRACE_MAX_BATCH:
+                raise ValueError("StepTrace: %d samples per step (1..%d)" % (N, H.TRACE_MAX_BATCH))
+            self._strides = self._stride(self.target, est, "target"), self._stride(self.weight, est, "weight")
+            need = lib.ddpm3d_trace_moments_workspace_bytes(N, voxels)
+            self._ws = torch.empty(max(need, 16) // 8, dtype=torch.float64, device=est.device)
+            self._table = torch.zeros((int(steps), N, H.TR_REC), dtype=torch.float64, device=est.device)
+            self._shape = tuple(est.shape)
+        if k >= self._table.shape[0] or tuple(est.shape) != self._shape:
+            raise ValueError("StepTrace: step %d of shape %s does not fit the trace begun with %d steps of shape %s "
+                             "(one StepTrace serves one run of one loop)"
+                             % (k, tuple(est.shape), self._table.shape[0], self._shape))
+        if prev is not None:
+            H.require_device(prev, "previous pred_xstart")
+            assert prev.shape == est.shape
+        H.check(lib.ddpm3d_trace_moments(H.ptr(est), H.ptr(prev), H.ptr(self.target), H.ptr(self.weight), N, voxels,
+                                         self._strides[0], self._strides[1], H.ptr(self._ws), self._ws.numel() * 8,
+                                         H.ptr(self._table[k]), H.stream()))
+        self.t.append(int(t))
+
+    def device_records(self):
+        """The (T, N, REC) float64 table on the device, no copy and no wait: rows not yet written are 0."""
+        if self._table is None:
+            raise ValueError("StepTrace: no step was traced")
+        return self._table
+
+    def records(self):
+        """The rows written so far as a float64 numpy array (T, N, REC): the one device-to-host copy (it waits for
+        the stream)."""
+        if self._table is None:
+            raise ValueError("StepTrace: no step was traced")
+        return self._table[:len(self.t)].cpu().numpy()
+
+    def figures(self, data_range=None):
+        """trace_figures of records(), pooled over the samples."""
+        return trace_figures(self.records(), data_range=data_range, has_target=self.target is not None)
+
+
+def trace_figures(records, data_range=None, has_target=True):
+    """Host only.  records: (T, M, REC) ddpm3d_trace_moments records (or (T, REC)), pooled per step by summing the M
+    records in index order.  -> a list of T dicts: psnr = 10 log10(L^2 / mse) with L = data_range and
+    mse = SUM_SQ_E / W, nrmse = sqrt(SUM_SQ_E / SUM_SQ_Y), mae, bias, mean = SUM_X / W,
+    std = sqrt(max(SUM_SQ_X / W - mean^2, 0)), delta_rms = sqrt(SUM_SQ_D / W) (None on the first step),
+    clipped = CLIPPED / W, weight = W, and mse itself.  A figure is None when its denominator is 0, psnr also when
+    data_range is None, and psnr, nrmse, mae, bias and mse when no target was given (has_target=False)."""
+    rec = np.asarray(records, dtype=np.float64)
+    if rec.ndim == 2:
+        rec = rec[:, None, :]
+    if rec.ndim != 3 or rec.shape[2] != H.TR_REC:
+        raise ValueError("trace_figures: records of shape %s (want (T, M, %d) or (T, %d))"
+                         % (rec.shape, H.TR_REC, H.TR_REC))
+    if data_range is not None and not (isinstance(data_range, (int, float)) and math.isfinite(data_range)
+                                       and data_range > 0):
+        raise ValueError("trace_figures: data_range must be a positive finite number or None (got %r)"
+                         % (data_range,))
+    pooled = np.zeros((rec.shape[0], H.TR_REC), dtype=np.float64)
+    for m in range(rec.shape[1]):                   # a fixed order: the same bits however the records were batched
+        pooled += rec[:, m]
+    rows = []
+    for k, r in enumerate(pooled.tolist()):
+        W = r[H.TR_W]
+        over = (lambda v: v / W) if W > 0 else (lambda v: None)
+        err = has_target and W > 0
+        mse = r[H.TR_SUM_SQ_E] / W if err else None
+        mean = over(r[H.TR_SUM_X])
+        rows.append({
+            "psnr": psnr(mse, data_range) if err and data_range is not None else None,
+            "nrmse": math.sqrt(r[H.TR_SUM_SQ_E] / r[H.TR_SUM_SQ_Y]) if err and r[H.TR_SUM_SQ_Y] > 0 else None,
+            "mae": r[H.TR_SUM_ABS_E] / W if err else None,
+            "bias": r[H.TR_SUM_E] / W if err else None,
+            "mse": mse,
+            "mean": mean,
+            "std": None if mean is None else math.sqrt(max(r[H.TR_SUM_SQ_X] / W - mean * mean, 0.0)),
+            "delta_rms": None if k == 0 or not W > 0 else math.sqrt(r[H.TR_SUM_SQ_D] / W),
+            "clipped": over(r[H.TR_CLIPPED]),
+            "weight": W,
+        })
+    return rows
 
 
 # ----------------------------------------------------------------- per-region statistics (DESIGN.md 3.10)

@@ -146,6 +146,31 @@ def blend_cover(grid, shape_dhw, resolution):
     return cover
 
 
+def blend_shares(starts, extent, res):
+    """(len(starts), res) float64: patch i's share of stitch_patches' one-shot Hann blend along one axis, per
+    coordinate of the patch: hanning(res)[c - s_i] / sum_j hanning(res)[c - s_j] at c = s_i + column, 0 where that
+    sum is 0 (the outermost planes of the volume) and 0 for c >= extent (the zero-padded part of a patch).  The window
+    and the grids are separable, so patch p's share of a voxel is the product of three such rows; unlike _axis_table
+    no plane gets an equal share: the shares sum to 1 over the patches on the voxels blend_cover marks, to 0 on the
+    others."""
+    extent, res = int(extent), int(res)
+    h = np.hanning(res)
+    hann = np.zeros((len(starts), max(extent, 0)), dtype=np.float64)
+    for i, s in enumerate(starts):
+        n = min(res, extent - s)
+        if s < 0 or n < 1:
+            raise ValueError("blend_shares: patch start %d outside 0..%d" % (s, extent - 1))
+        hann[i, s:s + n] = h[:n]
+    total = hann.sum(axis=0)
+    live = total > 0
+    share = np.where(live, hann / np.where(live, total, 1.0), 0.0)
+    out = np.zeros((len(starts), res), dtype=np.float64)
+    for i, s in enumerate(starts):
+        n = min(res, extent - s)
+        out[i, :n] = share[i, s:s + n]
+    return out
+
+
 def load_volume(path):
     """Input volume as (D,H,W) float32.  .npz ('arr_0' or the first array) and .npy
     besides the reference's .tif/.tiff (tiff_io: tifffile when importable, else its own reader; scripts/test.py

@@ -83,7 +83,16 @@ every region.  The filtered volumes are not written;
 least 11 after N - 1 halvings) adds "msssim", the multi-scale SSIM over N
 scales (guided_diffusion/metrics.py msssim3d), to the "denoised", "input" and
 baseline rows of metrics_<name>.json, and "msssim_scales" and
-"msssim_weights" beside them.
+"msssim_weights" beside them;
+`--trace True` (any path, any sampler, no other flag needed) records how every
+reverse step's pred_xstart moves (guided_diffusion/metrics.py StepTrace: one
+small reduction per step on the GPU, nothing waits inside the loop) and writes
+trace_<name>.json beside the .npz: per step the mean, std, share of clipped
+voxels and RMS change against the step before and, with `--target_samples`,
+PSNR, NRMSE, MAE and bias against the target over the voxels the metrics file
+counts.  On the independent paths the patches are scored before blending, each
+voxel of a patch weighted with the patch's share of the Hann blend
+("pooling": "patch"); `--joint_patches` scores the blended canvas ("canvas").
 """
 
 import argparse
@@ -127,6 +136,8 @@ def create_argparser():
                     target_samples="", data_range=0.0, metrics_mask_threshold=0.0,
                     # scales of the multi-scale SSIM added to every metric row (not in the reference); 0 = none
                     msssim_scales=0,
+                    # a per-step convergence trace of pred_xstart, written as trace_<name>.json (not in the reference)
+                    trace=False,
                     # integer label volume for per-region statistics and the reference region of contrast and CNR
                     # (not in the reference); "" = no region statistics, -1 = no reference region
                     roi_labels="", roi_background=-1,
@@ -209,8 +220,14 @@ def main(argv=None):
     bs = max(1, args.batch_size)
     n_batches = (len(grid) + bs - 1) // bs
     sample_loop, extra = _sampler(args, diffusion)
+    tracer = None
+    if args.trace:
+        D, Hh, W = vol.shape
+        tracer = _PatchTrace(args, diffusion, vol, target, grid, bs, (patches.xy_starts(Hh, res),
+                                                                      patches.xy_starts(W, res),
+                                                                      patches.z_starts(D, res)))
     if args.num_draws > 1:
-        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target, roi)
+        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target, roi, tracer)
     done = {}
     for b in dist_util.partition(n_batches):
         block = th.zeros(bs, 1, res, res, res, device=dev)                  # padded so collectives stay aligned
@@ -227,12 +244,16 @@ def main(argv=None):
 
             noise = draw()
             logger.log(f"rank {rank}: patches {idx} shape={shape}")
+            if tracer is not None:
+                extra["trace"] = tracer.begin(idx)
             sample = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
                                  model_kwargs={"low_res": cond}, step_noise=draw, **extra)
             block[:len(idx)] = sample.permute(0, 1, 3, 4, 2)                # (B,1,Z,H,W) -> (B,1,H,W,Z)
         for bb, blk in dist_util.gather_round(block, b):
             for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
                 done[i] = blk[j, 0].cpu().numpy()
+        if tracer is not None:
+            tracer.gather(extra.get("trace"), b)
     if not done:
         logger.log("No samples were generated. Exiting.")
         return None
@@ -253,7 +274,9 @@ def main(argv=None):
             tiff_path = out_path.replace(".npz", ".tif")
             tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))   # (H,W,Z) -> (Z,H,W), no scaling
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        _write_metrics(args, out_path, target, vol, result, weight=weight, roi=roi)
+        mpath = _write_metrics(args, out_path, target, vol, result, weight=weight, roi=roi)
+        if tracer is not None:
+            tracer.write(out_path, mpath)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
@@ -614,6 +637,132 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
     return path
 
 
+def _counted(args, target):
+    """--metrics_mask_threshold as _write_metrics applies it: (D, H, W) bool on the device, or None"""
+    if target is None or not args.metrics_mask_threshold > 0:
+        return None
+    tgt = th.from_numpy(target).to(device=dist_util.dev(), dtype=th.float32)
+    return tgt > args.metrics_mask_threshold * tgt.max()
+
+
+class _PatchTrace:
+    """--trace True on the independent paths: every batch gets a metrics.StepTrace whose target is the batch's
+    target patches and whose weight is each patch's share of the one-shot Hann blend (patches.blend_shares; the
+    product of three rows, rounded once to fp32), times the mask of --metrics_mask_threshold: every voxel the
+    metrics file counts carries a total weight of 1 over the patches.  Target, mask and shares are cut once per
+    batch.  The records travel with each round (dist_util.gather_round); rank 0 keeps them per (patch, draw) and
+    pools them in that order, so the file depends on neither the batch size nor the world size."""
+
+    def __init__(self, args, diffusion, vol, target, grid, bs, starts):
+        self.args, self.grid, self.bs = args, grid, bs
+        self.K, self.res, self.T = args.num_draws, args.large_size, diffusion.num_timesteps
+        tmap = getattr(diffusion, "timestep_map", None) or list(range(self.T))
+        self.t = [int(tmap[i]) for i in range(self.T - 1, -1, -1)]
+        D, Hh, W = vol.shape
+        xs, ys, zs = (list(v) for v in starts)           # the grid is their product, p = (ix * ny + iy) * nz + iz
+        assert grid == [(x, y, z) for x in xs for y in ys for z in zs]
+        self.ny, self.nz = len(ys), len(zs)
+        self.sx, self.sy, self.sz = (patches.blend_shares(v, extent, self.res)
+                                     for v, extent in ((xs, Hh), (ys, W), (zs, D)))
+        self.target = target
+        counted = _counted(args, target)
+        self.counted = None if counted is None else counted.cpu().numpy()
+        self.recs = {}
+
+    def _cut(self, volume, g, dtype):
+        xs, ys, zs = g
+        r = self.res
+        out = np.zeros((r, r, r), dtype=dtype)
+        p = volume[zs:zs + r, xs:xs + r, ys:ys + r]
+        out[:p.shape[0], :p.shape[1], :p.shape[2]] = p
+        return out
+
+    def begin(self, idx):
+        """The StepTrace of the batch of patches idx (patch-major, draw-minor, like the batch)."""
+        dev = dist_util.dev()
+        weight, target = [], []
+        for i in idx:
+            ix, iy, iz = i // (self.ny * self.nz), (i // self.nz) % self.ny, i % self.nz
+            w = ((self.sx[ix][None, :, None] * self.sy[iy][None, None, :])
+                 * self.sz[iz][:, None, None]).astype(np.float32)                # (Z, H, W), like the samples
+            if self.counted is not None:
+                w = w * self._cut(self.counted, self.grid[i], np.float32)
+            weight.append(w)
+            if self.target is not None:
+                target.append(self._cut(self.target, self.grid[i], np.float32))
+
+        def up(blocks):
+            t = th.from_numpy(np.stack(blocks)[:, None]).to(dev)
+            return (t.repeat_interleave(self.K, dim=0) if self.K > 1 else t).contiguous()
+
+        return metrics.StepTrace(target=up(target) if target else None, weight=up(weight))
+
+    def gather(self, trace, b):
+        """After round b's samples (every rank calls it; trace is None on a padding round)."""
+        rows = self.bs * self.K
+        block = th.zeros((self.T, rows, _hip.TR_REC), dtype=th.float64, device=dist_util.dev())
+        if b is not None:
+            rec = trace.device_records()
+            block[:, :rec.shape[1]] = rec
+        for bb, blk in dist_util.gather_round(block, b):
+            if dist_util.rank() != 0:
+                continue
+            host = blk.cpu().numpy()
+            for j, i in enumerate(range(bb * self.bs, min((bb + 1) * self.bs, len(self.grid)))):
+                for d in range(self.K):
+                    self.recs[(i, d)] = host[:, j * self.K + d]
+
+    def write(self, out_path, metrics_path):
+        keys = sorted(self.recs)
+        assert keys == [(i, d) for i in range(len(self.grid)) for d in range(self.K)], "a patch was not traced"
+        records = np.stack([self.recs[k] for k in keys], axis=1)               # (T, P * K, REC)
+        return _write_trace(self.args, out_path, metrics_path, "patch", records, self.t, self.target is not None)
+
+
+def _canvas_trace(args, vol, target, geom):
+    """--trace True with --joint_patches: a StepTrace over the blended canvases; the weight is 1 inside the volume
+    and on the mask of --metrics_mask_threshold, 0 on the rest of the canvas."""
+    dev = dist_util.dev()
+    D, Hh, W = vol.shape
+    weight = th.zeros(tuple(geom.canvas), dtype=th.float32, device=dev)
+    counted = _counted(args, target)
+    weight[:D, :Hh, :W] = 1.0 if counted is None else counted.to(th.float32)
+    tgt = None
+    if target is not None:
+        tgt = th.zeros(tuple(geom.canvas), dtype=th.float32, device=dev)
+        tgt[:D, :Hh, :W] = th.from_numpy(target).to(dev)
+    return metrics.StepTrace(target=tgt, weight=weight)
+
+
+def _write_trace(args, out_path, metrics_path, pooling, records, t, has_target):
+    """Rank 0, after the metrics file: trace_<name>.json beside the .npz from the (T, M, REC) records, pooled in
+    index order; data_range is the number the metrics file reports."""
+    data_range = None
+    if metrics_path is not None:
+        with open(metrics_path) as f:
+            data_range = json.load(f)["denoised"]["data_range"]
+    rows = metrics.trace_figures(records, data_range=data_range, has_target=has_target)
+    keys = ("psnr", "nrmse", "mae", "bias", "mean", "std", "delta_rms", "clipped")
+    sampler = "dpm_solver" if args.use_dpm_solver else "ddim" if args.use_ddim else "ddpm"
+    report = {"sampler": sampler, "steps": len(rows), "pooling": pooling,
+              "target": args.target_samples or None, "data_range": data_range,
+              "mask_threshold": args.metrics_mask_threshold, "draws": args.num_draws,
+              "n_voxels": int(round(rows[-1]["weight"] / args.num_draws)),
+              "rows": [{"step": k, "t": t[k], **{key: r[key] for key in keys}} for k, r in enumerate(rows)]}
+    show = lambda v, f="%.5g": "n/a" if v is None else f % v
+    logger.log("per-step trace of pred_xstart (%s, %d steps, pooled per %s):" % (sampler, len(rows), pooling))
+    for k in sorted({int(round(v)) for v in np.linspace(0, len(rows) - 1, min(len(rows), 10))}):
+        r = report["rows"][k]
+        logger.log("  step %4d  t %4d  PSNR %s dB  NRMSE %s  mean %s  std %s  delta_rms %s  clipped %s"
+                   % (k, r["t"], show(r["psnr"], "%.3f"), show(r["nrmse"]), show(r["mean"]), show(r["std"]),
+                      show(r["delta_rms"]), show(r["clipped"])))
+    path = os.path.join(os.path.dirname(out_path), "trace_%s.json" % _base_name(args.base_samples))
+    with open(path, "w") as f:
+        json.dump(report, f, indent=2)
+    logger.log(f"saved trace to {path}")
+    return path
+
+
 def _sampler(args, diffusion):
     if args.use_dpm_solver:
         return diffusion.dpm_solver_sample_loop, dict(order=args.solver_order, stochastic=args.solver_stochastic)
@@ -630,7 +779,8 @@ def _base_name(path):
     return base
 
 
-def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target=None, roi=None):
+def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target=None, roi=None,
+                tracer=None):
     """--num_draws K >= 2: every forward batch is bs patches x K draws, patch-major (N = bs * K); the noise of draw d of
     patch i comes from volume_generator(i, draw=d), so it depends on neither K, the batch size nor the world size.
     Gathered rounds are stitched on rank 0's device in ascending patch order (DrawStitcher), then reduced to the
@@ -652,6 +802,8 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
 
             noise = draw()
             logger.log(f"rank {rank}: patches {idx} x {K} draws shape={shape}")
+            if tracer is not None:
+                extra["trace"] = tracer.begin(idx)
             block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
                                                model_kwargs={"low_res": cond}, step_noise=draw, **extra)
         for bb, blk in dist_util.gather_round(block, b):
@@ -660,6 +812,8 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             blk = blk.to(dev)
             for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
                 stitcher.add(i, blk[j * K:(j + 1) * K], grid[i])
+        if tracer is not None:
+            tracer.gather(extra.get("trace"), b)
     out_path = None
     if rank == 0:
         logger.log(f"Reconstructing {K} draws with Hann window blending...")
@@ -679,8 +833,10 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             std_path = out_path.replace(".npz", "_std.tif")
             tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
-        _write_metrics(args, out_path, target, vol, mean, std=std, weight=weight, roi=roi,
-                       draws=(stitcher.draw(k) for k in range(K)))
+        mpath = _write_metrics(args, out_path, target, vol, mean, std=std, weight=weight, roi=roi,
+                               draws=(stitcher.draw(k) for k in range(K)))
+        if tracer is not None:
+            tracer.write(out_path, mpath)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
@@ -702,6 +858,8 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
     sample_loop, extra = _sampler(args, diffusion)
     canvas = joint._canvas_of(vol, geom, dev)
     stitcher = uncertainty.VolumeStitcher(vol.shape, res, K, dev) if rank == 0 else None
+    tracer = (_PatchTrace(args, diffusion, vol, target, grid, bs, (geom.x_starts, geom.y_starts, geom.z_starts))
+              if args.trace else None)
     for b in dist_util.partition((len(grid) + bs - 1) // bs):
         block = th.zeros(bs * K, 1, res, res, res, device=dev)               # padded so collectives stay aligned
         if b is not None:
@@ -717,6 +875,8 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
 
             noise = draw()
             logger.log(f"rank {rank}: patches {idx[0]}..{idx[-1]} x {K} draws shape={shape}")
+            if tracer is not None:
+                extra["trace"] = tracer.begin(idx)
             block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
                                                model_kwargs={"low_res": cond}, step_noise=draw, **extra)
         for bb, blk in dist_util.gather_round(block, b):
@@ -725,6 +885,8 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
             blk = blk.to(dev)
             for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
                 stitcher.add(i, blk[j * K:(j + 1) * K], grid[i])
+        if tracer is not None:
+            tracer.gather(extra.get("trace"), b)
     out_path = None
     if rank == 0:
         logger.log("Reconstructing full image with Hann window blending...")
@@ -750,8 +912,10 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra_out["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        _write_metrics(args, out_path, target, vol, result, std=std, weight=weight, roi=roi,
-                       draws=(stitcher.draw(k) for k in range(K)) if K > 1 else None)
+        mpath = _write_metrics(args, out_path, target, vol, result, std=std, weight=weight, roi=roi,
+                               draws=(stitcher.draw(k) for k in range(K)) if K > 1 else None)
+        if tracer is not None:
+            tracer.write(out_path, mpath)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
@@ -765,9 +929,12 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
     K, res = args.num_draws, args.large_size
     geom = patches.joint_geometry(vol.shape, res, min_overlap=args.patch_overlap if args.patch_overlap >= 0 else None)
     logger.log(f"volume {vol.shape}: {geom.n_patches} patches of {res}^3, sampled jointly on a {geom.canvas} canvas")
+    more = {}
+    if args.trace:
+        more["trace"] = trace = _canvas_trace(args, vol, target, geom)
     sample = joint.sample_loop(diffusion, model, vol, geom, kind="ddim" if args.use_ddim else "ddpm", num_draws=K,
                                batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
-                               device=dist_util.dev())
+                               device=dist_util.dev(), **more)
     draws = sample[:, :vol.shape[0], :vol.shape[1], :vol.shape[2]].contiguous()     # (K, D, H, W)
     extra = {}
     if K > 1:
@@ -791,8 +958,10 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        _write_metrics(args, out_path, target, vol, result, std=extra.get("std"), roi=roi,
-                       draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None)
+        mpath = _write_metrics(args, out_path, target, vol, result, std=extra.get("std"), roi=roi,
+                               draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None)
+        if args.trace:
+            _write_trace(args, out_path, mpath, "canvas", trace.records(), trace.t, target is not None)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path

@@ -742,6 +742,51 @@ size_t ddpm3d_ssim3d_workspace_bytes(int B, int D, int H, int W);
 int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, int B, int D, int H, int W, double C1,
                   double C2, void* ws, size_t ws_bytes, float* map, double* out, void* stream);
 /*
+ * Per-step convergence trace of a sampling loop (added within ABI 13; the reference has no metric code): weighted
+ * moments of B estimates, one step's pred_xstart, against their targets and against the previous step's estimates.
+ * est is [B][voxels] fp32, B in 1..DDPM3D_TRACE_MAX_BATCH; prev, optional, has the same layout.  target and weight are
+ * optional fp32: with stride `voxels` each is [B][voxels] (every estimate has its own target patch and its own
+ * weights), with stride 0 each is [voxels], shared by all B; no other stride is accepted, and a NULL pointer takes
+ * stride 0.  A NULL weight means w = 1.
+ *
+ * ddpm3d_trace_moments writes out[B][DDPM3D_TR_REC] doubles (device memory).  Only voxels with w > 0 are summed: a
+ * voxel with w = 0 (or a NaN weight) contributes nothing, whatever est, prev or target hold there, NaN included.
+ * Every term is formed and added in fp64 without contraction, w, x, y, p the values widened to double, e = x - y,
+ * d = x - p:
+ *   W = sum w, N = number of voxels with w > 0, SUM_E = sum w * e, SUM_ABS_E = sum w * |e|,
+ *   SUM_SQ_E = sum w * (e * e), SUM_SQ_Y = sum w * (y * y), SUM_X = sum w * x, SUM_SQ_X = sum w * (x * x),
+ *   SUM_SQ_D = sum w * (d * d), CLIPPED = sum of w over the voxels with |x| >= 1.
+ * The columns of e and y are 0 without a target, SUM_SQ_D is 0 without prev.  The host divides: mse = SUM_SQ_E / W,
+ * mae, bias, nrmse = sqrt(SUM_SQ_E / SUM_SQ_Y), mean = SUM_X / W, std, delta_rms = sqrt(SUM_SQ_D / W).
+ *
+ * One workgroup per (chunk, estimate) writes one fp64 record to the caller's workspace and a second launch folds an
+ * estimate's records in a fixed order: no atomics, the same bits on every run, and the plan depends on `voxels`
+ * alone, so row b does not depend on B.  16-byte loads where voxels % 4 == 0 and est, prev, target and weight are
+ * 16-byte aligned, 4-byte loads otherwise.  Enqueue-only: no allocation, no synchronisation.
+ * ws: ddpm3d_trace_moments_workspace_bytes(B, voxels) bytes, 16-byte aligned (0 is the answer for a shape the entry
+ * refuses).  Returns DDPM3D_EINVAL before any launch for a NULL est, ws or out, B outside
+ * 1..DDPM3D_TRACE_MAX_BATCH, voxels outside 1..2^40, a stride that is neither 0 nor voxels, a non-zero stride for a
+ * NULL pointer, and a workspace that is too small or misaligned.
+ */
+#define DDPM3D_TRACE_MAX_BATCH 4096
+enum {
+    DDPM3D_TR_W = 0,
+    DDPM3D_TR_N = 1,
+    DDPM3D_TR_SUM_E = 2,
+    DDPM3D_TR_SUM_ABS_E = 3,
+    DDPM3D_TR_SUM_SQ_E = 4,
+    DDPM3D_TR_SUM_SQ_Y = 5,
+    DDPM3D_TR_SUM_X = 6,
+    DDPM3D_TR_SUM_SQ_X = 7,
+    DDPM3D_TR_SUM_SQ_D = 8,
+    DDPM3D_TR_CLIPPED = 9,
+    DDPM3D_TR_REC = 10          /* doubles per record */
+};
+size_t ddpm3d_trace_moments_workspace_bytes(int B, int64_t voxels);
+int ddpm3d_trace_moments(const float* est, const float* prev, const float* target, const float* weight, int B,
+                         int64_t voxels, int64_t target_stride, int64_t weight_stride, void* ws, size_t ws_bytes,
+                         double* out, void* stream);
+/*
  * Multi-scale 3-D SSIM (added within ABI 13; the reference has no metric code): Wang, Simoncelli, Bovik 2003,
  * extended to 3-D as ddpm3d_ssim3d extends SSIM.  Scales j = 0..M-1, M in 1..DDPM3D_MSSSIM_MAX_SCALES.
  *
