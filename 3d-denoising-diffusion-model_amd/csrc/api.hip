@@ -7,6 +7,7 @@
 #include "conv3d_params.h"
 #include "ddpm3d.h"
 #include "ops.h"
+#include "noise.h"
 
 static thread_local char g_err[512] = "";
 
@@ -482,7 +483,7 @@ int ddpm3d_p_sample_step(const float* model_out, const float* x, const float* no
                          float* pred_xstart, void* stream) {
     if (!step_args_ok(model_out, x, noise, coef, t_idx, N, voxels, sample))
         return fail(DDPM3D_EINVAL, "p_sample_step: bad arguments");
-    return launched(ddpm3d_launch_sample_step(false, model_out, x, noise, coef, t_idx, N, voxels, flags, 0.0f,
+    return launched(ddpm3d_launch_sample_step(false, model_out, x, noise, nullptr, coef, t_idx, N, voxels, flags, 0.0f,
                                               sample, pred_xstart, (hipStream_t)stream),
                     "p_sample_step");
 }
@@ -492,7 +493,7 @@ int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise,
                      float* pred_xstart, void* stream) {
     if (!step_args_ok(model_out, x, noise, coef, t_idx, N, voxels, sample))
         return fail(DDPM3D_EINVAL, "ddim_step: bad arguments");
-    return launched(ddpm3d_launch_sample_step(true, model_out, x, noise, coef, t_idx, N, voxels, flags, eta,
+    return launched(ddpm3d_launch_sample_step(true, model_out, x, noise, nullptr, coef, t_idx, N, voxels, flags, eta,
                                               sample, pred_xstart, (hipStream_t)stream),
                     "ddim_step");
 }
@@ -517,7 +518,7 @@ int ddpm3d_q_sample(const float* x_start, const float* noise, const float* qcoef
                     int voxels, int T, float* x_t, void* stream) {
     if (!x_start || !noise || !qcoef || !t_idx || !x_t || !vb_shape_ok(N, voxels, T))
         return fail(DDPM3D_EINVAL, "q_sample: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
-    return launched(ddpm3d_launch_q_sample(x_start, noise, qcoef, t_idx, N, voxels, T, x_t, (hipStream_t)stream),
+    return launched(ddpm3d_launch_q_sample(x_start, noise, nullptr, qcoef, t_idx, N, voxels, T, x_t, (hipStream_t)stream),
                     "q_sample");
 }
 
@@ -592,18 +593,114 @@ int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float
 }
 
 // ------------------------------------------------- DPM-Solver++ multistep step (added within ABI 13)
-int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
-                           const float* noise, const float* coef, const float* scoef, const int64_t* t_idx, int N,
-                           int voxels, int T, int flags, int order, float* sample, float* pred_xstart, void* stream) {
+static int dpm_solver_step_any(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
+                               const float* noise, const ddpm3d_noise_key* key, const float* coef, const float* scoef,
+                               const int64_t* t_idx, int N, int voxels, int T, int flags, int order, float* sample,
+                               float* pred_xstart, void* stream) {
     const int rc = step_entry_ok("dpm_solver_step", model_out && x && coef && scoef && t_idx && sample && pred_xstart,
                                  N, voxels, T, flags);
     if (rc != DDPM3D_OK) return rc;
     if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d is not 1, 2 or 3", order);
     if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
         return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d needs %d earlier x0 predictions", order, order - 1);
-    return launched(ddpm3d_launch_dpm_solver_step(model_out, x, x0_prev1, x0_prev2, noise, coef, scoef, t_idx, N,
+    return launched(ddpm3d_launch_dpm_solver_step(model_out, x, x0_prev1, x0_prev2, noise, key, coef, scoef, t_idx, N,
                                                   voxels, T, flags, order, sample, pred_xstart, (hipStream_t)stream),
                     "dpm_solver_step");
+}
+
+int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
+                           const float* noise, const float* coef, const float* scoef, const int64_t* t_idx, int N,
+                           int voxels, int T, int flags, int order, float* sample, float* pred_xstart, void* stream) {
+    return dpm_solver_step_any(model_out, x, x0_prev1, x0_prev2, noise, nullptr, coef, scoef, t_idx, N, voxels, T,
+                               flags, order, sample, pred_xstart, stream);
+}
+
+// ------------------------------------------------- sampler noise from a counter-based key (added within ABI 13)
+// The host side of a key; `geometry`: the entry reads origin / patch / canvas (ddpm3d_noise_bits does not).
+static int noise_key_ok(const char* what, const ddpm3d_noise_key* key, int N, int voxels, bool geometry) {
+    if (!key || !key->stream) return fail(DDPM3D_EINVAL, "%s: NULL key or key->stream", what);
+    if (N <= 0 || N > 65535 || voxels <= 0)
+        return fail(DDPM3D_EINVAL, "%s: bad arguments (N=%d voxels=%d)", what, N, voxels);
+    if (key->draw < 0 || key->draw > 0xffffffffll)
+        return fail(DDPM3D_EINVAL, "%s: draw %lld outside 0 .. 2^32 - 1", what, (long long)key->draw);
+    if (geometry && key->origin) {
+        for (int a = 0; a < 3; ++a)
+            if (key->patch[a] <= 0 || key->canvas[a] <= 0)
+                return fail(DDPM3D_EINVAL, "%s: patch (%d, %d, %d) and canvas (%d, %d, %d) extents must be positive",
+                            what, key->patch[0], key->patch[1], key->patch[2], key->canvas[0], key->canvas[1],
+                            key->canvas[2]);
+        // three factors below 2^31 each: the partial products fit 64 bits only after the first check
+        const uint64_t LIMIT = 1ull << 34;
+        const uint64_t p01 = (uint64_t)key->patch[0] * (uint64_t)key->patch[1];
+        if (p01 > (uint64_t)voxels || p01 * (uint64_t)key->patch[2] != (uint64_t)voxels)
+            return fail(DDPM3D_EINVAL, "%s: patch %d x %d x %d is not voxels=%d", what, key->patch[0], key->patch[1],
+                        key->patch[2], voxels);
+        const uint64_t c01 = (uint64_t)key->canvas[0] * (uint64_t)key->canvas[1];
+        if (c01 > LIMIT || c01 * (uint64_t)key->canvas[2] > LIMIT)
+            return fail(DDPM3D_EINVAL, "%s: canvas %d x %d x %d holds more than 2^34 voxels", what, key->canvas[0],
+                        key->canvas[1], key->canvas[2]);
+    }
+    return DDPM3D_OK;
+}
+
+int ddpm3d_noise_fill(const ddpm3d_noise_key* key, int N, int voxels, float* out, void* stream) {
+    const int rc = noise_key_ok("noise_fill", key, N, voxels, true);
+    if (rc != DDPM3D_OK) return rc;
+    if (!out) return fail(DDPM3D_EINVAL, "noise_fill: NULL out");
+    return launched(ddpm3d_launch_noise_fill(*key, N, voxels, out, (hipStream_t)stream), "noise_fill");
+}
+
+int ddpm3d_noise_bits(const ddpm3d_noise_key* key, int N, int quads, uint32_t* out, void* stream) {
+    const int rc = noise_key_ok("noise_bits", key, N, quads, false);
+    if (rc != DDPM3D_OK) return rc;
+    if (!out) return fail(DDPM3D_EINVAL, "noise_bits: NULL out");
+    return launched(ddpm3d_launch_noise_bits(*key, N, quads, out, (hipStream_t)stream), "noise_bits");
+}
+
+int ddpm3d_p_sample_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key, const float* coef,
+                               const int64_t* t_idx, int N, int voxels, int flags, float* sample, float* pred_xstart,
+                               void* stream) {
+    const int rc = noise_key_ok("p_sample_step_keyed", key, N, voxels, true);
+    if (rc != DDPM3D_OK) return rc;
+    if (!model_out || !x || !coef || !t_idx || !sample)
+        return fail(DDPM3D_EINVAL, "p_sample_step_keyed: bad arguments");
+    return launched(ddpm3d_launch_sample_step(false, model_out, x, nullptr, key, coef, t_idx, N, voxels, flags, 0.0f,
+                                              sample, pred_xstart, (hipStream_t)stream),
+                    "p_sample_step_keyed");
+}
+
+int ddpm3d_ddim_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key, const float* coef,
+                           const int64_t* t_idx, int N, int voxels, int flags, float eta, float* sample,
+                           float* pred_xstart, void* stream) {
+    const int rc = noise_key_ok("ddim_step_keyed", key, N, voxels, true);
+    if (rc != DDPM3D_OK) return rc;
+    if (!model_out || !x || !coef || !t_idx || !sample) return fail(DDPM3D_EINVAL, "ddim_step_keyed: bad arguments");
+    return launched(ddpm3d_launch_sample_step(true, model_out, x, nullptr, key, coef, t_idx, N, voxels, flags, eta,
+                                              sample, pred_xstart, (hipStream_t)stream),
+                    "ddim_step_keyed");
+}
+
+int ddpm3d_dpm_solver_step_keyed(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
+                                 const ddpm3d_noise_key* key, const float* coef, const float* scoef,
+                                 const int64_t* t_idx, int N, int voxels, int T, int flags, int order, float* sample,
+                                 float* pred_xstart, void* stream) {
+    if (key != nullptr) {                       // a NULL key is the ODE form
+        const int rc = noise_key_ok("dpm_solver_step_keyed", key, N, voxels, true);
+        if (rc != DDPM3D_OK) return rc;
+    }
+    return dpm_solver_step_any(model_out, x, x0_prev1, x0_prev2, nullptr, key, coef, scoef, t_idx, N, voxels, T, flags,
+                               order, sample, pred_xstart, stream);
+}
+
+int ddpm3d_q_sample_keyed(const float* x_start, const ddpm3d_noise_key* key, const float* qcoef, const int64_t* t_idx,
+                          int N, int voxels, int T, float* x_t, void* stream) {
+    const int rc = noise_key_ok("q_sample_keyed", key, N, voxels, true);
+    if (rc != DDPM3D_OK) return rc;
+    if (!x_start || !qcoef || !t_idx || !x_t || T <= 0)
+        return fail(DDPM3D_EINVAL, "q_sample_keyed: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
+    return launched(ddpm3d_launch_q_sample(x_start, nullptr, key, qcoef, t_idx, N, voxels, T, x_t,
+                                           (hipStream_t)stream),
+                    "q_sample_keyed");
 }
 
 // ------------------------------------------------- uncertainty maps from K draws (added within ABI 13)

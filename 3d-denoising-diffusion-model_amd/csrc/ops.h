@@ -22,9 +22,12 @@ hipError_t ddpm3d_launch_transpose(const float* in, int N, int R, int S, float* 
 hipError_t ddpm3d_launch_to_ndhwc_pad(const float* in, int N, int C, int voxels, int Cpad, float* out, hipStream_t st);
 hipError_t ddpm3d_launch_subsample_hw2(const float* in, int N, int D, int H, int W, int C, float* out,
                                        hipStream_t st);
+// the step launchers that read noise take it from `key` (noise.h) when one is given, from the tensor otherwise
+struct ddpm3d_noise_key;
 hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
-                                     const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
-                                     float eta, float* sample, float* pred_xstart, hipStream_t st);
+                                     const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N,
+                                     int voxels, int flags, float eta, float* sample, float* pred_xstart,
+                                     hipStream_t st);
 // p_mean_variance and the DDIM reverse (inversion) step; T = rows of coef, t outside [0, T) gives NaN
 hipError_t ddpm3d_launch_p_mean_variance(const float* mo, const float* x, const float* coef, const int64_t* t_idx,
                                          int N, int voxels, int T, int flags, float* mean, float* variance,
@@ -35,13 +38,13 @@ hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, cons
 // one DPM-Solver++ multistep step; scoef = [T][DDPM3D_NSCOEF] weights, m1 / m2 read at order >= 2 / 3, noise may be
 // NULL; t outside [0, T) gives NaN
 hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* x, const float* m1, const float* m2,
-                                         const float* noise, const float* coef, const float* scoef,
-                                         const int64_t* t_idx, int N, int voxels, int T, int flags, int order,
-                                         float* sample, float* pred_xstart, hipStream_t st);
+                                         const float* noise, const ddpm3d_noise_key* key, const float* coef,
+                                         const float* scoef, const int64_t* t_idx, int N, int voxels, int T, int flags,
+                                         int order, float* sample, float* pred_xstart, hipStream_t st);
 // variational bound (calc_bpd_loop): ws holds ddpm3d_vb_parts(voxels) 32-byte records per sample
 int ddpm3d_vb_parts(int voxels);
-hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,
-                                  int N, int voxels, int T, float* xt, hipStream_t st);
+hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const ddpm3d_noise_key* key, const float* qcoef,
+                                  const int64_t* t_idx, int N, int voxels, int T, float* xt, hipStream_t st);
 hipError_t ddpm3d_launch_vb_terms(const float* mo, const float* x_start, const float* x_t, const float* noise,
                                   const float* coef, const float* qcoef, const int64_t* t_idx, int N, int voxels,
                                   int T, int flags, double* ws, float* vb, float* xstart_mse, float* mse, int ld,

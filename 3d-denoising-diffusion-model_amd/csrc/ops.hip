@@ -6,6 +6,7 @@
 #include "conv3d_params.h"
 #include "conv3d_load.h"   // affine_act, act_quad, half_pack
 #include "ops.h"
+#include "noise.h"
 
 // ------------------------------------------------------------------ packing
 // OIDHW -> [tap][ci/8][CoutPad][8]  (zero padded in ci and cout).  The inner 8
@@ -771,13 +772,21 @@ static dim3 step_grid(int N, int voxels) {
     return dim3(bx, N);
 }
 
-template <bool DDIM>
+// Noise: where the step's normal comes from (noise.h) -- the caller's tensor, or the keyed function.  A keyed sample
+// whose patch leaves the canvas gets step_nan_fill.
+template <bool DDIM, class Noise>
 __global__ __launch_bounds__(256) void sample_step_kernel(
-    const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ noise,
+    const float* __restrict__ mo, const float* __restrict__ x, const Noise noise,
     const float* __restrict__ coef, const int64_t* __restrict__ t_idx, int voxels, int flags, float eta,
     float* __restrict__ sample, float* __restrict__ pred_xstart) {
     const int n = blockIdx.y;
     const int64_t ti = t_idx[n];
+    const auto z = noise.sample(n);
+    if (!z.ok()) {
+        step_nan_fill(n, voxels, gridDim.x * blockDim.x, sample, pred_xstart, pred_xstart != nullptr, nullptr, nullptr,
+                      false);
+        return;
+    }
     const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
     const float c_recip = c[DDPM3D_C_SQRT_RECIP_ACP], c_recipm1 = c[DDPM3D_C_SQRT_RECIPM1_ACP];
     const float c1 = c[DDPM3D_C_POST_MEAN_COEF1], c2 = c[DDPM3D_C_POST_MEAN_COEF2];
@@ -795,28 +804,40 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
             const float logvar = learn ? learned_logvar(mo[((size_t)n * ch + 1) * voxels + v], min_log, max_log)
                                        : min_log;
             const float mean = c1 * x0 + c2 * xv;                           // :216-219
-            out = mean + mask * expf(0.5f * logvar) * noise[i];             // :438
+            out = mean + mask * expf(0.5f * logvar) * z.at(i, v);             // :438
         } else {
             const float eps = eps_from_x0(xv, x0, c_recip, c_recipm1);
             const float sigma = eta * sqrtf((1.0f - ab_prev) / (1.0f - ab)) * sqrtf(1.0f - ab / ab_prev);
             const float mean_pred = x0 * sqrtf(ab_prev) + sqrtf(1.0f - ab_prev - sigma * sigma) * eps;
-            out = mean_pred + mask * sigma * noise[i];                      // :584
+            out = mean_pred + mask * sigma * z.at(i, v);                     // :584
         }
         sample[i] = out;
         if (pred_xstart != nullptr) pred_xstart[i] = x0;
     }
 }
 
-hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
-                                     const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
-                                     float eta, float* sample, float* pred_xstart, hipStream_t st) {
+template <class Noise>
+static hipError_t launch_sample_step(bool ddim, const float* mo, const float* x, const Noise noise, const float* coef,
+                                     const int64_t* t_idx, int N, int voxels, int flags, float eta, float* sample,
+                                     float* pred_xstart, hipStream_t st) {
     if (ddim)
-        hipLaunchKernelGGL(sample_step_kernel<true>, step_grid(N, voxels), dim3(256), 0, st, mo, x, noise, coef,
-                           t_idx, voxels, flags, eta, sample, pred_xstart);
+        hipLaunchKernelGGL((sample_step_kernel<true, Noise>), step_grid(N, voxels), dim3(256), 0, st, mo, x, noise,
+                           coef, t_idx, voxels, flags, eta, sample, pred_xstart);
     else
-        hipLaunchKernelGGL(sample_step_kernel<false>, step_grid(N, voxels), dim3(256), 0, st, mo, x, noise, coef,
-                           t_idx, voxels, flags, eta, sample, pred_xstart);
+        hipLaunchKernelGGL((sample_step_kernel<false, Noise>), step_grid(N, voxels), dim3(256), 0, st, mo, x, noise,
+                           coef, t_idx, voxels, flags, eta, sample, pred_xstart);
     return hipGetLastError();
+}
+
+hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
+                                     const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N,
+                                     int voxels, int flags, float eta, float* sample, float* pred_xstart,
+                                     hipStream_t st) {
+    if (key != nullptr)
+        return launch_sample_step(ddim, mo, x, KeyNoise{noise_key_dev(*key)}, coef, t_idx, N, voxels, flags, eta,
+                                  sample, pred_xstart, st);
+    return launch_sample_step(ddim, mo, x, TensorNoise{noise}, coef, t_idx, N, voxels, flags, eta, sample,
+                              pred_xstart, st);
 }
 
 // ------------------------------------------------- p_mean_variance, DDIM inversion
@@ -904,19 +925,22 @@ hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, cons
 // whose weights the host expanded in fp64 into row t of scoef ([T][DDPM3D_NSCOEF]: c_x, w0, w1, w2, c_z), summed in
 // that order.  m1 is read only at order >= 2, m2 only at order 3, z only when noise is non-null.  A sample whose t
 // lies outside [0, T) reads neither table and gets NaN.
+template <class Noise>
 __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
     const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ m1,
-    const float* __restrict__ m2, const float* __restrict__ noise, const float* __restrict__ coef,
+    const float* __restrict__ m2, const Noise noise, const float* __restrict__ coef,
     const float* __restrict__ scoef, const int64_t* __restrict__ t_idx, int voxels, int T, int flags, int order,
     float* __restrict__ sample, float* __restrict__ pred_xstart) {
     const int n = blockIdx.y;
     const int64_t ti = t_idx[n];
     const int ch = (flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1;
     const int stride = gridDim.x * blockDim.x;
-    if (ti < 0 || ti >= T) {
+    const auto z = noise.sample(n);
+    if (ti < 0 || ti >= T || !z.ok()) {
         step_nan_fill(n, voxels, stride, sample, pred_xstart, true, nullptr, nullptr, false);
         return;
     }
+    const bool has_z = noise.present();
     const float* c = coef + (size_t)ti * DDPM3D_NCOEF;
     const float c_recip = c[DDPM3D_C_SQRT_RECIP_ACP], c_recipm1 = c[DDPM3D_C_SQRT_RECIPM1_ACP];
     const float* w = scoef + (size_t)ti * DDPM3D_NSCOEF;
@@ -929,18 +953,23 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
         float out = c_x * xv + w0 * x0;
         if (order >= 2) out = out + w1 * m1[i];
         if (order >= 3) out = out + w2 * m2[i];
-        if (noise != nullptr) out = out + c_z * noise[i];
+        if (has_z) out = out + c_z * z.at(i, v);
         sample[i] = out;
         pred_xstart[i] = x0;
     }
 }
 
 hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* x, const float* m1, const float* m2,
-                                         const float* noise, const float* coef, const float* scoef,
-                                         const int64_t* t_idx, int N, int voxels, int T, int flags, int order,
-                                         float* sample, float* pred_xstart, hipStream_t st) {
-    hipLaunchKernelGGL(dpm_solver_step_kernel, step_grid(N, voxels), dim3(256), 0, st, mo, x, m1, m2, noise, coef,
-                       scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
+                                         const float* noise, const ddpm3d_noise_key* key, const float* coef,
+                                         const float* scoef, const int64_t* t_idx, int N, int voxels, int T, int flags,
+                                         int order, float* sample, float* pred_xstart, hipStream_t st) {
+    if (key != nullptr)
+        hipLaunchKernelGGL(dpm_solver_step_kernel<KeyNoise>, step_grid(N, voxels), dim3(256), 0, st, mo, x, m1, m2,
+                           KeyNoise{noise_key_dev(*key)}, coef, scoef, t_idx, voxels, T, flags, order, sample,
+                           pred_xstart);
+    else
+        hipLaunchKernelGGL(dpm_solver_step_kernel<TensorNoise>, step_grid(N, voxels), dim3(256), 0, st, mo, x, m1, m2,
+                           TensorNoise{noise}, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
     return hipGetLastError();
 }
 
@@ -969,12 +998,18 @@ __device__ __forceinline__ void vb_chunk(int voxels, int parts, int part, long l
     v1 = v0 + chunk < voxels ? v0 + chunk : voxels;
 }
 
-__global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+template <class Noise>
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const Noise noise,
                                                        const float* __restrict__ qcoef,
                                                        const int64_t* __restrict__ t_idx, int voxels, int T,
                                                        float* __restrict__ xt) {
     const int n = blockIdx.y;
     const int64_t ti = t_idx[n];
+    const auto z = noise.sample(n);
+    if (!z.ok()) {                                // a keyed patch that leaves its canvas
+        step_nan_fill(n, voxels, gridDim.x * blockDim.x, xt, nullptr, false, nullptr, nullptr, false);
+        return;
+    }
     float a = __builtin_nanf(""), b = a;          // t outside [0, T): no table row is read, x_t is NaN
     if (ti >= 0 && ti < T) {
         a = qcoef[(size_t)ti * DDPM3D_NQCOEF + DDPM3D_Q_SQRT_ACP];
@@ -982,7 +1017,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
     for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += gridDim.x * blockDim.x) {
         const size_t i = (size_t)n * voxels + v;
-        xt[i] = a * x0[i] + b * noise[i];         // :202-206
+        xt[i] = a * x0[i] + b * z.at(i, v);         // :202-206
     }
 }
 
@@ -1137,10 +1172,14 @@ __global__ __launch_bounds__(256) void vb_fold_kernel(const double* __restrict__
     }
 }
 
-hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const float* qcoef, const int64_t* t_idx,
-                                  int N, int voxels, int T, float* xt, hipStream_t st) {
-    hipLaunchKernelGGL(q_sample_kernel, step_grid(N, voxels), dim3(256), 0, st, x0, noise, qcoef, t_idx, voxels, T,
-                       xt);
+hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const ddpm3d_noise_key* key, const float* qcoef,
+                                  const int64_t* t_idx, int N, int voxels, int T, float* xt, hipStream_t st) {
+    if (key != nullptr)
+        hipLaunchKernelGGL(q_sample_kernel<KeyNoise>, step_grid(N, voxels), dim3(256), 0, st, x0,
+                           KeyNoise{noise_key_dev(*key)}, qcoef, t_idx, voxels, T, xt);
+    else
+        hipLaunchKernelGGL(q_sample_kernel<TensorNoise>, step_grid(N, voxels), dim3(256), 0, st, x0, TensorNoise{noise},
+                           qcoef, t_idx, voxels, T, xt);
     return hipGetLastError();
 }
 

@@ -136,6 +136,13 @@ class RoiIndex(C.Structure):
                 ("d_offsets", C.c_void_p), ("d_chunks", C.c_void_p), ("d_index", C.c_void_p)]
 
 
+class NoiseKeyDesc(C.Structure):
+    """struct ddpm3d_noise_key: seed, device stream ids [N], draw, device origins [N][3] or NULL, and the patch and
+    canvas extents (D, H, W order) the origins refer to"""
+    _fields_ = [("seed", C.c_uint64), ("stream", C.c_void_p), ("draw", C.c_int64), ("origin", C.c_void_p),
+                ("patch", C.c_int32 * 3), ("canvas", C.c_int32 * 3)]
+
+
 LAYER_RES, LAYER_ATTN, LAYER_DOWNCONV, LAYER_UPCONV = 1, 2, 3, 4
 UPDOWN = {None: 0, "down": 1, "up": 2}
 
@@ -222,6 +229,15 @@ EXPORTS = {
     "ddpm3d_gauss_smooth_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ddpm3d_gauss_smooth": (C.c_int, [_fp] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 3 + [_fp, _fp, C.c_size_t, _fp]),
     "ddpm3d_nlm": (C.c_int, [_fp] + [C.c_int] * 9 + [C.c_float, C.c_float, _fp, _fp]),
+    "ddpm3d_noise_fill": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
+    "ddpm3d_noise_bits": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
+    "ddpm3d_p_sample_step_keyed": (C.c_int, [_fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                             _fp, _fp, _fp]),
+    "ddpm3d_ddim_step_keyed": (C.c_int, [_fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, _fp, _fp, _fp]),
+    "ddpm3d_dpm_solver_step_keyed": (C.c_int, [_fp, _fp, _fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, _fp, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "ddpm3d_q_sample_keyed": (C.c_int, [_fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

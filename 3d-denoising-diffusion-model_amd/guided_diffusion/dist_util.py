@@ -101,6 +101,18 @@ def volume_generator(global_index, seed=10, device=None, draw=0):
     return g
 
 
+def noise_stream(global_index, draw=0):
+    """The stream id (gaussian_diffusion.NoiseKey) of draw `draw` of global patch / volume `global_index`:
+    global_index + (draw << 32), so the noise of a sample depends on neither the batch size nor the world size.  A
+    64-bit id: none of volume_generator's 2^24 / MAX_DRAW limits apply (global_index below 2^32, draw below 2^32)."""
+    g, d = int(global_index), int(draw)
+    if not 0 <= g < (1 << 32):
+        raise ValueError("global_index must be in 0 .. 2^32 - 1, got %s" % (global_index,))
+    if not 0 <= d < (1 << 32):
+        raise ValueError("draw must be in 0 .. 2^32 - 1, got %s" % (draw,))
+    return g + (d << 32)
+
+
 def gather_round(sample, index):
     """all_gather one round's samples (scripts/test.py:74-78).  `index` is this
     rank's item index for the round or None (padding).  Returns [(index, tensor)]

@@ -23,6 +23,12 @@ The DPM-Solver++ multistep sampler (dpm_solver_sample_loop, an extension; Lu et
 al. 2022, arXiv:2211.01095) runs on one more kernel, reading the sampler table
 for x0 and a [T][8] table of the solver's fp64-expanded weights: one plan
 replay plus one launch per step.
+
+Keyed noise (NoiseKey, `noise_key=` on every loop; an extension): the normals of x_T and of every
+step are a counter-based function of (seed, stream, draw, voxel index) that the step kernels evaluate themselves
+(ddpm3d_*_keyed), so a loop creates no noise tensor and its result depends on neither the batch size nor the number
+of ranks.  Draw 0 is x_T, draw k + 1 the loop's k-th step.  This is not torch's generator: a keyed and an un-keyed
+run are two different draws of the same distribution.
 """
 
 import enum
@@ -72,6 +78,124 @@ def betas_for_alpha_bar(num_diffusion_timesteps, alpha_bar, max_beta=0.999):
     """gaussian_diffusion.py:45-62."""
     n = num_diffusion_timesteps
     return np.array([min(1 - alpha_bar((i + 1) / n) / alpha_bar(i / n), max_beta) for i in range(n)])
+
+
+def _as_int64(v):
+    """Any 64-bit value, signed or unsigned, as the int64 of the same bits."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError("stream ids must be integers, got %r" % (v,))
+    v = int(v)
+    if not -(1 << 63) <= v < (1 << 64):
+        raise ValueError("stream id %d does not fit 64 bits" % v)
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+class NoiseKey:
+    """The key of a keyed loop: `seed` (any 64-bit value) and one stream id per sample of the batch (`streams`: a
+    sequence of N ints, e.g. dist_util.noise_stream(global_index, draw), or an int64 tensor on the device).  The
+    normal of voxel v of sample n at draw d is a function of (seed, streams[n], d, index) alone; index is v, or, with a
+    geometry, the voxel's linear index on a canvas: `origin` ((N, 3) ints, (z0, y0, x0) per sample), `patch` = the
+    samples' (pd, ph, pw) and `canvas` = (Dc, Hc, Wc), all three together (joint sampling: every patch that covers a
+    canvas voxel reads the same normal there).  The object holds the device arrays; `device` defaults to the current
+    HIP device."""
+
+    def __init__(self, seed, streams, origin=None, patch=None, canvas=None, device=None):
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+            raise ValueError("seed must be an integer in 0 .. 2^64 - 1, got %r" % (seed,))
+        self.seed = int(seed)
+        if (origin is None) != (patch is None) or (origin is None) != (canvas is None):
+            raise ValueError("origin, patch and canvas come together (all three or none)")
+        if isinstance(streams, th.Tensor):
+            if streams.dtype != th.int64 or streams.dim() != 1 or streams.numel() == 0:
+                raise ValueError("streams must be a non-empty 1-D int64 tensor, got %s %s"
+                                 % (streams.dtype, tuple(streams.shape)))
+            if not streams.is_cuda:
+                raise RuntimeError("a streams tensor must live on the GPU (got %s)" % streams.device)
+            host_streams, n = None, int(streams.numel())
+        else:
+            host_streams = [_as_int64(v) for v in streams]
+            n = len(host_streams)
+            if n == 0:
+                raise ValueError("streams must name at least one sample")
+        self.patch = self.canvas = None
+        host_origin = None
+        if origin is not None:
+            self.patch, self.canvas = tuple(int(v) for v in patch), tuple(int(v) for v in canvas)
+            if len(self.patch) != 3 or len(self.canvas) != 3 or min(self.patch + self.canvas) <= 0:
+                raise ValueError("patch and canvas are three positive extents each, got %r and %r" % (patch, canvas))
+            if self.canvas[0] * self.canvas[1] * self.canvas[2] > (1 << 34):
+                raise ValueError("a canvas of %d x %d x %d voxels exceeds the 2^34 indices of a stream" % self.canvas)
+            if isinstance(origin, th.Tensor):
+                if origin.dtype != th.int32 or tuple(origin.shape) != (n, 3) or not origin.is_cuda:
+                    raise ValueError("an origin tensor must be (%d, 3) int32 on the GPU" % n)
+            else:
+                host_origin = np.asarray(origin, dtype=np.int64)
+                if host_origin.shape != (n, 3):
+                    raise ValueError("origin must hold (z0, y0, x0) for each of the %d samples, got shape %s"
+                                     % (n, host_origin.shape))
+                if np.abs(host_origin).max() >= (1 << 31):
+                    raise ValueError("origins must fit 32 bits")
+        # checks done: the device arrays
+        if host_streams is not None:
+            device = th.device("cuda", th.cuda.current_device()) if device is None else th.device(device)
+            streams = th.tensor(host_streams, dtype=th.int64).to(device)
+        self.streams = streams.contiguous()
+        self.origin = None
+        if origin is not None:
+            self.origin = (origin.contiguous() if host_origin is None
+                           else th.from_numpy(host_origin.astype(np.int32)).to(self.streams.device))
+            if self.origin.device != self.streams.device:
+                raise ValueError("streams on %s, origin on %s" % (self.streams.device, self.origin.device))
+
+    @property
+    def n(self):
+        return int(self.streams.numel())
+
+    @property
+    def device(self):
+        return self.streams.device
+
+    def rows(self, lo, hi):
+        """The key of samples lo .. hi - 1 (views of the same device arrays)."""
+        if not 0 <= lo < hi <= self.n:
+            raise ValueError("rows %d..%d of a key of %d samples" % (lo, hi, self.n))
+        k = NoiseKey.__new__(NoiseKey)
+        k.seed, k.patch, k.canvas = self.seed, self.patch, self.canvas
+        k.streams = self.streams[lo:hi]
+        k.origin = None if self.origin is None else self.origin[lo:hi]
+        return k
+
+    def desc(self, draw, like=None):
+        """struct ddpm3d_noise_key for `draw`; `like`: the (N, ...) tensor the call works on, checked against the key."""
+        if isinstance(draw, bool) or not isinstance(draw, (int, np.integer)) or not 0 <= int(draw) < (1 << 32):
+            raise ValueError("draw must be an integer in 0 .. 2^32 - 1, got %r" % (draw,))
+        if like is not None:
+            if like.shape[0] != self.n:
+                raise ValueError("a key of %d streams for a batch of %d" % (self.n, like.shape[0]))
+            if like.device != self.device:
+                raise ValueError("the key lives on %s, the batch on %s" % (self.device, like.device))
+        d = H.NoiseKeyDesc()
+        d.seed, d.stream, d.draw = self.seed, self.streams.data_ptr(), int(draw)
+        d.origin = None if self.origin is None else self.origin.data_ptr()
+        for a in range(3):
+            d.patch[a] = 0 if self.patch is None else self.patch[a]
+            d.canvas[a] = 0 if self.canvas is None else self.canvas[a]
+        return d
+
+    def fill(self, draw, shape, out=None):
+        """The (N, ...) float32 normals of `draw` a keyed step reads, on ddpm3d_noise_fill: x_T is fill(0, shape)."""
+        shape = tuple(int(v) for v in shape)
+        if len(shape) < 2 or shape[0] != self.n:
+            raise ValueError("shape %s for a key of %d streams: (N, ...) expected" % (shape, self.n))
+        if out is None:
+            out = th.empty(shape, dtype=th.float32, device=self.device)
+        H.require_device(out, "out")
+        if tuple(out.shape) != shape:
+            raise ValueError("out of shape %s, expected %s" % (tuple(out.shape), shape))
+        d = self.desc(draw, out)
+        with th.cuda.device(self.device):
+            H.check(H.load().ddpm3d_noise_fill(d, self.n, out[0].numel(), H.ptr(out), H.stream()))
+        return out
 
 
 class GaussianDiffusion:
@@ -256,16 +380,20 @@ class GaussianDiffusion:
         SpacedDiffusion, respace.py:123-128)."""
         return self._scale_timesteps(t)
 
-    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None):
+    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None, noise_key=None, draw=0):
         """One fused reverse step.  `out`: (sample, pred_xstart) tensors of x's shape to write into (the joint loop's
-        patch buffers); fresh tensors otherwise."""
+        patch buffers); fresh tensors otherwise.  With `noise_key` the kernel evaluates the key's `draw` itself and
+        `noise` is not read."""
         lib = H.load()
         N = x.shape[0]
         vox = x[0].numel()
         flags = self._flags(clip_denoised)
         self._model_step_output(model_output, x, flags)
         H.require_device(x, "x")
-        self._check_noise(noise, x)
+        if noise_key is None:
+            self._check_noise(noise, x)
+        else:
+            kd = noise_key.desc(draw, x)
         st = self._device_state(x.device)
         sample, x0 = out if out is not None else (th.empty_like(x), th.empty_like(x))
         for name, o in (("out[0] (sample)", sample), ("out[1] (pred_xstart)", x0)):
@@ -273,7 +401,13 @@ class GaussianDiffusion:
             assert o.shape == x.shape and o.device == x.device, "%s: %s on %s for x %s on %s" % (
                 name, tuple(o.shape), o.device, tuple(x.shape), x.device)
         t = t.to(device=x.device, dtype=th.int64).contiguous()
-        if kind == "ddpm":
+        if noise_key is not None and kind == "ddpm":
+            H.check(lib.ddpm3d_p_sample_step_keyed(H.ptr(model_output), H.ptr(x), kd, H.ptr(st["coef"]), H.ptr(t), N,
+                                                   vox, flags, H.ptr(sample), H.ptr(x0), H.stream()))
+        elif noise_key is not None:
+            H.check(lib.ddpm3d_ddim_step_keyed(H.ptr(model_output), H.ptr(x), kd, H.ptr(st["coef"]), H.ptr(t), N, vox,
+                                               flags, float(eta), H.ptr(sample), H.ptr(x0), H.stream()))
+        elif kind == "ddpm":
             H.check(lib.ddpm3d_p_sample_step(H.ptr(model_output), H.ptr(x), H.ptr(noise), H.ptr(st["coef"]),
                                              H.ptr(t), N, vox, flags, H.ptr(sample), H.ptr(x0), H.stream()))
         else:
@@ -310,6 +444,14 @@ class GaussianDiffusion:
         assert noise.shape == x.shape
 
     @staticmethod
+    def _check_key(noise_key, step_noise):
+        if noise_key is not None:
+            if step_noise is not None:
+                raise ValueError("noise_key and explicit noise (step_noise / noise) both name the noise: give one of them")
+            if not isinstance(noise_key, NoiseKey):
+                raise ValueError("noise_key must be a NoiseKey, got %r" % type(noise_key))
+
+    @staticmethod
     def _draw_noise(step_noise, k, like):
         """The k-th step's noise: randn_like, or `step_noise` (extension, for parity runs): a sequence of
         tensors in draw order, or a callable (k, like) -> tensor (e.g. per-volume generators, scripts/test.py)."""
@@ -344,22 +486,25 @@ class GaussianDiffusion:
 
     # --------------------------------------------------------------- one step
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                 noise=None):
-        """gaussian_diffusion.py:395-439.  `noise`: optional injected randn_like draw."""
+                 noise=None, noise_key=None, draw=0):
+        """gaussian_diffusion.py:395-439.  `noise`: optional injected randn_like draw; `noise_key`, `draw`
+        (extension): the step's noise is that draw of the key, evaluated by the kernel."""
         self._reject_hooks(denoised_fn, cond_fn)
+        self._check_key(noise_key, noise)
         out = self._call_model(model, x, t, model_kwargs)
-        if noise is None:
+        if noise is None and noise_key is None:
             noise = th.randn_like(x)
-        return self._update("ddpm", out, x, t, noise, clip_denoised)
+        return self._update("ddpm", out, x, t, noise, clip_denoised, noise_key=noise_key, draw=draw)
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                    eta=0.0, noise=None):
-        """gaussian_diffusion.py:537-585."""
+                    eta=0.0, noise=None, noise_key=None, draw=0):
+        """gaussian_diffusion.py:537-585.  `noise_key`, `draw` as in p_sample."""
         self._reject_hooks(denoised_fn, cond_fn)
+        self._check_key(noise_key, noise)
         out = self._call_model(model, x, t, model_kwargs)
-        if noise is None:
+        if noise is None and noise_key is None:
             noise = th.randn_like(x)
-        return self._update("ddim", out, x, t, noise, clip_denoised, eta)
+        return self._update("ddim", out, x, t, noise, clip_denoised, eta, noise_key=noise_key, draw=draw)
 
     # ------------------------------------------------------------------ loops
     def _trace_step(self, trace, res, prev, i):
@@ -371,16 +516,16 @@ class GaussianDiffusion:
         return res["pred_xstart"]
 
     def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-              progress, eta, step_noise, trace=None):
+              progress, eta, step_noise, trace=None, noise_key=None):
         self._reject_hooks(denoised_fn, cond_fn)
+        self._check_key(noise_key, step_noise)
         if device is None:
             device = next(model.parameters()).device
         device = th.device(device)
         if device.type != "cuda":
             raise RuntimeError("sampling runs on HIP kernels only; got device %s" % device)
         assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        H.require_device(img, "noise")
+        img = self._start_noise(noise, shape, device, noise_key)
         indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
         # grad mode and the current device are changed around the COMPUTE of a step only and are
         # back to the caller's before every yield (the reference wraps p_sample alone in no_grad and
@@ -392,46 +537,57 @@ class GaussianDiffusion:
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
                 out = net(img, i)
-                z = self._draw_noise(step_noise, k, img)
-                res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta)
+                z = self._draw_noise(step_noise, k, img) if noise_key is None else None
+                res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta, noise_key=noise_key, draw=k + 1)
                 if trace is not None:
                     prev = self._trace_step(trace, res, prev, i)
             yield res
             img = res["sample"]
 
+    @staticmethod
+    def _start_noise(noise, shape, device, noise_key):
+        """x_T: the caller's `noise`, else draw 0 of the key, else randn."""
+        if noise is None:
+            noise = noise_key.fill(0, shape) if noise_key is not None else th.randn(*shape, device=device)
+        H.require_device(noise, "noise")
+        return noise
+
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, progress=False,
-                                  step_noise=None, trace=None):
+                                  step_noise=None, trace=None, noise_key=None):
         """gaussian_diffusion.py:487-535.  `step_noise` (extension): a sequence of
         T tensors used instead of randn_like, in draw order, for parity runs.  `trace` (extension, on every loop): a
         metrics.StepTrace that receives one record per step and sample of that step's pred_xstart (one reduction
-        per step, nothing waits for the device); None launches nothing more."""
+        per step, nothing waits for the device); None launches nothing more.  `noise_key` (extension, on every loop): a
+        NoiseKey of shape[0] streams; x_T is its draw 0 (unless `noise` is given) and step k reads draw k + 1 inside
+        the step kernel -- no noise tensor is created.  Not together with `step_noise`."""
         yield from self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, 0.0, step_noise, trace)
+                              device, progress, 0.0, step_noise, trace, noise_key)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, progress=False, step_noise=None, trace=None):
+                      model_kwargs=None, device=None, progress=False, step_noise=None, trace=None, noise_key=None):
         """gaussian_diffusion.py:441-485."""
         final = None
         for final in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
-                                                    model_kwargs, device, progress, step_noise, trace):
+                                                    model_kwargs, device, progress, step_noise, trace, noise_key):
             pass
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None, trace=None):
+                                     step_noise=None, trace=None, noise_key=None):
         """gaussian_diffusion.py:659-707."""
         yield from self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, eta, step_noise, trace)
+                              device, progress, eta, step_noise, trace, noise_key)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                         model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, trace=None):
+                         model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, trace=None,
+                         noise_key=None):
         """gaussian_diffusion.py:625-657."""
         final = None
         for final in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
                                                        cond_fn, model_kwargs, device, progress, eta,
-                                                       step_noise, trace):
+                                                       step_noise, trace, noise_key):
             pass
         return final["sample"]
 
@@ -476,23 +632,31 @@ class GaussianDiffusion:
         log_variance = self._extract(self.posterior_log_variance_clipped, t, x_t)
         return mean, variance, log_variance
 
-    def _q_sample(self, x_start, t, noise, out):
+    def _q_sample(self, x_start, t, noise, out, noise_key=None, draw=0):
         st = self._device_state(x_start.device)
+        if noise_key is not None:
+            H.check(H.load().ddpm3d_q_sample_keyed(H.ptr(x_start), noise_key.desc(draw, x_start), H.ptr(st["qcoef"]),
+                                                   H.ptr(t), x_start.shape[0], x_start[0].numel(), self.num_timesteps,
+                                                   H.ptr(out), H.stream()))
+            return out
         H.check(H.load().ddpm3d_q_sample(H.ptr(x_start), H.ptr(noise), H.ptr(st["qcoef"]), H.ptr(t), x_start.shape[0],
                                          x_start[0].numel(), self.num_timesteps, H.ptr(out), H.stream()))
         return out
 
-    def q_sample(self, x_start, t, noise=None):
-        """gaussian_diffusion.py:188-206: sqrt_acp[t] x_start + sqrt_1m_acp[t] noise, on the q_sample kernel."""
+    def q_sample(self, x_start, t, noise=None, noise_key=None, draw=0):
+        """gaussian_diffusion.py:188-206: sqrt_acp[t] x_start + sqrt_1m_acp[t] noise, on the q_sample kernel.
+        `noise_key`, `draw` (extension): the noise is that draw of the key, evaluated by the kernel."""
         H.require_device(x_start, "x_start")
+        self._check_key(noise_key, noise)
         t = self._check_t(t, x_start.shape[0])
-        if noise is None:
-            noise = th.randn_like(x_start)
-        assert noise.shape == x_start.shape
-        H.require_device(noise, "noise")
+        if noise_key is None:
+            if noise is None:
+                noise = th.randn_like(x_start)
+            assert noise.shape == x_start.shape
+            H.require_device(noise, "noise")
         t = t.to(device=x_start.device, dtype=th.int64).contiguous()
         with th.cuda.device(x_start.device):
-            return self._q_sample(x_start, t, noise, th.empty_like(x_start))
+            return self._q_sample(x_start, t, noise, th.empty_like(x_start), noise_key, draw)
 
     def _vb_terms(self, model_output, x_start, x_t, t, noise, flags, ws, vb, xstart_mse, mse, ld, pred_xstart):
         """One ddpm3d_vb_terms launch; the outputs are written through pointers (column views allowed)."""
@@ -537,14 +701,17 @@ class GaussianDiffusion:
                                               self.num_timesteps, H.ptr(ws), ws.numel(), H.ptr(out), H.stream()))
         return out
 
-    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, step_noise=None):
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, step_noise=None, noise_key=None):
         """gaussian_diffusion.py:839-894: the whole variational bound in bits per dim.  Returns total_bpd,
         prior_bpd [N] and vb, xstart_mse, mse [N, T], fp32 on the device; column k is the loop's k-th step,
         t = T - 1 - k.  `step_noise` (extension, as in the sampler loops): a sequence of T tensors, or a callable
         (k, x_start) -> tensor, used instead of randn_like in draw order.  Per step: one q_sample launch, the
         network (one plan replay on the engine path), one VLB-terms launch and its fold writing column k in
-        place; nothing inside the loop waits for the device."""
+        place; nothing inside the loop waits for the device.  `noise_key` (extension): step k's q_sample reads draw k + 1
+        of the key inside its kernel; the bound's eps-MSE column reads the same normals once more, from one buffer
+        that ddpm3d_noise_fill rewrites per step (the only noise tensor of the keyed loop)."""
         H.require_device(x_start, "x_start")
+        self._check_key(noise_key, step_noise)
         device = x_start.device
         N = x_start.shape[0]
         T = self.num_timesteps
@@ -558,9 +725,13 @@ class GaussianDiffusion:
             t_all, net = self._step_model(model, x_start.shape, model_kwargs or {}, device)
             for k, i in enumerate(range(T - 1, -1, -1)):
                 t = t_all[i]
-                noise = self._draw_noise(step_noise, k, x_start)
-                self._check_noise(noise, x_start)
-                self._q_sample(x_start, t, noise, x_t)
+                if noise_key is None:
+                    noise = self._draw_noise(step_noise, k, x_start)
+                    self._check_noise(noise, x_start)
+                    self._q_sample(x_start, t, noise, x_t)
+                else:
+                    self._q_sample(x_start, t, None, x_t, noise_key, k + 1)
+                    noise = noise_key.fill(k + 1, x_start.shape, out=noise if k else None)
                 out = net(x_t, i)
                 self._vb_terms(out, x_start, x_t, t, noise, flags, ws, vb[:, k], xstart_mse[:, k], mse[:, k], T,
                                None)
@@ -677,8 +848,9 @@ class GaussianDiffusion:
         return final["sample"]
 
     # ------------------------------------------------- DPM-Solver++ multistep
-    def _solver_step(self, model_output, x, m1, m2, z, t, flags, order, stochastic, p):
-        """One ddpm3d_dpm_solver_step launch at effective order p; t: int64 on x's device."""
+    def _solver_step(self, model_output, x, m1, m2, z, t, flags, order, stochastic, p, noise_key=None, draw=0):
+        """One ddpm3d_dpm_solver_step launch at effective order p; t: int64 on x's device.  With `noise_key` the keyed
+        entry reads the key's `draw` instead of z."""
         if z is not None:
             self._check_noise(z, x)
         self._model_step_output(model_output, x, flags)
@@ -686,6 +858,12 @@ class GaussianDiffusion:
         scoef = self._solver_state(x.device, order, stochastic)
         sample = th.empty_like(x)
         x0 = th.empty_like(x)
+        if noise_key is not None:
+            H.check(H.load().ddpm3d_dpm_solver_step_keyed(H.ptr(model_output), H.ptr(x), H.ptr(m1), H.ptr(m2),
+                                                          noise_key.desc(draw, x), H.ptr(st["coef"]), H.ptr(scoef),
+                                                          H.ptr(t), x.shape[0], x[0].numel(), self.num_timesteps,
+                                                          flags, p, H.ptr(sample), H.ptr(x0), H.stream()))
+            return {"sample": sample, "pred_xstart": x0}
         H.check(H.load().ddpm3d_dpm_solver_step(H.ptr(model_output), H.ptr(x), H.ptr(m1), H.ptr(m2), H.ptr(z),
                                                 H.ptr(st["coef"]), H.ptr(scoef), H.ptr(t), x.shape[0],
                                                 x[0].numel(), self.num_timesteps, flags, p, H.ptr(sample),
@@ -694,7 +872,7 @@ class GaussianDiffusion:
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                            cond_fn=None, model_kwargs=None, device=None, progress=False, order=2,
-                                           stochastic=False, step_noise=None, trace=None):
+                                           stochastic=False, step_noise=None, trace=None, noise_key=None):
         """DPM-Solver++ multistep sampling (extension; Lu et al. 2022, arXiv:2211.01095), yielding
         {"sample", "pred_xstart"} per step as ddim_sample_loop_progressive does.  Step k leaves index
         s = T - 1 - k at order min(order, k + 1); the last step returns its pred_xstart.  The weights are
@@ -705,8 +883,10 @@ class GaussianDiffusion:
         form draws nothing after the initial noise.  Step spacing is the diffusion's: "logsnrN" suits the solver.
         The engine path, with model_kwargs == {"low_res"} on a 5-D shape, evaluates the film rows for the whole
         schedule once, then runs one plan replay and one solver launch per step; nothing inside the loop waits
-        for the device.  Bad arguments are refused before the model runs."""
+        for the device.  Bad arguments are refused before the model runs.  `noise_key`: as in the other loops (x_T is draw
+        0; the stochastic form reads draw k + 1 at step k, the ODE form nothing more)."""
         self._check_solver(order, stochastic)
+        self._check_key(noise_key, step_noise)
         self._reject_hooks(denoised_fn, cond_fn)
         if device is None:
             device = next(model.parameters()).device
@@ -716,24 +896,24 @@ class GaussianDiffusion:
         assert isinstance(shape, (tuple, list))
         flags = self._flags(clip_denoised)
         return self._solver_loop(model, shape, noise, flags, model_kwargs or {}, device, progress, order,
-                                 stochastic, step_noise, trace)
+                                 stochastic, step_noise, trace, noise_key)
 
     def _solver_loop(self, model, shape, noise, flags, model_kwargs, device, progress, order, stochastic,
-                     step_noise, trace=None):
+                     step_noise, trace=None, noise_key=None):
         indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
         # as in _loop: grad mode and the current device change around each step's compute only
         with th.no_grad(), th.cuda.device(device):
-            img = noise if noise is not None else th.randn(*shape, device=device)
-            H.require_device(img, "noise")
+            img = self._start_noise(noise, shape, device, noise_key)
             t_all, net = self._step_model(model, shape, model_kwargs, device)
+        key = noise_key if stochastic else None
         hist = []                       # pred_xstart of the last one or two steps, newest first
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
                 out = net(img, i)
-                z = self._draw_noise(step_noise, k, img) if stochastic else None
+                z = self._draw_noise(step_noise, k, img) if stochastic and key is None else None
                 p = 1 if i == 0 else min(order, k + 1)
                 res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z,
-                                        t_all[i], flags, order, stochastic, p)
+                                        t_all[i], flags, order, stochastic, p, key, k + 1)
                 if trace is not None:       # prev is the newest entry of the solver's own history
                     self._trace_step(trace, res, hist[0] if hist else None, i)
             yield res
@@ -742,11 +922,11 @@ class GaussianDiffusion:
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, order=2, stochastic=False,
-                               step_noise=None, trace=None):
+                               step_noise=None, trace=None, noise_key=None):
         """DPM-Solver++ multistep sampling (extension): the last sample of dpm_solver_sample_loop_progressive."""
         final = None
         for final in self.dpm_solver_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
                                                              cond_fn, model_kwargs, device, progress, order,
-                                                             stochastic, step_noise, trace):
+                                                             stochastic, step_noise, trace, noise_key):
             pass
         return final["sample"]

@@ -29,6 +29,7 @@ import torch as th
 
 from . import _hip as H
 from . import dist_util
+from . import gaussian_diffusion as gd
 from . import logger
 from . import patches
 
@@ -151,7 +152,8 @@ def _canvas_of(volume, geom, device):
 
 
 def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm", num_draws=1, batch_size=1,
-                            noise=None, step_noise=None, clip_denoised=True, eta=0.0, device=None, trace=None):
+                            noise=None, step_noise=None, clip_denoised=True, eta=0.0, device=None, trace=None,
+                            noise_key=None):
     """Joint DDPM ("ddpm") or DDIM ("ddim", any eta) sampling of one volume; yields, per reverse step,
     {"sample", "pred_xstart"}: (K, Dc, H, W) canvases on the device, K = num_draws.
 
@@ -162,6 +164,10 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                     order or a callable (k, like) as in the independent loops.  Without them, draw d takes all its
                     noise from dist_util.volume_generator(0, draw=d), one whole canvas at a time, so the result
                     depends on neither the batch size nor the world size.
+    noise_key       a gaussian_diffusion.NoiseKey of K streams, one per draw's canvas (draw_key(seed, K) names them
+                    dist_util.noise_stream(0, d)): x_T is its draw 0 (unless `noise` is given) and step k reads draw
+                    k + 1 inside the step kernel, indexed by the canvas voxel, so every patch that covers a voxel reads
+                    the same normal there.  No noise canvas is drawn, held or gathered.  Not with `step_noise`.
     trace           a metrics.StepTrace: every step's blended pred_xstart canvases are its estimates, so its target
                     and weight are (Dc, H, W) or (K, Dc, H, W) canvases (weight 0 outside the volume)
     With several ranks, batch b runs on rank b mod W; the ranks exchange their updated patches once per round and
@@ -172,6 +178,9 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
     K, bs = int(num_draws), max(1, int(batch_size))
     if not 1 <= K <= H.MAX_DRAWS:
         raise ValueError("num_draws must be in 1..%d, got %d" % (H.MAX_DRAWS, K))
+    diffusion._check_key(noise_key, step_noise)
+    if noise_key is not None and (noise_key.n != K or noise_key.origin is not None):
+        raise ValueError("noise_key must hold one stream per draw (%d) and no geometry of its own" % K)
     if device is None:
         params = getattr(model, "parameters", None)
         device = next(params()).device if params is not None else dist_util.dev()
@@ -187,17 +196,25 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
         return b * bs * K, min((b + 1) * bs, P) * K
 
     with th.no_grad(), th.cuda.device(device):
-        gens = [dist_util.volume_generator(0, seed=10, device=device, draw=d) for d in range(K)]
+        if noise_key is None:
+            gens = [dist_util.volume_generator(0, seed=10, device=device, draw=d) for d in range(K)]
 
-        def draw():
-            return th.stack([th.randn(cshape[1:], device=device, generator=g) for g in gens])
+            def draw():
+                return th.stack([th.randn(cshape[1:], device=device, generator=g) for g in gens])
 
-        img = noise if noise is not None else draw()
+            patch_key = None
+        else:
+            # row p * K + d of the patch buffers: stream of draw d, origin (z, h, w) of patch p -- one small table
+            origin = np.repeat(np.asarray([(zs, xs, ys) for xs, ys, zs in geom.grid], dtype=np.int32), K, axis=0)
+            patch_key = gd.NoiseKey(noise_key.seed, noise_key.streams.repeat(P),
+                                    origin=th.from_numpy(origin).to(device), patch=(r, r, r), canvas=geom.canvas)
+
+        img = noise if noise is not None else (draw() if noise_key is None else noise_key.fill(0, cshape))
         H.require_device(img, "noise")
         if tuple(img.shape) != cshape:
             raise ValueError("noise of shape %s, expected %s" % (tuple(img.shape), cshape))
         xg = th.empty((bs * K, 1, r, r, r), dtype=th.float32, device=device)
-        zg = th.empty_like(xg)
+        zg = th.empty_like(xg) if noise_key is None else None
         sliding = geom.min_overlap is not None
         if sliding:
             # any number of patches: the conditioning patches are cut per batch, not held for the whole volume
@@ -232,18 +249,24 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
 
     for k, i in enumerate(range(diffusion.num_timesteps - 1, -1, -1)):
         with th.no_grad(), th.cuda.device(device):
-            z = draw() if step_noise is None else diffusion._draw_noise(step_noise, k, img)
-            diffusion._check_noise(z, img)
+            if noise_key is None:
+                z = draw() if step_noise is None else diffusion._draw_noise(step_noise, k, img)
+                diffusion._check_noise(z, img)
             for b in rounds:
                 if b is not None:
                     lo, hi = rows(b)
                     t_all, net = nets[hi - lo]
-                    x, zb = xg[:hi - lo], zg[:hi - lo]
+                    x = xg[:hi - lo]
                     gather(img, geom, lo // K, (hi - lo) // K, out=x)
-                    gather(z, geom, lo // K, (hi - lo) // K, out=zb)
                     dst = updated[:, lo:hi] if world == 1 else block[:, :hi - lo]
-                    diffusion._update(kind, net(x, i, cond(lo, hi)), x, t_all[i], zb, clip_denoised, eta,
-                                      out=(dst[0], dst[1]))
+                    if noise_key is None:
+                        zb = zg[:hi - lo]
+                        gather(z, geom, lo // K, (hi - lo) // K, out=zb)
+                        diffusion._update(kind, net(x, i, cond(lo, hi)), x, t_all[i], zb, clip_denoised, eta,
+                                          out=(dst[0], dst[1]))
+                    else:
+                        diffusion._update(kind, net(x, i, cond(lo, hi)), x, t_all[i], None, clip_denoised, eta,
+                                          out=(dst[0], dst[1]), noise_key=patch_key.rows(lo, hi), draw=k + 1)
                 if world > 1:
                     for bb, blk in dist_util.gather_round(block, b):
                         lo, hi = rows(bb)
@@ -253,6 +276,11 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                 prev = diffusion._trace_step(trace, out, prev, i)
         yield out
         img = out["sample"]
+
+
+def draw_key(seed, num_draws=1, device=None):
+    """The NoiseKey of a joint loop of `num_draws` draws: draw d's canvas is stream dist_util.noise_stream(0, d)."""
+    return gd.NoiseKey(seed, [dist_util.noise_stream(0, d) for d in range(int(num_draws))], device=device)
 
 
 def sample_loop(diffusion, model, low_res_volume, geom, **kwargs):

@@ -37,7 +37,12 @@ script (one draw, seed 10) cannot produce; `--joint_patches True` samples the
 patches jointly (guided_diffusion/joint.py): one state and one noise draw per
 voxel of the whole volume, blended after every reverse step, so that overlaps
 are not an average of independent draws (which lowers `std` there in the
-pattern of the patch grid).  DDPM and DDIM only.  Unlike the one-shot blend,
+pattern of the patch grid).  DDPM and DDIM only.  `--device_noise True` (any
+path, any sampler; `--noise_seed N`, default 10) takes all sampler noise from a
+counter-based key evaluated inside the step kernels (no
+generators, no noise tensors; stream = patch index + (draw << 32)); it is not
+torch's stream, so the result is another draw than the default path's, which
+stays byte for byte what it was.  Unlike the one-shot blend,
 whose Hann weights are 0 on the outermost planes of the volume (those voxels
 are written as 0), the joint path writes real values there;
 `--target_samples full_dose.npz` (a volume of the input's shape) scores the
@@ -106,6 +111,7 @@ import numpy as np
 import torch as th
 
 from guided_diffusion import _hip, dist_util, joint, logger, metrics, patches, synth, uncertainty
+from guided_diffusion.gaussian_diffusion import NoiseKey
 from guided_diffusion.script_util import (
     add_dict_to_argparser,
     args_to_dict,
@@ -132,6 +138,10 @@ def create_argparser():
                     # minimum overlap of neighbouring patches of the gap-free sliding grid (not in the reference);
                     # -1 = the reference's fixed 3 x 3 x (1 | 2) grid
                     patch_overlap=-1,
+                    # sampler noise from a counter-based key, evaluated inside the step kernels (not in the reference;
+                    # DESIGN.md 3.16): no generators, no noise tensors, one stream per (patch, draw).  noise_seed is
+                    # read only with device_noise; the default path's seed stays the literal 10
+                    device_noise=False, noise_seed=10,
                     # full-dose volume to score the result against (not in the reference); "" = no metrics
                     target_samples="", data_range=0.0, metrics_mask_threshold=0.0,
                     # scales of the multi-scale SSIM added to every metric row (not in the reference); 0 = none
@@ -172,6 +182,11 @@ def main(argv=None):
     if args.patch_overlap != -1 and not 2 <= args.patch_overlap <= args.large_size - 1:
         parser.error("--patch_overlap must be in 2..%d for patches of %d (got %d); -1 keeps the fixed 3 x 3 x (1 | 2) "
                      "grid" % (args.large_size - 1, args.large_size, args.patch_overlap))
+    if not args.device_noise and args.noise_seed != 10:
+        parser.error("--noise_seed needs --device_noise True (the default path draws from torch generators seeded "
+                     "with the literal 10, and its outputs stay as they are)")
+    if not 0 <= args.noise_seed < 2 ** 64:
+        parser.error("--noise_seed must be in 0 .. 2^64 - 1 (got %d)" % args.noise_seed)
     _check_segmentation(parser, args)
     args.peak = _check_spacing(parser, args)
     args.baselines = _check_baselines(parser, args)
@@ -195,6 +210,9 @@ def main(argv=None):
         model.convert_to_fp16()
     model.step_graph, model.native_plan = args.step_graph, args.native_plan
     model.eval()
+    if args.device_noise:
+        logger.log("sampler noise: Philox4x32-10 keyed by (seed %d, patch and draw, step, voxel), evaluated in the "
+                   "step kernels (not torch's stream)" % args.noise_seed)
 
     logger.log("loading data...")
     if vol is None:
@@ -237,17 +255,12 @@ def main(argv=None):
             shape = tuple(cond.shape)
             # all randomness keyed by the GLOBAL patch index (one generator per patch): the result
             # depends neither on the world size nor on the batch size
-            gens = [dist_util.volume_generator(i, seed=10, device=dev) for i in idx]
-
-            def draw(_k=None, _img=None):
-                return th.cat([th.randn(1, *shape[1:], device=dev, generator=g) for g in gens])
-
-            noise = draw()
+            noise, noise_args = _batch_noise(args, dev, idx, 1, shape)
             logger.log(f"rank {rank}: patches {idx} shape={shape}")
             if tracer is not None:
                 extra["trace"] = tracer.begin(idx)
             sample = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
-                                 model_kwargs={"low_res": cond}, step_noise=draw, **extra)
+                                 model_kwargs={"low_res": cond}, **noise_args, **extra)
             block[:len(idx)] = sample.permute(0, 1, 3, 4, 2)                # (B,1,Z,H,W) -> (B,1,H,W,Z)
         for bb, blk in dist_util.gather_round(block, b):
             for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
@@ -771,6 +784,22 @@ def _sampler(args, diffusion):
     return diffusion.p_sample_loop, {}
 
 
+def _batch_noise(args, dev, idx, K, shape):
+    """(x_T, the loop's noise arguments) of one batch: patches idx x K draws, patch-major.  All randomness is keyed by
+    the GLOBAL patch index and the draw, so the result depends on neither the world size nor the batch size: one torch
+    generator per (patch, draw), or, with --device_noise True, one stream of a NoiseKey each (x_T is then the key's
+    draw 0, made by the loop)."""
+    if args.device_noise:
+        key = NoiseKey(args.noise_seed, [dist_util.noise_stream(i, d) for i in idx for d in range(K)], device=dev)
+        return None, {"noise_key": key}
+    gens = [dist_util.volume_generator(i, seed=10, device=dev, draw=d) for i in idx for d in range(K)]
+
+    def draw(_k=None, _img=None):
+        return th.cat([th.randn(1, *shape[1:], device=dev, generator=g) for g in gens])
+
+    return draw(), {"step_noise": draw}
+
+
 def _base_name(path):
     base = os.path.basename(path)
     for ext in (".tiff", ".tif", ".npz", ".npy"):
@@ -795,17 +824,12 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             idx = list(range(b * bs, min((b + 1) * bs, len(grid))))
             cond = th.from_numpy(low_res[idx]).to(dev).repeat_interleave(K, dim=0)
             shape = tuple(cond.shape)
-            gens = [dist_util.volume_generator(i, seed=10, device=dev, draw=d) for i in idx for d in range(K)]
-
-            def draw(_k=None, _img=None):
-                return th.cat([th.randn(1, *shape[1:], device=dev, generator=g) for g in gens])
-
-            noise = draw()
+            noise, noise_args = _batch_noise(args, dev, idx, K, shape)
             logger.log(f"rank {rank}: patches {idx} x {K} draws shape={shape}")
             if tracer is not None:
                 extra["trace"] = tracer.begin(idx)
             block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
-                                               model_kwargs={"low_res": cond}, step_noise=draw, **extra)
+                                               model_kwargs={"low_res": cond}, **noise_args, **extra)
         for bb, blk in dist_util.gather_round(block, b):
             if stitcher is None:
                 continue
@@ -868,17 +892,12 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
             if K > 1:
                 cond = cond.repeat_interleave(K, dim=0)
             shape = tuple(cond.shape)
-            gens = [dist_util.volume_generator(i, seed=10, device=dev, draw=d) for i in idx for d in range(K)]
-
-            def draw(_k=None, _img=None):
-                return th.cat([th.randn(1, *shape[1:], device=dev, generator=g) for g in gens])
-
-            noise = draw()
+            noise, noise_args = _batch_noise(args, dev, idx, K, shape)
             logger.log(f"rank {rank}: patches {idx[0]}..{idx[-1]} x {K} draws shape={shape}")
             if tracer is not None:
                 extra["trace"] = tracer.begin(idx)
             block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
-                                               model_kwargs={"low_res": cond}, step_noise=draw, **extra)
+                                               model_kwargs={"low_res": cond}, **noise_args, **extra)
         for bb, blk in dist_util.gather_round(block, b):
             if stitcher is None:
                 continue
@@ -932,6 +951,8 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
     more = {}
     if args.trace:
         more["trace"] = trace = _canvas_trace(args, vol, target, geom)
+    if args.device_noise:
+        more["noise_key"] = joint.draw_key(args.noise_seed, K, dist_util.dev())
     sample = joint.sample_loop(diffusion, model, vol, geom, kind="ddim" if args.use_ddim else "ddpm", num_draws=K,
                                batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
                                device=dist_util.dev(), **more)

@@ -1003,6 +1003,57 @@ enum {
 double ddpm3d_mfma_probe_flops_per_iter(int kind);
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream);
 
+
+/*
+ * Sampler noise from a counter-based key (added within ABI 13: new entries only).  The normal a
+ * step consumes is a pure function of (seed, stream, draw, index), evaluated inside the kernel that consumes it:
+ * no noise tensor, the same value whatever the batch size, the number of ranks or the launch geometry.  It is
+ * NOT torch's stream: a keyed and an un-keyed run are two different draws of the same distribution.
+ *
+ * Generator: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ * 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter = (index >> 2, draw, stream & 0xffffffff,
+ * stream >> 32).  Its words (w0, w1) give the normals of index & 3 == 0 and 1, (w2, w3) those of 2 and 3, by
+ * Box-Muller in fp32: u1 = fmaf((float)w_a, 2^-32, 2^-33) in (0, 1], u2 = (float)w_b * 2^-32,
+ * r = sqrtf(-2 logf(u1)); the even lane is r cospi(2 u2), the odd lane r sinpi(2 u2).  |z| <= 6.77.
+ *
+ * index: without an origin the voxel's offset within its sample, 0 .. voxels - 1.  With one (joint sampling), sample
+ * n is the patch of extents patch[] = (pd, ph, pw) at origin[n] = (z0, y0, x0) on a canvas of extents canvas[] =
+ * (Dc, Hc, Wc), voxels = pd * ph * pw, and patch voxel (z, y, x) has index ((z0 + z) * Hc + y0 + y) * Wc + x0 + x:
+ * every patch that covers a canvas voxel reads the same normal.  A sample whose patch does not lie on the canvas
+ * gets NaN in every per-voxel output (the origins are device memory: this is the kernel's check).
+ *
+ * Every entry below returns DDPM3D_EINVAL before any launch for a NULL key or key->stream, N or voxels below 1 (or N
+ * above 65535), draw outside 0 .. 2^32 - 1, and, with an origin, a patch or canvas extent below 1, a patch product
+ * that is not voxels, or a canvas of more than 2^34 voxels.  Nothing allocates or synchronises.
+ */
+typedef struct ddpm3d_noise_key {
+    uint64_t seed;
+    const int64_t* stream;      /* device, [N]: one stream id per sample of the batch                */
+    int64_t draw;               /* which draw of the stream: loops use 0 for x_T, k + 1 for step k   */
+    const int32_t* origin;      /* device, [N][3] (z0, y0, x0), or NULL: index = offset in sample    */
+    int32_t patch[3], canvas[3];/* read only when origin != NULL                                     */
+} ddpm3d_noise_key;
+/* out[n][v] = the normal a keyed step reads for sample n, voxel v: (N, voxels) fp32.  The x_T of a keyed loop. */
+int ddpm3d_noise_fill(const ddpm3d_noise_key* key, int N, int voxels, float* out, void* stream);
+/* Calibration: out[n][q][0..3] = the four Philox words of counter q = 0 .. quads - 1 of sample n's stream
+ * ((N, quads, 4) uint32).  Reads seed, stream and draw only. */
+int ddpm3d_noise_bits(const ddpm3d_noise_key* key, int N, int quads, uint32_t* out, void* stream);
+/* The step entries above with their noise tensor replaced by a key; everything else, bit for bit, as the un-keyed
+ * entry fed with what ddpm3d_noise_fill writes for the same key.  A NULL key is refused, except by the solver step,
+ * where it selects the ODE form (no noise), as a NULL noise does above. */
+int ddpm3d_p_sample_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key,
+                               const float* coef, const int64_t* t_idx, int N, int voxels,
+                               int flags, float* sample, float* pred_xstart, void* stream);
+int ddpm3d_ddim_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key,
+                           const float* coef, const int64_t* t_idx, int N, int voxels,
+                           int flags, float eta, float* sample, float* pred_xstart, void* stream);
+int ddpm3d_dpm_solver_step_keyed(const float* model_out, const float* x, const float* x0_prev1,
+                                 const float* x0_prev2, const ddpm3d_noise_key* key, const float* coef,
+                                 const float* scoef, const int64_t* t_idx, int N, int voxels, int T,
+                                 int flags, int order, float* sample, float* pred_xstart, void* stream);
+int ddpm3d_q_sample_keyed(const float* x_start, const ddpm3d_noise_key* key, const float* qcoef,
+                          const int64_t* t_idx, int N, int voxels, int T, float* x_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
