@@ -1164,6 +1164,79 @@ int ddpm3d_nlm(const float* vol, int D, int H, int W, int s0, int s1, int s2, in
     return launched(ddpm3d_launch_nlm(vol, D, H, W, search, patch, (float)k1, (float)k2, out, (hipStream_t)stream), "nlm");
 }
 
+// ------------------------------------------------- volume regridding (added within ABI 13)
+static const int64_t REGRID_MAX_VOXELS = 0x7fffffff;
+// every stage of the chain, per volume: the input, the two intermediates and the output
+static bool regrid_shape_ok(int D, int H, int W, int Do, int Ho, int Wo, int64_t stage[3]) {
+    if (D < 1 || H < 1 || W < 1 || Do < 1 || Ho < 1 || Wo < 1) return false;
+    if ((int64_t)D * H > REGRID_MAX_VOXELS || (int64_t)D * H * W > REGRID_MAX_VOXELS) return false;
+    if ((int64_t)Do * Ho > REGRID_MAX_VOXELS || (int64_t)Ho * Wo > REGRID_MAX_VOXELS) return false;
+    if ((int64_t)D * Ho > REGRID_MAX_VOXELS) return false;
+    ddpm3d_regrid_stages(D, H, W, Do, Ho, Wo, stage);
+    return stage[0] <= REGRID_MAX_VOXELS && stage[1] <= REGRID_MAX_VOXELS && stage[2] <= REGRID_MAX_VOXELS;
+}
+static bool regrid_ratio_ok(int in_len, int out_len) {
+    return (int64_t)in_len <= 4 * (int64_t)out_len && (int64_t)out_len <= 4 * (int64_t)in_len;
+}
+static size_t regrid_ws_bytes(int B, const int64_t stage[3]) {
+    const size_t a = ((size_t)B * stage[0] * sizeof(float) + 15) & ~(size_t)15;
+    const size_t b = ((size_t)B * stage[1] * sizeof(float) + 15) & ~(size_t)15;
+    return a + b;
+}
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+size_t ddpm3d_regrid_workspace_bytes(int B, int D, int H, int W, int Do, int Ho, int Wo) {
+    int64_t stage[3];
+    if (B < 1 || B > DDPM3D_MAX_DRAWS || !regrid_shape_ok(D, H, W, Do, Ho, Wo, stage)) return 0;
+    if (!regrid_ratio_ok(D, Do) || !regrid_ratio_ok(H, Ho) || !regrid_ratio_ok(W, Wo)) return 0;
+    return regrid_ws_bytes(B, stage);
+}
+
+int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_regrid_axis axes[3], float* out, void* ws,
+                  size_t ws_bytes, void* stream) {
+    if (!vol || !out || !axes) return fail(DDPM3D_EINVAL, "regrid: null pointer (vol, out or axes)");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS) return fail(DDPM3D_EINVAL, "regrid: B=%d volumes (1..%d)", B, DDPM3D_MAX_DRAWS);
+    const int in_len[3] = {D, H, W};
+    static const char* const name[3] = {"D", "H", "W"};
+    for (int a = 0; a < 3; ++a) {
+        const ddpm3d_regrid_axis& x = axes[a];
+        if (x.taps < 0 || x.taps > DDPM3D_REGRID_MAX_TAPS)
+            return fail(DDPM3D_EINVAL, "regrid: axes[%d] (%s): taps=%d (0..%d)", a, name[a], x.taps,
+                        DDPM3D_REGRID_MAX_TAPS);
+        if (x.in_len < 1 || x.out_len < 1)
+            return fail(DDPM3D_EINVAL, "regrid: axes[%d] (%s): in_len=%d out_len=%d (1 or more each)", a, name[a],
+                        x.in_len, x.out_len);
+        if (x.in_len != in_len[a])
+            return fail(DDPM3D_EINVAL, "regrid: axes[%d] (%s): in_len=%d, the volume has %s=%d", a, name[a], x.in_len,
+                        name[a], in_len[a]);
+        if (x.taps == 0 && x.in_len != x.out_len)
+            return fail(DDPM3D_EINVAL, "regrid: axes[%d] (%s): taps=0 is the identity, but in_len=%d and out_len=%d "
+                                       "differ", a, name[a], x.in_len, x.out_len);
+        if (!regrid_ratio_ok(x.in_len, x.out_len))
+            return fail(DDPM3D_EINVAL, "regrid: axes[%d] (%s): ratio in_len / out_len = %d / %d outside [1/4, 4]", a,
+                        name[a], x.in_len, x.out_len);
+        if (x.taps > 0 && (!x.first || !x.count || !x.weights))
+            return fail(DDPM3D_EINVAL, "regrid: axes[%d] (%s): null pointer (first, count or weights)", a, name[a]);
+    }
+    const int Do = axes[0].out_len, Ho = axes[1].out_len, Wo = axes[2].out_len;
+    int64_t stage[3];
+    if (!regrid_shape_ok(D, H, W, Do, Ho, Wo, stage))
+        return fail(DDPM3D_EINVAL, "regrid: bad shape (D=%d H=%d W=%d -> %d %d %d; 1 or more each and at most 2^31 - 1 "
+                                   "voxels per volume before and after every pass)", D, H, W, Do, Ho, Wo);
+    const int rc = metric_ws_ok("regrid", regrid_ws_bytes(B, stage), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    const size_t vol_bytes = (size_t)B * D * H * W * sizeof(float), out_bytes = (size_t)B * stage[2] * sizeof(float);
+    if (ranges_overlap(vol, vol_bytes, out, out_bytes))
+        return fail(DDPM3D_EINVAL, "regrid: out overlaps vol (every voxel is read by its neighbours)");
+    if (ranges_overlap(ws, regrid_ws_bytes(B, stage), vol, vol_bytes) ||
+        ranges_overlap(ws, regrid_ws_bytes(B, stage), out, out_bytes))
+        return fail(DDPM3D_EINVAL, "regrid: the workspace overlaps vol or out");
+    return launched(ddpm3d_launch_regrid(vol, B, D, H, W, axes, out, (float*)ws, (hipStream_t)stream), "regrid");
+}
+
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }
 
 int ddpm3d_mfma_probe(int kind, int iters, int blocks, float* out, uint64_t* clocks, void* stream) {

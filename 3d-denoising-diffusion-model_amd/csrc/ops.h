@@ -118,6 +118,13 @@ hipError_t ddpm3d_launch_nlm(const float* vol, int D, int H, int W, const int* s
                              float k2, float* out, hipStream_t st);
 // the tile (TD, TH; TW = 64) and the LDS bytes that launch uses for halos (R0, R1, R2), R_a = s_a + p_a
 void ddpm3d_nlm_tile(int R0, int R1, int R2, int* TD, int* TH, size_t* lds_bytes);
+// regrid.hip: B volumes of one shape onto another grid, passes along W, H, D with the tables of axes[] (D, H, W order)
+// in device memory (the caller has checked the shapes, the taps, the ratios and the workspace); stage[] gets the voxels
+// per volume after the W, the H and the D pass, of which the first two, times B, are the workspace's two buffers
+struct ddpm3d_regrid_axis;
+void ddpm3d_regrid_stages(int D, int H, int W, int Do, int Ho, int Wo, int64_t stage[3]);
+hipError_t ddpm3d_launch_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_regrid_axis* axes,
+                                float* out, float* ws, hipStream_t st);
 // joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
 // patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
 struct ddpm3d_joint_starts;

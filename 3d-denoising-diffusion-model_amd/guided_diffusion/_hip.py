@@ -143,6 +143,16 @@ class NoiseKeyDesc(C.Structure):
                 ("patch", C.c_int32 * 3), ("canvas", C.c_int32 * 3)]
 
 
+REGRID_MAX_TAPS = 18    # DDPM3D_REGRID_MAX_TAPS: the most taps per output coordinate of a ddpm3d_regrid axis
+
+
+class RegridAxis(C.Structure):
+    """struct ddpm3d_regrid_axis: extents, tap capacity (0 = identity) and the device tables first [out_len], count
+    [out_len] and weights [taps][out_len]"""
+    _fields_ = [("in_len", C.c_int), ("out_len", C.c_int), ("taps", C.c_int), ("first", C.c_void_p),
+                ("count", C.c_void_p), ("weights", C.c_void_p)]
+
+
 LAYER_RES, LAYER_ATTN, LAYER_DOWNCONV, LAYER_UPCONV = 1, 2, 3, 4
 UPDOWN = {None: 0, "down": 1, "up": 2}
 
@@ -229,6 +239,8 @@ EXPORTS = {
     "ddpm3d_gauss_smooth_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ddpm3d_gauss_smooth": (C.c_int, [_fp] + [C.c_int] * 6 + [C.POINTER(C.c_float)] * 3 + [_fp, _fp, C.c_size_t, _fp]),
     "ddpm3d_nlm": (C.c_int, [_fp] + [C.c_int] * 9 + [C.c_float, C.c_float, _fp, _fp]),
+    "ddpm3d_regrid_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "ddpm3d_regrid": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(RegridAxis), _fp, _fp, C.c_size_t, _fp]),
     "ddpm3d_noise_fill": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_noise_bits": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_p_sample_step_keyed": (C.c_int, [_fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,

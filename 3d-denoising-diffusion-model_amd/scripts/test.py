@@ -97,7 +97,22 @@ voxels and RMS change against the step before and, with `--target_samples`,
 PSNR, NRMSE, MAE and bias against the target over the voxels the metrics file
 counts.  On the independent paths the patches are scored before blending, each
 voxel of a patch weighted with the patch's share of the Hann blend
-("pooling": "patch"); `--joint_patches` scores the blended canvas ("canvas").
+("pooling": "patch"); `--joint_patches` scores the blended canvas ("canvas");
+`--model_spacing M0 M1 M2` (mm per voxel of the grid the model was trained at,
+along the input file's (D, H, W); needs `--voxel_spacing`, which then needs
+neither a target nor regions) regrids the volume on the GPU to
+regrid.grid_shape(shape, voxel_spacing, model_spacing) before sampling
+(guided_diffusion/regrid.py, DESIGN.md 3.17: separable, anti-aliased when
+shrinking; `--regrid_mode linear|cubic`, default linear; cubic can undershoot
+below 0 and the output is not clamped), runs the chosen path on that volume
+(any of the four, any sampler) and regrids the stitched result back before it
+is written: `arr_0`, `std` and the .tif have the file's shape.  With
+`--num_draws` the K stitched draws go back as one stack and mean and std are
+taken on the file's grid.  The target, the labels, the baselines and the
+"input" row of the metrics file stay on the file's grid; the voxels the
+one-shot blend leaves at 0 become regrid.keep_after's mask; metrics_<name>.json
+gains "regrid".  Equal spacings give the run without the flags.  Not with
+`--trace True`.
 """
 
 import argparse
@@ -110,7 +125,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch as th
 
-from guided_diffusion import _hip, dist_util, joint, logger, metrics, patches, synth, uncertainty
+from guided_diffusion import _hip, dist_util, joint, logger, metrics, patches, regrid, synth, uncertainty
 from guided_diffusion.gaussian_diffusion import NoiseKey
 from guided_diffusion.script_util import (
     add_dict_to_argparser,
@@ -168,6 +183,10 @@ def create_argparser():
     parser.add_argument("--baseline_nlm_search", type=int, default=3, metavar="N")
     parser.add_argument("--baseline_nlm_patch", type=int, default=1, metavar="N")
     parser.add_argument("--baseline_nlm_sigma", type=float, default=0.0, metavar="S")
+    # mm per voxel of the grid the model was trained at, along the input file's (D, H, W): the volume is regridded to it
+    # before sampling and the result back to the file's grid (needs --voxel_spacing); linear or cubic taps
+    parser.add_argument("--model_spacing", type=float, nargs="+", default=None, metavar="MM")
+    parser.add_argument("--regrid_mode", type=str, default="linear")
     return parser
 
 
@@ -188,9 +207,11 @@ def main(argv=None):
     if not 0 <= args.noise_seed < 2 ** 64:
         parser.error("--noise_seed must be in 0 .. 2^64 - 1 (got %d)" % args.noise_seed)
     _check_segmentation(parser, args)
+    _check_regrid(parser, args)
     args.peak = _check_spacing(parser, args)
     args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
+    vol = _plan_regrid(parser, args, vol)
     roi = _load_roi(parser, args, vol)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
@@ -217,6 +238,9 @@ def main(argv=None):
     logger.log("loading data...")
     if vol is None:
         vol = patches.load_volume(args.base_samples)             # (D, H, W)
+    native = vol
+    if args.regrid is not None:
+        vol = _regrid_forward(args, vol)                         # from here on vol is on the model's grid
     res = args.large_size
     if _segmenting(args):
         roi = _segment_target(parser, args, vol, target)
@@ -274,7 +298,8 @@ def main(argv=None):
     logger.log("Reconstructing full image with Hann window blending...")
     ordered = [done[i] for i in range(len(grid))]
     result, weight = patches.stitch_patches(ordered, grid, vol.shape, res)  # (H, W, Z)
-    orig_std, den_std = float(vol.std()), float(result.std())
+    result, weight = _regrid_back(args, result), _regrid_keep(args, weight)
+    orig_std, den_std = float(native.std()), float(result.std())
     logger.log(f"  Original std: {orig_std:.4f}  Denoised std: {den_std:.4f}")
 
     out_path = None
@@ -287,7 +312,7 @@ def main(argv=None):
             tiff_path = out_path.replace(".npz", ".tif")
             tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))   # (H,W,Z) -> (Z,H,W), no scaling
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        mpath = _write_metrics(args, out_path, target, vol, result, weight=weight, roi=roi)
+        mpath = _write_metrics(args, out_path, target, native, result, weight=weight, roi=roi)
         if tracer is not None:
             tracer.write(out_path, mpath)
     dist_util.barrier()
@@ -389,10 +414,12 @@ def _check_spacing(parser, args):
     if not all(np.isfinite(v) and v > 0 for v in args.voxel_spacing):
         parser.error("--voxel_spacing must be three positive finite numbers (got %s)" % (args.voxel_spacing,))
     if not args.target_samples:
+        if args.model_spacing is not None:
+            return None                        # the spacing serves the regridding alone
         parser.error("--voxel_spacing needs --target_samples: its figures are taken per region against the target")
     if not (args.roi_labels or _segmenting(args)):
-        if args.baseline_gaussian_fwhm is not None:
-            return None                        # the spacing serves the Gaussian baseline alone
+        if args.baseline_gaussian_fwhm is not None or args.model_spacing is not None:
+            return None                        # the spacing serves the Gaussian baseline or the regridding alone
         parser.error("--voxel_spacing needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
     s0, s1, s2 = args.voxel_spacing
     try:
@@ -400,6 +427,93 @@ def _check_spacing(parser, args):
     except ValueError as e:
         parser.error("--voxel_spacing: %s" % e)
     return {"spacing": (s1, s2, s0), "footprint": footprint}
+
+
+def _check_regrid(parser, args):
+    """--model_spacing / --regrid_mode, checked before any file is read (and before --voxel_spacing, whose own checks
+    follow); args.regrid is None until _plan_regrid has the volume's shape"""
+    args.regrid = None
+    if args.regrid_mode not in regrid.MODES:
+        parser.error("--regrid_mode must be linear or cubic (got %r)" % args.regrid_mode)
+    if args.model_spacing is None:
+        return
+    if len(args.model_spacing) != 3:
+        parser.error("--model_spacing takes three numbers, mm per voxel along (D, H, W) (got %d)"
+                     % len(args.model_spacing))
+    if not all(np.isfinite(v) and v > 0 for v in args.model_spacing):
+        parser.error("--model_spacing must be three positive finite numbers (got %s)" % (args.model_spacing,))
+    if args.voxel_spacing is None:
+        parser.error("--model_spacing needs --voxel_spacing: the file's own spacing, mm per voxel along (D, H, W)")
+    if args.trace:
+        parser.error("--trace True cannot be combined with --model_spacing: the trace scores the sampled grid, the "
+                     "target lives on the file's")
+
+
+def _plan_regrid(parser, args, vol):
+    """--model_spacing: the regridding plan from the volume's shape, on the host and before the model is built; the
+    volume is read now if --target_samples has not done so.  -> the (D, H, W) volume (None without the flag and
+    without a target, as before).  args.regrid = {"plan", "native": the volume on the file's grid}."""
+    if args.model_spacing is None:
+        return vol
+    if vol is None:
+        if not os.path.isfile(args.base_samples):
+            parser.error("--base_samples: no such file: %r" % args.base_samples)
+        vol = patches.load_volume(args.base_samples)
+    try:
+        shape = regrid.grid_shape(vol.shape, args.voxel_spacing, args.model_spacing)
+        plan = regrid.plan(vol.shape, shape, args.regrid_mode)
+    except ValueError as e:
+        parser.error("--model_spacing: %s" % e)
+    args.regrid = {"plan": plan, "native": vol}
+    return vol
+
+
+def _regridding(args):
+    """True when some axis changes its extent: with equal spacings nothing is regridded and the run is the run without
+    the flags"""
+    rg = getattr(args, "regrid", None)
+    return rg is not None and not rg["plan"].identity
+
+
+def _regrid_forward(args, vol):
+    """The (D, H, W) host volume on the model's grid (regridded on the device), with the log's line"""
+    plan = args.regrid["plan"]
+    logger.log(f"regridding {plan.shape_in} at {tuple(args.voxel_spacing)} mm to {plan.shape_out} at "
+               f"{tuple(args.model_spacing)} mm ({plan.mode}); outputs return to {plan.shape_in}")
+    if plan.identity:
+        return vol
+    x = th.from_numpy(np.ascontiguousarray(vol, dtype=np.float32)).to(dist_util.dev())
+    return regrid.apply(x, plan).cpu().numpy()
+
+
+def _regrid_back(args, x):
+    """A stitched (H, W, Z) volume or (K, H, W, Z) stack on the model's grid -> the same on the file's grid, host
+    array or device tensor as given: regridded as (D, H, W) with the inverse plan.  Unchanged without --model_spacing."""
+    if not _regridding(args):
+        return x
+    t = th.as_tensor(x).to(device=dist_util.dev(), dtype=th.float32)
+    to_dhw, to_hwz = ((2, 0, 1), (1, 2, 0)) if t.dim() == 3 else ((0, 3, 1, 2), (0, 2, 3, 1))
+    y = regrid.apply(t.permute(*to_dhw).contiguous(), args.regrid["plan"].inverse()).permute(*to_hwz).contiguous()
+    return y if isinstance(x, th.Tensor) else y.cpu().numpy()
+
+
+def _regrid_keep(args, weight):
+    """The one-shot blend's (H, W, Z) weight sum on the model's grid -> the uint8 mask of the file's voxels that no
+    weight-0 voxel enters (regrid.keep_after), which stands in for the weight from there on.  Unchanged without
+    --model_spacing."""
+    if not _regridding(args):
+        return weight
+    live = (th.as_tensor(weight).to(dist_util.dev()) > 0).to(th.uint8).permute(2, 0, 1).contiguous()
+    keep = regrid.keep_after(live, args.regrid["plan"].inverse()).permute(1, 2, 0).contiguous()
+    return keep if isinstance(weight, th.Tensor) else keep.cpu().numpy()
+
+
+def _native_draws(args, stitcher, K):
+    """--num_draws with --model_spacing: the K stitched draws regridded back as one stack, and their moments on the
+    file's grid -> ((K, H, W, Z) draws, mean, std)"""
+    draws = _regrid_back(args, th.stack([stitcher.draw(k) for k in range(K)]))
+    mean, std = uncertainty.draw_moments(draws)
+    return draws, mean, std
 
 
 def _check_baselines(parser, args):
@@ -471,6 +585,7 @@ def _segment_target(parser, args, vol, target):
         grid = (patches.sliding_grid(vol.shape, res, args.patch_overlap) if args.patch_overlap >= 0
                 else patches.patch_grid(vol.shape, res))
         keep = th.from_numpy(patches.blend_cover(grid, vol.shape, res).astype(np.uint8)).to(dev).contiguous()
+        keep = _regrid_keep(args, keep)
     if args.roi_threshold is not None:
         threshold = float(np.float32(args.roi_threshold))
     else:
@@ -643,6 +758,12 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
         keep = None if weight is None else live.to(th.uint8).contiguous()
         report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=out_path,
                                    baselines={name: x for name, (x, _) in filtered.items()})
+    if getattr(args, "regrid", None) is not None:
+        plan = args.regrid["plan"]
+        report["regrid"] = {"voxel_spacing": list(args.voxel_spacing), "model_spacing": list(args.model_spacing),
+                            "mode": plan.mode, "native_shape": list(plan.shape_in),
+                            "model_shape": list(plan.shape_out),
+                            "effective_spacing": [s * r for s, r in zip(args.voxel_spacing, plan.scale)]}
     path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
     with open(path, "w") as f:
         json.dump(report, f, indent=2)
@@ -842,9 +963,14 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
     if rank == 0:
         logger.log(f"Reconstructing {K} draws with Hann window blending...")
         mean, std, weight = stitcher.finish()
+        native, draws = vol, None
+        if _regridding(args):
+            native = args.regrid["native"]
+            draws, mean, std = _native_draws(args, stitcher, K)
+            weight = _regrid_keep(args, weight)
         result, std_np = mean.cpu().numpy(), std.cpu().numpy()             # (H, W, Z)
         covered = std[weight > 0]
-        logger.log(f"  Original std: {float(vol.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+        logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
         logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
                    f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
         out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
@@ -857,8 +983,8 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             std_path = out_path.replace(".npz", "_std.tif")
             tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
-        mpath = _write_metrics(args, out_path, target, vol, mean, std=std, weight=weight, roi=roi,
-                               draws=(stitcher.draw(k) for k in range(K)))
+        mpath = _write_metrics(args, out_path, target, native, mean, std=std, weight=weight, roi=roi,
+                               draws=(stitcher.draw(k) for k in range(K)) if draws is None else iter(draws))
         if tracer is not None:
             tracer.write(out_path, mpath)
     dist_util.barrier()
@@ -910,8 +1036,14 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
     if rank == 0:
         logger.log("Reconstructing full image with Hann window blending...")
         extra_out, std = {}, None
+        native, draws = vol, None
+        if _regridding(args):
+            native = args.regrid["native"]
         if K > 1:
             mean, std, weight = stitcher.finish()
+            if _regridding(args):
+                draws, mean, std = _native_draws(args, stitcher, K)
+                weight = _regrid_keep(args, weight)
             result = mean.cpu().numpy()                                    # (H, W, Z)
             extra_out["std"] = std.cpu().numpy()
             covered = std[weight > 0]
@@ -919,7 +1051,8 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
                        f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
         else:
             result, weight = stitcher.finish_single()
-        logger.log(f"  Original std: {float(vol.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+            result, weight = _regrid_back(args, result), _regrid_keep(args, weight)
+        logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
         out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
         logger.log(f"saving to {out_path}")
         np.savez(out_path, result, **extra_out)                            # arr_0 [+ std], (H,W,Z)
@@ -931,8 +1064,10 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra_out["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        mpath = _write_metrics(args, out_path, target, vol, result, std=std, weight=weight, roi=roi,
-                               draws=(stitcher.draw(k) for k in range(K)) if K > 1 else None)
+        if draws is None and K > 1:
+            draws = (stitcher.draw(k) for k in range(K))
+        mpath = _write_metrics(args, out_path, target, native, result, std=std, weight=weight, roi=roi,
+                               draws=None if draws is None else iter(draws))
         if tracer is not None:
             tracer.write(out_path, mpath)
     dist_util.barrier()
@@ -957,6 +1092,10 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
                                batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
                                device=dist_util.dev(), **more)
     draws = sample[:, :vol.shape[0], :vol.shape[1], :vol.shape[2]].contiguous()     # (K, D, H, W)
+    native = vol
+    if _regridding(args):
+        native = args.regrid["native"]
+        draws = regrid.apply(draws, args.regrid["plan"].inverse())                  # the K draws back as one stack
     extra = {}
     if K > 1:
         mean, std = uncertainty.draw_moments(draws)
@@ -965,7 +1104,7 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
     else:
         mean = draws[0]
     result = mean.permute(1, 2, 0).cpu().numpy()                              # (D, H, W) -> (H, W, Z)
-    logger.log(f"  Original std: {float(vol.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+    logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
     out_path = None
     if rank == 0:
         out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
@@ -979,7 +1118,7 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
                 tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
                                 extra["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
-        mpath = _write_metrics(args, out_path, target, vol, result, std=extra.get("std"), roi=roi,
+        mpath = _write_metrics(args, out_path, target, native, result, std=extra.get("std"), roi=roi,
                                draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None)
         if args.trace:
             _write_trace(args, out_path, mpath, "canvas", trace.records(), trace.t, target is not None)

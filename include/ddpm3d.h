@@ -983,6 +983,43 @@ int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, i
 int ddpm3d_nlm(const float* vol, int D, int H, int W, int s0, int s1, int s2, int p0, int p1, int p2, float h,
                float sigma, float* out, void* stream);
 /*
+ * Volume regridding (added within ABI 13; the reference has no such code): B fp32 volumes [D][H][W],
+ * W innermost, onto a grid [Do][Ho][Wo] of the same physical extent (scanner spacing <-> model spacing).  Separable:
+ * per axis a banded linear map whose rows the caller builds on the host in fp64 and rounds once to fp32,
+ *   out[o] = sum_{t < count[o]} weights[t * out_len + o] * in[first[o] + t]
+ * with the weights of a row already divided by their sum (taps beyond a face are not counted; nothing is divided on
+ * the device).  For scale = in_len / out_len, fs = max(1, scale), c = (o + 0.5) scale and a kernel f of support S
+ * (triangle, S = 1; Keys' cubic with a = -0.5, S = 2): first = max(0, int(c - S fs + 0.5)),
+ * end = min(in_len, int(c + S fs + 0.5)), w_k = f((k + 0.5 - c) / fs): half-voxel centres, the volumes' faces aligned,
+ * the kernel widened when shrinking.  0.25 <= in_len / out_len <= 4 per axis, so at most 2 S fs + 1 = 17 taps.
+ *
+ * One launch per axis with taps > 0, in the order W, H, D (taps == 0: the identity, in_len == out_len, not launched;
+ * with none, out is a copy of vol), chained through ws so that vol is only read.  A thread owns one output voxel and
+ * adds its counted taps in ascending input index, the first as a product, the others by fma: with n counted taps and
+ * u = 2^-24, per pass |y - sum w x| <= gamma_n sum |w| |x|, gamma_n = n u / (1 - n u).  No atomics, the same bits on
+ * every run, and volume b does not depend on the others.  first, count and weights are device memory the host cannot
+ * read: the kernel clamps count to 0..taps and every input index to 0..in_len - 1, so a bad table gives wrong numbers,
+ * never a read outside vol; a tap at or beyond count[o] never enters the sum (where one is read at all, it is read
+ * inside vol and dropped by a select, not multiplied by a zero weight: a NaN there stays where it is).
+ *
+ * ws: ddpm3d_regrid_workspace_bytes(B, D, H, W, Do, Ho, Wo) bytes, 16-byte aligned, apart from vol and out: the W
+ * pass's and the H pass's outputs (B * D * H * Wo and B * D * Ho * Wo words), whichever passes run; 0 is the answer
+ * for a shape or a ratio the entry refuses.  DDPM3D_EINVAL before any launch for a NULL pointer, B outside
+ * 1..DDPM3D_MAX_DRAWS, taps outside 0..DDPM3D_REGRID_MAX_TAPS, an extent below 1, an in_len that is not the volume's,
+ * an identity axis whose lengths differ, a ratio outside [1/4, 4], more than 2^31 - 1 voxels per volume before or
+ * after any pass, a workspace that is NULL, too small, misaligned or overlapping a volume, and out overlapping vol.
+ */
+#define DDPM3D_REGRID_MAX_TAPS 18
+typedef struct ddpm3d_regrid_axis {
+    int in_len, out_len, taps;        /* taps == 0: identity, in_len == out_len */
+    const int32_t* first;             /* device, [out_len] */
+    const int32_t* count;             /* device, [out_len], 0..taps */
+    const float*   weights;           /* device, taps * out_len: [tap][out_len] */
+} ddpm3d_regrid_axis;
+size_t ddpm3d_regrid_workspace_bytes(int B, int D, int H, int W, int Do, int Ho, int Wo);
+int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_regrid_axis axes[3] /* D, H, W */,
+                  float* out, void* ws, size_t ws_bytes, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
