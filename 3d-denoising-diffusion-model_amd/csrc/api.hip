@@ -732,6 +732,39 @@ int ddpm3d_draw_moments(const float* acc, const float* wsum, int K, int64_t voxe
                     "draw_moments");
 }
 
+int ddpm3d_draw_quantiles(const float* acc, const float* wsum, int K, int64_t voxels, int nq, const int* lower,
+                          const float* frac, const float* target, float* quant, uint8_t* below, uint8_t* equal,
+                          void* stream) {
+    if (!acc) return fail(DDPM3D_EINVAL, "draw_quantiles: null pointer");
+    if (K < 2 || K > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "draw_quantiles: K=%d draws (2..%d)", K, DDPM3D_MAX_DRAWS);
+    // one thread per voxel: the grid's x extent bounds the volume
+    if (voxels <= 0 || voxels > ((int64_t)0x7fffffff) * 256)
+        return fail(DDPM3D_EINVAL, "draw_quantiles: voxels=%lld", (long long)voxels);
+    if (nq < 0 || nq > DDPM3D_MAX_QUANTILES)
+        return fail(DDPM3D_EINVAL, "draw_quantiles: nq=%d quantiles (0..%d)", nq, DDPM3D_MAX_QUANTILES);
+    if ((target != nullptr) != (below != nullptr) || (target != nullptr) != (equal != nullptr))
+        return fail(DDPM3D_EINVAL, "draw_quantiles: target, below and equal come together or not at all");
+    if (nq == 0 && !target) return fail(DDPM3D_EINVAL, "draw_quantiles: no quantile and no target: nothing to do");
+    if (nq > 0 && (!quant || !lower || !frac))
+        return fail(DDPM3D_EINVAL, "draw_quantiles: null quant, lower or frac with nq=%d", nq);
+    ddpm3d_quantile_pos pos = {};
+    for (int i = 0; i < nq; ++i) {
+        if (lower[i] < 0 || lower[i] > K - 1)
+            return fail(DDPM3D_EINVAL, "draw_quantiles: lower[%d]=%d outside 0..%d", i, lower[i], K - 1);
+        if (!(frac[i] >= 0.0f && frac[i] < 1.0f))
+            return fail(DDPM3D_EINVAL, "draw_quantiles: frac[%d]=%g outside [0, 1)", i, (double)frac[i]);
+        if (lower[i] == K - 1 && frac[i] != 0.0f)
+            return fail(DDPM3D_EINVAL, "draw_quantiles: lower[%d]=%d is the last draw but frac=%g", i, lower[i],
+                        (double)frac[i]);
+        pos.lower[i] = lower[i];
+        pos.frac[i] = frac[i];
+    }
+    return launched(ddpm3d_launch_draw_quantiles(acc, wsum, K, voxels, nq, pos, target, quant, below, equal,
+                                                 (hipStream_t)stream),
+                    "draw_quantiles");
+}
+
 // ------------------------------------------------- joint patch sampling (added within ABI 13)
 static int joint_check(const char* what, int B, int Dc, int H, int W, int res, const ddpm3d_joint_starts* s,
                        bool covered) {

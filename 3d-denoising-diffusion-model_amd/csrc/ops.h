@@ -68,6 +68,16 @@ hipError_t ddpm3d_launch_draw_stitch(const float* samples, int K, int res, const
                                      int zs, int H, int W, int D, float* acc, float* wsum, hipStream_t st);
 hipError_t ddpm3d_launch_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean,
                                       float* std, hipStream_t st);
+// quantiles.hip: per-voxel quantiles of K accumulators (wsum may be NULL) and the rank of a target among them.  The
+// positions travel by value in the kernel arguments; the caller has checked them (lower in 0..K-1, frac in [0, 1),
+// frac == 0 at lower == K-1) and that target / below / equal come together and quant with nq > 0
+struct ddpm3d_quantile_pos {
+    int lower[8];                               // DDPM3D_MAX_QUANTILES (quantiles.hip asserts it)
+    float frac[8];
+};
+hipError_t ddpm3d_launch_draw_quantiles(const float* acc, const float* wsum, int K, int64_t voxels, int nq,
+                                        const ddpm3d_quantile_pos& pos, const float* target, float* quant,
+                                        uint8_t* below, uint8_t* equal, hipStream_t st);
 // metrics.hip: error moments and 3-D SSIM of B estimates against one target (the caller has checked shapes and the
 // workspace; the *_workspace_bytes take valid shapes only)
 size_t ddpm3d_em_workspace_bytes(int B, int64_t voxels);

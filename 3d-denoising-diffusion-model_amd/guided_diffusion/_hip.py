@@ -34,6 +34,7 @@ IO_SRC0_BF16, IO_SRC1_BF16, IO_OUT_BF16, IO_RES_BF16 = 1, 2, 4, 8
 IO_HALF_IS_F16 = 16    # the flagged tensors hold IEEE f16 (the --use_fp16 storage), not bf16
 ABI_VERSION = 13
 MAX_DRAWS = 64  # DDPM3D_MAX_DRAWS: draws per uncertainty map (ddpm3d_draw_stitch / ddpm3d_draw_moments)
+MAX_QUANTILES = 8   # DDPM3D_MAX_QUANTILES: quantile levels per ddpm3d_draw_quantiles call
 # ddpm3d_conv_desc.kernel_hint bits (launch orders of identical arithmetic; tests and A/B measurements)
 HINT_WSTAT_OFF, HINT_WSTAT_ON = 0x100, 0x200
 HINT_SPLITK_SHIFT = 16      # bits 16..21: forced split factor (measurement only, tools/splitk_sweep.py)
@@ -210,6 +211,8 @@ EXPORTS = {
     "ddpm3d_draw_stitch": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _fp, _fp, _fp]),
     "ddpm3d_draw_moments": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, _fp, _fp, _fp]),
+    "ddpm3d_draw_quantiles": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_float), _fp, _fp, _fp, _fp, _fp]),
     "ddpm3d_joint_gather": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JointStarts),
                                       C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_joint_blend": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JointStarts), _fp,

@@ -34,6 +34,9 @@ step and sample, the weighted moments of that step's pred_xstart against a targe
 pred_xstart, one call of ddpm3d_trace_moments (csrc/trace.hip) per step and no host synchronisation before
 records(); trace_figures turns pooled records into PSNR, NRMSE, MAE, bias, mean, std, delta_rms and clipped per step
 on the host.
+
+Credible intervals: interval_figures scores two per-voxel quantile maps of
+uncertainty.draw_quantiles against the target: the share of voxels the interval covers and its mean width.
 """
 
 import ctypes
@@ -304,6 +307,34 @@ def evaluate(estimate, target, data_range=None, mask=None, std=None, msssim_scal
     if msssim_scales:
         res["msssim"] = msssim3d(estimate, target, data_range, msssim_scales, mask=mask)
     return res
+
+
+def interval_figures(q_lo, q_hi, target, mask=None):
+    """A per-voxel credible interval [q_lo, q_hi] (two quantile maps of uncertainty.draw_quantiles) against the target,
+    over the voxels the mask counts (all without one): {"coverage": the share with q_lo <= target <= q_hi, an integer
+    count over n_voxels, "mean_width": the fp64 mean of q_hi - q_lo, "n_voxels"}.  A voxel with a NaN bound is not
+    covered.  torch reductions on the device, one copy to the host."""
+    for t, what in ((q_lo, "q_lo"), (q_hi, "q_hi"), (target, "target")):
+        H.require_device(t, what)
+    if not tuple(q_lo.shape) == tuple(q_hi.shape) == tuple(target.shape):
+        raise ValueError("interval_figures: q_lo %s, q_hi %s and target %s must share one shape"
+                         % (tuple(q_lo.shape), tuple(q_hi.shape), tuple(target.shape)))
+    inside = (q_lo <= target) & (target <= q_hi)
+    width = q_hi.double() - q_lo.double()
+    if mask is not None:
+        if not (isinstance(mask, torch.Tensor) and mask.is_cuda and tuple(mask.shape) == tuple(target.shape)):
+            raise ValueError("interval_figures: mask must be a GPU tensor of the target's shape %s"
+                             % (tuple(target.shape),))
+        counted = mask != 0
+        n = counted.sum()
+        inside, width = inside & counted, torch.where(counted, width, torch.zeros_like(width))
+    else:
+        n = torch.tensor(target.numel(), device=target.device)
+    n, covered, total = torch.stack([n.double(), inside.sum().double(), width.sum()]).cpu().tolist()
+    n, covered = int(n), int(covered)
+    if n == 0:
+        raise ValueError("interval_figures: the mask counts no voxel")
+    return {"coverage": covered / n, "mean_width": total / n, "n_voxels": n}
 
 
 # ----------------------------------------------------------------- per-step convergence trace (DESIGN.md 3.15)

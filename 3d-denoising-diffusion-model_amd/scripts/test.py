@@ -112,7 +112,24 @@ taken on the file's grid.  The target, the labels, the baselines and the
 "input" row of the metrics file stay on the file's grid; the voxels the
 one-shot blend leaves at 0 become regrid.keep_after's mask; metrics_<name>.json
 gains "regrid".  Equal spacings give the run without the flags.  Not with
-`--trace True`.
+`--trace True`;
+`--draw_quantiles Q [Q ...]` (at most 8 levels in [0, 1], strictly ascending;
+needs `--num_draws K >= 2`; any of the four paths, any sampler, with or without
+`--device_noise`) adds the per-voxel quantiles of the K stitched draws at those
+levels (numpy.quantile's "linear" method; guided_diffusion/uncertainty.py
+draw_quantiles) to the .npz as `quantiles`, (levels, H, W, Z)
+float32 in the layout of `arr_0`, with `quantile_levels`; no .tif is written
+for them.  With `--model_spacing`, and on the joint path, they are taken of the
+draws on the file's grid, like the std.  With `--target_samples` the "denoised"
+row of metrics_<name>.json gains "quantiles": the rank histogram of the target
+among the K draws over the voxels the row counts ("rank_histogram", K + 1 bins:
+flat if the target is exchangeable with the draws, U-shaped if their spread is
+too small, a dome if it is too large, a slope if they are biased; voxels where
+a draw equals the target are counted in "rank_ties" instead), with two levels
+or more "interval" (the outermost pair's coverage of the target and mean width;
+"nominal" is simply upper - lower, which K draws can only meet approximately:
+for small K the rank histogram is the exact calibration statement) and, with
+0.5 among the levels, "median": the row's figures for the median volume.
 """
 
 import argparse
@@ -187,6 +204,9 @@ def create_argparser():
     # before sampling and the result back to the file's grid (needs --voxel_spacing); linear or cubic taps
     parser.add_argument("--model_spacing", type=float, nargs="+", default=None, metavar="MM")
     parser.add_argument("--regrid_mode", type=str, default="linear")
+    # per-voxel quantiles of the --num_draws draws at these levels in [0, 1] (at most 8, ascending): the .npz gains
+    # "quantiles" and "quantile_levels", the metrics file the rank histogram of the target among the draws
+    parser.add_argument("--draw_quantiles", type=float, nargs="+", default=None, metavar="Q")
     return parser
 
 
@@ -206,6 +226,7 @@ def main(argv=None):
                      "with the literal 10, and its outputs stay as they are)")
     if not 0 <= args.noise_seed < 2 ** 64:
         parser.error("--noise_seed must be in 0 .. 2^64 - 1 (got %d)" % args.noise_seed)
+    _check_quantiles(parser, args)
     _check_segmentation(parser, args)
     _check_regrid(parser, args)
     args.peak = _check_spacing(parser, args)
@@ -376,6 +397,76 @@ def _load_roi(parser, args, vol):
     if args.roi_background != -1 and (args.roi_background <= 0 or args.roi_background not in found):
         parser.error("--roi_background: %d is not a positive label of --roi_labels" % args.roi_background)
     return labels
+
+
+def _check_quantiles(parser, args):
+    """--draw_quantiles, checked before any file is read"""
+    levels = args.draw_quantiles
+    if levels is None:
+        return
+    if args.num_draws < 2:
+        parser.error("--draw_quantiles needs --num_draws K with K >= 2: the quantiles are taken over the K draws")
+    if len(levels) > _hip.MAX_QUANTILES:
+        parser.error("--draw_quantiles takes at most %d levels (got %d)" % (_hip.MAX_QUANTILES, len(levels)))
+    if not all(0.0 <= q <= 1.0 for q in levels):
+        parser.error("--draw_quantiles: every level must lie in [0, 1] (got %s)" % (levels,))
+    if any(b <= a for a, b in zip(levels, levels[1:])):
+        parser.error("--draw_quantiles: the levels must be strictly ascending (got %s)" % (levels,))
+
+
+def _quantile_maps(args, stitcher=None, draws=None, to_hwz=None):
+    """--draw_quantiles on rank 0: the per-voxel quantiles of the K stitched draws, from the stitcher's accumulators
+    (no K-volume temporary) or from the (K, ...) stack the draw moments are taken of; to_hwz permutes the stack's volume
+    axes to the written (H, W, Z) layout.  -> None without the flag, else {"quant": (nq, H, W, Z) device tensor,
+    "ranks": (H, W, Z) target -> (below, equal), the second launch _write_metrics makes once it has the target}."""
+    levels = args.draw_quantiles
+    if levels is None:
+        return None
+    if draws is None:
+        return {"quant": stitcher.quantiles(levels), "ranks": lambda tgt: stitcher.quantiles((), target=tgt)[1:]}
+    if to_hwz is None:
+        return {"quant": uncertainty.draw_quantiles(draws, levels),
+                "ranks": lambda tgt: uncertainty.draw_quantiles(draws, (), target=tgt)[1:]}
+    back = tuple(int(v) for v in np.argsort(to_hwz))
+
+    def ranks(tgt):
+        _, below, equal = uncertainty.draw_quantiles(draws, (), target=tgt.permute(*back).contiguous())
+        return below.permute(*to_hwz).contiguous(), equal.permute(*to_hwz).contiguous()
+
+    quant = uncertainty.draw_quantiles(draws, levels)
+    return {"quant": quant.permute(0, *(1 + v for v in to_hwz)).contiguous(), "ranks": ranks}
+
+
+def _quantile_arrays(args, qmaps):
+    """The .npz entries of --draw_quantiles ({} without the flag): "quantiles" (nq, H, W, Z) float32, the layout of
+    arr_0, and "quantile_levels" float64"""
+    if qmaps is None:
+        return {}
+    return {"quantiles": qmaps["quant"].cpu().numpy(),
+            "quantile_levels": np.asarray(args.draw_quantiles, dtype=np.float64)}
+
+
+def _quantile_block(args, qmaps, tgt, mask, evaluate):
+    """"quantiles" of the metrics file's "denoised" row, over the voxels that row counts (mask): the rank histogram
+    of the target among the K draws, the outermost interval's coverage and width, and the median scored like the
+    mean (evaluate: volume -> the row's figures)."""
+    levels, K = list(args.draw_quantiles), args.num_draws
+    quant = qmaps["quant"]
+    below, equal = qmaps["ranks"](tgt)
+    hist = uncertainty.rank_histogram(below, equal, K, mask=mask)
+    block = {"levels": levels, "rank_histogram": hist["counts"], "rank_ties": hist["ties"], "rank_n": hist["n"]}
+    ends = (hist["counts"][0] + hist["counts"][K]) / max(hist["n"], 1)
+    logger.log("  rank histogram of the target among %d draws: %.4f of %d voxels in the two end bins (%.4f if the "
+               "target were one more draw), %d ties" % (K, ends, hist["n"], 2.0 / (K + 1), hist["ties"]))
+    if len(levels) >= 2:
+        f = metrics.interval_figures(quant[0], quant[-1], tgt, mask=mask)
+        block["interval"] = {"lower": levels[0], "upper": levels[-1], "nominal": levels[-1] - levels[0],
+                             "coverage": f["coverage"], "mean_width": f["mean_width"]}
+        logger.log("  interval [q%g, q%g]: covers %.4f of the target (nominal %.4f), mean width %.5g"
+                   % (levels[0], levels[-1], f["coverage"], levels[-1] - levels[0], f["mean_width"]))
+    if 0.5 in levels:
+        block["median"] = evaluate(quant[levels.index(0.5)])
+    return block
 
 
 def _segmenting(args):
@@ -696,13 +787,14 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
             "detection": _detection_block(seg, regions, inp, den, draw_found), **spaced}
 
 
-def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, roi=None, draws=None):
+def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, roi=None, draws=None, quantiles=None):
     """Rank 0, after the .npz is written: scores the written volume `result` (and `std`, with --num_draws) and the
     low-dose input `vol` against `target` on the device and writes metrics_<name>.json beside the .npz.  target and
     vol are (D, H, W) host arrays; result, std and weight (the one-shot blend's Hann weight sum, whose zeros are not
     counted) are (H, W, Z) host arrays or device tensors.  With --roi_labels (roi, (D, H, W) int32) the file gains the
     "roi" entry; draws then yields the K draws of --num_draws as (H, W, Z) device tensors.  Nothing happens without
-    --target_samples."""
+    --target_samples.  quantiles: _quantile_maps' dict with --draw_quantiles, which adds "quantiles" to the "denoised"
+    row."""
     if target is None:
         return None
     dev = dist_util.dev()
@@ -745,6 +837,11 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
         r = report["denoised"]
         logger.log("  std map coverage: %.4f of the errors within 1 std, %.4f within 2"
                    % (r["coverage_1"], r["coverage_2"]))
+    if quantiles is not None:
+        report["denoised"]["quantiles"] = _quantile_block(
+            args, quantiles, tgt, mask,
+            lambda x: metrics.evaluate(x.contiguous(), tgt, data_range=data_range, mask=mask,
+                                       std=None if std is None else hwz(std), **more))
     filtered = _baseline_volumes(args, inp)
     if filtered:
         report["baselines"] = {}
@@ -968,6 +1065,7 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             native = args.regrid["native"]
             draws, mean, std = _native_draws(args, stitcher, K)
             weight = _regrid_keep(args, weight)
+        qmaps = _quantile_maps(args, stitcher, draws)
         result, std_np = mean.cpu().numpy(), std.cpu().numpy()             # (H, W, Z)
         covered = std[weight > 0]
         logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
@@ -975,7 +1073,7 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
                    f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
         out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
         logger.log(f"saving to {out_path}")
-        np.savez(out_path, result, std=std_np)                             # arr_0 = mean, std: both (H,W,Z)
+        np.savez(out_path, result, std=std_np, **_quantile_arrays(args, qmaps))   # arr_0 = mean, std: both (H,W,Z)
         if args.base_samples.lower().endswith((".tif", ".tiff")):
             from guided_diffusion import tiff_io
             tiff_path = out_path.replace(".npz", ".tif")
@@ -984,7 +1082,8 @@ def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batch
             tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
         mpath = _write_metrics(args, out_path, target, native, mean, std=std, weight=weight, roi=roi,
-                               draws=(stitcher.draw(k) for k in range(K)) if draws is None else iter(draws))
+                               draws=(stitcher.draw(k) for k in range(K)) if draws is None else iter(draws),
+                               quantiles=qmaps)
         if tracer is not None:
             tracer.write(out_path, mpath)
     dist_util.barrier()
@@ -1035,7 +1134,7 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
     out_path = None
     if rank == 0:
         logger.log("Reconstructing full image with Hann window blending...")
-        extra_out, std = {}, None
+        extra_out, std, qmaps = {}, None, None
         native, draws = vol, None
         if _regridding(args):
             native = args.regrid["native"]
@@ -1046,6 +1145,8 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
                 weight = _regrid_keep(args, weight)
             result = mean.cpu().numpy()                                    # (H, W, Z)
             extra_out["std"] = std.cpu().numpy()
+            qmaps = _quantile_maps(args, stitcher, draws)
+            extra_out.update(_quantile_arrays(args, qmaps))
             covered = std[weight > 0]
             logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
                        f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
@@ -1067,7 +1168,7 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
         if draws is None and K > 1:
             draws = (stitcher.draw(k) for k in range(K))
         mpath = _write_metrics(args, out_path, target, native, result, std=std, weight=weight, roi=roi,
-                               draws=None if draws is None else iter(draws))
+                               draws=None if draws is None else iter(draws), quantiles=qmaps)
         if tracer is not None:
             tracer.write(out_path, mpath)
     dist_util.barrier()
@@ -1107,6 +1208,8 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
     logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
     out_path = None
     if rank == 0:
+        qmaps = _quantile_maps(args, draws=draws, to_hwz=(1, 2, 0)) if K > 1 else None
+        extra.update(_quantile_arrays(args, qmaps))
         out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
         logger.log(f"saving to {out_path}")
         np.savez(out_path, result, **extra)                                   # arr_0 [+ std], (H,W,Z)
@@ -1119,7 +1222,8 @@ def _main_joint(args, model, diffusion, vol, target=None, roi=None):
                                 extra["std"].transpose(2, 0, 1).astype(np.float32))
             logger.log(f"Saved denoised TIFF: {tiff_path}")
         mpath = _write_metrics(args, out_path, target, native, result, std=extra.get("std"), roi=roi,
-                               draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None)
+                               draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None,
+                               quantiles=qmaps)
         if args.trace:
             _write_trace(args, out_path, mpath, "canvas", trace.records(), trace.t, target is not None)
     dist_util.barrier()

@@ -628,6 +628,32 @@ int ddpm3d_draw_stitch(const float* samples, int K, int res, const double* windo
 int ddpm3d_draw_moments(const float* acc, const float* wsum, int K, int64_t voxels, float* mean, float* std,
                         void* stream);
 /*
+ * Per-voxel quantiles of the K draws and the rank of a target among them (added within ABI 13; the distribution-free
+ * companions of the std map the reference's README.md:44 reports: median, credible interval, rank histogram).
+ * ddpm3d_draw_quantiles reads acc[K][voxels] once and, per voxel, takes x_d = acc[d] / wsum (the division of
+ * ddpm3d_draw_moments; wsum NULL: a plain stack of K draws), sorts the K values ascending to s_0 <= ... <= s_{K-1} and
+ * writes quantile i as s_{lower[i]} when frac[i] == 0 and fmaf(frac[i], s_{lower[i]+1} - s_{lower[i]}, s_{lower[i]})
+ * otherwise: numpy.quantile's method "linear" (Hyndman-Fan type 7) for a level q with h = q (K - 1), lower =
+ * floor(h), frac = h - lower, which the caller computes (in fp64).  With a target it also writes
+ * below = #{d : x_d < target} and equal = #{d : x_d == target}; without ties the target's rank among the draws is
+ * below, one of K + 1 bins.
+ *   lower, frac  host arrays of nq entries, read before the call returns
+ *   target       [voxels] fp32 or NULL
+ *   quant        [nq][voxels] fp32; NULL iff nq == 0
+ *   below, equal [voxels] uint8 each; set iff target is
+ * A voxel with wsum <= 0 gets 0 in every quantile and 255 ("not counted"; K <= 64) in below and equal.  A voxel with a
+ * NaN among its draws gets NaN in every quantile, as numpy.quantile gives, and 255 in below and equal; a NaN target
+ * value gives 255 too.  Enqueue-only: no allocation, no synchronisation; every output element has one writer.
+ * Returns DDPM3D_EINVAL before any launch for a NULL acc, K outside 2..DDPM3D_MAX_DRAWS, voxels below 1, nq outside
+ * 0..DDPM3D_MAX_QUANTILES, nq == 0 without a target, a NULL quant (or lower or frac) with nq > 0, a lower[i] outside
+ * 0..K-1, a frac[i] that is not finite or outside [0, 1), lower[i] == K-1 with frac[i] != 0, or target, below and
+ * equal not all set or all NULL.
+ */
+#define DDPM3D_MAX_QUANTILES 8
+int ddpm3d_draw_quantiles(const float* acc, const float* wsum, int K, int64_t voxels, int nq, const int* lower,
+                          const float* frac, const float* target, float* quant, uint8_t* below, uint8_t* equal,
+                          void* stream);
+/*
  * Joint patch sampling (added within ABI 13): one state per volume, cut into the overlapping patches before every
  * network call and blended back after every reverse step, so that patches share x_t and the step's noise where they
  * overlap (the one-shot blend of scripts/test.py:100-146 averages independent draws there and shrinks their spread).
