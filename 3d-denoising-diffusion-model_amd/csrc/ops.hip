@@ -350,7 +350,8 @@ __global__ __launch_bounds__(1024) void gn_finalize_kernel(
         s2 += red[1][w];
         m2 = fmaxf(m2, redm[w]);
     }
-    // every |x| of the group is at most the square root of the largest row's sum of squares
+    // every |x| of the group is at most the square root of the largest row's sum of squares -- of its EXACT sum of
+    // squares: the conv epilogues' pivoted fp32 sums can leave it short by the relative slack delta of ddpm3d.h
     const float xmax = sqrtf(m2);
     if (gamma == nullptr) {                          // bounds only (tensor consumed without a GroupNorm)
         if (threadIdx.x == 0 && bound != nullptr) {

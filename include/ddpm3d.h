@@ -134,7 +134,9 @@ typedef struct ddpm3d_conv_desc {
      * hi/lo split (the epilogue multiplies by the exact inverse).  So no input magnitude is clipped
      * and small-magnitude tensors keep their low bits; a bound that is too SMALL makes f16 overflow
      * and the output non-finite (never silently wrong).  Producers: ddpm3d_gn_finalize (normalised
-     * and raw bounds from the GroupNorm partial sums), ddpm3d_absmax (tensors without statistics). */
+     * and raw bounds from the GroupNorm partial sums; they may understate by that call's relative slack
+     * delta < 1e-3, which the factor of two between 2^15 and f16's 65504 absorbs), ddpm3d_absmax (tensors
+     * without statistics). */
     int32_t in_bound_count;
     const float* in_bound;
     int32_t in_bound_stride;
@@ -380,13 +382,21 @@ int ddpm3d_gn_finalize(const double* stats0, int C0, int rows0,
                        const float* gamma, const float* beta,
                        const float* film, int film_stride, int film_off,
                        float* aff_a, float* aff_b, float* bound, void* stream);
-/* `bound` (may be NULL) = [N][groups][2] upper bounds for ddpm3d_conv_desc.in_bound, from the same
- * partial sums: a value of channel c is at most xmax = sqrt(largest sum of squares of any statistics
- * row of its group), so
- *   bound[n][g][0] = max_c |A[n][c]| * xmax + max_c |B[n][c]|   >= |act(A*x + B)|  (|SiLU(y)| <= |y|)
- *   bound[n][g][1] = xmax                                       >= |x|  (the tensor read raw)
- * gamma == NULL (then beta, film, aff_a, aff_b are ignored): bounds only, for tensors that are
- * consumed without a GroupNorm. */
+/* `bound` (may be NULL) = [N][groups][2] bounds for ddpm3d_conv_desc.in_bound, from the same partial
+ * sums, with xmax = sqrtf(largest sum of squares of any statistics row of the group):
+ *   bound[n][g][0] = max_c |A[n][c]| * xmax + max_c |B[n][c]|   >= |act(A*x + B)| * (1 - delta)  (|SiLU(y)| <= |y|)
+ *   bound[n][g][1] = xmax                                       >= |x| * (1 - delta)  (the tensor read raw)
+ * On exact sums xmax bounds every |x| of the group.  The rows a conv writes are fp32 sums around a pivot,
+ * converted once in fp64 (sum x^2 = s2 + 2 p s1 + n p^2), and that conversion cancels when the pivot is a hot
+ * voxel on a flat background: xmax can fall short of the hot value by the relative slack
+ *   delta(n) = 1 - sqrt(1 - g (3 (n - 1) + 2 sqrt(n - 1))) + 3 * 2^-24,   g = (n + 2) 2^-24 / (1 - (n + 2) 2^-24),
+ * n = the most values one lane accumulates (at most 64 in this library: delta <= 4.1e-4; rows of
+ * ddpm3d_gn_stats are fp64 throughout: 3 * 2^-24).  The consumers' scale rule takes it in: it puts the bound
+ * below 2^15, and 2^15 (1 + 2^-11) / (1 - delta) stays below f16's 65504 for any delta < 0.499.  A caller that
+ * needs a strict upper bound multiplies by 1 / (1 - delta).  (Derivation: DESIGN.md section 2, "Range".)
+ * NaN rows are ignored by the maximum (the group's A and B are NaN).
+ * gamma == NULL (then beta, film, aff_a, aff_b are ignored and aff_a, aff_b are not written): bounds only,
+ * for tensors that are consumed without a GroupNorm. */
 
 /* bound[n * count + t] = max |x| over sample n of tensor t, for up to two tensors of `per_sample`
  * floats per sample (count = 1 or 2; x1 may be NULL): ddpm3d_conv_desc.in_bound of inputs that have

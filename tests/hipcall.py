@@ -116,21 +116,28 @@ LAST_PLAN = {}     # what the last conv3d() call ran as (tests assert that a pat
 
 
 def gn_finalize(stats_list, count, gamma, beta, film=None, film_stride=0, film_off=0, groups=32,
-                with_bound=False):
+                with_bound=False, eps=1e-5, null_bound=False, poison=float("nan"), expect_rc=None):
+    """gamma None: the bounds-only form (gamma and beta NULL; A and B are still passed, and must stay as they
+    were).  null_bound: `bound` NULL (the returned bound buffer is then ours alone).  A, B and bound start out
+    as `poison`.  expect_rc: the call must return this code instead of DDPM3D_OK."""
     lib = H.load()
     s0 = stats_list[0]
     s1 = stats_list[1] if len(stats_list) > 1 else None
     N = s0.shape[0]
     Cn = s0.shape[1] + (s1.shape[1] if s1 is not None else 0)
-    A = torch.empty(N, Cn, dtype=torch.float32, device=s0.device)
-    B = torch.empty(N, Cn, dtype=torch.float32, device=s0.device)
-    bound = torch.full((N, groups, 2), float("nan"), dtype=torch.float32, device=s0.device)
-    H.check(lib.ddpm3d_gn_finalize(H.ptr(s0), s0.shape[1], s0.shape[2],
-                                   H.ptr(s1), s1.shape[1] if s1 is not None else 0,
-                                   s1.shape[2] if s1 is not None else 0,
-                                   N, groups, float(count), 1e-5, H.ptr(gamma), H.ptr(beta),
-                                   H.ptr(film), film_stride, film_off, H.ptr(A), H.ptr(B), H.ptr(bound),
-                                   H.stream()))
+    A = torch.full((N, Cn), poison, dtype=torch.float32, device=s0.device)
+    B = torch.full((N, Cn), poison, dtype=torch.float32, device=s0.device)
+    bound = torch.full((N, groups, 2), poison, dtype=torch.float32, device=s0.device)
+    rc = lib.ddpm3d_gn_finalize(H.ptr(s0), s0.shape[1], s0.shape[2],
+                                H.ptr(s1), s1.shape[1] if s1 is not None else 0,
+                                s1.shape[2] if s1 is not None else 0,
+                                N, groups, float(count), eps, H.ptr(gamma), H.ptr(beta),
+                                H.ptr(film), film_stride, film_off, H.ptr(A), H.ptr(B),
+                                0 if null_bound else H.ptr(bound), H.stream())
+    if expect_rc is None:
+        H.check(rc)
+    else:
+        assert rc == expect_rc, rc
     torch.cuda.synchronize()
     return (A, B, bound) if with_bound else (A, B)
 
