@@ -19,10 +19,12 @@ volume only up to 3 x 3 x 2 patch sizes (H, W, D): beyond that it leaves gaps
 2..patch size - 1) tiles a volume of any size without gaps instead, with as many
 evenly spread patches per axis as it takes for neighbours to overlap by at
 least N voxels (patches.sliding_starts; 44 extends the reference's grid for
-200 x 200 volumes).  With it the volume is uploaded once, every batch's
-conditioning patches are cut on the device and finished patches are blended on
-rank 0's device as they arrive, for all of the one-shot path, `--num_draws` and
-`--joint_patches`; `--use_ddim`
+200 x 200 volumes).  With it the volume is uploaded once and every batch's
+conditioning patches are cut on the device, for all of the one-shot path,
+`--num_draws` and `--joint_patches`.  On either grid the independent paths
+(one draw or `--num_draws`) run one round loop, and finished patches are blended
+on rank 0's device as they arrive, with the arithmetic of
+patches.stitch_patches; `--use_ddim`
 is honoured (the reference parses it but always runs DDPM, scripts/test.py:63);
 `--use_dpm_solver True` (with `--solver_order`, `--solver_stochastic`) samples
 with DPM-Solver++ instead and takes precedence over `--use_ddim`; pair it with
@@ -133,6 +135,7 @@ for small K the rank histogram is the exact calibration statement) and, with
 """
 
 import argparse
+import collections
 import json
 import os
 import sys
@@ -262,80 +265,16 @@ def main(argv=None):
     native = vol
     if args.regrid is not None:
         vol = _regrid_forward(args, vol)                         # from here on vol is on the model's grid
-    res = args.large_size
     if _segmenting(args):
         roi = _segment_target(parser, args, vol, target)
     if args.joint_patches:
-        return _main_joint(args, model, diffusion, vol, target, roi)
-    if args.patch_overlap >= 0:
-        return _main_sliding(args, model, diffusion, vol, target, roi)
-    low_res, grid = patches.split_volume(vol, res)               # (P, 1, Z, H, W)
-    logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3")
-    gaps = patches.grid_gaps(vol.shape, res)
-    if any(gaps.values()):
-        logger.log("WARNING: the fixed 3 x 3 x (1 | 2) grid does not cover this volume (coordinates without a patch: "
-                   + ", ".join("%d of %d along %s" % (gaps[a], n, a) for a, n in zip("DHW", vol.shape) if gaps[a])
-                   + "); those voxels are written as 0.  --patch_overlap N tiles a volume of any size without gaps.")
-
-    # Work units are batches of --batch_size patches; batch b goes to rank b mod W
-    # (scripts/test.py:243 with batch_size 1), every rank runs the same number of rounds.
-    rank = dist_util.rank()
-    bs = max(1, args.batch_size)
-    n_batches = (len(grid) + bs - 1) // bs
-    sample_loop, extra = _sampler(args, diffusion)
-    tracer = None
-    if args.trace:
-        D, Hh, W = vol.shape
-        tracer = _PatchTrace(args, diffusion, vol, target, grid, bs, (patches.xy_starts(Hh, res),
-                                                                      patches.xy_starts(W, res),
-                                                                      patches.z_starts(D, res)))
-    if args.num_draws > 1:
-        return _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target, roi, tracer)
-    done = {}
-    for b in dist_util.partition(n_batches):
-        block = th.zeros(bs, 1, res, res, res, device=dev)                  # padded so collectives stay aligned
-        if b is not None:
-            idx = list(range(b * bs, min((b + 1) * bs, len(grid))))
-            cond = th.from_numpy(low_res[idx]).to(dev)
-            shape = tuple(cond.shape)
-            # all randomness keyed by the GLOBAL patch index (one generator per patch): the result
-            # depends neither on the world size nor on the batch size
-            noise, noise_args = _batch_noise(args, dev, idx, 1, shape)
-            logger.log(f"rank {rank}: patches {idx} shape={shape}")
-            if tracer is not None:
-                extra["trace"] = tracer.begin(idx)
-            sample = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
-                                 model_kwargs={"low_res": cond}, **noise_args, **extra)
-            block[:len(idx)] = sample.permute(0, 1, 3, 4, 2)                # (B,1,Z,H,W) -> (B,1,H,W,Z)
-        for bb, blk in dist_util.gather_round(block, b):
-            for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
-                done[i] = blk[j, 0].cpu().numpy()
-        if tracer is not None:
-            tracer.gather(extra.get("trace"), b)
-    if not done:
-        logger.log("No samples were generated. Exiting.")
-        return None
-
-    logger.log("Reconstructing full image with Hann window blending...")
-    ordered = [done[i] for i in range(len(grid))]
-    result, weight = patches.stitch_patches(ordered, grid, vol.shape, res)  # (H, W, Z)
-    result, weight = _regrid_back(args, result), _regrid_keep(args, weight)
-    orig_std, den_std = float(native.std()), float(result.std())
-    logger.log(f"  Original std: {orig_std:.4f}  Denoised std: {den_std:.4f}")
-
+        out = _main_joint(args, model, diffusion, vol, target)
+    else:
+        tiling = _sliding_tiling(args, vol) if args.patch_overlap >= 0 else _fixed_tiling(args, vol)
+        out = _run_patches(args, model, diffusion, vol, tiling, target)
     out_path = None
-    if rank == 0:
-        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
-        logger.log(f"saving to {out_path}")
-        np.savez(out_path, result)                                           # key 'arr_0', (H,W,Z) like the reference
-        if args.base_samples.lower().endswith((".tif", ".tiff")):
-            from guided_diffusion import tiff_io
-            tiff_path = out_path.replace(".npz", ".tif")
-            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))   # (H,W,Z) -> (Z,H,W), no scaling
-            logger.log(f"Saved denoised TIFF: {tiff_path}")
-        mpath = _write_metrics(args, out_path, target, native, result, weight=weight, roi=roi)
-        if tracer is not None:
-            tracer.write(out_path, mpath)
+    if dist_util.rank() == 0:
+        out_path = _write_outputs(args, native, target, roi, **out)
     dist_util.barrier()
     logger.log("Full image denoising complete")
     return out_path
@@ -597,14 +536,6 @@ def _regrid_keep(args, weight):
     live = (th.as_tensor(weight).to(dist_util.dev()) > 0).to(th.uint8).permute(2, 0, 1).contiguous()
     keep = regrid.keep_after(live, args.regrid["plan"].inverse()).permute(1, 2, 0).contiguous()
     return keep if isinstance(weight, th.Tensor) else keep.cpu().numpy()
-
-
-def _native_draws(args, stitcher, K):
-    """--num_draws with --model_spacing: the K stitched draws regridded back as one stack, and their moments on the
-    file's grid -> ((K, H, W, Z) draws, mean, std)"""
-    draws = _regrid_back(args, th.stack([stitcher.draw(k) for k in range(K)]))
-    mean, std = uncertainty.draw_moments(draws)
-    return draws, mean, std
 
 
 def _check_baselines(parser, args):
@@ -1026,94 +957,61 @@ def _base_name(path):
     return base
 
 
-def _main_draws(args, model, sample_loop, extra, vol, low_res, grid, bs, n_batches, target=None, roi=None,
-                tracer=None):
-    """--num_draws K >= 2: every forward batch is bs patches x K draws, patch-major (N = bs * K); the noise of draw d of
-    patch i comes from volume_generator(i, draw=d), so it depends on neither K, the batch size nor the world size.
-    Gathered rounds are stitched on rank 0's device in ascending patch order (DrawStitcher), then reduced to the
-    per-voxel mean and sample std."""
+class _Tiling(collections.namedtuple("_Tiling", "grid starts cond")):
+    """How the independent paths see a grid: grid, the patch origins in patch order; starts = (x_starts, y_starts,
+    z_starts), whose product the grid is; cond(idx) -> the (len(idx), 1, res, res, res) float32 device tensor of the
+    conditioning patches idx (consecutive indices)."""
+
+
+def _fixed_tiling(args, vol):
+    """The reference's fixed 3 x 3 x (1 | 2) grid: patches cut (and zero-padded) on the host, uploaded per batch"""
+    res = args.large_size
+    low_res, grid = patches.split_volume(vol, res)               # (P, 1, Z, H, W)
+    logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3")
+    gaps = patches.grid_gaps(vol.shape, res)
+    if any(gaps.values()):
+        logger.log("WARNING: the fixed 3 x 3 x (1 | 2) grid does not cover this volume (coordinates without a patch: "
+                   + ", ".join("%d of %d along %s" % (gaps[a], n, a) for a, n in zip("DHW", vol.shape) if gaps[a])
+                   + "); those voxels are written as 0.  --patch_overlap N tiles a volume of any size without gaps.")
+    D, Hh, W = vol.shape
     dev = dist_util.dev()
-    rank = dist_util.rank()
-    K, res = args.num_draws, args.large_size
-    stitcher = uncertainty.DrawStitcher(vol.shape, res, K, dev) if rank == 0 else None
-    for b in dist_util.partition(n_batches):
-        block = th.zeros(bs * K, 1, res, res, res, device=dev)               # padded so collectives stay aligned
-        if b is not None:
-            idx = list(range(b * bs, min((b + 1) * bs, len(grid))))
-            cond = th.from_numpy(low_res[idx]).to(dev).repeat_interleave(K, dim=0)
-            shape = tuple(cond.shape)
-            noise, noise_args = _batch_noise(args, dev, idx, K, shape)
-            logger.log(f"rank {rank}: patches {idx} x {K} draws shape={shape}")
-            if tracer is not None:
-                extra["trace"] = tracer.begin(idx)
-            block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
-                                               model_kwargs={"low_res": cond}, **noise_args, **extra)
-        for bb, blk in dist_util.gather_round(block, b):
-            if stitcher is None:
-                continue
-            blk = blk.to(dev)
-            for j, i in enumerate(range(bb * bs, min((bb + 1) * bs, len(grid)))):
-                stitcher.add(i, blk[j * K:(j + 1) * K], grid[i])
-        if tracer is not None:
-            tracer.gather(extra.get("trace"), b)
-    out_path = None
-    if rank == 0:
-        logger.log(f"Reconstructing {K} draws with Hann window blending...")
-        mean, std, weight = stitcher.finish()
-        native, draws = vol, None
-        if _regridding(args):
-            native = args.regrid["native"]
-            draws, mean, std = _native_draws(args, stitcher, K)
-            weight = _regrid_keep(args, weight)
-        qmaps = _quantile_maps(args, stitcher, draws)
-        result, std_np = mean.cpu().numpy(), std.cpu().numpy()             # (H, W, Z)
-        covered = std[weight > 0]
-        logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
-        logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
-                   f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
-        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
-        logger.log(f"saving to {out_path}")
-        np.savez(out_path, result, std=std_np, **_quantile_arrays(args, qmaps))   # arr_0 = mean, std: both (H,W,Z)
-        if args.base_samples.lower().endswith((".tif", ".tiff")):
-            from guided_diffusion import tiff_io
-            tiff_path = out_path.replace(".npz", ".tif")
-            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))
-            std_path = out_path.replace(".npz", "_std.tif")
-            tiff_io.imwrite(std_path, std_np.transpose(2, 0, 1).astype(np.float32))
-            logger.log(f"Saved denoised TIFFs: {tiff_path}, {std_path}")
-        mpath = _write_metrics(args, out_path, target, native, mean, std=std, weight=weight, roi=roi,
-                               draws=(stitcher.draw(k) for k in range(K)) if draws is None else iter(draws),
-                               quantiles=qmaps)
-        if tracer is not None:
-            tracer.write(out_path, mpath)
-    dist_util.barrier()
-    logger.log("Full image denoising complete")
-    return out_path
+    return _Tiling(grid, (patches.xy_starts(Hh, res), patches.xy_starts(W, res), patches.z_starts(D, res)),
+                   lambda idx: th.from_numpy(low_res[idx]).to(dev))
 
 
-def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
-    """--patch_overlap N: the one-shot path (and --num_draws K) on the gap-free sliding grid.  The volume is uploaded
-    once as a zero-extended canvas; every batch's conditioning patches are cut from it on the device
-    (ddpm3d_tiles_gather); gathered rounds are blended on rank 0's device in ascending patch order as they arrive
-    (uncertainty.VolumeStitcher: patches.stitch_patches' arithmetic), so no rank holds all patches.  Noise is keyed
-    by the global patch index (and draw), as in the default path."""
+def _sliding_tiling(args, vol):
+    """--patch_overlap N: the gap-free sliding grid.  The volume is uploaded once as a zero-extended canvas and every
+    batch's conditioning patches are cut from it on the device (ddpm3d_tiles_gather)."""
+    res = args.large_size
+    geom = patches.joint_geometry(vol.shape, res, min_overlap=args.patch_overlap)
+    logger.log(f"volume {vol.shape}: {len(geom.grid)} patches of {res}^3 ({len(geom.x_starts)} x "
+               f"{len(geom.y_starts)} x {len(geom.z_starts)} along H, W, D; neighbours overlap by at least "
+               f"{args.patch_overlap})")
+    canvas = joint._canvas_of(vol, geom, dist_util.dev())
+    return _Tiling(geom.grid, (geom.x_starts, geom.y_starts, geom.z_starts),
+                   lambda idx: joint.gather(canvas, geom, idx[0], len(idx)))
+
+
+def _run_patches(args, model, diffusion, vol, tiling, target=None):
+    """The independent paths, either grid, K = --num_draws >= 1.  Work units are batches of --batch_size patches;
+    batch b goes to rank b mod W (scripts/test.py:243 with batch_size 1) and every rank runs the same number of
+    rounds.  Every forward batch is bs patches x K draws, patch-major; the noise of draw d of patch i is keyed by
+    (i, d) (_batch_noise), so the result depends on neither K, the batch size nor the world size.  Gathered rounds
+    are blended on rank 0's device in ascending patch order as they arrive (uncertainty.VolumeStitcher:
+    patches.stitch_patches' arithmetic), so no rank holds all patches.  -> _write_outputs' volumes on rank 0, None
+    on the others."""
     dev = dist_util.dev()
     rank = dist_util.rank()
     K, res, bs = args.num_draws, args.large_size, max(1, args.batch_size)
-    geom = patches.joint_geometry(vol.shape, res, min_overlap=args.patch_overlap)
-    grid = geom.grid
-    logger.log(f"volume {vol.shape}: {len(grid)} patches of {res}^3 ({len(geom.x_starts)} x {len(geom.y_starts)} x "
-               f"{len(geom.z_starts)} along H, W, D; neighbours overlap by at least {args.patch_overlap})")
+    grid = tiling.grid
     sample_loop, extra = _sampler(args, diffusion)
-    canvas = joint._canvas_of(vol, geom, dev)
     stitcher = uncertainty.VolumeStitcher(vol.shape, res, K, dev) if rank == 0 else None
-    tracer = (_PatchTrace(args, diffusion, vol, target, grid, bs, (geom.x_starts, geom.y_starts, geom.z_starts))
-              if args.trace else None)
+    tracer = _PatchTrace(args, diffusion, vol, target, grid, bs, tiling.starts) if args.trace else None
     for b in dist_util.partition((len(grid) + bs - 1) // bs):
         block = th.zeros(bs * K, 1, res, res, res, device=dev)               # padded so collectives stay aligned
         if b is not None:
             idx = list(range(b * bs, min((b + 1) * bs, len(grid))))
-            cond = joint.gather(canvas, geom, idx[0], len(idx))
+            cond = tiling.cond(idx)
             if K > 1:
                 cond = cond.repeat_interleave(K, dim=0)
             shape = tuple(cond.shape)
@@ -1131,104 +1029,88 @@ def _main_sliding(args, model, diffusion, vol, target=None, roi=None):
                 stitcher.add(i, blk[j * K:(j + 1) * K], grid[i])
         if tracer is not None:
             tracer.gather(extra.get("trace"), b)
-    out_path = None
-    if rank == 0:
-        logger.log("Reconstructing full image with Hann window blending...")
-        extra_out, std, qmaps = {}, None, None
-        native, draws = vol, None
-        if _regridding(args):
-            native = args.regrid["native"]
-        if K > 1:
-            mean, std, weight = stitcher.finish()
-            if _regridding(args):
-                draws, mean, std = _native_draws(args, stitcher, K)
-                weight = _regrid_keep(args, weight)
-            result = mean.cpu().numpy()                                    # (H, W, Z)
-            extra_out["std"] = std.cpu().numpy()
-            qmaps = _quantile_maps(args, stitcher, draws)
-            extra_out.update(_quantile_arrays(args, qmaps))
-            covered = std[weight > 0]
-            logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
-                       f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
-        else:
-            result, weight = stitcher.finish_single()
-            result, weight = _regrid_back(args, result), _regrid_keep(args, weight)
-        logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
-        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
-        logger.log(f"saving to {out_path}")
-        np.savez(out_path, result, **extra_out)                            # arr_0 [+ std], (H,W,Z)
-        if args.base_samples.lower().endswith((".tif", ".tiff")):
-            from guided_diffusion import tiff_io
-            tiff_path = out_path.replace(".npz", ".tif")
-            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))
-            if K > 1:
-                tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
-                                extra_out["std"].transpose(2, 0, 1).astype(np.float32))
-            logger.log(f"Saved denoised TIFF: {tiff_path}")
-        if draws is None and K > 1:
-            draws = (stitcher.draw(k) for k in range(K))
-        mpath = _write_metrics(args, out_path, target, native, result, std=std, weight=weight, roi=roi,
-                               draws=None if draws is None else iter(draws), quantiles=qmaps)
-        if tracer is not None:
-            tracer.write(out_path, mpath)
-    dist_util.barrier()
-    logger.log("Full image denoising complete")
+    if rank != 0:
+        return None
+    logger.log("Reconstructing full image with Hann window blending...")
+    return dict(_stitched_volumes(args, stitcher), trace=None if tracer is None else tracer.write)
+
+
+def _stitched_volumes(args, stitcher):
+    """Rank 0: the stitcher's accumulators -> the volumes _write_outputs takes, all (H, W, Z) on the file's grid:
+    result, weight (the Hann weight sum, or with --model_spacing regrid.keep_after's mask), and with K >= 2 draws
+    std, draws (the K stitched draws, one volume at a time) and qmaps (_quantile_maps)."""
+    K = args.num_draws
+    if K == 1:
+        result, weight = stitcher.finish_single()
+        return {"result": _regrid_back(args, result), "weight": _regrid_keep(args, weight)}
+    mean, std, weight = stitcher.finish()
+    draws = None
+    if _regridding(args):                      # the K draws go back as one stack; moments on the file's grid
+        draws = _regrid_back(args, th.stack([stitcher.draw(k) for k in range(K)]))
+        mean, std = uncertainty.draw_moments(draws)
+        weight = _regrid_keep(args, weight)
+    qmaps = _quantile_maps(args, stitcher, draws)
+    covered = std[weight > 0]
+    logger.log(f"  Mean per-voxel std over {K} draws (voxels of non-zero weight): "
+               f"{float(covered.double().mean()) if covered.numel() else 0.0:.6f}")
+    return {"result": mean, "std": std, "weight": weight, "qmaps": qmaps,
+            "draws": (stitcher.draw(k) for k in range(K)) if draws is None else iter(draws)}
+
+
+def _write_outputs(args, native, target, roi, result, std=None, weight=None, draws=None, qmaps=None, trace=None):
+    """Rank 0, every path: denoised_<name>.npz (arr_0 [+ std, quantiles, quantile_levels], (H, W, Z) like the
+    reference), for .tif input denoised_<name>.tif [+ _std.tif] as (Z, H, W) float32 without scaling, then the
+    metrics file and the trace file (trace(out_path, metrics_path) writes it).  native is the (D, H, W) input on the
+    file's grid; result and std come as (H, W, Z) host arrays or device tensors and go on as host arrays.
+    -> the .npz's path"""
+    host = lambda x: x.cpu().numpy() if isinstance(x, th.Tensor) else x
+    result, std = host(result), host(std)
+    logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
+    out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
+    logger.log(f"saving to {out_path}")
+    np.savez(out_path, result, **({} if std is None else {"std": std}), **_quantile_arrays(args, qmaps))
+    if args.base_samples.lower().endswith((".tif", ".tiff")):
+        from guided_diffusion import tiff_io
+        for path, x in ((out_path.replace(".npz", ".tif"), result), (out_path.replace(".npz", "_std.tif"), std)):
+            if x is not None:
+                tiff_io.imwrite(path, x.transpose(2, 0, 1).astype(np.float32))       # (H,W,Z) -> (Z,H,W)
+                logger.log(f"Saved TIFF: {path}")
+    mpath = _write_metrics(args, out_path, target, native, result, std=std, weight=weight, roi=roi, draws=draws,
+                           quantiles=qmaps)
+    if trace is not None:
+        trace(out_path, mpath)
     return out_path
 
 
-def _main_joint(args, model, diffusion, vol, target=None, roi=None):
+def _main_joint(args, model, diffusion, vol, target=None):
     """--joint_patches True: every rank holds the whole canvas and runs its share of each step's forwards
-    (joint.sample_loop_progressive); rank 0 writes the canvas cropped to the volume, (H, W, Z) like the other paths.
-    With --num_draws K >= 2 the K canvases are reduced to the per-voxel mean and sample std."""
-    rank = dist_util.rank()
+    (joint.sample_loop_progressive); rank 0 crops the canvas to the volume.  With --num_draws K >= 2 the K canvases
+    are reduced to the per-voxel mean and sample std.  -> _write_outputs' volumes on rank 0, None on the others."""
     K, res = args.num_draws, args.large_size
     geom = patches.joint_geometry(vol.shape, res, min_overlap=args.patch_overlap if args.patch_overlap >= 0 else None)
     logger.log(f"volume {vol.shape}: {geom.n_patches} patches of {res}^3, sampled jointly on a {geom.canvas} canvas")
-    more = {}
+    more, out = {}, {}
     if args.trace:
         more["trace"] = trace = _canvas_trace(args, vol, target, geom)
+        out["trace"] = lambda out_path, mpath: _write_trace(args, out_path, mpath, "canvas", trace.records(),
+                                                            trace.t, target is not None)
     if args.device_noise:
         more["noise_key"] = joint.draw_key(args.noise_seed, K, dist_util.dev())
     sample = joint.sample_loop(diffusion, model, vol, geom, kind="ddim" if args.use_ddim else "ddpm", num_draws=K,
                                batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
                                device=dist_util.dev(), **more)
+    if dist_util.rank() != 0:
+        return None
     draws = sample[:, :vol.shape[0], :vol.shape[1], :vol.shape[2]].contiguous()     # (K, D, H, W)
-    native = vol
     if _regridding(args):
-        native = args.regrid["native"]
         draws = regrid.apply(draws, args.regrid["plan"].inverse())                  # the K draws back as one stack
-    extra = {}
-    if K > 1:
-        mean, std = uncertainty.draw_moments(draws)
-        extra["std"] = std.permute(1, 2, 0).cpu().numpy()
-        logger.log(f"  Mean per-voxel std over {K} draws: {float(std.double().mean()):.6f}")
-    else:
-        mean = draws[0]
-    result = mean.permute(1, 2, 0).cpu().numpy()                              # (D, H, W) -> (H, W, Z)
-    logger.log(f"  Original std: {float(native.std()):.4f}  Denoised std: {float(result.std()):.4f}")
-    out_path = None
-    if rank == 0:
-        qmaps = _quantile_maps(args, draws=draws, to_hwz=(1, 2, 0)) if K > 1 else None
-        extra.update(_quantile_arrays(args, qmaps))
-        out_path = os.path.join(logger.get_dir(), f"denoised_{_base_name(args.base_samples)}.npz")
-        logger.log(f"saving to {out_path}")
-        np.savez(out_path, result, **extra)                                   # arr_0 [+ std], (H,W,Z)
-        if args.base_samples.lower().endswith((".tif", ".tiff")):
-            from guided_diffusion import tiff_io
-            tiff_path = out_path.replace(".npz", ".tif")
-            tiff_io.imwrite(tiff_path, result.transpose(2, 0, 1).astype(np.float32))
-            if K > 1:
-                tiff_io.imwrite(out_path.replace(".npz", "_std.tif"),
-                                extra["std"].transpose(2, 0, 1).astype(np.float32))
-            logger.log(f"Saved denoised TIFF: {tiff_path}")
-        mpath = _write_metrics(args, out_path, target, native, result, std=extra.get("std"), roi=roi,
-                               draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)) if K > 1 else None,
-                               quantiles=qmaps)
-        if args.trace:
-            _write_trace(args, out_path, mpath, "canvas", trace.records(), trace.t, target is not None)
-    dist_util.barrier()
-    logger.log("Full image denoising complete")
-    return out_path
+    if K == 1:
+        return dict(out, result=draws[0].permute(1, 2, 0))                          # (D, H, W) -> (H, W, Z)
+    mean, std = uncertainty.draw_moments(draws)
+    logger.log(f"  Mean per-voxel std over {K} draws: {float(std.double().mean()):.6f}")
+    return dict(out, result=mean.permute(1, 2, 0), std=std.permute(1, 2, 0),
+                draws=(draws[k].permute(1, 2, 0).contiguous() for k in range(K)),
+                qmaps=_quantile_maps(args, draws=draws, to_hwz=(1, 2, 0)))
 
 
 if __name__ == "__main__":

@@ -354,7 +354,7 @@ def test_script_segments_the_target(extra, draws, seg, tmp_path, monkeypatch, ca
             raise AssertionError("the script went on to sample")
 
         monkeypatch.setattr(mod, "_sampler", sampled)
-        monkeypatch.setattr(mod, "_main_sliding", sampled)
+        monkeypatch.setattr(mod, "_run_patches", sampled)
         monkeypatch.setattr(mod, "_main_joint", sampled)
         capsys.readouterr()
         with pytest.raises(SystemExit) as e:
