@@ -483,7 +483,7 @@ int ddpm3d_p_sample_step(const float* model_out, const float* x, const float* no
                          float* pred_xstart, void* stream) {
     if (!step_args_ok(model_out, x, noise, coef, t_idx, N, voxels, sample))
         return fail(DDPM3D_EINVAL, "p_sample_step: bad arguments");
-    return launched(ddpm3d_launch_sample_step(false, model_out, x, noise, nullptr, coef, t_idx, N, voxels, flags, 0.0f,
+    return launched(ddpm3d_launch_sample_step(false, model_out, nullptr, x, noise, nullptr, coef, t_idx, N, voxels, flags, 0.0f,
                                               sample, pred_xstart, (hipStream_t)stream),
                     "p_sample_step");
 }
@@ -493,7 +493,7 @@ int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise,
                      float* pred_xstart, void* stream) {
     if (!step_args_ok(model_out, x, noise, coef, t_idx, N, voxels, sample))
         return fail(DDPM3D_EINVAL, "ddim_step: bad arguments");
-    return launched(ddpm3d_launch_sample_step(true, model_out, x, noise, nullptr, coef, t_idx, N, voxels, flags, eta,
+    return launched(ddpm3d_launch_sample_step(true, model_out, nullptr, x, noise, nullptr, coef, t_idx, N, voxels, flags, eta,
                                               sample, pred_xstart, (hipStream_t)stream),
                     "ddim_step");
 }
@@ -603,7 +603,7 @@ static int dpm_solver_step_any(const float* model_out, const float* x, const flo
     if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d is not 1, 2 or 3", order);
     if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
         return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d needs %d earlier x0 predictions", order, order - 1);
-    return launched(ddpm3d_launch_dpm_solver_step(model_out, x, x0_prev1, x0_prev2, noise, key, coef, scoef, t_idx, N,
+    return launched(ddpm3d_launch_dpm_solver_step(model_out, nullptr, x, x0_prev1, x0_prev2, noise, key, coef, scoef, t_idx, N,
                                                   voxels, T, flags, order, sample, pred_xstart, (hipStream_t)stream),
                     "dpm_solver_step");
 }
@@ -664,7 +664,7 @@ int ddpm3d_p_sample_step_keyed(const float* model_out, const float* x, const ddp
     if (rc != DDPM3D_OK) return rc;
     if (!model_out || !x || !coef || !t_idx || !sample)
         return fail(DDPM3D_EINVAL, "p_sample_step_keyed: bad arguments");
-    return launched(ddpm3d_launch_sample_step(false, model_out, x, nullptr, key, coef, t_idx, N, voxels, flags, 0.0f,
+    return launched(ddpm3d_launch_sample_step(false, model_out, nullptr, x, nullptr, key, coef, t_idx, N, voxels, flags, 0.0f,
                                               sample, pred_xstart, (hipStream_t)stream),
                     "p_sample_step_keyed");
 }
@@ -675,7 +675,7 @@ int ddpm3d_ddim_step_keyed(const float* model_out, const float* x, const ddpm3d_
     const int rc = noise_key_ok("ddim_step_keyed", key, N, voxels, true);
     if (rc != DDPM3D_OK) return rc;
     if (!model_out || !x || !coef || !t_idx || !sample) return fail(DDPM3D_EINVAL, "ddim_step_keyed: bad arguments");
-    return launched(ddpm3d_launch_sample_step(true, model_out, x, nullptr, key, coef, t_idx, N, voxels, flags, eta,
+    return launched(ddpm3d_launch_sample_step(true, model_out, nullptr, x, nullptr, key, coef, t_idx, N, voxels, flags, eta,
                                               sample, pred_xstart, (hipStream_t)stream),
                     "ddim_step_keyed");
 }
@@ -1143,9 +1143,26 @@ size_t ddpm3d_gauss_smooth_workspace_bytes(int D, int H, int W) {
     return baseline_shape_ok(D, H, W) ? (((size_t)D * H * W * sizeof(float) + 15) & ~(size_t)15) : 0;
 }
 
+// the radii (0..DDPM3D_SMOOTH_MAX_RADIUS) and the host tap tables (positive, finite, symmetric) of a Gaussian entry
+static int smooth_taps_ok(const char* what, const int radii[3], const float* const taps[3]) {
+    const int R = DDPM3D_SMOOTH_MAX_RADIUS;
+    for (int a = 0; a < 3; ++a) {
+        if (radii[a] < 0 || radii[a] > R)
+            return fail(DDPM3D_EINVAL, "%s: radii r0=%d r1=%d r2=%d (0..%d)", what, radii[0], radii[1], radii[2], R);
+        const int n = 2 * radii[a] + 1;
+        for (int j = 0; j < n; ++j) {
+            const float t = taps[a][j];
+            if (!(t > 0.0f) || t > 3.402823466e38f)
+                return fail(DDPM3D_EINVAL, "%s: taps%d[%d]=%g (positive and finite)", what, a, j, (double)t);
+            if (t != taps[a][n - 1 - j])
+                return fail(DDPM3D_EINVAL, "%s: taps%d is not symmetric (at [%d])", what, a, j);
+        }
+    }
+    return DDPM3D_OK;
+}
+
 int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, int r2, const float* taps0,
                         const float* taps1, const float* taps2, float* out, void* ws, size_t ws_bytes, void* stream) {
-    const int R = DDPM3D_SMOOTH_MAX_RADIUS;
     if (!vol || !out || !taps0 || !taps1 || !taps2) return fail(DDPM3D_EINVAL, "gauss_smooth: null pointer");
     if (vol == out) return fail(DDPM3D_EINVAL, "gauss_smooth: out must not be vol (every voxel is read by its neighbours)");
     if (!baseline_shape_ok(D, H, W))
@@ -1153,19 +1170,8 @@ int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, i
                     D, H, W);
     const int radii[3] = {r0, r1, r2};
     const float* taps[3] = {taps0, taps1, taps2};
-    for (int a = 0; a < 3; ++a) {
-        if (radii[a] < 0 || radii[a] > R)
-            return fail(DDPM3D_EINVAL, "gauss_smooth: radii r0=%d r1=%d r2=%d (0..%d)", r0, r1, r2, R);
-        const int n = 2 * radii[a] + 1;
-        for (int j = 0; j < n; ++j) {
-            const float t = taps[a][j];
-            if (!(t > 0.0f) || t > 3.402823466e38f)
-                return fail(DDPM3D_EINVAL, "gauss_smooth: taps%d[%d]=%g (positive and finite)", a, j, (double)t);
-            if (t != taps[a][n - 1 - j])
-                return fail(DDPM3D_EINVAL, "gauss_smooth: taps%d is not symmetric (at [%d])", a, j);
-        }
-    }
-    const int rc = metric_ws_ok("gauss_smooth", ddpm3d_gauss_smooth_workspace_bytes(D, H, W), ws, ws_bytes);
+    int rc = smooth_taps_ok("gauss_smooth", radii, taps);
+    if (rc == DDPM3D_OK) rc = metric_ws_ok("gauss_smooth", ddpm3d_gauss_smooth_workspace_bytes(D, H, W), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     if (ws == (const void*)vol || ws == (void*)out)
         return fail(DDPM3D_EINVAL, "gauss_smooth: the workspace must be neither vol nor out");
@@ -1268,6 +1274,107 @@ int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_reg
         ranges_overlap(ws, regrid_ws_bytes(B, stage), out, out_bytes))
         return fail(DDPM3D_EINVAL, "regrid: the workspace overlaps vol or out");
     return launched(ddpm3d_launch_regrid(vol, B, D, H, W, axes, out, (float*)ws, (hipStream_t)stream), "regrid");
+}
+
+// ------------------------------------------------- low-pass pull of x_start and the steps that take x0 (added within ABI 13)
+static bool pull_shape_ok(int N, int D, int H, int W) {
+    return N >= 1 && N <= 65535 && baseline_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;
+}
+
+size_t ddpm3d_xstart_pull_workspace_bytes(int N, int D, int H, int W) {
+    return pull_shape_ok(N, D, H, W) ? (((size_t)N * D * H * W * sizeof(float) + 15) & ~(size_t)15) : 0;
+}
+
+int ddpm3d_xstart_pull(const float* model_out, const float* x, const float* measurement, const float* coef,
+                       const int64_t* t_idx, int N, int D, int H, int W, int T, int flags, float weight, int r0, int r1,
+                       int r2, const float* taps0, const float* taps1, const float* taps2, float* xstart_out, void* ws,
+                       size_t ws_bytes, void* stream) {
+    if (!model_out || !x || !measurement || !coef || !t_idx || !xstart_out || !taps0 || !taps1 || !taps2)
+        return fail(DDPM3D_EINVAL, "xstart_pull: null pointer");
+    if (!pull_shape_ok(N, D, H, W) || T < 1)
+        return fail(DDPM3D_EINVAL, "xstart_pull: bad shape (N=%d D=%d H=%d W=%d T=%d; 1 or more each, N <= 65535, "
+                                   "N * D * H * W <= 2^31 - 1)", N, D, H, W, T);
+    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "xstart_pull: unknown flag bits %#x", flags);
+    if (!(weight >= 0.0f && weight <= 1.0f))
+        return fail(DDPM3D_EINVAL, "xstart_pull: weight %g outside [0, 1]", (double)weight);
+    const int radii[3] = {r0, r1, r2};
+    const float* taps[3] = {taps0, taps1, taps2};
+    const size_t need = ddpm3d_xstart_pull_workspace_bytes(N, D, H, W);
+    int rc = smooth_taps_ok("xstart_pull", radii, taps);
+    if (rc == DDPM3D_OK) rc = metric_ws_ok("xstart_pull", need, ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    const size_t bytes = (size_t)N * D * H * W * sizeof(float);
+    const size_t mo_bytes = bytes * ((flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1);
+    if (ranges_overlap(xstart_out, bytes, model_out, mo_bytes) || ranges_overlap(xstart_out, bytes, x, bytes) ||
+        ranges_overlap(xstart_out, bytes, measurement, bytes))
+        return fail(DDPM3D_EINVAL, "xstart_pull: xstart_out overlaps an input (every voxel is read by its neighbours)");
+    if (ranges_overlap(ws, need, xstart_out, bytes) || ranges_overlap(ws, need, model_out, mo_bytes) ||
+        ranges_overlap(ws, need, x, bytes) || ranges_overlap(ws, need, measurement, bytes))
+        return fail(DDPM3D_EINVAL, "xstart_pull: the workspace overlaps a tensor of the call");
+    return launched(ddpm3d_launch_xstart_pull(model_out, x, measurement, coef, t_idx, N, D, H, W, T, flags, weight,
+                                              radii, taps, xstart_out, (float*)ws, (hipStream_t)stream),
+                    "xstart_pull");
+}
+
+// what the three *_step_x0 entries share: the pointers, the outputs apart from each other and from what is read, the
+// flags, the noise source (`noise_count`: how many of noise and key must be given, -1 for at most one)
+static int step_x0_ok(const char* what, const float* model_out, const float* xstart, const float* x, const float* noise,
+                      const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                      int flags, bool reads_variance, bool ode_allowed, const float* sample, const float* pred_xstart) {
+    if (!xstart || !x || !coef || !t_idx || !sample) return fail(DDPM3D_EINVAL, "%s: null pointer", what);
+    if (N < 1 || N > 65535 || voxels < 1) return fail(DDPM3D_EINVAL, "%s: bad arguments (N=%d voxels=%d)", what, N, voxels);
+    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "%s: unknown flag bits %#x", what, flags);
+    if (reads_variance && (flags & DDPM3D_F_LEARN_SIGMA) && !model_out)
+        return fail(DDPM3D_EINVAL, "%s: F_LEARN_SIGMA reads model_out's second half: model_out is NULL", what);
+    if (noise && key) return fail(DDPM3D_EINVAL, "%s: noise and key both name the noise: one of them must be NULL", what);
+    if (!noise && !key && !ode_allowed) return fail(DDPM3D_EINVAL, "%s: one of noise and key must be given", what);
+    if (sample == pred_xstart || sample == xstart || sample == x || sample == noise || sample == model_out ||
+        (pred_xstart && (pred_xstart == xstart || pred_xstart == x || pred_xstart == noise || pred_xstart == model_out)))
+        return fail(DDPM3D_EINVAL, "%s: sample and pred_xstart must be tensors of their own", what);
+    if (key) return noise_key_ok(what, key, N, voxels, true);
+    return DDPM3D_OK;
+}
+
+int ddpm3d_p_sample_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
+                            const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                            int flags, float* sample, float* pred_xstart, void* stream) {
+    const int rc = step_x0_ok("p_sample_step_x0", model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags, true,
+                              false, sample, pred_xstart);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_sample_step(false, model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags,
+                                              0.0f, sample, pred_xstart, (hipStream_t)stream),
+                    "p_sample_step_x0");
+}
+
+int ddpm3d_ddim_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
+                        const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                        int flags, float eta, float* sample, float* pred_xstart, void* stream) {
+    const int rc = step_x0_ok("ddim_step_x0", model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags, false,
+                              false, sample, pred_xstart);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_sample_step(true, model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags, eta,
+                                              sample, pred_xstart, (hipStream_t)stream),
+                    "ddim_step_x0");
+}
+
+int ddpm3d_dpm_solver_step_x0(const float* model_out, const float* xstart, const float* x, const float* x0_prev1,
+                              const float* x0_prev2, const float* noise, const ddpm3d_noise_key* key,
+                              const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels, int T,
+                              int flags, int order, float* sample, float* pred_xstart, void* stream) {
+    const int rc = step_x0_ok("dpm_solver_step_x0", model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags,
+                              false, true, sample, pred_xstart);
+    if (rc != DDPM3D_OK) return rc;
+    if (!scoef || !pred_xstart || T < 1)
+        return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: bad arguments (scoef, pred_xstart or T=%d)", T);
+    if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: order %d is not 1, 2 or 3", order);
+    if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
+        return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: order %d needs %d earlier x0 predictions", order, order - 1);
+    if (sample == x0_prev1 || sample == x0_prev2 || pred_xstart == x0_prev1 || pred_xstart == x0_prev2)
+        return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: sample and pred_xstart must be tensors of their own");
+    return launched(ddpm3d_launch_dpm_solver_step(model_out, xstart, x, x0_prev1, x0_prev2, noise, key, coef, scoef,
+                                                  t_idx, N, voxels, T, flags, order, sample, pred_xstart,
+                                                  (hipStream_t)stream),
+                    "dpm_solver_step_x0");
 }
 
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }

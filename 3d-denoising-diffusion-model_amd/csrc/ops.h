@@ -22,9 +22,10 @@ hipError_t ddpm3d_launch_transpose(const float* in, int N, int R, int S, float* 
 hipError_t ddpm3d_launch_to_ndhwc_pad(const float* in, int N, int C, int voxels, int Cpad, float* out, hipStream_t st);
 hipError_t ddpm3d_launch_subsample_hw2(const float* in, int N, int D, int H, int W, int C, float* out,
                                        hipStream_t st);
-// the step launchers that read noise take it from `key` (noise.h) when one is given, from the tensor otherwise
+// the step launchers that read noise take it from `key` (noise.h) when one is given, from the tensor otherwise; with
+// a non-NULL xs (the *_step_x0 entries) x0 is xs, not derived from mo's first half
 struct ddpm3d_noise_key;
-hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
+hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* xs, const float* x, const float* noise,
                                      const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N,
                                      int voxels, int flags, float eta, float* sample, float* pred_xstart,
                                      hipStream_t st);
@@ -37,10 +38,11 @@ hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, cons
                                            hipStream_t st);
 // one DPM-Solver++ multistep step; scoef = [T][DDPM3D_NSCOEF] weights, m1 / m2 read at order >= 2 / 3, noise may be
 // NULL; t outside [0, T) gives NaN
-hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* x, const float* m1, const float* m2,
-                                         const float* noise, const ddpm3d_noise_key* key, const float* coef,
-                                         const float* scoef, const int64_t* t_idx, int N, int voxels, int T, int flags,
-                                         int order, float* sample, float* pred_xstart, hipStream_t st);
+hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* xs, const float* x, const float* m1,
+                                         const float* m2, const float* noise, const ddpm3d_noise_key* key,
+                                         const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels,
+                                         int T, int flags, int order, float* sample, float* pred_xstart,
+                                         hipStream_t st);
 // variational bound (calc_bpd_loop): ws holds ddpm3d_vb_parts(voxels) 32-byte records per sample
 int ddpm3d_vb_parts(int voxels);
 hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const ddpm3d_noise_key* key, const float* qcoef,
@@ -122,6 +124,12 @@ void ddpm3d_sphere_mean_tile(int r0, int r1, int rw, bool keep, int* TD, int* TH
 // (D, H, W order, 0..DDPM3D_SMOOTH_MAX_RADIUS), the three host tap tables and the workspace of one volume)
 hipError_t ddpm3d_launch_gauss_smooth(const float* vol, int D, int H, int W, const int* radii, const float* const* taps,
                                       float* out, float* ws, hipStream_t st);
+// guide.hip: x0 = clip(x0_raw + weight * G(y - x0_raw)) of N samples, G as above and batched (the caller has checked
+// the shape, the radii, the taps, the weight and the workspace of N volumes); t outside [0, T) gives NaN
+hipError_t ddpm3d_launch_xstart_pull(const float* mo, const float* x, const float* y, const float* coef,
+                                     const int64_t* t_idx, int N, int D, int H, int W, int T, int flags, float weight,
+                                     const int* radii, const float* const* taps, float* out, float* ws,
+                                     hipStream_t st);
 // nlm.hip: non-local means of one volume (the caller has checked the shape and the radii); the weight of a candidate
 // is exp(-max(fma(sum of squared patch differences, k1, -k2), 0)), k1 = 1 / (n_p h^2), k2 = 2 sigma^2 / h^2
 hipError_t ddpm3d_launch_nlm(const float* vol, int D, int H, int W, const int* search, const int* patch, float k1,

@@ -741,6 +741,15 @@ __device__ __forceinline__ float step_x0(float xv, float e, float c_recip, float
     return x0;
 }
 
+// X0 selects a step kernel's x0 source: the model output's first half (step_x0), or a finished x0 the caller passes
+// (the *_step_x0 entries: xs, e.g. ddpm3d_xstart_pull's output), clipped once more under F_CLIP -- the clip is idempotent
+template <bool X0>
+__device__ __forceinline__ float step_x0_from(const float* __restrict__ mo, const float* __restrict__ xs, size_t i,
+                                              size_t first_half, float xv, float c_recip, float c_recipm1, int flags) {
+    if (X0) return step_x0(xv, xs[i], c_recip, c_recipm1, flags | DDPM3D_F_PREDICT_XSTART);
+    return step_x0(xv, mo[first_half], c_recip, c_recipm1, flags);
+}
+
 // LEARNED_RANGE: the model's second half vv in [-1, 1] between the two log-variances
 __device__ __forceinline__ float learned_logvar(float vv, float min_log, float max_log) {
     const float frac = (vv + 1.0f) / 2.0f;                      // :274
@@ -775,9 +784,9 @@ static dim3 step_grid(int N, int voxels) {
 
 // Noise: where the step's normal comes from (noise.h) -- the caller's tensor, or the keyed function.  A keyed sample
 // whose patch leaves the canvas gets step_nan_fill.
-template <bool DDIM, class Noise>
+template <bool DDIM, class Noise, bool X0 = false>
 __global__ __launch_bounds__(256) void sample_step_kernel(
-    const float* __restrict__ mo, const float* __restrict__ x, const Noise noise,
+    const float* __restrict__ mo, const float* __restrict__ xs, const float* __restrict__ x, const Noise noise,
     const float* __restrict__ coef, const int64_t* __restrict__ t_idx, int voxels, int flags, float eta,
     float* __restrict__ sample, float* __restrict__ pred_xstart) {
     const int n = blockIdx.y;
@@ -799,7 +808,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += gridDim.x * blockDim.x) {
         const size_t i = (size_t)n * voxels + v;
         const float xv = x[i];
-        const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
+        const float x0 = step_x0_from<X0>(mo, xs, i, ((size_t)n * ch) * voxels + v, xv, c_recip, c_recipm1, flags);
         float out;
         if (!DDIM) {
             const float logvar = learn ? learned_logvar(mo[((size_t)n * ch + 1) * voxels + v], min_log, max_log)
@@ -817,27 +826,37 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     }
 }
 
-template <class Noise>
-static hipError_t launch_sample_step(bool ddim, const float* mo, const float* x, const Noise noise, const float* coef,
-                                     const int64_t* t_idx, int N, int voxels, int flags, float eta, float* sample,
-                                     float* pred_xstart, hipStream_t st) {
-    if (ddim)
-        hipLaunchKernelGGL((sample_step_kernel<true, Noise>), step_grid(N, voxels), dim3(256), 0, st, mo, x, noise,
-                           coef, t_idx, voxels, flags, eta, sample, pred_xstart);
+template <bool DDIM, class Noise>
+static hipError_t launch_sample_step_from(const float* mo, const float* xs, const float* x, const Noise noise,
+                                          const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
+                                          float eta, float* sample, float* pred_xstart, hipStream_t st) {
+    if (xs != nullptr)
+        hipLaunchKernelGGL((sample_step_kernel<DDIM, Noise, true>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x,
+                           noise, coef, t_idx, voxels, flags, eta, sample, pred_xstart);
     else
-        hipLaunchKernelGGL((sample_step_kernel<false, Noise>), step_grid(N, voxels), dim3(256), 0, st, mo, x, noise,
-                           coef, t_idx, voxels, flags, eta, sample, pred_xstart);
+        hipLaunchKernelGGL((sample_step_kernel<DDIM, Noise, false>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x,
+                           noise, coef, t_idx, voxels, flags, eta, sample, pred_xstart);
     return hipGetLastError();
 }
 
-hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* x, const float* noise,
+template <class Noise>
+static hipError_t launch_sample_step(bool ddim, const float* mo, const float* xs, const float* x, const Noise noise,
+                                     const float* coef, const int64_t* t_idx, int N, int voxels, int flags, float eta,
+                                     float* sample, float* pred_xstart, hipStream_t st) {
+    if (ddim)
+        return launch_sample_step_from<true>(mo, xs, x, noise, coef, t_idx, N, voxels, flags, eta, sample, pred_xstart,
+                                             st);
+    return launch_sample_step_from<false>(mo, xs, x, noise, coef, t_idx, N, voxels, flags, eta, sample, pred_xstart, st);
+}
+
+hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* xs, const float* x, const float* noise,
                                      const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N,
                                      int voxels, int flags, float eta, float* sample, float* pred_xstart,
                                      hipStream_t st) {
     if (key != nullptr)
-        return launch_sample_step(ddim, mo, x, KeyNoise{noise_key_dev(*key)}, coef, t_idx, N, voxels, flags, eta,
+        return launch_sample_step(ddim, mo, xs, x, KeyNoise{noise_key_dev(*key)}, coef, t_idx, N, voxels, flags, eta,
                                   sample, pred_xstart, st);
-    return launch_sample_step(ddim, mo, x, TensorNoise{noise}, coef, t_idx, N, voxels, flags, eta, sample,
+    return launch_sample_step(ddim, mo, xs, x, TensorNoise{noise}, coef, t_idx, N, voxels, flags, eta, sample,
                               pred_xstart, st);
 }
 
@@ -926,9 +945,10 @@ hipError_t ddpm3d_launch_ddim_reverse_step(const float* mo, const float* x, cons
 // whose weights the host expanded in fp64 into row t of scoef ([T][DDPM3D_NSCOEF]: c_x, w0, w1, w2, c_z), summed in
 // that order.  m1 is read only at order >= 2, m2 only at order 3, z only when noise is non-null.  A sample whose t
 // lies outside [0, T) reads neither table and gets NaN.
-template <class Noise>
+template <class Noise, bool X0 = false>
 __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
-    const float* __restrict__ mo, const float* __restrict__ x, const float* __restrict__ m1,
+    const float* __restrict__ mo, const float* __restrict__ xs, const float* __restrict__ x,
+    const float* __restrict__ m1,
     const float* __restrict__ m2, const Noise noise, const float* __restrict__ coef,
     const float* __restrict__ scoef, const int64_t* __restrict__ t_idx, int voxels, int T, int flags, int order,
     float* __restrict__ sample, float* __restrict__ pred_xstart) {
@@ -950,7 +970,7 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
     for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < voxels; v += stride) {
         const size_t i = (size_t)n * voxels + v;
         const float xv = x[i];
-        const float x0 = step_x0(xv, mo[((size_t)n * ch) * voxels + v], c_recip, c_recipm1, flags);
+        const float x0 = step_x0_from<X0>(mo, xs, i, ((size_t)n * ch) * voxels + v, xv, c_recip, c_recipm1, flags);
         float out = c_x * xv + w0 * x0;
         if (order >= 2) out = out + w1 * m1[i];
         if (order >= 3) out = out + w2 * m2[i];
@@ -960,18 +980,30 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
     }
 }
 
-hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* x, const float* m1, const float* m2,
-                                         const float* noise, const ddpm3d_noise_key* key, const float* coef,
-                                         const float* scoef, const int64_t* t_idx, int N, int voxels, int T, int flags,
-                                         int order, float* sample, float* pred_xstart, hipStream_t st) {
-    if (key != nullptr)
-        hipLaunchKernelGGL(dpm_solver_step_kernel<KeyNoise>, step_grid(N, voxels), dim3(256), 0, st, mo, x, m1, m2,
-                           KeyNoise{noise_key_dev(*key)}, coef, scoef, t_idx, voxels, T, flags, order, sample,
-                           pred_xstart);
+template <class Noise>
+static hipError_t launch_dpm_solver_step(const float* mo, const float* xs, const float* x, const float* m1,
+                                         const float* m2, const Noise noise, const float* coef, const float* scoef,
+                                         const int64_t* t_idx, int N, int voxels, int T, int flags, int order,
+                                         float* sample, float* pred_xstart, hipStream_t st) {
+    if (xs != nullptr)
+        hipLaunchKernelGGL((dpm_solver_step_kernel<Noise, true>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x, m1,
+                           m2, noise, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
     else
-        hipLaunchKernelGGL(dpm_solver_step_kernel<TensorNoise>, step_grid(N, voxels), dim3(256), 0, st, mo, x, m1, m2,
-                           TensorNoise{noise}, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
+        hipLaunchKernelGGL((dpm_solver_step_kernel<Noise, false>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x, m1,
+                           m2, noise, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
     return hipGetLastError();
+}
+
+hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* xs, const float* x, const float* m1,
+                                         const float* m2, const float* noise, const ddpm3d_noise_key* key,
+                                         const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels,
+                                         int T, int flags, int order, float* sample, float* pred_xstart,
+                                         hipStream_t st) {
+    if (key != nullptr)
+        return launch_dpm_solver_step(mo, xs, x, m1, m2, KeyNoise{noise_key_dev(*key)}, coef, scoef, t_idx, N, voxels,
+                                      T, flags, order, sample, pred_xstart, st);
+    return launch_dpm_solver_step(mo, xs, x, m1, m2, TensorNoise{noise}, coef, scoef, t_idx, N, voxels, T, flags, order,
+                                  sample, pred_xstart, st);
 }
 
 // ------------------------------------------------------- variational bound

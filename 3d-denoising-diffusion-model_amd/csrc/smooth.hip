@@ -9,40 +9,17 @@
 #include <stdint.h>
 #include "ddpm3d.h"
 #include "ops.h"
+#include "smooth_pass.h"
 
 namespace {
 
-constexpr int SMOOTH_THREADS = 256;
-constexpr int SMOOTH_TAPS = 2 * DDPM3D_SMOOTH_MAX_RADIUS + 1;
-
-struct SmoothArgs {
-    int64_t voxels;
-    int64_t stride;                                           // words between neighbours along the pass's axis
-    int L;                                                    // the extent along it
-    int r;
-    float taps[SMOOTH_TAPS];                                  // taps[j + r], j = -r..r
-    double prefix[SMOOTH_TAPS + 1];                           // prefix[k] = taps[0] + ... + taps[k - 1] in fp64
-};
-
 __global__ __launch_bounds__(SMOOTH_THREADS) void gauss_pass_kernel(const float* __restrict__ in,
                                                                     float* __restrict__ out, const SmoothArgs a) {
-    __shared__ double s_prefix[SMOOTH_TAPS + 1];              // read with a per-lane index at the faces
-    for (int i = threadIdx.x; i <= 2 * a.r + 1; i += SMOOTH_THREADS) s_prefix[i] = a.prefix[i];
-    __syncthreads();
+    __shared__ double s_prefix[SMOOTH_TAPS + 1];
+    smooth_stage_prefix(a, s_prefix);
     const int64_t i = (int64_t)blockIdx.x * SMOOTH_THREADS + threadIdx.x;
     if (i >= a.voxels) return;
-    const int c = (int)((i / a.stride) % a.L);
-    const int lo = c < a.r ? -c : -a.r, hi = a.L - 1 - c < a.r ? a.L - 1 - c : a.r;   // the counted offsets
-    float acc = 0.0f;
-    for (int j = -a.r; j <= a.r; ++j) {                       // the same trip count for all lanes; taps[] is scalar
-        const bool counted = j >= lo && j <= hi;
-        const float x = counted ? in[i + (int64_t)j * a.stride] : 0.0f;
-        const float t = a.taps[j + a.r];
-        const float next = j == lo ? t * x : __builtin_fmaf(t, x, acc);
-        acc = counted ? next : acc;
-    }
-    const float den = (float)(s_prefix[hi + a.r + 1] - s_prefix[lo + a.r]);
-    out[i] = acc / den;
+    out[i] = smooth_pass_value(a, s_prefix, i, [&](int64_t k) { return in[k]; });
 }
 
 }  // namespace
@@ -67,13 +44,8 @@ hipError_t ddpm3d_launch_gauss_smooth(const float* vol, int D, int H, int W, con
     for (int k = 0; k < 3; ++k) {
         if (axis_r[k] == 0) continue;
         SmoothArgs a;
-        a.voxels = voxels, a.stride = axis_stride[k], a.L = axis_len[k], a.r = axis_r[k];
-        const int n = 2 * a.r + 1;
-        a.prefix[0] = 0.0;
-        for (int j = 0; j < SMOOTH_TAPS; ++j) {
-            a.taps[j] = j < n ? axis_t[k][j] : 0.0f;
-            a.prefix[j + 1] = a.prefix[j] + (double)a.taps[j];
-        }
+        a.voxels = voxels, a.stride = axis_stride[k], a.L = axis_len[k];
+        smooth_args_taps(a, axis_r[k], axis_t[k]);
         const unsigned blocks = (unsigned)((voxels + SMOOTH_THREADS - 1) / SMOOTH_THREADS);   // at most 2^23
         hipLaunchKernelGGL(gauss_pass_kernel, dim3(blocks), dim3(SMOOTH_THREADS), 0, st, src, dst[done], a);
         const hipError_t e = hipGetLastError();

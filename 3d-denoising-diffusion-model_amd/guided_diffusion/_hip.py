@@ -253,6 +253,15 @@ EXPORTS = {
     "ddpm3d_dpm_solver_step_keyed": (C.c_int, [_fp, _fp, _fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, _fp, C.c_int,
                                                C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
     "ddpm3d_q_sample_keyed": (C.c_int, [_fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ddpm3d_xstart_pull_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ddpm3d_xstart_pull": (C.c_int, [_fp] * 5 + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 3
+                           + [C.POINTER(C.c_float)] * 3 + [_fp, _fp, C.c_size_t, _fp]),
+    "ddpm3d_p_sample_step_x0": (C.c_int, [_fp, _fp, _fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int,
+                                          C.c_int, _fp, _fp, _fp]),
+    "ddpm3d_ddim_step_x0": (C.c_int, [_fp, _fp, _fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                      C.c_float, _fp, _fp, _fp]),
+    "ddpm3d_dpm_solver_step_x0": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, _fp,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
     "ddpm3d_mfma_probe_flops_per_iter": (C.c_double, [C.c_int]),
     "ddpm3d_mfma_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
 }

@@ -380,10 +380,12 @@ class GaussianDiffusion:
         SpacedDiffusion, respace.py:123-128)."""
         return self._scale_timesteps(t)
 
-    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None, noise_key=None, draw=0):
+    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None, noise_key=None, draw=0,
+                xstart=None):
         """One fused reverse step.  `out`: (sample, pred_xstart) tensors of x's shape to write into (the joint loop's
         patch buffers); fresh tensors otherwise.  With `noise_key` the kernel evaluates the key's `draw` itself and
-        `noise` is not read."""
+        `noise` is not read.  With `xstart` (a guide's pulled x0, of x's shape) the step runs on the *_step_x0 entry:
+        x0 is that tensor instead of the model output's first half."""
         lib = H.load()
         N = x.shape[0]
         vox = x[0].numel()
@@ -394,6 +396,9 @@ class GaussianDiffusion:
             self._check_noise(noise, x)
         else:
             kd = noise_key.desc(draw, x)
+        if xstart is not None:
+            H.require_device(xstart, "xstart")
+            assert xstart.shape == x.shape and xstart.device == x.device
         st = self._device_state(x.device)
         sample, x0 = out if out is not None else (th.empty_like(x), th.empty_like(x))
         for name, o in (("out[0] (sample)", sample), ("out[1] (pred_xstart)", x0)):
@@ -401,7 +406,14 @@ class GaussianDiffusion:
             assert o.shape == x.shape and o.device == x.device, "%s: %s on %s for x %s on %s" % (
                 name, tuple(o.shape), o.device, tuple(x.shape), x.device)
         t = t.to(device=x.device, dtype=th.int64).contiguous()
-        if noise_key is not None and kind == "ddpm":
+        if xstart is not None:
+            args = (H.ptr(model_output), H.ptr(xstart), H.ptr(x), H.ptr(noise) if noise_key is None else None,
+                    kd if noise_key is not None else None, H.ptr(st["coef"]), H.ptr(t), N, vox, flags)
+            if kind == "ddpm":
+                H.check(lib.ddpm3d_p_sample_step_x0(*args, H.ptr(sample), H.ptr(x0), H.stream()))
+            else:
+                H.check(lib.ddpm3d_ddim_step_x0(*args, float(eta), H.ptr(sample), H.ptr(x0), H.stream()))
+        elif noise_key is not None and kind == "ddpm":
             H.check(lib.ddpm3d_p_sample_step_keyed(H.ptr(model_output), H.ptr(x), kd, H.ptr(st["coef"]), H.ptr(t), N,
                                                    vox, flags, H.ptr(sample), H.ptr(x0), H.stream()))
         elif noise_key is not None:
@@ -484,27 +496,59 @@ class GaussianDiffusion:
             raise NotImplementedError("denoised_fn / cond_fn are unused by every caller in the reference "
                                       "and are not wired into the fused update kernel")
 
+    # ------------------------------------------------------------------ guide
+    @staticmethod
+    def _guide_measurement(guide, shape, model_kwargs, device=None):
+        """A loop's `guide=` checked before the model runs -> its measurement for batches of `shape` (None: no guide)."""
+        from . import guidance
+        guidance.check_guide(guide)
+        return None if guide is None else guide.resolve(shape, model_kwargs, device)
+
+    def _guided_x0(self, guide, y, model_output, x, t, i, clip_denoised):
+        """The pulled x0 of the step at index i (one ddpm3d_xstart_pull call), or None where the guide is absent or
+        inactive: nothing is launched then and the step is today's."""
+        if guide is None or not guide.active(self, i):
+            return None
+        return guide.apply(model_output, x, t, self._flags(clip_denoised), self, measurement=y)
+
+    def _guided_x0_at(self, guide, model_output, x, t, clip_denoised, model_kwargs):
+        """_guided_x0 for the single-step calls, whose t is a tensor: every sample on the same side of stop_t."""
+        if guide is None:
+            return None
+        y = self._guide_measurement(guide, x.shape, model_kwargs, x.device)
+        on = {guide.active(self, int(v)) for v in self._check_t(t, x.shape[0]).detach().cpu().tolist()}
+        if len(on) != 1:
+            raise ValueError("guide: the batch's timesteps lie on both sides of stop_t=%d" % guide.stop_t)
+        if not on.pop():
+            return None
+        return guide.apply(model_output, x, t, self._flags(clip_denoised), self, measurement=y)
+
     # --------------------------------------------------------------- one step
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                 noise=None, noise_key=None, draw=0):
+                 noise=None, noise_key=None, draw=0, guide=None):
         """gaussian_diffusion.py:395-439.  `noise`: optional injected randn_like draw; `noise_key`, `draw`
-        (extension): the step's noise is that draw of the key, evaluated by the kernel."""
+        (extension): the step's noise is that draw of the key, evaluated by the kernel.  `guide` (extension): a
+        guidance.LowPassPull applied to the x_start prediction where the reference applies denoised_fn (:293-314)."""
         self._reject_hooks(denoised_fn, cond_fn)
         self._check_key(noise_key, noise)
+        self._guide_measurement(guide, x.shape, model_kwargs)
         out = self._call_model(model, x, t, model_kwargs)
         if noise is None and noise_key is None:
             noise = th.randn_like(x)
-        return self._update("ddpm", out, x, t, noise, clip_denoised, noise_key=noise_key, draw=draw)
+        xs = self._guided_x0_at(guide, out, x, t, clip_denoised, model_kwargs)
+        return self._update("ddpm", out, x, t, noise, clip_denoised, noise_key=noise_key, draw=draw, xstart=xs)
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                    eta=0.0, noise=None, noise_key=None, draw=0):
-        """gaussian_diffusion.py:537-585.  `noise_key`, `draw` as in p_sample."""
+                    eta=0.0, noise=None, noise_key=None, draw=0, guide=None):
+        """gaussian_diffusion.py:537-585.  `noise_key`, `draw`, `guide` as in p_sample."""
         self._reject_hooks(denoised_fn, cond_fn)
         self._check_key(noise_key, noise)
+        self._guide_measurement(guide, x.shape, model_kwargs)
         out = self._call_model(model, x, t, model_kwargs)
         if noise is None and noise_key is None:
             noise = th.randn_like(x)
-        return self._update("ddim", out, x, t, noise, clip_denoised, eta, noise_key=noise_key, draw=draw)
+        xs = self._guided_x0_at(guide, out, x, t, clip_denoised, model_kwargs)
+        return self._update("ddim", out, x, t, noise, clip_denoised, eta, noise_key=noise_key, draw=draw, xstart=xs)
 
     # ------------------------------------------------------------------ loops
     def _trace_step(self, trace, res, prev, i):
@@ -516,9 +560,10 @@ class GaussianDiffusion:
         return res["pred_xstart"]
 
     def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-              progress, eta, step_noise, trace=None, noise_key=None):
+              progress, eta, step_noise, trace=None, noise_key=None, guide=None):
         self._reject_hooks(denoised_fn, cond_fn)
         self._check_key(noise_key, step_noise)
+        self._guide_measurement(guide, shape, model_kwargs)            # refused here, before the device is looked at
         if device is None:
             device = next(model.parameters()).device
         device = th.device(device)
@@ -533,12 +578,15 @@ class GaussianDiffusion:
         # leaves nothing changed.
         with th.no_grad(), th.cuda.device(device):
             t_all, net = self._step_model(model, shape, model_kwargs or {}, device)
+            y = self._guide_measurement(guide, shape, model_kwargs, device)
         prev = None                     # the previous step's pred_xstart, kept for `trace` only
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
                 out = net(img, i)
                 z = self._draw_noise(step_noise, k, img) if noise_key is None else None
-                res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta, noise_key=noise_key, draw=k + 1)
+                xs = self._guided_x0(guide, y, out, img, t_all[i], i, clip_denoised)
+                res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta, noise_key=noise_key, draw=k + 1,
+                                   xstart=xs)
                 if trace is not None:
                     prev = self._trace_step(trace, res, prev, i)
             yield res
@@ -554,40 +602,46 @@ class GaussianDiffusion:
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   cond_fn=None, model_kwargs=None, device=None, progress=False,
-                                  step_noise=None, trace=None, noise_key=None):
+                                  step_noise=None, trace=None, noise_key=None, guide=None):
         """gaussian_diffusion.py:487-535.  `step_noise` (extension): a sequence of
         T tensors used instead of randn_like, in draw order, for parity runs.  `trace` (extension, on every loop): a
         metrics.StepTrace that receives one record per step and sample of that step's pred_xstart (one reduction
         per step, nothing waits for the device); None launches nothing more.  `noise_key` (extension, on every loop): a
         NoiseKey of shape[0] streams; x_T is its draw 0 (unless `noise` is given) and step k reads draw k + 1 inside
-        the step kernel -- no noise tensor is created.  Not together with `step_noise`."""
+        the step kernel -- no noise tensor is created.  Not together with `step_noise`.  `guide` (extension, on every
+        sampling loop): a guidance.LowPassPull; on the steps it is active on, the step's x_start prediction is pulled
+        towards the measurement's local means before the clip and the posterior mean (the reference's denoised_fn
+        position, :293-314) by one ddpm3d_xstart_pull call, and pred_xstart (also `trace`'s) is the pulled one.  On the
+        other steps, and with None, nothing more is launched."""
         yield from self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, 0.0, step_noise, trace, noise_key)
+                              device, progress, 0.0, step_noise, trace, noise_key, guide)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, progress=False, step_noise=None, trace=None, noise_key=None):
+                      model_kwargs=None, device=None, progress=False, step_noise=None, trace=None, noise_key=None,
+                      guide=None):
         """gaussian_diffusion.py:441-485."""
         final = None
         for final in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
-                                                    model_kwargs, device, progress, step_noise, trace, noise_key):
+                                                    model_kwargs, device, progress, step_noise, trace, noise_key,
+                                                    guide):
             pass
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None, trace=None, noise_key=None):
+                                     step_noise=None, trace=None, noise_key=None, guide=None):
         """gaussian_diffusion.py:659-707."""
         yield from self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                              device, progress, eta, step_noise, trace, noise_key)
+                              device, progress, eta, step_noise, trace, noise_key, guide)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, trace=None,
-                         noise_key=None):
+                         noise_key=None, guide=None):
         """gaussian_diffusion.py:625-657."""
         final = None
         for final in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
                                                        cond_fn, model_kwargs, device, progress, eta,
-                                                       step_noise, trace, noise_key):
+                                                       step_noise, trace, noise_key, guide):
             pass
         return final["sample"]
 
@@ -848,9 +902,11 @@ class GaussianDiffusion:
         return final["sample"]
 
     # ------------------------------------------------- DPM-Solver++ multistep
-    def _solver_step(self, model_output, x, m1, m2, z, t, flags, order, stochastic, p, noise_key=None, draw=0):
+    def _solver_step(self, model_output, x, m1, m2, z, t, flags, order, stochastic, p, noise_key=None, draw=0,
+                     xstart=None):
         """One ddpm3d_dpm_solver_step launch at effective order p; t: int64 on x's device.  With `noise_key` the keyed
-        entry reads the key's `draw` instead of z."""
+        entry reads the key's `draw` instead of z; with `xstart` (a guide's pulled x0) the *_x0 entry takes it as the
+        data prediction."""
         if z is not None:
             self._check_noise(z, x)
         self._model_step_output(model_output, x, flags)
@@ -858,6 +914,14 @@ class GaussianDiffusion:
         scoef = self._solver_state(x.device, order, stochastic)
         sample = th.empty_like(x)
         x0 = th.empty_like(x)
+        if xstart is not None:
+            H.check(H.load().ddpm3d_dpm_solver_step_x0(H.ptr(model_output), H.ptr(xstart), H.ptr(x), H.ptr(m1),
+                                                       H.ptr(m2), H.ptr(z) if noise_key is None else None,
+                                                       None if noise_key is None else noise_key.desc(draw, x),
+                                                       H.ptr(st["coef"]), H.ptr(scoef), H.ptr(t), x.shape[0],
+                                                       x[0].numel(), self.num_timesteps, flags, p, H.ptr(sample),
+                                                       H.ptr(x0), H.stream()))
+            return {"sample": sample, "pred_xstart": x0}
         if noise_key is not None:
             H.check(H.load().ddpm3d_dpm_solver_step_keyed(H.ptr(model_output), H.ptr(x), H.ptr(m1), H.ptr(m2),
                                                           noise_key.desc(draw, x), H.ptr(st["coef"]), H.ptr(scoef),
@@ -872,7 +936,8 @@ class GaussianDiffusion:
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                            cond_fn=None, model_kwargs=None, device=None, progress=False, order=2,
-                                           stochastic=False, step_noise=None, trace=None, noise_key=None):
+                                           stochastic=False, step_noise=None, trace=None, noise_key=None,
+                                           guide=None):
         """DPM-Solver++ multistep sampling (extension; Lu et al. 2022, arXiv:2211.01095), yielding
         {"sample", "pred_xstart"} per step as ddim_sample_loop_progressive does.  Step k leaves index
         s = T - 1 - k at order min(order, k + 1); the last step returns its pred_xstart.  The weights are
@@ -884,10 +949,12 @@ class GaussianDiffusion:
         The engine path, with model_kwargs == {"low_res"} on a 5-D shape, evaluates the film rows for the whole
         schedule once, then runs one plan replay and one solver launch per step; nothing inside the loop waits
         for the device.  Bad arguments are refused before the model runs.  `noise_key`: as in the other loops (x_T is draw
-        0; the stochastic form reads draw k + 1 at step k, the ODE form nothing more)."""
+        0; the stochastic form reads draw k + 1 at step k, the ODE form nothing more).  `guide`: as in the other loops; the
+        pulled x0 is the data prediction and what the history keeps."""
         self._check_solver(order, stochastic)
         self._check_key(noise_key, step_noise)
         self._reject_hooks(denoised_fn, cond_fn)
+        self._guide_measurement(guide, shape, model_kwargs)
         if device is None:
             device = next(model.parameters()).device
         device = th.device(device)
@@ -896,15 +963,16 @@ class GaussianDiffusion:
         assert isinstance(shape, (tuple, list))
         flags = self._flags(clip_denoised)
         return self._solver_loop(model, shape, noise, flags, model_kwargs or {}, device, progress, order,
-                                 stochastic, step_noise, trace, noise_key)
+                                 stochastic, step_noise, trace, noise_key, guide, clip_denoised)
 
     def _solver_loop(self, model, shape, noise, flags, model_kwargs, device, progress, order, stochastic,
-                     step_noise, trace=None, noise_key=None):
+                     step_noise, trace=None, noise_key=None, guide=None, clip_denoised=True):
         indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
         # as in _loop: grad mode and the current device change around each step's compute only
         with th.no_grad(), th.cuda.device(device):
             img = self._start_noise(noise, shape, device, noise_key)
             t_all, net = self._step_model(model, shape, model_kwargs, device)
+            y = self._guide_measurement(guide, shape, model_kwargs, device)
         key = noise_key if stochastic else None
         hist = []                       # pred_xstart of the last one or two steps, newest first
         for k, i in enumerate(indices):
@@ -913,7 +981,8 @@ class GaussianDiffusion:
                 z = self._draw_noise(step_noise, k, img) if stochastic and key is None else None
                 p = 1 if i == 0 else min(order, k + 1)
                 res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z,
-                                        t_all[i], flags, order, stochastic, p, key, k + 1)
+                                        t_all[i], flags, order, stochastic, p, key, k + 1,
+                                        self._guided_x0(guide, y, out, img, t_all[i], i, clip_denoised))
                 if trace is not None:       # prev is the newest entry of the solver's own history
                     self._trace_step(trace, res, hist[0] if hist else None, i)
             yield res
@@ -922,11 +991,11 @@ class GaussianDiffusion:
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, order=2, stochastic=False,
-                               step_noise=None, trace=None, noise_key=None):
+                               step_noise=None, trace=None, noise_key=None, guide=None):
         """DPM-Solver++ multistep sampling (extension): the last sample of dpm_solver_sample_loop_progressive."""
         final = None
         for final in self.dpm_solver_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
                                                              cond_fn, model_kwargs, device, progress, order,
-                                                             stochastic, step_noise, trace, noise_key):
+                                                             stochastic, step_noise, trace, noise_key, guide):
             pass
         return final["sample"]

@@ -30,6 +30,7 @@ import torch as th
 from . import _hip as H
 from . import dist_util
 from . import gaussian_diffusion as gd
+from . import guidance
 from . import logger
 from . import patches
 
@@ -153,7 +154,7 @@ def _canvas_of(volume, geom, device):
 
 def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm", num_draws=1, batch_size=1,
                             noise=None, step_noise=None, clip_denoised=True, eta=0.0, device=None, trace=None,
-                            noise_key=None):
+                            noise_key=None, guide=None):
     """Joint DDPM ("ddpm") or DDIM ("ddim", any eta) sampling of one volume; yields, per reverse step,
     {"sample", "pred_xstart"}: (K, Dc, H, W) canvases on the device, K = num_draws.
 
@@ -170,6 +171,10 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                     the same normal there.  No noise canvas is drawn, held or gathered.  Not with `step_noise`.
     trace           a metrics.StepTrace: every step's blended pred_xstart canvases are its estimates, so its target
                     and weight are (Dc, H, W) or (K, Dc, H, W) canvases (weight 0 outside the volume)
+    guide           a guidance.LowPassPull without a measurement of its own: on the steps it is active on, every patch's
+                    x_start prediction is pulled towards that patch's own conditioning (the low_res patch the network
+                    reads) before the step, and the blend averages the pulled patches.  Within a radius of a patch face
+                    the low-pass is one-sided; the Hann weights are small there.
     With several ranks, batch b runs on rank b mod W; the ranks exchange their updated patches once per round and
     every rank blends all of them: all ranks hold the same canvas after every step, bit for bit."""
     if kind not in ("ddpm", "ddim"):
@@ -179,6 +184,10 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
     if not 1 <= K <= H.MAX_DRAWS:
         raise ValueError("num_draws must be in 1..%d, got %d" % (H.MAX_DRAWS, K))
     diffusion._check_key(noise_key, step_noise)
+    guidance.check_guide(guide)
+    if guide is not None and guide.measurement is not None:
+        raise ValueError("joint sampling pulls every patch towards its own conditioning: a guide with a measurement of "
+                         "its own is refused")
     if noise_key is not None and (noise_key.n != K or noise_key.origin is not None):
         raise ValueError("noise_key must hold one stream per draw (%d) and no geometry of its own" % K)
     if device is None:
@@ -259,14 +268,16 @@ def sample_loop_progressive(diffusion, model, low_res_volume, geom, kind="ddpm",
                     x = xg[:hi - lo]
                     gather(img, geom, lo // K, (hi - lo) // K, out=x)
                     dst = updated[:, lo:hi] if world == 1 else block[:, :hi - lo]
+                    lr = cond(lo, hi)
+                    mo = net(x, i, lr)
+                    xs = diffusion._guided_x0(guide, lr, mo, x, t_all[i], i, clip_denoised)
                     if noise_key is None:
                         zb = zg[:hi - lo]
                         gather(z, geom, lo // K, (hi - lo) // K, out=zb)
-                        diffusion._update(kind, net(x, i, cond(lo, hi)), x, t_all[i], zb, clip_denoised, eta,
-                                          out=(dst[0], dst[1]))
+                        diffusion._update(kind, mo, x, t_all[i], zb, clip_denoised, eta, out=(dst[0], dst[1]), xstart=xs)
                     else:
-                        diffusion._update(kind, net(x, i, cond(lo, hi)), x, t_all[i], None, clip_denoised, eta,
-                                          out=(dst[0], dst[1]), noise_key=patch_key.rows(lo, hi), draw=k + 1)
+                        diffusion._update(kind, mo, x, t_all[i], None, clip_denoised, eta, out=(dst[0], dst[1]),
+                                          noise_key=patch_key.rows(lo, hi), draw=k + 1, xstart=xs)
                 if world > 1:
                     for bb, blk in dist_util.gather_round(block, b):
                         lo, hi = rows(bb)

@@ -131,12 +131,25 @@ a draw equals the target are counted in "rank_ties" instead), with two levels
 or more "interval" (the outermost pair's coverage of the target and mean width;
 "nominal" is simply upper - lower, which K draws can only meet approximately:
 for small K the rank histogram is the exact calibration statement) and, with
-0.5 among the levels, "median": the row's figures for the median volume.
+0.5 among the levels, "median": the row's figures for the median volume;
+`--consistency_fwhm MM` (0: pointwise; a positive one needs `--voxel_spacing`,
+which then needs neither a target nor regions; any of the four paths, any
+sampler, with or without `--device_noise`) pulls every reverse step's x_start
+prediction towards the input volume's local means in the band of a Gaussian of
+that FWHM, before the clip and the posterior mean (guided_diffusion/guidance.py
+LowPassPull): `--consistency_weight W` in [0, 1] (default 1; 0
+samples as without the flags and only reports), on the steps whose original
+timestep is >= `--consistency_stop_t T` (default 0).  With `--model_spacing`
+the taps are built at the sampled grid's effective spacing.  metrics_<name>.json
+gains "consistency": the parameters and "lowpass_rms", the RMS of the low-passed
+difference between the input and the written volume; without `--target_samples`
+the file holds that block alone.
 """
 
 import argparse
 import collections
 import json
+import math
 import os
 import sys
 
@@ -145,7 +158,7 @@ sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch as th
 
-from guided_diffusion import _hip, dist_util, joint, logger, metrics, patches, regrid, synth, uncertainty
+from guided_diffusion import _hip, dist_util, guidance, joint, logger, metrics, patches, regrid, synth, uncertainty
 from guided_diffusion.gaussian_diffusion import NoiseKey
 from guided_diffusion.script_util import (
     add_dict_to_argparser,
@@ -209,6 +222,11 @@ def create_argparser():
     parser.add_argument("--regrid_mode", type=str, default="linear")
     # per-voxel quantiles of the --num_draws draws at these levels in [0, 1] (at most 8, ascending): the .npz gains
     # "quantiles" and "quantile_levels", the metrics file the rank histogram of the target among the draws
+    # low-pass data-consistency guidance (guidance.LowPassPull on every sampling loop): the FWHM of the band in mm (0:
+    # pointwise; a positive one needs --voxel_spacing), the weight in [0, 1] and the original timestep it stops below
+    parser.add_argument("--consistency_fwhm", type=float, default=None, metavar="MM")
+    parser.add_argument("--consistency_weight", type=float, default=None, metavar="W")
+    parser.add_argument("--consistency_stop_t", type=int, default=None, metavar="T")
     parser.add_argument("--draw_quantiles", type=float, nargs="+", default=None, metavar="Q")
     return parser
 
@@ -232,15 +250,19 @@ def main(argv=None):
     _check_quantiles(parser, args)
     _check_segmentation(parser, args)
     _check_regrid(parser, args)
+    _check_consistency(parser, args)
     args.peak = _check_spacing(parser, args)
     args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
     vol = _plan_regrid(parser, args, vol)
+    _plan_consistency(parser, args)
     roi = _load_roi(parser, args, vol)
     dist_util.setup_dist(backend=args.dist_backend or None, share_gpu=args.share_gpu)
     logger.configure(dir=args.save_dir)
     dev = dist_util.dev()
 
+    if args.consistency is not None:
+        logger.log(args.consistency["log"])
     logger.log("creating model...")
     model, diffusion = sr_create_model_and_diffusion(
         **args_to_dict(args, sr_model_and_diffusion_defaults().keys()))
@@ -444,12 +466,13 @@ def _check_spacing(parser, args):
     if not all(np.isfinite(v) and v > 0 for v in args.voxel_spacing):
         parser.error("--voxel_spacing must be three positive finite numbers (got %s)" % (args.voxel_spacing,))
     if not args.target_samples:
-        if args.model_spacing is not None:
-            return None                        # the spacing serves the regridding alone
+        if args.model_spacing is not None or args.consistency_fwhm is not None:
+            return None                        # the spacing serves the regridding or the guidance alone
         parser.error("--voxel_spacing needs --target_samples: its figures are taken per region against the target")
     if not (args.roi_labels or _segmenting(args)):
-        if args.baseline_gaussian_fwhm is not None or args.model_spacing is not None:
-            return None                        # the spacing serves the Gaussian baseline or the regridding alone
+        if (args.baseline_gaussian_fwhm is not None or args.model_spacing is not None
+                or args.consistency_fwhm is not None):
+            return None                        # the spacing serves the Gaussian baseline, the regridding or the guidance
         parser.error("--voxel_spacing needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
     s0, s1, s2 = args.voxel_spacing
     try:
@@ -536,6 +559,72 @@ def _regrid_keep(args, weight):
     live = (th.as_tensor(weight).to(dist_util.dev()) > 0).to(th.uint8).permute(2, 0, 1).contiguous()
     keep = regrid.keep_after(live, args.regrid["plan"].inverse()).permute(1, 2, 0).contiguous()
     return keep if isinstance(weight, th.Tensor) else keep.cpu().numpy()
+
+
+def _check_consistency(parser, args):
+    """--consistency_fwhm / _weight / _stop_t, checked before any file is read; args.consistency is None without the
+    flag and until _plan_consistency has the sampled grid's spacing"""
+    args.consistency = None
+    fwhm, w, stop = args.consistency_fwhm, args.consistency_weight, args.consistency_stop_t
+    if fwhm is None:
+        if w is not None or stop is not None:
+            parser.error("--consistency_weight and --consistency_stop_t need --consistency_fwhm")
+        return
+    if not (np.isfinite(fwhm) and fwhm >= 0):
+        parser.error("--consistency_fwhm must be a finite number of mm, 0 (pointwise) or more (got %r)" % fwhm)
+    if w is not None and not 0 <= w <= 1:                      # NaN fails both comparisons
+        parser.error("--consistency_weight must be in [0, 1] (got %r)" % w)
+    if stop is not None and stop < 0:
+        parser.error("--consistency_stop_t must not be negative (got %d)" % stop)
+    if fwhm > 0 and args.voxel_spacing is None:
+        parser.error("--consistency_fwhm needs --voxel_spacing: the FWHM is in mm")
+    if fwhm > 0 and len(args.voxel_spacing) == 3 and all(np.isfinite(v) and v > 0 for v in args.voxel_spacing):
+        try:
+            guidance.pull_taps(fwhm, args.voxel_spacing)
+        except ValueError as e:
+            parser.error("--consistency_fwhm: %s" % e)
+
+
+def _plan_consistency(parser, args):
+    """--consistency_fwhm: the pull, built on the host before the model is (after _plan_regrid: with --model_spacing
+    its taps are taken at the sampled grid's effective spacing).  args.consistency = {"pull": what the loops take as
+    guide= (None at weight 0: nothing is launched), "taps": the Gaussian on the file's (H, W, Z) grid for the report,
+    the report's own parameters, per-axis figures along the sampled grid's (D, H, W), and the log's one line}"""
+    if args.consistency_fwhm is None:
+        return
+    fwhm = args.consistency_fwhm
+    w = 1.0 if args.consistency_weight is None else args.consistency_weight
+    stop = 0 if args.consistency_stop_t is None else args.consistency_stop_t
+    spacing = args.voxel_spacing
+    if spacing is not None and args.regrid is not None:
+        spacing = [s * r for s, r in zip(args.voxel_spacing, args.regrid["plan"].scale)]
+    try:
+        pull = guidance.LowPassPull(fwhm, spacing, weight=w, stop_t=stop)
+        s0, s1, s2 = args.voxel_spacing if fwhm > 0 else (1.0, 1.0, 1.0)
+        file_taps = guidance.pull_taps(fwhm, (s1, s2, s0))                   # (D, H, W) -> (H, W, Z)
+    except ValueError as e:
+        parser.error("--consistency_fwhm: %s" % e)
+    args.consistency = {"pull": pull if pull.weight > 0 else None, "taps": file_taps,
+                        "log": "consistency guidance: FWHM %g mm (radii %s voxels), weight %g, original timesteps >= %d"
+                               % (fwhm, list(pull.radii), pull.weight, stop)
+                               + ("" if pull.weight > 0 else "; weight 0 samples as without it and only reports"),
+                        "params": {"fwhm_mm": fwhm, "sigma_voxels": list(pull.taps.sigma_voxels),
+                                   "radii": list(pull.radii), "weight": pull.weight, "stop_t": stop}}
+
+
+def _guide(args):
+    """guide= of the sampling loops: {} without --consistency_fwhm and at weight 0"""
+    cons = getattr(args, "consistency", None)
+    return {} if cons is None or cons["pull"] is None else {"guide": cons["pull"]}
+
+
+def _consistency_block(args, inp, den, mask):
+    """metrics_<name>.json's "consistency": the pull's parameters and lowpass_rms, the RMS of G(input - written volume)
+    over the counted voxels on the file's grid (inp, den: (H, W, Z) device tensors)"""
+    cons = args.consistency
+    low = metrics.gaussian_smooth((inp - den).contiguous(), cons["taps"])
+    rms = math.sqrt(metrics.error_moments(low, th.zeros_like(low), mask=mask)["mse"])
+    return dict(cons["params"], lowpass_rms=rms)
 
 
 def _check_baselines(parser, args):
@@ -726,7 +815,8 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
     "roi" entry; draws then yields the K draws of --num_draws as (H, W, Z) device tensors.  Nothing happens without
     --target_samples.  quantiles: _quantile_maps' dict with --draw_quantiles, which adds "quantiles" to the "denoised"
     row."""
-    if target is None:
+    cons = getattr(args, "consistency", None)
+    if target is None and cons is None:
         return None
     dev = dist_util.dev()
 
@@ -734,6 +824,13 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
         t = th.as_tensor(a).to(device=dev, dtype=th.float32)
         return (t.permute(1, 2, 0) if permute else t).contiguous()
 
+    path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
+    if target is None:                          # --consistency_fwhm alone: its block is the whole file
+        live = None if weight is None else (th.as_tensor(weight).to(dev) > 0).to(th.uint8).contiguous()
+        with open(path, "w") as f:
+            json.dump({"consistency": _consistency_block(args, hwz(vol, True), hwz(result), live)}, f, indent=2)
+        logger.log(f"saved metrics to {path}")
+        return path
     tgt, inp, den = hwz(target, True), hwz(vol, True), hwz(result)
     counted = None
     if args.metrics_mask_threshold > 0:
@@ -792,7 +889,8 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
                             "mode": plan.mode, "native_shape": list(plan.shape_in),
                             "model_shape": list(plan.shape_out),
                             "effective_spacing": [s * r for s, r in zip(args.voxel_spacing, plan.scale)]}
-    path = os.path.join(os.path.dirname(out_path), "metrics_%s.json" % _base_name(args.base_samples))
+    if cons is not None:
+        report["consistency"] = _consistency_block(args, inp, den, mask)
     with open(path, "w") as f:
         json.dump(report, f, indent=2)
     logger.log(f"saved metrics to {path}")
@@ -1020,7 +1118,7 @@ def _run_patches(args, model, diffusion, vol, tiling, target=None):
             if tracer is not None:
                 extra["trace"] = tracer.begin(idx)
             block[:len(idx) * K] = sample_loop(model, shape, noise, clip_denoised=args.clip_denoised,
-                                               model_kwargs={"low_res": cond}, **noise_args, **extra)
+                                               model_kwargs={"low_res": cond}, **noise_args, **extra, **_guide(args))
         for bb, blk in dist_util.gather_round(block, b):
             if stitcher is None:
                 continue
@@ -1098,7 +1196,7 @@ def _main_joint(args, model, diffusion, vol, target=None):
         more["noise_key"] = joint.draw_key(args.noise_seed, K, dist_util.dev())
     sample = joint.sample_loop(diffusion, model, vol, geom, kind="ddim" if args.use_ddim else "ddpm", num_draws=K,
                                batch_size=max(1, args.batch_size), clip_denoised=args.clip_denoised, eta=args.eta,
-                               device=dist_util.dev(), **more)
+                               device=dist_util.dev(), **more, **_guide(args))
     if dist_util.rank() != 0:
         return None
     draws = sample[:, :vol.shape[0], :vol.shape[1], :vol.shape[2]].contiguous()     # (K, D, H, W)

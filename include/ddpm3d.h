@@ -1127,6 +1127,63 @@ int ddpm3d_dpm_solver_step_keyed(const float* model_out, const float* x, const f
 int ddpm3d_q_sample_keyed(const float* x_start, const ddpm3d_noise_key* key, const float* qcoef,
                           const int64_t* t_idx, int N, int voxels, int T, float* x_t, void* stream);
 
+/*
+ * Low-pass data-consistency pull of a step's x_start prediction, and the step entries that take the finished x0
+ * (added within ABI 13: new entries only).  The operator sits where the reference applies
+ * denoised_fn (gaussian_diffusion.py:293-314: process_xstart = denoised_fn, then the clip, then the posterior mean):
+ *   x0_raw = model_out's first half under F_PREDICT_XSTART, else c_recip[t] x - c_recipm1[t] eps  (:305-311, :328-333)
+ *   x0     = x0_raw + w G(y - x0_raw),  then clamped to [-1, 1] under F_CLIP                     (:294-297)
+ * for N samples [D][H][W] (one channel, W innermost), y the measurement in x's units, w = weight in [0, 1].  G is
+ * ddpm3d_gauss_smooth's separable Gaussian with renormalised faces, per sample: the same per-pass rule in fp32, the
+ * passes along W, then H, then D, a pass with radius 0 skipped; all radii 0 is the pointwise pull x0_raw + w (y -
+ * x0_raw).  y - x0_raw is one fp32 subtraction, w g and the final sum two more roundings (no fma).  model_out is
+ * [N][2][voxels] under F_LEARN_SIGMA (the second half is not read), [N][voxels] otherwise; taps_a as in
+ * ddpm3d_gauss_smooth (HOST arrays of 2 r_a + 1 weights).  T is the number of rows of coef: a sample whose t lies outside
+ * [0, T) reads no table row and gets NaN in its output.  One launch per axis with r_a > 0 (one launch when all are 0):
+ * the first derives x0_raw and the residual where it reads them, so x0_raw never reaches memory, the last finishes x0;
+ * the passes chain through ws and xstart_out.  Sample n reads sample n only; no atomics, every sum in a fixed order:
+ * the same bits on every run, whatever the launch geometry.
+ *
+ * Against fp64 arithmetic on the same fp32 x0_raw, y, taps and w, with u = 2^-24, m the exact filter of y - x0_raw, M
+ * the exact filter of |y - x0_raw| and c_a = n_a + 2 as in ddpm3d_gauss_smooth (c_a = 0 for a skipped pass):
+ *   |x0 - (x0_raw + w m)| <= u |x0_raw + w m| + w ((1 + u)^3 (1 + c_0 u)(1 + c_1 u)(1 + c_2 u) - 1) M
+ * before the clip, which does not widen it (the residual's rounding, the product's and the sum's on top of the three
+ * passes' composed bound).
+ *
+ * ws: ddpm3d_xstart_pull_workspace_bytes(N, D, H, W) bytes (N volumes), 16-byte aligned; 0 is the answer for a shape
+ * the entry refuses.  DDPM3D_EINVAL before any launch for a NULL pointer, an extent or T below 1, N above 65535,
+ * N * D * H * W above 2^31 - 1, unknown flag bits, a radius outside 0..DDPM3D_SMOOTH_MAX_RADIUS, a tap that is not
+ * positive and finite, a tap table that is not symmetric, a weight outside [0, 1] or not finite, a workspace that is
+ * NULL, too small or misaligned, and xstart_out or ws overlapping each other or a tensor the call reads.
+ */
+size_t ddpm3d_xstart_pull_workspace_bytes(int N, int D, int H, int W);
+int ddpm3d_xstart_pull(const float* model_out, const float* x, const float* measurement, const float* coef,
+                       const int64_t* t_idx, int N, int D, int H, int W, int T, int flags, float weight, int r0, int r1,
+                       int r2, const float* taps0, const float* taps1, const float* taps2, float* xstart_out, void* ws,
+                       size_t ws_bytes, void* stream);
+/*
+ * ddpm3d_p_sample_step / ddpm3d_ddim_step / ddpm3d_dpm_solver_step with x0 taken from `xstart` ([N][voxels], e.g.
+ * ddpm3d_xstart_pull's output) instead of model_out's first half: the same kernels with the x0 source switched, so
+ * everything downstream of x0 (the posterior mean :216-219, eps re-derived from x0 :566, the solver's data prediction
+ * and pred_xstart) is bit for bit the existing entry called with F_PREDICT_XSTART and xstart as the first half.
+ * xstart is clipped once more under F_CLIP (the clip is idempotent).  Only p_sample_step_x0 under F_LEARN_SIGMA reads
+ * model_out (its second half, the learned variance); elsewhere model_out may be NULL.  Noise: exactly one of `noise`
+ * and `key` is non-NULL; for the solver both NULL selects the ODE form.  DDPM3D_EINVAL before any launch for a NULL
+ * xstart, x, coef, t_idx or sample (the solver: scoef, pred_xstart too), N outside 1..65535, voxels below 1, unknown
+ * flag bits, a wrong number of noise sources, a bad key (as the keyed entries), sample or pred_xstart equal to each
+ * other or to a tensor the call reads, and the solver's order and history as ddpm3d_dpm_solver_step.
+ */
+int ddpm3d_p_sample_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
+                            const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                            int flags, float* sample, float* pred_xstart, void* stream);
+int ddpm3d_ddim_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
+                        const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                        int flags, float eta, float* sample, float* pred_xstart, void* stream);
+int ddpm3d_dpm_solver_step_x0(const float* model_out, const float* xstart, const float* x, const float* x0_prev1,
+                              const float* x0_prev2, const float* noise, const ddpm3d_noise_key* key,
+                              const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels, int T,
+                              int flags, int order, float* sample, float* pred_xstart, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
