@@ -22,7 +22,6 @@ static int launched(hipError_t e, const char* what) {
     if (e == hipSuccess) return DDPM3D_OK;
     return fail(DDPM3D_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 extern "C" {
 
@@ -428,7 +427,6 @@ int ddpm3d_add_embedding(float* emb, const float* table, const int64_t* idx, int
                          void* stream) {
     if (!emb || !table || !idx || rows <= 0 || dim <= 0 || num_classes <= 0)
         return fail(DDPM3D_EINVAL, "add_embedding: bad arguments");
-    (void)num_classes;   // the indices live on the device; the caller validates their range
     return launched(ddpm3d_launch_add_embedding(emb, table, idx, rows, dim, num_classes, (hipStream_t)stream), "add_embedding");
 }
 
@@ -765,9 +763,9 @@ int ddpm3d_draw_quantiles(const float* acc, const float* wsum, int K, int64_t vo
                     "draw_quantiles");
 }
 
-// ------------------------------------------------- joint patch sampling (added within ABI 13)
-static int joint_check(const char* what, int B, int Dc, int H, int W, int res, const ddpm3d_joint_starts* s,
-                       bool covered) {
+// ------------------------------------------------- patch gather and blend: joint patch sampling and sliding-window
+// tiling (both added within ABI 13) check their canvases and their starts, axis by axis, through the same two functions
+static int canvas_check(const char* what, int B, int Dc, int H, int W, int res) {
     if (B < 1 || B > DDPM3D_MAX_DRAWS)
         return fail(DDPM3D_EINVAL, "%s: B=%d canvases (1..%d)", what, B, DDPM3D_MAX_DRAWS);
     if (res < 1 || res > 1024) return fail(DDPM3D_EINVAL, "%s: res=%d (1..1024)", what, res);
@@ -776,29 +774,65 @@ static int joint_check(const char* what, int B, int Dc, int H, int W, int res, c
     if (Dc < 1 || H < 1 || W < 1 || Dc > 65535 || H > 65535 || W > 65535 || (int64_t)H * W > 0x7fffffff - 256)
         return fail(DDPM3D_EINVAL, "%s: bad canvas (Dc=%d H=%d W=%d; 1..65535 each, H * W <= 2^31 - 257)", what, Dc, H,
                     W);
-    const struct { const char* name; int n; const int32_t* starts; int extent; } axes[3] = {
-        {"H", s->nx, s->xs, H}, {"W", s->ny, s->ys, W}, {"D", s->nz, s->zs, Dc}};
-    for (const auto& a : axes) {
-        if (a.n < 1 || a.n > DDPM3D_JOINT_MAX_STARTS)
-            return fail(DDPM3D_EINVAL, "%s: %d starts on axis %s (1..%d)", what, a.n, a.name, DDPM3D_JOINT_MAX_STARTS);
-        for (int i = 0; i < a.n; ++i)
-            if (a.starts[i] < 0 || a.starts[i] > a.extent - res)
-                return fail(DDPM3D_EINVAL, "%s: patch at %d on axis %s outside the canvas (starts 0..%d)", what,
-                            a.starts[i], a.name, a.extent - res);
-        if (!covered) continue;
-        // the union of [start, start + res) must hold every coordinate: sweep from 0, always taking the start that
-        // reaches furthest among those at or below the first uncovered coordinate
-        int reach = 0;
-        while (reach < a.extent) {
-            int next = reach;
-            for (int i = 0; i < a.n; ++i)
-                if (a.starts[i] <= reach && a.starts[i] + res > next) next = a.starts[i] + res;
-            if (next == reach)
-                return fail(DDPM3D_EINVAL, "%s: coordinate %d of axis %s is covered by no patch", what, reach, a.name);
-            reach = next;
+    return DDPM3D_OK;
+}
+
+struct patch_axis { const char* name; int n; const int32_t* starts; int extent; };
+
+// The host starts of each axis.  ascending: the tiles entries' rule (any number of strictly ascending starts);
+// otherwise the joint entries' (at most DDPM3D_JOINT_MAX_STARTS, any order, repeats allowed).  cover: the union of
+// [start, start + res) must hold every coordinate of the axis.
+static int axes_check(const char* what, const patch_axis (&axes)[3], int res, bool ascending, bool cover) {
+    for (const patch_axis& a : axes) {
+        const int n = a.n, extent = a.extent;
+        const int32_t* s = a.starts;
+        if (ascending) {
+            // a patch covers at least one coordinate of its own, so an axis holds at most `extent` ascending starts
+            if (n < 1 || n > extent || !s)
+                return fail(DDPM3D_EINVAL, "%s: %d starts on axis %s (1..%d, not NULL)", what, n, a.name, extent);
+        } else if (n < 1 || n > DDPM3D_JOINT_MAX_STARTS) {
+            return fail(DDPM3D_EINVAL, "%s: %d starts on axis %s (1..%d)", what, n, a.name, DDPM3D_JOINT_MAX_STARTS);
         }
+        for (int i = 0; i < n; ++i) {
+            if (s[i] < 0 || s[i] > extent - res)
+                return fail(DDPM3D_EINVAL, "%s: patch at %d on axis %s outside the canvas (starts 0..%d)", what, s[i],
+                            a.name, extent - res);
+            if (ascending && i && s[i] <= s[i - 1])
+                return fail(DDPM3D_EINVAL, "%s: starts on axis %s do not ascend (%d after %d)", what, a.name, s[i],
+                            s[i - 1]);
+        }
+        if (!cover) continue;
+        int gap = -1;                             // the first coordinate that no patch covers
+        if (ascending) {
+            // the union is the axis iff it begins at 0, ends at the extent and no neighbour starts beyond its
+            // predecessor's end
+            if (s[0] > 0) gap = 0;
+            for (int i = 1; i < n && gap < 0; ++i)
+                if (s[i] > s[i - 1] + res) gap = s[i - 1] + res;
+            if (gap < 0 && s[n - 1] + res < extent) gap = s[n - 1] + res;
+        } else {
+            // any order: sweep from 0, always taking the start that reaches furthest among those at or below the
+            // first uncovered coordinate
+            for (int reach = 0; reach < extent && gap < 0;) {
+                int next = reach;
+                for (int i = 0; i < n; ++i)
+                    if (s[i] <= reach && s[i] + res > next) next = s[i] + res;
+                if (next == reach) gap = reach;
+                reach = next;
+            }
+        }
+        if (gap >= 0)
+            return fail(DDPM3D_EINVAL, "%s: coordinate %d of axis %s is covered by no patch", what, gap, a.name);
     }
     return DDPM3D_OK;
+}
+
+static int joint_check(const char* what, int B, int Dc, int H, int W, int res, const ddpm3d_joint_starts* s,
+                       bool covered) {
+    const int rc = canvas_check(what, B, Dc, H, W, res);
+    if (rc != DDPM3D_OK) return rc;
+    const patch_axis axes[3] = {{"H", s->nx, s->xs, H}, {"W", s->ny, s->ys, W}, {"D", s->nz, s->zs, Dc}};
+    return axes_check(what, axes, res, false, covered);
 }
 
 int ddpm3d_joint_gather(const float* canvas, int B, int Dc, int H, int W, int res, const ddpm3d_joint_starts* starts,
@@ -824,49 +858,20 @@ int ddpm3d_joint_blend(const float* patch_values, int B, int Dc, int H, int W, i
                     "joint_blend");
 }
 
-// ------------------------------------------------- sliding-window tiling (added within ABI 13)
 static int tiling_check(const char* what, int B, int Dc, int H, int W, int res, const ddpm3d_tiling* t, bool blend,
                         int64_t* patches) {
-    if (B < 1 || B > DDPM3D_MAX_DRAWS)
-        return fail(DDPM3D_EINVAL, "%s: B=%d canvases (1..%d)", what, B, DDPM3D_MAX_DRAWS);
-    if (res < 1 || res > 1024) return fail(DDPM3D_EINVAL, "%s: res=%d (1..1024)", what, res);
-    if (Dc < 1 || H < 1 || W < 1 || Dc > 65535 || H > 65535 || W > 65535 || (int64_t)H * W > 0x7fffffff - 256)
-        return fail(DDPM3D_EINVAL, "%s: bad canvas (Dc=%d H=%d W=%d; 1..65535 each, H * W <= 2^31 - 257)", what, Dc, H,
-                    W);
+    int rc = canvas_check(what, B, Dc, H, W, res);
+    if (rc != DDPM3D_OK) return rc;
     if (!t->d_starts || (blend && (!t->d_cover || !t->d_tables)))
         return fail(DDPM3D_EINVAL, "%s: null device table in the tiling descriptor", what);
     if (blend && ((reinterpret_cast<uintptr_t>(t->d_cover) | reinterpret_cast<uintptr_t>(t->d_tables)) & 7))
         return fail(DDPM3D_EINVAL, "%s: d_cover and d_tables must be 8-byte aligned", what);
-    const struct { const char* name; int extent; } axes[3] = {{"H", H}, {"W", W}, {"D", Dc}};
-    int64_t P = 1;
-    for (int a = 0; a < 3; ++a) {
-        const int n = t->n[a], extent = axes[a].extent;
-        const int32_t* s = t->starts[a];
-        // a patch covers at least one coordinate of its own, so an axis holds at most `extent` ascending starts
-        if (n < 1 || n > extent || !s)
-            return fail(DDPM3D_EINVAL, "%s: %d starts on axis %s (1..%d, not NULL)", what, n, axes[a].name, extent);
-        for (int i = 0; i < n; ++i) {
-            if (s[i] < 0 || s[i] > extent - res)
-                return fail(DDPM3D_EINVAL, "%s: patch at %d on axis %s outside the canvas (starts 0..%d)", what, s[i],
-                            axes[a].name, extent - res);
-            if (i && s[i] <= s[i - 1])
-                return fail(DDPM3D_EINVAL, "%s: starts on axis %s do not ascend (%d after %d)", what, axes[a].name,
-                            s[i], s[i - 1]);
-        }
-        if (blend) {
-            // ascending starts: the union of [start, start + res) is the axis iff it begins at 0, ends at the extent
-            // and no neighbour starts beyond its predecessor's end
-            int gap = s[0] > 0 ? 0 : -1;
-            for (int i = 1; i < n && gap < 0; ++i)
-                if (s[i] > s[i - 1] + res) gap = s[i - 1] + res;
-            if (gap < 0 && s[n - 1] + res < extent) gap = s[n - 1] + res;
-            if (gap >= 0)
-                return fail(DDPM3D_EINVAL, "%s: coordinate %d of axis %s is covered by no patch", what, gap,
-                            axes[a].name);
-        }
-        P *= n;                                   // at most 65535^3 < 2^48
-    }
-    // rows are indexed in 32 bits inside the kernels, elements in 64
+    const patch_axis axes[3] = {{"H", t->n[0], t->starts[0], H}, {"W", t->n[1], t->starts[1], W},
+                                {"D", t->n[2], t->starts[2], Dc}};
+    rc = axes_check(what, axes, res, true, blend);
+    if (rc != DDPM3D_OK) return rc;
+    // rows are indexed in 32 bits inside the kernels, elements in 64; P is at most 65535^3 < 2^48
+    const int64_t P = (int64_t)t->n[0] * t->n[1] * t->n[2];
     const int64_t rows = P * B, r3 = (int64_t)res * res * res;
     if (rows > 0x7fffffff || rows > ((int64_t)1 << 61) / r3)
         return fail(DDPM3D_EINVAL, "%s: %lld patches x %d canvases of %d^3 are too many rows", what, (long long)P, B,

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// the 16-byte (four-wide) forms of a kernel need this of every pointer they read or write
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int prec, void* out, hipStream_t st);
 hipError_t ddpm3d_launch_pack_up_phase(const float* w, int Cout, int Cin, void* out, hipStream_t st);
 hipError_t ddpm3d_launch_gn_finalize(const double* st0, int C0, int rows0, const double* st1, int C1,
@@ -143,15 +146,17 @@ struct ddpm3d_regrid_axis;
 void ddpm3d_regrid_stages(int D, int H, int W, int Do, int Ho, int Wo, int64_t stage[3]);
 hipError_t ddpm3d_launch_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_regrid_axis* axes,
                                 float* out, float* ws, hipStream_t st);
-// joint.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
-// patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry)
+// tiling.hip: B canvases (Dc, H, W) -> rows [first_patch * B, (first_patch + n_patches) * B) of the (patch, draw)-major
+// patch tensor, and all patches -> B canvases with the normalised Hann blend (the caller has checked the geometry).
+// One gather and one blend kernel, instantiated for starts in the kernel arguments (joint: at most
+// DDPM3D_JOINT_MAX_STARTS per axis) ...
 struct ddpm3d_joint_starts;
 hipError_t ddpm3d_launch_joint_gather(const float* canvas, int B, int Dc, int H, int W, int res,
                                       const ddpm3d_joint_starts& s, int first_patch, int n_patches, float* out,
                                       hipStream_t st);
 hipError_t ddpm3d_launch_joint_blend(const float* patches, int B, int Dc, int H, int W, int res,
                                      const ddpm3d_joint_starts& s, const double* tables, float* out, hipStream_t st);
-// tiling.hip: the same two operations for any number of starts per axis (tables in device memory)
+// ... and for starts and a per-coordinate cover lookup in device memory (tiles: any number per axis)
 struct ddpm3d_tiling;
 hipError_t ddpm3d_launch_tiles_gather(const float* canvas, int B, int Dc, int H, int W, int res,
                                       const ddpm3d_tiling& t, int first_patch, int n_patches, float* out,

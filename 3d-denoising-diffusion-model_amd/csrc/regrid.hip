@@ -131,8 +131,6 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void regrid_row_kernel(const float*
     *reinterpret_cast<float4*>(out + (int64_t)blockIdx.z * p.out_voxels + (int64_t)q * p.inner + x) = acc;
 }
 
-bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 template <int CAP>
 hipError_t launch_pass(const float* src, float* dst, const ddpm3d_regrid_axis& a, const RegridPass& p, int B,
                        hipStream_t st) {

@@ -122,8 +122,6 @@ __global__ __launch_bounds__(256) void draw_moments_kernel(const float* __restri
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 hipError_t ddpm3d_launch_draw_stitch(const float* samples, int K, int res, const double* window, int xs, int ys,

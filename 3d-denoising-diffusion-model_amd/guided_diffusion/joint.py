@@ -14,13 +14,15 @@ every voxel (ddpm3d_joint_blend).  Every patch sees the same x_t and the same
 noise in an overlap, and the noise is never averaged.  The forwards per volume
 are unchanged (patches x steps); DESIGN.md 3.7.
 
-Both kernels are HIP (csrc/joint.hip); there is no host fallback.  A sliding
+Both kernels are HIP (csrc/tiling.hip); there is no host fallback.  A sliding
 geometry (patches.joint_geometry(..., min_overlap=N): any volume size, any
 number of patches per axis) takes the same two steps through
-ddpm3d_tiles_gather / ddpm3d_tiles_blend (csrc/tiling.hip), which keep the
-starts in device memory and visit only the patches that cover a voxel.
+ddpm3d_tiles_gather / ddpm3d_tiles_blend, the same two kernels instantiated
+to keep the starts in device memory and to visit only the patches that cover
+a voxel.
 """
 
+import collections
 import ctypes
 import weakref
 
@@ -35,48 +37,51 @@ from . import logger
 from . import patches
 
 
-_DEVICE_GEOMETRY = weakref.WeakKeyDictionary()       # JointGeometry -> {device: (starts, tables)}
+_DEVICE_GEOMETRY = weakref.WeakKeyDictionary()       # JointGeometry -> {device: _Descriptor}
+
+# entries: "ddpm3d_joint" or "ddpm3d_tiles"; args: what their _gather and _blend take for the geometry (the blend
+# after them blend_args); keep: the arrays that args point into
+_Descriptor = collections.namedtuple("_Descriptor", "entries args blend_args keep")
 
 
-def _device_geometry(geom, device):
-    """(ddpm3d_joint_starts, the three tables back to back on `device`), built once per geometry and device."""
+def _descriptor(geom, device):
+    """What the geometry's two entries take on `device`, built once per geometry and device: a ddpm3d_joint_starts
+    and, for the blend, the three weight tables back to back for the fixed grid (min_overlap is None); for a sliding
+    geometry a ddpm3d_tiling of the host starts, their device copy, the per-coordinate {first covering patch, count}
+    lookup (patches.axis_cover) and the tables."""
     cache = _DEVICE_GEOMETRY.setdefault(geom, {})
     key = str(device)
-    if key not in cache:
-        s = H.JointStarts()
-        for n, arr, starts in (("nx", s.xs, geom.x_starts), ("ny", s.ys, geom.y_starts), ("nz", s.zs, geom.z_starts)):
-            if len(starts) > H.JOINT_MAX_STARTS:
-                raise ValueError("at most %d patches per axis, got %d" % (H.JOINT_MAX_STARTS, len(starts)))
-            setattr(s, n, len(starts))
-            for i, v in enumerate(starts):
-                arr[i] = int(v)
-        tables = np.concatenate([np.ascontiguousarray(t, dtype=np.float64).ravel()
-                                 for t in (geom.a_x, geom.a_y, geom.a_z)])
-        cache[key] = (s, th.from_numpy(tables).to(device))
-    return cache[key]
-
-
-def _device_tiling(geom, device):
-    """ddpm3d_tiling of a sliding geometry on `device`: the host starts, their device copy, the per-coordinate
-    {first covering patch, count} lookup (patches.axis_cover) and the three weight tables.  Built once per geometry
-    and device; the cache entry keeps the arrays the descriptor points into alive."""
-    cache = _DEVICE_GEOMETRY.setdefault(geom, {})
-    key = "tiling:" + str(device)
     if key not in cache:
         Dc, Hh, W = geom.canvas
         axes = ((geom.x_starts, Hh), (geom.y_starts, W), (geom.z_starts, Dc))
         host = [np.ascontiguousarray(starts, dtype=np.int32) for starts, _ in axes]
-        cover = np.concatenate([patches.axis_cover(starts, extent, geom.res) for starts, extent in axes])
-        tables = np.concatenate([np.ascontiguousarray(t, dtype=np.float64).ravel()
-                                 for t in (geom.a_x, geom.a_y, geom.a_z)])
-        dev = [th.from_numpy(a).to(device) for a in (np.concatenate(host), np.ascontiguousarray(cover), tables)]
-        t = H.Tiling()
-        for a, arr in enumerate(host):
-            t.n[a] = len(arr)
-            t.starts[a] = arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-        t.d_starts, t.d_cover, t.d_tables = (d.data_ptr() for d in dev)
-        cache[key] = (t, host, dev)
-    return cache[key][0]
+        for starts in host:
+            if geom.min_overlap is None and len(starts) > H.JOINT_MAX_STARTS:
+                raise ValueError("at most %d patches per axis, got %d" % (H.JOINT_MAX_STARTS, len(starts)))
+        tables = th.from_numpy(np.concatenate([np.ascontiguousarray(t, dtype=np.float64).ravel()
+                                               for t in (geom.a_x, geom.a_y, geom.a_z)])).to(device)
+        if geom.min_overlap is None:
+            s = H.JointStarts()
+            for n, arr, starts in zip(("nx", "ny", "nz"), (s.xs, s.ys, s.zs), host):
+                setattr(s, n, len(starts))
+                arr[:len(starts)] = starts.tolist()
+            cache[key] = _Descriptor("ddpm3d_joint", s, (H.ptr(tables),), (tables,))
+        else:
+            cover = np.concatenate([patches.axis_cover(starts, extent, geom.res) for starts, extent in axes])
+            dev = [th.from_numpy(a).to(device) for a in (np.concatenate(host), np.ascontiguousarray(cover))]
+            t = H.Tiling()
+            for a, arr in enumerate(host):
+                t.n[a] = len(arr)
+                t.starts[a] = arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            t.d_starts, t.d_cover, t.d_tables = dev[0].data_ptr(), dev[1].data_ptr(), tables.data_ptr()
+            cache[key] = _Descriptor("ddpm3d_tiles", t, (), (host, dev, tables))
+    return cache[key]
+
+
+def _device_tiling(geom, device):
+    """The cached ddpm3d_tiling of a sliding geometry on `device` (the GPU tests put their own host starts beside
+    its device tables)."""
+    return _descriptor(geom, device).args
 
 
 def gather(canvas, geom, first_patch=0, n_patches=None, out=None):
@@ -96,15 +101,10 @@ def gather(canvas, geom, first_patch=0, n_patches=None, out=None):
             raise ValueError("out holds %d elements, %d patches x %d draws need %d"
                              % (out.numel(), n, B, n * B * r ** 3))
     Dc, Hh, W = geom.canvas
-    if geom.min_overlap is not None:
-        with th.cuda.device(canvas.device):
-            H.check(H.load().ddpm3d_tiles_gather(H.ptr(canvas), B, Dc, Hh, W, r, _device_tiling(geom, canvas.device),
-                                                 int(first_patch), n, H.ptr(out), H.stream()))
-        return out
-    starts, _ = _device_geometry(geom, canvas.device)
+    d = _descriptor(geom, canvas.device)
     with th.cuda.device(canvas.device):
-        H.check(H.load().ddpm3d_joint_gather(H.ptr(canvas), B, Dc, Hh, W, r, starts, int(first_patch), n, H.ptr(out),
-                                             H.stream()))
+        H.check(getattr(H.load(), d.entries + "_gather")(H.ptr(canvas), B, Dc, Hh, W, r, d.args, int(first_patch), n,
+                                                         H.ptr(out), H.stream()))
     return out
 
 
@@ -123,15 +123,10 @@ def blend(patch_values, geom, num_draws=1, out=None):
         if tuple(out.shape) != (B,) + tuple(geom.canvas):
             raise ValueError("out of shape %s, expected %s" % (tuple(out.shape), (B,) + tuple(geom.canvas)))
     Dc, Hh, W = geom.canvas
-    if geom.min_overlap is not None:
-        with th.cuda.device(patch_values.device):
-            H.check(H.load().ddpm3d_tiles_blend(H.ptr(patch_values), B, Dc, Hh, W, r,
-                                                _device_tiling(geom, patch_values.device), H.ptr(out), H.stream()))
-        return out
-    starts, tables = _device_geometry(geom, patch_values.device)
+    d = _descriptor(geom, patch_values.device)
     with th.cuda.device(patch_values.device):
-        H.check(H.load().ddpm3d_joint_blend(H.ptr(patch_values), B, Dc, Hh, W, r, starts, H.ptr(tables), H.ptr(out),
-                                            H.stream()))
+        H.check(getattr(H.load(), d.entries + "_blend")(H.ptr(patch_values), B, Dc, Hh, W, r, d.args, *d.blend_args,
+                                                        H.ptr(out), H.stream()))
     return out
 
 

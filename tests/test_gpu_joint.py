@@ -18,6 +18,7 @@ from guided_diffusion import joint, patches
 from guided_diffusion import script_util as su
 from guided_diffusion import synth
 from oracle import sampler_ref, schedule_ref, unet_ref
+from tiling_ref import np_blend as _np_blend, np_gather as _np_gather
 
 pytestmark = pytest.mark.gpu
 
@@ -41,18 +42,6 @@ def build(over, resp=""):
     model.load_state_dict(sd)
     model.to("cuda").eval()
     return model, diff, sd
-
-
-def _np_gather(canvases, geom):
-    """(B, Dc, H, W) -> (P * B, 1, res^3): patch-major, draw-minor"""
-    per_draw = np.stack([patches.joint_gather(c, geom) for c in canvases], axis=1)       # (P, B, 1, r, r, r)
-    return per_draw.reshape((-1,) + per_draw.shape[2:])
-
-
-def _np_blend(rows, geom, B):
-    r = geom.res
-    per = rows.reshape(geom.n_patches, B, 1, r, r, r)
-    return np.stack([patches.joint_blend(per[:, b], geom) for b in range(B)])
 
 
 @pytest.mark.parametrize("D,Hh,W,res,B", [g + (b,) for g in ALIGNED[1:] + MISALIGNED for b in (1, 3)]

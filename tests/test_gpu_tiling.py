@@ -27,6 +27,7 @@ from guided_diffusion import _hip as H
 from guided_diffusion import dist_util, joint, patches
 from guided_diffusion import script_util as su
 from guided_diffusion import synth
+from tiling_ref import np_blend as _np_blend, np_gather as _np_gather
 
 pytestmark = pytest.mark.gpu
 
@@ -50,17 +51,6 @@ TINY = dict(large_size=16, small_size=16, num_channels=32, num_res_blocks=1, num
 # the fixed grid's own geometry; one zero-padded patch
 GEOMETRIES = [((20, 70, 40), 16, 10), ((40, 70, 52), 16, 4), ((10, 70, 12), 16, 4), ((30, 100, 33), 16, 7),
               ((24, 40, 40), 16, 4), ((5, 7, 9), 16, 2)]
-
-
-def _np_gather(canvases, geom):
-    per_draw = np.stack([patches.joint_gather(c, geom) for c in canvases], axis=1)       # (P, B, 1, r, r, r)
-    return per_draw.reshape((-1,) + per_draw.shape[2:])
-
-
-def _np_blend(rows, geom, B):
-    r = geom.res
-    per = rows.reshape(geom.n_patches, B, 1, r, r, r)
-    return np.stack([patches.joint_blend(per[:, b], geom) for b in range(B)])
 
 
 def _as_sliding(g):
