@@ -525,8 +525,8 @@ size_t ddpm3d_vb_terms_workspace_bytes(int N, int voxels) {
     return (size_t)N * (size_t)ddpm3d_vb_parts(voxels) * 4 * sizeof(double);
 }
 
-static int vb_ws_ok(const char* what, int N, int voxels, const void* ws, size_t ws_bytes) {
-    const size_t need = ddpm3d_vb_terms_workspace_bytes(N, voxels);
+// the one workspace check of every entry that takes a caller's workspace of `need` bytes
+static int ws_ok(const char* what, size_t need, const void* ws, size_t ws_bytes) {
     if (!ws || ws_bytes < need || !aligned16(ws))
         return fail(DDPM3D_EINVAL, "%s: needs %zu bytes of 16-byte aligned workspace (got %zu)", what, need,
                     ws ? ws_bytes : (size_t)0);
@@ -544,7 +544,7 @@ int ddpm3d_vb_terms(const float* model_out, const float* x_start, const float* x
     if ((noise == nullptr) != (mse == nullptr))
         return fail(DDPM3D_EINVAL, "vb_terms: noise and mse must come together");
     int rc = step_entry_ok("vb_terms", true, N, voxels, T, flags);
-    if (rc == DDPM3D_OK) rc = vb_ws_ok("vb_terms", N, voxels, ws, ws_bytes);
+    if (rc == DDPM3D_OK) rc = ws_ok("vb_terms", ddpm3d_vb_terms_workspace_bytes(N, voxels), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_vb_terms(model_out, x_start, x_t, noise, coef, qcoef, t_idx, N, voxels, T, flags,
                                            (double*)ws, vb, xstart_mse, mse, ld_out, pred_xstart,
@@ -556,7 +556,7 @@ int ddpm3d_prior_bpd(const float* x_start, const float* qcoef, int N, int voxels
                      float* out, void* stream) {
     if (!x_start || !qcoef || !out || !vb_shape_ok(N, voxels, T))
         return fail(DDPM3D_EINVAL, "prior_bpd: bad arguments (N=%d voxels=%d T=%d)", N, voxels, T);
-    const int rc = vb_ws_ok("prior_bpd", N, voxels, ws, ws_bytes);
+    const int rc = ws_ok("prior_bpd", ddpm3d_vb_terms_workspace_bytes(N, voxels), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_prior_bpd(x_start, qcoef, N, voxels, T, (double*)ws, out, (hipStream_t)stream),
                     "prior_bpd");
@@ -911,12 +911,6 @@ static bool ssim_shape_ok(int D, int H, int W) {
     return D >= 11 && H >= 11 && W >= 11 && D <= 65535 && H <= 65535 && W <= 65535 &&
            (int64_t)H * W <= 0x7fffffff && (int64_t)D * H * W <= EM_MAX_VOXELS;
 }
-static int metric_ws_ok(const char* what, size_t need, const void* ws, size_t ws_bytes) {
-    if (!ws || ws_bytes < need || !aligned16(ws))
-        return fail(DDPM3D_EINVAL, "%s: needs %zu bytes of 16-byte aligned workspace (got %zu)", what, need,
-                    ws ? ws_bytes : (size_t)0);
-    return DDPM3D_OK;
-}
 
 size_t ddpm3d_error_moments_workspace_bytes(int B, int64_t voxels) {
     if (B < 1 || B > DDPM3D_MAX_DRAWS || voxels <= 0 || voxels > EM_MAX_VOXELS) return 0;
@@ -930,7 +924,7 @@ int ddpm3d_error_moments(const float* est, const float* target, const uint8_t* m
         return fail(DDPM3D_EINVAL, "error_moments: B=%d estimates (1..%d)", B, DDPM3D_MAX_DRAWS);
     if (voxels <= 0 || voxels > EM_MAX_VOXELS)
         return fail(DDPM3D_EINVAL, "error_moments: voxels=%lld (1..2^40)", (long long)voxels);
-    const int rc = metric_ws_ok("error_moments", ddpm3d_em_workspace_bytes(B, voxels), ws, ws_bytes);
+    const int rc = ws_ok("error_moments", ddpm3d_em_workspace_bytes(B, voxels), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_error_moments(est, target, mask, std, B, voxels, (double*)ws, out,
                                                 (hipStream_t)stream),
@@ -953,7 +947,7 @@ int ddpm3d_ssim3d(const float* est, const float* target, const uint8_t* mask, in
     // !(c >= 0) also catches NaN; the kernel evaluates S in fp32, so the constants must be finite there
     if (!(C1 >= 0.0) || !(C2 >= 0.0) || C1 > 3.0e38 || C2 > 3.0e38)
         return fail(DDPM3D_EINVAL, "ssim3d: C1=%g C2=%g must be finite and not negative", C1, C2);
-    const int rc = metric_ws_ok("ssim3d", ddpm3d_ss_workspace_bytes(B, D, H, W), ws, ws_bytes);
+    const int rc = ws_ok("ssim3d", ddpm3d_ss_workspace_bytes(B, D, H, W), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_ssim3d(est, target, mask, B, D, H, W, (float)C1, (float)C2, (double*)ws, map, out,
                                          (hipStream_t)stream),
@@ -983,7 +977,7 @@ int ddpm3d_trace_moments(const float* est, const float* prev, const float* targe
                     (long long)target_stride, (long long)weight_stride, (long long)voxels);
     if ((!target && target_stride != 0) || (!weight && weight_stride != 0))
         return fail(DDPM3D_EINVAL, "trace_moments: a NULL target / weight takes stride 0");
-    const int rc = metric_ws_ok("trace_moments", ddpm3d_tr_workspace_bytes(B, voxels), ws, ws_bytes);
+    const int rc = ws_ok("trace_moments", ddpm3d_tr_workspace_bytes(B, voxels), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_trace_moments(est, prev, target, weight, B, voxels, target_stride, weight_stride,
                                                 (double*)ws, out, (hipStream_t)stream),
@@ -1029,7 +1023,7 @@ int ddpm3d_msssim3d(const float* est, const float* target, const uint8_t* mask, 
     // !(c >= 0) also catches NaN; the kernel evaluates S in fp32, so the constants must be finite there
     if (!(C1 >= 0.0) || !(C2 >= 0.0) || C1 > 3.0e38 || C2 > 3.0e38)
         return fail(DDPM3D_EINVAL, "msssim3d: C1=%g C2=%g must be finite and not negative", C1, C2);
-    const int rc = metric_ws_ok("msssim3d", ddpm3d_ms_workspace_bytes(B, D, H, W, scales), ws, ws_bytes);
+    const int rc = ws_ok("msssim3d", ddpm3d_ms_workspace_bytes(B, D, H, W, scales), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_msssim3d(est, target, mask, B, D, H, W, scales, (float)C1, (float)C2, ws, out,
                                            (hipStream_t)stream),
@@ -1080,7 +1074,7 @@ int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t vox
     int64_t chunks = 0;
     int rc = roi_index_check(B, index, &chunks);
     if (rc != DDPM3D_OK) return rc;
-    rc = metric_ws_ok("roi_moments", roi_ws_bytes(B, chunks), ws, ws_bytes);
+    rc = ws_ok("roi_moments", roi_ws_bytes(B, chunks), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_roi_moments(est, target, B, voxels, *index, chunks, (double*)ws, out,
                                               (hipStream_t)stream),
@@ -1105,7 +1099,7 @@ int ddpm3d_label_components(const float* vol, const uint8_t* keep, float thresho
         return fail(DDPM3D_EINVAL, "label_components: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= "
                                    "2^31 - 1)", D, H, W);
     if (threshold != threshold) return fail(DDPM3D_EINVAL, "label_components: the threshold is NaN");
-    const int rc = metric_ws_ok("label_components", ddpm3d_ccl_workspace_bytes(D, H, W), ws, ws_bytes);
+    const int rc = ws_ok("label_components", ddpm3d_ccl_workspace_bytes(D, H, W), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_label_components(vol, keep, threshold, connectivity, D, H, W, roots, ws, status,
                                                    (hipStream_t)stream),
@@ -1176,7 +1170,7 @@ int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, i
     const int radii[3] = {r0, r1, r2};
     const float* taps[3] = {taps0, taps1, taps2};
     int rc = smooth_taps_ok("gauss_smooth", radii, taps);
-    if (rc == DDPM3D_OK) rc = metric_ws_ok("gauss_smooth", ddpm3d_gauss_smooth_workspace_bytes(D, H, W), ws, ws_bytes);
+    if (rc == DDPM3D_OK) rc = ws_ok("gauss_smooth", ddpm3d_gauss_smooth_workspace_bytes(D, H, W), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     if (ws == (const void*)vol || ws == (void*)out)
         return fail(DDPM3D_EINVAL, "gauss_smooth: the workspace must be neither vol nor out");
@@ -1270,7 +1264,7 @@ int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_reg
     if (!regrid_shape_ok(D, H, W, Do, Ho, Wo, stage))
         return fail(DDPM3D_EINVAL, "regrid: bad shape (D=%d H=%d W=%d -> %d %d %d; 1 or more each and at most 2^31 - 1 "
                                    "voxels per volume before and after every pass)", D, H, W, Do, Ho, Wo);
-    const int rc = metric_ws_ok("regrid", regrid_ws_bytes(B, stage), ws, ws_bytes);
+    const int rc = ws_ok("regrid", regrid_ws_bytes(B, stage), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     const size_t vol_bytes = (size_t)B * D * H * W * sizeof(float), out_bytes = (size_t)B * stage[2] * sizeof(float);
     if (ranges_overlap(vol, vol_bytes, out, out_bytes))
@@ -1306,7 +1300,7 @@ int ddpm3d_xstart_pull(const float* model_out, const float* x, const float* meas
     const float* taps[3] = {taps0, taps1, taps2};
     const size_t need = ddpm3d_xstart_pull_workspace_bytes(N, D, H, W);
     int rc = smooth_taps_ok("xstart_pull", radii, taps);
-    if (rc == DDPM3D_OK) rc = metric_ws_ok("xstart_pull", need, ws, ws_bytes);
+    if (rc == DDPM3D_OK) rc = ws_ok("xstart_pull", need, ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     const size_t bytes = (size_t)N * D * H * W * sizeof(float);
     const size_t mo_bytes = bytes * ((flags & DDPM3D_F_LEARN_SIGMA) ? 2 : 1);

@@ -2,28 +2,18 @@
 // include/ddpm3d.h).  Both entries reduce B estimates against one shared target in one launch plus a fold:
 // every workgroup writes one fp64 record to the caller's workspace and a second, small launch folds a volume's
 // records in a fixed order.  No floating-point atomics: the same bits on every run.  Offsets are 64-bit
-// (B * voxels passes 2^31 for 16 whole-body draws).  Records are written with 4-byte stores (halves of the
-// doubles), the map with one float per lane: no wide store whose data registers could be rewritten behind it.
+// (B * voxels passes 2^31 for 16 whole-body draws).  The reduction is record_reduce.h's; records are written with
+// 4-byte stores (halves of the doubles), the map with one float per lane: no wide store whose data registers could be
+// rewritten behind it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "ddpm3d.h"
 #include "ops.h"
+#include "record_reduce.h"
 #include "ssim3d_body.h"
 
 namespace {
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // ------------------------------------------------------------------------------------------- error moments
 constexpr int EM_THREADS = 256;
@@ -31,28 +21,11 @@ constexpr int EM_VEC = 4;
 constexpr int EM_MAX_PARTS = 2048;         // 8 workgroups per CU: enough loads in flight to stream from HBM
 constexpr int EM_REC = DDPM3D_EM_REC;
 
-// Folds the ten per-thread values over the workgroup (sums in columns 0..5 and 8..9, min / max in 6 / 7), each in
-// a fixed order, and has lanes 0..19 write the record.
-__device__ __forceinline__ void em_write_record(double (&v)[EM_REC], double* __restrict__ rec) {
-    __shared__ double red[EM_REC][EM_THREADS / 64];
-#pragma unroll
-    for (int k = 0; k < EM_REC; ++k)
-        v[k] = k == DDPM3D_EM_MIN_Y ? wave_min(v[k]) : k == DDPM3D_EM_MAX_Y ? wave_max(v[k]) : wave_sum(v[k]);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < EM_REC; ++k) red[k][wave] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * EM_REC) {
-        const int k = threadIdx.x >> 1;
-        double tot = red[k][0];
-        for (int w = 1; w < EM_THREADS / 64; ++w)
-            tot = k == DDPM3D_EM_MIN_Y ? fmin(tot, red[k][w]) : k == DDPM3D_EM_MAX_Y ? fmax(tot, red[k][w])
-                                                                                  : tot + red[k][w];
-        store_double(rec + k, threadIdx.x & 1, tot);
-    }
-}
+// sums in columns 0..5 and 8..9, min / max in 6 / 7
+struct EmCols {
+    static constexpr int COLS = EM_REC, REC = EM_REC;
+    static constexpr RrOp op(int k) { return k == DDPM3D_EM_MIN_Y ? RR_MIN : k == DDPM3D_EM_MAX_Y ? RR_MAX : RR_SUM; }
+};
 
 // Workgroup (part, b) reduces voxels [part * chunk, (part + 1) * chunk) of estimate b; chunk is a multiple of
 // EM_THREADS * EM_VEC.  V = 4: 16-byte loads of x, y and std and one 4-byte load of the mask per thread and pass.
@@ -121,38 +94,14 @@ __global__ __launch_bounds__(EM_THREADS) void error_moments_kernel(
     rec[DDPM3D_EM_MAX_Y] = (double)mx;
     rec[DDPM3D_EM_COVER_1] = (double)c1;
     rec[DDPM3D_EM_COVER_2] = (double)c2;
-    em_write_record(rec, ws + ((size_t)b * parts + part) * EM_REC);
+    rr_write_record<EmCols, EM_THREADS>(rec, ws + ((size_t)b * parts + part) * EM_REC);
 }
 
 // One workgroup per estimate: its records in a fixed order.
 __global__ __launch_bounds__(EM_THREADS) void error_moments_fold_kernel(const double* __restrict__ ws, int parts,
                                                                         double* __restrict__ out) {
     const int b = blockIdx.x;
-    double rec[EM_REC];
-#pragma unroll
-    for (int k = 0; k < EM_REC; ++k) rec[k] = 0.0;
-    rec[DDPM3D_EM_MIN_Y] = INFINITY;
-    rec[DDPM3D_EM_MAX_Y] = -INFINITY;
-    for (int p = threadIdx.x; p < parts; p += EM_THREADS) {
-        const double* r = ws + ((size_t)b * parts + p) * EM_REC;
-#pragma unroll
-        for (int k = 0; k < EM_REC; ++k)
-            rec[k] = k == DDPM3D_EM_MIN_Y ? fmin(rec[k], r[k]) : k == DDPM3D_EM_MAX_Y ? fmax(rec[k], r[k])
-                                                                                  : rec[k] + r[k];
-    }
-    em_write_record(rec, out + (size_t)b * EM_REC);
-}
-
-struct EmPlan {
-    int parts;
-    int64_t chunk;
-};
-EmPlan em_plan(int64_t voxels) {
-    const int64_t per = EM_THREADS * EM_VEC;
-    const int64_t passes = (voxels + per - 1) / per;
-    const int parts = (int)(passes < EM_MAX_PARTS ? passes : EM_MAX_PARTS);
-    const int64_t chunk = (passes + parts - 1) / parts * per;
-    return {(int)((voxels + chunk - 1) / chunk), chunk};
+    rr_fold_record<EmCols, EM_THREADS>(ws + (size_t)b * parts * EM_REC, parts, out + (size_t)b * EM_REC);
 }
 
 // ---------------------------------------------------------------------------------------------- 3-D SSIM
@@ -172,15 +121,13 @@ __global__ __launch_bounds__(256) void ssim3d_fold_kernel(const double* __restri
 
 }  // namespace
 
-// an upper bound of the records a launch writes that never shrinks as the volume grows
 size_t ddpm3d_em_workspace_bytes(int B, int64_t voxels) {
-    const int64_t per = EM_THREADS * EM_VEC, passes = (voxels + per - 1) / per;
-    return (size_t)B * (size_t)(passes < EM_MAX_PARTS ? passes : EM_MAX_PARTS) * EM_REC * sizeof(double);
+    return rr_workspace_bytes(B, voxels, EM_THREADS * EM_VEC, EM_MAX_PARTS, EM_REC);
 }
 
 hipError_t ddpm3d_launch_error_moments(const float* est, const float* target, const uint8_t* mask, const float* std,
                                        int B, int64_t voxels, double* ws, double* out, hipStream_t st) {
-    const EmPlan p = em_plan(voxels);
+    const RrPlan p = rr_plan(voxels, EM_THREADS * EM_VEC, EM_MAX_PARTS);
     const bool wide = voxels % EM_VEC == 0 && aligned(est, 16) && aligned(target, 16) && (!mask || aligned(mask, 4)) &&
                       (!std || aligned(std, 16));
     const dim3 grid(p.parts, B);

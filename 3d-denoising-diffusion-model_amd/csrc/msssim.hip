@@ -62,8 +62,6 @@ __global__ __launch_bounds__(PL_TW * PL_TH) void pool2_kernel(
     }
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // ------------------------------------------------------------------------------------ per-scale SSIM parts
 __global__ __launch_bounds__(SS_THREADS) void msssim3d_parts_kernel(
     const float* __restrict__ est, const float* __restrict__ target, const uint8_t* __restrict__ mask, int D, int H,

@@ -5,6 +5,8 @@
 
 // the 16-byte (four-wide) forms of a kernel need this of every pointer they read or write
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the same for a kernel whose pointers need different (power-of-two) alignments
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int prec, void* out, hipStream_t st);
 hipError_t ddpm3d_launch_pack_up_phase(const float* w, int Cout, int Cin, void* out, hipStream_t st);

@@ -7,6 +7,7 @@
 #include "conv3d_load.h"   // affine_act, act_quad, half_pack
 #include "ops.h"
 #include "noise.h"
+#include "record_reduce.h"
 
 // ------------------------------------------------------------------ packing
 // OIDHW -> [tap][ci/8][CoutPad][8]  (zero padded in ci and cout).  The inner 8
@@ -264,11 +265,7 @@ hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int pre
 }
 
 // ------------------------------------------------------------- wave helpers
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+// (wave_sum(double) is record_reduce.h's)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -1067,25 +1064,10 @@ __device__ __forceinline__ float approx_std_normal_cdf(float x) {
     return 0.5f * (1.0f + (float)tanh((double)u));
 }
 
-// Block sum of three fp64 partials in a fixed order, written as record `rec` by eight lanes with one 4-byte store
-// each (halves of the doubles; no wide store whose data registers could be rewritten behind it).
-__device__ __forceinline__ void vb_write_record(double s0, double s1, double s2, double* __restrict__ rec) {
-    __shared__ double red[3][VB_THREADS / 64];
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; red[2][wave] = s2; }
-    __syncthreads();
-    if (threadIdx.x < 2 * VB_REC) {
-        const int k = threadIdx.x >> 1;
-        double tot = 0.0;
-        if (k < 3)
-            for (int w = 0; w < VB_THREADS / 64; ++w) tot += red[k][w];
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(tot);
-        reinterpret_cast<unsigned*>(rec)[threadIdx.x] = (threadIdx.x & 1) ? (unsigned)(bits >> 32) : (unsigned)bits;
-    }
-}
+// A record is {term, xstart sq, eps sq} and an explicit 0.0 in its fourth double (record_reduce.h).  The wave totals
+// are folded from the first wave's, where this file once started from 0.0: the same bits, because every per-thread
+// accumulator starts at +0.0 and so no partial sum can be -0.0 (the one value 0.0 + x would change).
+using VbCols = RrSum<3, VB_REC>;
 
 __global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
     const float* __restrict__ mo, const float* __restrict__ xs_p, const float* __restrict__ xt_p,
@@ -1150,7 +1132,8 @@ __global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
     } else {
         s_vb = s_x0 = s_eps = __builtin_nan("");
     }
-    vb_write_record(s_vb, s_x0, s_eps, slab + ((size_t)n * parts + part) * VB_REC);
+    double rec[3] = {s_vb, s_x0, s_eps};
+    rr_write_record<VbCols, VB_THREADS>(rec, slab + ((size_t)n * parts + part) * VB_REC);
 }
 
 // _prior_bpd: normal_kl(sqrt_acp[T-1] * x_start, log_1m_acp[T-1], 0, 0) per element; with mean2 = logvar2 = 0 the
@@ -1173,7 +1156,8 @@ __global__ __launch_bounds__(VB_THREADS) void prior_bpd_kernel(const float* __re
             s += (double)(0.5f * (((-1.0f - lv) + exp_r(lv)) + m * m));
         }
     }
-    vb_write_record(s, 0.0, 0.0, slab + ((size_t)n * parts + part) * VB_REC);
+    double rec[3] = {s, 0.0, 0.0};
+    rr_write_record<VbCols, VB_THREADS>(rec, slab + ((size_t)n * parts + part) * VB_REC);
 }
 
 // One workgroup per sample: the sample's records in a fixed order, then mean (/ ln 2 for the bound's term).
@@ -1181,27 +1165,13 @@ __global__ __launch_bounds__(256) void vb_fold_kernel(const double* __restrict__
                                                       float* __restrict__ vb, float* __restrict__ xstart_mse,
                                                       float* __restrict__ mse, int ld) {
     const int n = blockIdx.x;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int p = threadIdx.x; p < parts; p += 256) {
-        const double* r = slab + ((size_t)n * parts + p) * VB_REC;
-        s0 += r[0];
-        s1 += r[1];
-        s2 += r[2];
-    }
-    __shared__ double red[3][4];
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wave] = s0; red[1][wave] = s1; red[2][wave] = s2; }
-    __syncthreads();
+    double s[3];
+    rr_fold<VbCols, 256>(slab + (size_t)n * parts * VB_REC, parts, s);
+    const auto total = rr_reduce<VbCols, 256>(s);
     if (threadIdx.x == 0) {
-        s0 = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        s1 = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-        s2 = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
-        vb[(size_t)n * ld] = (float)(s0 / count / 0.69314718055994530942);   // mean_flat(.) / np.log(2.0)
-        if (xstart_mse != nullptr) xstart_mse[(size_t)n * ld] = (float)(s1 / count);
-        if (mse != nullptr) mse[(size_t)n * ld] = (float)(s2 / count);
+        vb[(size_t)n * ld] = (float)(total(0) / count / 0.69314718055994530942);   // mean_flat(.) / np.log(2.0)
+        if (xstart_mse != nullptr) xstart_mse[(size_t)n * ld] = (float)(total(1) / count);
+        if (mse != nullptr) mse[(size_t)n * ld] = (float)(total(2) / count);
     }
 }
 

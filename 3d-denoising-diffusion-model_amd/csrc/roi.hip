@@ -2,13 +2,14 @@
 // voxel-index list in CSR form (definitions in include/ddpm3d.h).  Region r's entries are cut into
 // consecutive chunks of DDPM3D_ROI_CHUNK; one workgroup per (chunk, estimate) gathers its values, reduces them in a
 // fixed order and writes one fp64 record to the caller's workspace; a second launch folds each (estimate, region)'s
-// records in a fixed order.  No atomics: the same bits on every run, and row b does not depend on B.  Records are
-// written with 4-byte stores (halves of the doubles), as in metrics.hip.
+// records in a fixed order.  No atomics: the same bits on every run, and row b does not depend on B.  The reduction
+// is record_reduce.h's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "ddpm3d.h"
 #include "ops.h"
+#include "record_reduce.h"
 
 namespace {
 
@@ -17,33 +18,11 @@ constexpr int ROI_PER = DDPM3D_ROI_CHUNK / ROI_THREADS;      // entries per thre
 constexpr int ROI_REC = DDPM3D_ROI_REC;
 static_assert(DDPM3D_ROI_CHUNK % ROI_THREADS == 0, "a chunk is a whole number of passes");
 
-__device__ __forceinline__ double roi_combine(int k, double a, double b) {
-    return k == DDPM3D_ROI_MIN_X ? fmin(a, b) : k == DDPM3D_ROI_MAX_X ? fmax(a, b) : a + b;
-}
-
-// Folds the eight per-thread values over the workgroup (lanes by xor butterfly, then the four waves in ascending
-// order) and has lanes 0..15 write the record, one half of a double each.
-__device__ __forceinline__ void roi_write_record(double (&v)[ROI_REC], double* __restrict__ rec) {
-    __shared__ double red[ROI_REC][ROI_THREADS / 64];
-#pragma unroll
-    for (int k = 0; k < ROI_REC; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] = roi_combine(k, v[k], __shfl_xor(v[k], o));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < ROI_REC; ++k) red[k][wave] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * ROI_REC) {
-        const int k = threadIdx.x >> 1;
-        double tot = red[k][0];
-        for (int w = 1; w < ROI_THREADS / 64; ++w) tot = roi_combine(k, tot, red[k][w]);
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(tot);
-        reinterpret_cast<unsigned*>(rec + k)[threadIdx.x & 1] = (threadIdx.x & 1) ? (unsigned)(bits >> 32) : (unsigned)bits;
-    }
-}
+// sums but for the minimum and the maximum of x
+struct RoiCols {
+    static constexpr int COLS = ROI_REC, REC = ROI_REC;
+    static constexpr RrOp op(int k) { return k == DDPM3D_ROI_MIN_X ? RR_MIN : k == DDPM3D_ROI_MAX_X ? RR_MAX : RR_SUM; }
+};
 
 // Workgroup (c, b): chunk c of the index belongs to the region r with chunks[r] <= c < chunks[r + 1] (a search of
 // the prefix table; empty regions own no chunk) and covers entries [e0, e1) of it.  A thread takes entries
@@ -106,7 +85,7 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_chunk_kernel(
     rec[DDPM3D_ROI_SUM_E] = se;
     rec[DDPM3D_ROI_SUM_ABS_E] = sa;
     rec[DDPM3D_ROI_SUM_SQ_E] = sq;
-    roi_write_record(rec, ws + ((int64_t)b * total + c) * ROI_REC);
+    rr_write_record<RoiCols, ROI_THREADS>(rec, ws + ((int64_t)b * total + c) * ROI_REC);
 }
 
 // Workgroup (r, b): region r's records of estimate b, chunk p to thread p mod 256 in ascending p, then the
@@ -116,17 +95,8 @@ __global__ __launch_bounds__(ROI_THREADS) void roi_fold_kernel(const double* __r
                                                                int R, double* __restrict__ out) {
     const int r = blockIdx.x, b = blockIdx.y;
     const int64_t c0 = chunks[r], c1 = chunks[r + 1];
-    double rec[ROI_REC];
-#pragma unroll
-    for (int k = 0; k < ROI_REC; ++k) rec[k] = 0.0;
-    rec[DDPM3D_ROI_MIN_X] = INFINITY;
-    rec[DDPM3D_ROI_MAX_X] = -INFINITY;
-    for (int64_t p = c0 + threadIdx.x; p < c1; p += ROI_THREADS) {
-        const double* w = ws + ((int64_t)b * total + p) * ROI_REC;
-#pragma unroll
-        for (int k = 0; k < ROI_REC; ++k) rec[k] = roi_combine(k, rec[k], w[k]);
-    }
-    roi_write_record(rec, out + ((int64_t)b * R + r) * ROI_REC);
+    rr_fold_record<RoiCols, ROI_THREADS>(ws + ((int64_t)b * total + c0) * ROI_REC, c1 - c0,
+                                         out + ((int64_t)b * R + r) * ROI_REC);
 }
 
 }  // namespace

@@ -1,24 +1,15 @@
 // The march of the 3-D SSIM, shared by ssim3d_kernel (metrics.hip) and the per-scale kernel of the
 // multi-scale SSIM (msssim.hip): one body templated on whether the contrast-structure term CS gets
 // a sum of its own.  Both kernels evaluate S by the same expression in the same order, so scale 0 of the multi-scale
-// entry carries the bits of ddpm3d_ssim3d.  Records are written with 4-byte stores (halves of the doubles), the map
-// with one float per lane: no wide store whose data registers could be rewritten behind it.
+// entry carries the bits of ddpm3d_ssim3d.  The records and their fold are record_reduce.h's, every column a sum; the
+// map is written with one float per lane: no wide store whose data registers could be rewritten behind it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "record_reduce.h"
 
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ void store_double(double* p, int lane_half, double v) {
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-    reinterpret_cast<unsigned*>(p)[lane_half] = lane_half ? (unsigned)(bits >> 32) : (unsigned)bits;
-}
 
 // A workgroup owns a 16 (h) x 32 (w) tile of interior voxels and marches along d through one chunk of the depth.
 // Per input plane: the tile plus its halo of 10 of both volumes goes to LDS with a pivot taken off, the five
@@ -85,7 +76,6 @@ __device__ __forceinline__ void ssim3d_march(
     constexpr int REC = SS_REC<CS>;
     __shared__ float tile[2][SS_IH][SS_IW];
     __shared__ float rowf[SS_FIELDS][SS_IH][SS_TW];
-    __shared__ double red[REC][SS_THREADS / 64];
     __shared__ float pmin[2][SS_THREADS / 64];
 
     const int tid = threadIdx.x, tx = tid % SS_TW, ty = tid / SS_TW;
@@ -228,21 +218,11 @@ __device__ __forceinline__ void ssim3d_march(
     }
 
     double tot[REC];
-    tot[0] = wave_sum(sum);
-    if constexpr (CS) tot[1] = wave_sum(sum_cs);
-    tot[REC - 1] = wave_sum((double)count);
-    const int wave = tid >> 6;
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < REC; ++k) red[k][wave] = tot[k];
-    }
-    __syncthreads();
-    if (tid < 2 * REC) {
-        const int k = tid >> 1;
-        const double t = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-        double* rec = ws + ((int64_t)b * recs + (int64_t)blockIdx.y * gridDim.x + blockIdx.x) * REC;
-        store_double(rec + k, tid & 1, t);
-    }
+    tot[0] = sum;
+    if constexpr (CS) tot[1] = sum_cs;
+    tot[REC - 1] = (double)count;
+    rr_write_record<RrSum<REC>, SS_THREADS>(
+        tot, ws + ((int64_t)b * recs + (int64_t)blockIdx.y * gridDim.x + blockIdx.x) * REC);
 }
 
 // The body of the fold kernel, 256 threads, one workgroup per estimate: the columns of its `used` records of REC
@@ -250,29 +230,8 @@ __device__ __forceinline__ void ssim3d_march(
 template <int REC>
 __device__ __forceinline__ void ssim3d_fold(const double* __restrict__ ws, int64_t recs, int used,
                                             double* __restrict__ out, int out_stride) {
-    __shared__ double red[REC][4];
     const int b = blockIdx.x;
-    double s[REC];
-#pragma unroll
-    for (int k = 0; k < REC; ++k) s[k] = 0.0;
-    for (int p = threadIdx.x; p < used; p += 256) {
-        const double* r = ws + ((int64_t)b * recs + p) * REC;
-#pragma unroll
-        for (int k = 0; k < REC; ++k) s[k] += r[k];
-    }
-#pragma unroll
-    for (int k = 0; k < REC; ++k) s[k] = wave_sum(s[k]);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < REC; ++k) red[k][wave] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * REC) {
-        const int k = threadIdx.x >> 1;
-        const double tot = ((red[k][0] + red[k][1]) + red[k][2]) + red[k][3];
-        store_double(out + (size_t)b * out_stride + k, threadIdx.x & 1, tot);
-    }
+    rr_fold_record<RrSum<REC>, 256>(ws + (int64_t)b * recs * REC, used, out + (size_t)b * out_stride);
 }
 
 }  // namespace

@@ -3,14 +3,13 @@
 // shape is metrics.hip's error-moments pair: workgroup (part, b) reduces one chunk of estimate b in a fixed order
 // and writes one fp64 record to the caller's workspace, a second, small launch folds a sample's records in a fixed
 // order.  No atomics: the same bits on every run, and the plan depends on `voxels` alone, so row b of a batch carries
-// the bits of a call on estimate b.  Offsets are 64-bit.  Records are written with 4-byte stores (halves of the
-// doubles): no wide store whose data registers could be rewritten behind it.
+// the bits of a call on estimate b.  Offsets are 64-bit.  The reduction is record_reduce.h's, every column a sum.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "ddpm3d.h"
 #include "ops.h"
-#include "ssim3d_body.h"        // wave_sum, store_double
+#include "record_reduce.h"
 
 namespace {
 
@@ -19,26 +18,7 @@ constexpr int TR_VEC = 4;
 constexpr int TR_MAX_PARTS = 2048;         // 8 workgroups per CU: enough loads in flight to stream from HBM
 constexpr int TR_REC = DDPM3D_TR_REC;
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// Sums the ten per-thread values over the workgroup, each in a fixed order, and has lanes 0..19 write the record.
-__device__ __forceinline__ void tr_write_record(double (&v)[TR_REC], double* __restrict__ rec) {
-    __shared__ double red[TR_REC][TR_THREADS / 64];
-#pragma unroll
-    for (int k = 0; k < TR_REC; ++k) v[k] = wave_sum(v[k]);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < TR_REC; ++k) red[k][wave] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * TR_REC) {
-        const int k = threadIdx.x >> 1;
-        double tot = red[k][0];
-        for (int w = 1; w < TR_THREADS / 64; ++w) tot += red[k][w];
-        store_double(rec + k, threadIdx.x & 1, tot);
-    }
-}
+using TrCols = RrSum<TR_REC>;
 
 template <int V>
 __device__ __forceinline__ void tr_load(const float* __restrict__ p, int64_t i, float (&v)[V]) {
@@ -111,48 +91,26 @@ __global__ __launch_bounds__(TR_THREADS) void trace_moments_kernel(
     rec[DDPM3D_TR_SUM_SQ_X] = sxx;
     rec[DDPM3D_TR_SUM_SQ_D] = sdd;
     rec[DDPM3D_TR_CLIPPED] = sc;
-    tr_write_record(rec, ws + ((size_t)b * parts + part) * TR_REC);
+    rr_write_record<TrCols, TR_THREADS>(rec, ws + ((size_t)b * parts + part) * TR_REC);
 }
 
 // One workgroup per estimate: its records in a fixed order.
 __global__ __launch_bounds__(TR_THREADS) void trace_moments_fold_kernel(const double* __restrict__ ws, int parts,
                                                                         double* __restrict__ out) {
     const int b = blockIdx.x;
-    double rec[TR_REC];
-#pragma unroll
-    for (int k = 0; k < TR_REC; ++k) rec[k] = 0.0;
-    for (int p = threadIdx.x; p < parts; p += TR_THREADS) {
-        const double* r = ws + ((size_t)b * parts + p) * TR_REC;
-#pragma unroll
-        for (int k = 0; k < TR_REC; ++k) rec[k] += r[k];
-    }
-    tr_write_record(rec, out + (size_t)b * TR_REC);
-}
-
-struct TrPlan {
-    int parts;
-    int64_t chunk;
-};
-TrPlan tr_plan(int64_t voxels) {
-    const int64_t per = TR_THREADS * TR_VEC;
-    const int64_t passes = (voxels + per - 1) / per;
-    const int parts = (int)(passes < TR_MAX_PARTS ? passes : TR_MAX_PARTS);
-    const int64_t chunk = (passes + parts - 1) / parts * per;
-    return {(int)((voxels + chunk - 1) / chunk), chunk};
+    rr_fold_record<TrCols, TR_THREADS>(ws + (size_t)b * parts * TR_REC, parts, out + (size_t)b * TR_REC);
 }
 
 }  // namespace
 
-// an upper bound of the records a launch writes that never shrinks as the estimates grow
 size_t ddpm3d_tr_workspace_bytes(int B, int64_t voxels) {
-    const int64_t per = TR_THREADS * TR_VEC, passes = (voxels + per - 1) / per;
-    return (size_t)B * (size_t)(passes < TR_MAX_PARTS ? passes : TR_MAX_PARTS) * TR_REC * sizeof(double);
+    return rr_workspace_bytes(B, voxels, TR_THREADS * TR_VEC, TR_MAX_PARTS, TR_REC);
 }
 
 hipError_t ddpm3d_launch_trace_moments(const float* est, const float* prev, const float* target, const float* weight,
                                        int B, int64_t voxels, int64_t target_stride, int64_t weight_stride, double* ws,
                                        double* out, hipStream_t st) {
-    const TrPlan p = tr_plan(voxels);
+    const RrPlan p = rr_plan(voxels, TR_THREADS * TR_VEC, TR_MAX_PARTS);
     // every row of every input starts a multiple of `voxels` floats behind its base: one test per pointer
     const bool wide = voxels % TR_VEC == 0 && aligned(est, 16) && (!prev || aligned(prev, 16)) &&
                       (!target || aligned(target, 16)) && (!weight || aligned(weight, 16));

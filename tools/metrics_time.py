@@ -27,7 +27,7 @@ KS = [1, 8]
 
 
 def timed(fn, reps):
-    """median device time of fn() in ms over reps runs, after two warm-up runs"""
+    """median, min and max device time of fn() in ms over reps runs, after two warm-up runs"""
     for _ in range(2):
         fn()
     torch.cuda.synchronize()
@@ -39,7 +39,7 @@ def timed(fn, reps):
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return float(np.median(times))
+    return float(np.median(times)), min(times), max(times)
 
 
 def scipy_ssim_seconds(x, y):
@@ -93,9 +93,9 @@ def main():
                 ("ssim3d+map", lambda: ssim(smap), 4.0 * voxels * (K + 1) + 4.0 * interior * K),
             ]
             for name, fn, nbytes in cases:
-                ms = timed(fn, args.reps)
-                rows.append(dict(entry=name, shape="%dx%dx%d" % shape, K=K, ms=ms, gb_per_s=nbytes / ms * 1e-6,
-                                 nominal_mb=nbytes * 1e-6))
+                ms, lo, hi = timed(fn, args.reps)
+                rows.append(dict(entry=name, shape="%dx%dx%d" % shape, K=K, ms=ms, ms_min=lo, ms_max=hi,
+                                 gb_per_s=nbytes / ms * 1e-6, nominal_mb=nbytes * 1e-6))
                 print("%-24s %-12s K=%d  %9.3f ms  %8.1f GB/s of %9.1f MB nominal"
                       % (name, rows[-1]["shape"], K, ms, rows[-1]["gb_per_s"], rows[-1]["nominal_mb"]), flush=True)
             del x, smap, ws

@@ -27,7 +27,7 @@ SHAPES = [((130, 200, 200), (4,)), ((700, 440, 440), (4, 5))]
 
 
 def timed(fn, reps):
-    """median device time of fn() in ms over reps runs, after two warm-up runs"""
+    """median, min and max device time of fn() in ms over reps runs, after two warm-up runs"""
     for _ in range(2):
         fn()
     torch.cuda.synchronize()
@@ -39,7 +39,7 @@ def timed(fn, reps):
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b))
-    return float(np.median(times))
+    return float(np.median(times)), min(times), max(times)
 
 
 def main():
@@ -87,8 +87,8 @@ def main():
                 cases.append(("msssim3d M=%d+mask" % M, lambda M=M: msssim(M, mask), None))
         base = {}
         for entry, fn, nbytes in cases:
-            ms = timed(fn, args.reps)
-            row = dict(entry=entry, shape=name, K=1, ms=ms)
+            ms, lo, hi = timed(fn, args.reps)
+            row = dict(entry=entry, shape=name, K=1, ms=ms, ms_min=lo, ms_max=hi)
             if nbytes is not None:
                 row.update(gb_per_s=nbytes / ms * 1e-6, nominal_mb=nbytes * 1e-6)
             if entry.startswith("ssim3d"):

@@ -36,7 +36,8 @@ ENTRY_CASES = [(1, (96, 96, 96)), (8, (96, 96, 96)), (1, (700, 440, 440))]
 
 
 def timed(fn, reps, inner):
-    """median device time of one fn() in ms: reps event pairs around `inner` calls each, after two warm-up calls"""
+    """median, min and max device time of one fn() in ms: reps event pairs around `inner` calls each, after two
+    warm-up calls"""
     for _ in range(2):
         fn()
     torch.cuda.synchronize()
@@ -49,7 +50,7 @@ def timed(fn, reps, inner):
         b.record()
         b.synchronize()
         times.append(a.elapsed_time(b) / inner)
-    return float(np.median(times))
+    return float(np.median(times)), min(times), max(times)
 
 
 def entry_rows(args, dev):
@@ -77,9 +78,9 @@ def entry_rows(args, dev):
         inner = args.inner if voxels < 10 ** 7 else 2
         for name, fn, nbytes in (("trace_moments", trace, 16.0 * B * voxels),
                                  ("error_moments", moments, 4.0 * voxels * (B + 1))):
-            ms = timed(fn, args.reps, inner)
-            rows.append(dict(entry=name, shape="%dx%dx%d" % shape, B=B, ms=ms, gb_per_s=nbytes / ms * 1e-6,
-                             nominal_mb=nbytes * 1e-6))
+            ms, lo, hi = timed(fn, args.reps, inner)
+            rows.append(dict(entry=name, shape="%dx%dx%d" % shape, B=B, ms=ms, ms_min=lo, ms_max=hi,
+                             gb_per_s=nbytes / ms * 1e-6, nominal_mb=nbytes * 1e-6))
             print("%-14s %-12s B=%d  %9.4f ms  %8.1f GB/s of %9.1f MB nominal"
                   % (name, rows[-1]["shape"], B, ms, rows[-1]["gb_per_s"], rows[-1]["nominal_mb"]), flush=True)
         del x, y, prev, w, ws
