@@ -29,7 +29,6 @@ int ddpm3d_abi_version(void) { return DDPM3D_ABI_VERSION; }
 const char* ddpm3d_last_error(void) { return g_err; }
 
 static bool prec_ok(int p) { return p >= DDPM3D_PREC_F32 && p <= DDPM3D_PREC_BF16_WZ; }
-static bool prec_wz(int p) { return p == DDPM3D_PREC_F16X3_WZ || p == DDPM3D_PREC_F16_WZ || p == DDPM3D_PREC_BF16_WZ; }
 // modes whose activation scale comes from in_bound (the bf16 modes need none: fp32's exponent range)
 static bool prec_scaled(int p) { return p != DDPM3D_PREC_F32 && p != DDPM3D_PREC_BF16 && p != DDPM3D_PREC_BF16_WZ; }
 
@@ -40,8 +39,8 @@ static bool wz_layer_ok(int Cout, int Cin, int ksize) {
 
 size_t ddpm3d_packed_weight_bytes(int Cout, int Cin, int ksize, int precision) {
     if (Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3) || !prec_ok(precision)) return 0;
-    if (prec_wz(precision) && !wz_layer_ok(Cout, Cin, ksize)) return 0;
-    return ddpm3d_packed_bytes(Cout, Cin, ksize, precision);
+    if (ddpm3d_prec_wz(precision) && !wz_layer_ok(Cout, Cin, ksize)) return 0;
+    return ddpm3d_packed_image(Cout, Cin, ksize, precision).bytes();
 }
 
 int ddpm3d_pack_conv_weight(const float* w, int Cout, int Cin, int ksize, int precision, void* out,
@@ -50,7 +49,7 @@ int ddpm3d_pack_conv_weight(const float* w, int Cout, int Cin, int ksize, int pr
         return fail(DDPM3D_EINVAL, "pack_conv_weight: bad arguments (Cout=%d Cin=%d k=%d precision=%d)", Cout,
                     Cin, ksize, precision);
     if (!aligned16(out)) return fail(DDPM3D_EINVAL, "pack_conv_weight: w_packed must be 16-byte aligned");
-    if (prec_wz(precision) && !wz_layer_ok(Cout, Cin, ksize))
+    if (ddpm3d_prec_wz(precision) && !wz_layer_ok(Cout, Cin, ksize))
         return fail(DDPM3D_ENOSUP, "pack_conv_weight: the Winograd-D form needs ksize 3, Cout %% 128 == 0, "
                                    "Cin %% 16 == 0 (got Cout=%d Cin=%d k=%d)", Cout, Cin, ksize);
     return launched(ddpm3d_launch_pack(w, Cout, Cin, ksize, precision, out, (hipStream_t)stream),
@@ -132,7 +131,7 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
             return fail(DDPM3D_EINVAL, "conv3d: a forced split factor needs Cout > 64 and S <= Cin / 16");
         ddpm3d_conv_cfg_split(c, s_forced, d->N, d->D, d->H, d->W, d->Cout);
     }
-    if (prec_wz(d->precision) &&
+    if (ddpm3d_prec_wz(d->precision) &&
         !(wz_layer_ok(d->Cout, d->Cin, d->ksize) && c.WN == 4 && c.MT == 4 &&
           (d->in_mode == DDPM3D_IN_SAME || d->in_mode == DDPM3D_IN_UP)))
         return fail(DDPM3D_ENOSUP, "conv3d: the Winograd-D form needs ksize 3, Cout %% 128 == 0 "
@@ -163,8 +162,10 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
         phase = ddpm3d_up_phase_geom(d->D, d->H, d->W, c, g) && d->res_mode != DDPM3D_RES_POOL;
         if (!phase) k.hint &= ~DDPM3D_HINT_UP_PHASE;
     }
-    const size_t w_front = phase ? ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision) : (size_t)0;
-    k.w = (const float*)((const char*)d->w_packed + w_front);
+    // the image this call reads: the phase image behind the Winograd-D one, else the buffer's (first) image
+    const PackedImage front = ddpm3d_packed_image(d->Cout, d->Cin, d->ksize, d->precision);
+    const PackedImage img = phase ? ddpm3d_up_phase_image(d->Cout, d->Cin) : front;
+    k.w = (const float*)((const char*)d->w_packed + (phase ? front.bytes() : (size_t)0));
     k.io = d->io_dtype;
     if (d->io_dtype & ~(DDPM3D_IO_SRC0_BF16 | DDPM3D_IO_SRC1_BF16 | DDPM3D_IO_OUT_BF16 | DDPM3D_IO_RES_BF16 |
                         DDPM3D_IO_HALF_IS_F16))
@@ -194,8 +195,7 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
         const long long vox = (long long)d->N * d->D * Hs * Ws;
         const long long b0 = vox * d->C0 * ((d->io_dtype & DDPM3D_IO_SRC0_BF16) ? 2 : 4);
         const long long b1 = vox * d->C1 * ((d->io_dtype & DDPM3D_IO_SRC1_BF16) ? 2 : 4);
-        const size_t wb = phase ? ddpm3d_up_phase_body_bytes(d->Cout, d->Cin)
-                                : ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision);
+        const size_t wb = phase ? img.body : img.bytes();
         if (b0 >= 0xFFFFFFF0LL || b1 >= 0xFFFFFFF0LL || wb >= 0xFFFFFFF0ULL)
             return fail(DDPM3D_E2BIG, "conv3d: a source tensor or the weights exceed 4 GiB; split the batch");
         // the epilogue addresses one SAMPLE of the output (or residual) with 32-bit offsets
@@ -207,12 +207,7 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
                   : (d->kernel_hint & DDPM3D_HINT_WSTAT_OFF) ? 0
                                                              : ((long long)wb > b0 + b1 ? 1 : 0);
     }
-    if (phase)
-        k.wscale = (const float*)((const char*)k.w + ddpm3d_up_phase_body_bytes(d->Cout, d->Cin));
-    else if (c.PREC != DDPM3D_PREC_F32)  // output scales sit behind the f16 image
-        k.wscale = (const float*)((const char*)d->w_packed +
-                                  ddpm3d_packed_bytes(d->Cout, d->Cin, d->ksize, d->precision) -
-                                  (size_t)ddpm3d_cout_pad(d->Cout) * 4);
+    if (img.scales) k.wscale = (const float*)((const char*)k.w + img.body);  // output scales sit behind the taps
     if (d->stats && d->stats_rows != k.stats_rows)
         return fail(DDPM3D_EINVAL, "conv3d: stats_rows=%d, this shape writes %d", d->stats_rows, k.stats_rows);
     if (d->stats && !aligned16(d->stats)) return fail(DDPM3D_EINVAL, "conv3d: stats must be 16-byte aligned");

@@ -191,25 +191,32 @@ static inline bool ddpm3d_skip_fuse_rule(int N, int D, int H, int W, int Cx, int
     return true;
 }
 
-// bytes of the packed weight image: fp32 [tap][ci/8][CoutPad][8] for PREC 0;
-// f16 [tap][ci/16][hi|lo][CoutPad][16] followed by CoutPad fp32 output scales for PREC 1
-static inline size_t ddpm3d_packed_bytes(int Cout, int Cin, int ksize, int prec) {
-    // Winograd-D form: 4 transformed depth taps x 3 x 3 = 36 instead of 27
-    const size_t taps = (prec == DDPM3D_PREC_F16X3_WZ || prec == DDPM3D_PREC_F16_WZ || prec == DDPM3D_PREC_BF16_WZ)
-                            ? 36 : (size_t)ksize * ksize * ksize;
-    const size_t body = taps * ddpm3d_cin_pad(Cin) * ddpm3d_cout_pad(Cout) * 4;
-    return prec != 0 ? body + (size_t)ddpm3d_cout_pad(Cout) * 4 : body;  // modes 1 and 2 share the image
+static inline bool ddpm3d_prec_wz(int p) {
+    return p == DDPM3D_PREC_F16X3_WZ || p == DDPM3D_PREC_F16_WZ || p == DDPM3D_PREC_BF16_WZ;
 }
+static inline bool ddpm3d_prec_bf16(int p) { return p == DDPM3D_PREC_BF16 || p == DDPM3D_PREC_BF16_WZ; }
 
-// ---- DDPM3D_HINT_UP_PHASE: an IN_UP 3x3x3 conv as four 2x2 phase convs on the low-resolution source
-// (conv3d_wz.h PHASE).  The phase body of the image: 4 phases x 16 taps of the shipped per-tap layout.
-static inline size_t ddpm3d_up_phase_body_bytes(int Cout, int Cin) {
-    return (size_t)64 * ddpm3d_cin_pad(Cin) * ddpm3d_cout_pad(Cout) * 4;
+// One packed weight image: `body` bytes of taps -- fp32 [tap][ci/8][CoutPad][8] for PREC 0, else 16-bit
+// [tap][ci/16][hi|lo][CoutPad][16] (4 bytes per element either way) -- then `scales` bytes of CoutPad fp32 output
+// scales (none for PREC 0), which therefore sit at offset `body`.
+struct PackedImage {
+    int taps;
+    size_t body, scales;
+    PackedImage(int taps_, int Cout, int Cin, bool scaled)
+        : taps(taps_), body((size_t)taps_ * ddpm3d_cin_pad(Cin) * ddpm3d_cout_pad(Cout) * 4),
+          scales(scaled ? (size_t)ddpm3d_cout_pad(Cout) * 4 : (size_t)0) {}
+    size_t bytes() const { return body + scales; }
+};
+// Winograd-D form: 4 transformed depth taps x 3 x 3 = 36 instead of 27; modes 1 and 2 share the image
+static inline PackedImage ddpm3d_packed_image(int Cout, int Cin, int ksize, int prec) {
+    return PackedImage(ddpm3d_prec_wz(prec) ? 36 : ksize * ksize * ksize, Cout, Cin, prec != DDPM3D_PREC_F32);
 }
-// [F16X3_WZ image incl. its scales][phase body][CoutPad fp32 scales of the phase body]
+// ---- DDPM3D_HINT_UP_PHASE: an IN_UP 3x3x3 conv as four 2x2 phase convs on the low-resolution source
+// (conv3d_wz.h PHASE).  The phase image: 4 phases x 16 taps of the shipped per-tap layout and their own scales.
+// ddpm3d_pack_up_phase_weight's buffer is [F16X3_WZ image incl. its scales][phase image].
+static inline PackedImage ddpm3d_up_phase_image(int Cout, int Cin) { return PackedImage(64, Cout, Cin, true); }
 static inline size_t ddpm3d_up_phase_bytes(int Cout, int Cin) {
-    return ddpm3d_packed_bytes(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ) + ddpm3d_up_phase_body_bytes(Cout, Cin) +
-           (size_t)ddpm3d_cout_pad(Cout) * 4;
+    return ddpm3d_packed_image(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ).bytes() + ddpm3d_up_phase_image(Cout, Cin).bytes();
 }
 // Tile form on the LOW-resolution grid (H/2 x W/2), chosen like the launcher chooses the output grid's
 // (8x4x4 where H/2 % 8 == 0 and D % 4 == 0, else 8x8x2, 4x4x8 below 8x8), ragged edges included.  The form is

@@ -51,7 +51,7 @@
 // the nearest-(1,2,2)-up-sampled plane the nine (dy, dx) taps of an output voxel of parity (py, px) meet 2x2 source
 // voxels (py = 0: source row i-1 | i, i; py = 1: i, i | i+1; the same along x), so a workgroup owns ONE phase of one
 // low-resolution tile: staged like an IN_SAME tile of the source grid (full 3x3 halo), 16 taps (j, a, b) per chunk
-// instead of 36 on the weights ops.hip summed per phase (pack_wz_up_kernel), tap (j, a, b) at LDS offset
+// instead of 36 on the weights ops.hip summed per phase (WzUpTaps), tap (j, a, b) at LDS offset
 // (j RZ + (a + py) RY + (b + px) VS) 16 with the phase's share folded into arow[] once, and an epilogue that places
 // row (y, x) at output (2y + py, 2x + px).  The phase is wave-uniform (from the workgroup id).
 // (the phase form is MODE_ WZ_F16X3_UP of the one kernel, so that the shipped forms keep their code and their names)

@@ -29,60 +29,13 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, int Cout, int Ci
     }
 }
 
-// Split-f16 image.  Pass 1: per output channel, the power-of-two scale
-// s = 2^floor(log2(W_TARGET / max|w|)) and the epilogue factor 1 / s.
-__global__ __launch_bounds__(256) void pack_x3_scale_kernel(const float* __restrict__ w, int Cout, int per_cout,
-                                                            float* __restrict__ wscale) {
-    const int co = blockIdx.x;
-    float m = 0.0f;
-    if (co < Cout)
-        for (int i = threadIdx.x; i < per_cout; i += 256) m = fmaxf(m, fabsf(w[(size_t)co * per_cout + i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        float s = 1.0f;
-        if (m > 0.0f && m < 3.0e38f) s = exp2f(floorf(log2f(DDPM3D_X3_W_TARGET / m)));
-        s = fminf(fmaxf(s, 1.0f / 16777216.0f), 16777216.0f);
-        wscale[co] = 1.0f / s;  // exact: powers of two
-    }
-}
-
-// Pass 2: OIDHW -> [tap][ci/16][hi|lo][CoutPad][16 f16] of w * s[cout] (zero padded),
-// with s = 1 / wscale[cout] recovered exactly from pass 1's output.
-// bf16 = true: the bf16 mode's image in the same layout -- hi = bf16(w) (no scale, wscale = 1), lo = 0
-__device__ __forceinline__ _Float16 bf16_bits_as_h(float v) {
-    return __builtin_bit_cast(_Float16, __builtin_bit_cast(unsigned short, (__bf16)v));
-}
-__global__ void pack_ones_kernel(float* __restrict__ wscale, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) wscale[i] = 1.0f;
-}
-
-__global__ void pack_x3_kernel(const float* __restrict__ w, const float* __restrict__ wscale, int Cout,
-                               int Cin, int taps, int CoutPad, int CinPad, _Float16* __restrict__ out, bool bf16) {
-    const size_t total = (size_t)taps * CinPad * CoutPad;  // one (hi, lo) pair per element
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const int j = (int)(i & 15);
-        size_t r = i >> 4;
-        const int co = (int)(r % CoutPad); r /= CoutPad;
-        const int cb = (int)(r % (CinPad / 16));
-        const int tap = (int)(r / (CinPad / 16));
-        const int ci = cb * 16 + j;
-        float v = 0.0f;
-        if (co < Cout && ci < Cin)
-            v = w[((size_t)co * Cin + ci) * taps + tap] * (1.0f / wscale[co]);
-        const _Float16 hi = bf16 ? bf16_bits_as_h(v) : (_Float16)v;
-        const _Float16 lo = bf16 ? (_Float16)0.0f : (_Float16)(v - (float)hi);
-        const size_t base = (((size_t)tap * (CinPad / 16) + cb) * 2) * CoutPad * 16;
-        out[base + (size_t)co * 16 + j] = hi;
-        out[base + (size_t)CoutPad * 16 + (size_t)co * 16 + j] = lo;
-    }
-}
+// The 16-bit images.  A weight source says how many taps a form has and what tap `tap` of a (cout, ci) pair
+// is in fp32; the two kernels below know nothing else about a form.
+struct PlainTaps {   // the OIDHW weights themselves (27 taps, or 1)
+    int n;
+    __device__ int taps() const { return n; }
+    __device__ float at(const float* __restrict__ w, size_t co_ci, int tap) const { return w[co_ci * n + tap]; }
+};
 
 // Winograd F(2,3) along depth (conv3d_wz.h): weight transform at pack time.  For every
 // (cout, ci, dy, dx): U0 = g0, U1 = (g0+g1+g2)/2, U2 = (g0-g1+g2)/2, U3 = g2 with g_k the
@@ -93,51 +46,12 @@ __device__ __forceinline__ float wz_weight(const float* __restrict__ w, size_t c
     if (j == 3) return g2;
     return j == 1 ? 0.5f * ((g0 + g2) + g1) : 0.5f * ((g0 + g2) - g1);
 }
-
-__global__ __launch_bounds__(256) void pack_wz_scale_kernel(const float* __restrict__ w, int Cout, int Cin,
-                                                            float* __restrict__ wscale) {
-    const int co = blockIdx.x;
-    float m = 0.0f;
-    if (co < Cout)
-        for (int i = threadIdx.x; i < Cin * 36; i += 256) {
-            const int ci = i / 36, tap = i % 36;
-            m = fmaxf(m, fabsf(wz_weight(w, (size_t)co * Cin + ci, tap / 9, tap % 9)));
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    __shared__ float red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        float s = 1.0f;
-        if (m > 0.0f && m < 3.0e38f) s = exp2f(floorf(log2f(DDPM3D_X3_W_TARGET / m)));
-        s = fminf(fmaxf(s, 1.0f / 16777216.0f), 16777216.0f);
-        wscale[co] = 1.0f / s;
+struct WzTaps {
+    __device__ static constexpr int taps() { return 36; }
+    __device__ float at(const float* __restrict__ w, size_t co_ci, int tap) const {
+        return wz_weight(w, co_ci, tap / 9, tap % 9);
     }
-}
-
-__global__ void pack_wz_kernel(const float* __restrict__ w, const float* __restrict__ wscale, int Cout, int Cin,
-                               int CoutPad, int CinPad, _Float16* __restrict__ out, bool bf16) {
-    const size_t total = (size_t)36 * CinPad * CoutPad;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const int jj = (int)(i & 15);
-        size_t r = i >> 4;
-        const int co = (int)(r % CoutPad); r /= CoutPad;
-        const int cb = (int)(r % (CinPad / 16));
-        const int tap = (int)(r / (CinPad / 16));
-        const int ci = cb * 16 + jj;
-        float v = 0.0f;
-        if (co < Cout && ci < Cin)
-            v = wz_weight(w, (size_t)co * Cin + ci, tap / 9, tap % 9) * (1.0f / wscale[co]);
-        const _Float16 hi = bf16 ? bf16_bits_as_h(v) : (_Float16)v;
-        const _Float16 lo = bf16 ? (_Float16)0.0f : (_Float16)(v - (float)hi);
-        const size_t base = (((size_t)tap * (CinPad / 16) + cb) * 2) * CoutPad * 16;
-        out[base + (size_t)co * 16 + jj] = hi;
-        out[base + (size_t)CoutPad * 16 + (size_t)co * 16 + jj] = lo;
-    }
-}
+};
 
 // Phase weights of an IN_UP conv (DDPM3D_HINT_UP_PHASE, conv3d_wz.h PHASE): on the 2x nearest-up-sampled plane
 // the taps dy of an output row of parity py meet two source rows -- py = 0: {0} | {1, 2}, py = 1: {0, 1} | {2} --
@@ -157,17 +71,24 @@ __device__ __forceinline__ float wz_up_weight(const float* __restrict__ w, size_
         }
     return s;
 }
+struct WzUpTaps {   // 64 "taps": phase * 16 + phase tap
+    __device__ static constexpr int taps() { return 64; }
+    __device__ float at(const float* __restrict__ w, size_t co_ci, int tap) const {
+        return wz_up_weight(w, co_ci, tap >> 4, tap & 15);
+    }
+};
 
-// one scale per cout over all 64 phase taps (the rule of pack_wz_scale_kernel)
-__global__ __launch_bounds__(256) void pack_wz_up_scale_kernel(const float* __restrict__ w, int Cout, int Cin,
-                                                               float* __restrict__ wscale) {
+// Pass 1: per output channel, over all of the form's taps, the power-of-two scale
+// s = 2^floor(log2(W_TARGET / max|w|)) and the epilogue factor 1 / s.  unit (the bf16 images, which are not
+// scaled): 1 without reading w.
+template <class Src>
+__global__ __launch_bounds__(256) void pack_scale_kernel(Src src, const float* __restrict__ w, int Cout, int Cin,
+                                                         bool unit, float* __restrict__ wscale) {
     const int co = blockIdx.x;
     float m = 0.0f;
-    if (co < Cout)
-        for (int i = threadIdx.x; i < Cin * 64; i += 256) {
-            const int ci = i >> 6, pt = i & 63;
-            m = fmaxf(m, fabsf(wz_up_weight(w, (size_t)co * Cin + ci, pt >> 4, pt & 15)));
-        }
+    if (co < Cout && !unit)
+        for (int i = threadIdx.x; i < Cin * src.taps(); i += 256)
+            m = fmaxf(m, fabsf(src.at(w, (size_t)co * Cin + i / src.taps(), i % src.taps())));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     __shared__ float red[4];
@@ -178,90 +99,75 @@ __global__ __launch_bounds__(256) void pack_wz_up_scale_kernel(const float* __re
         float s = 1.0f;
         if (m > 0.0f && m < 3.0e38f) s = exp2f(floorf(log2f(DDPM3D_X3_W_TARGET / m)));
         s = fminf(fmaxf(s, 1.0f / 16777216.0f), 16777216.0f);
-        wscale[co] = 1.0f / s;
+        wscale[co] = 1.0f / s;  // exact: powers of two
     }
 }
 
-// [phase][tap 16][ci/16][hi|lo][CoutPad][16 f16]: per (phase, tap) the layout of pack_wz_kernel
-__global__ void pack_wz_up_kernel(const float* __restrict__ w, const float* __restrict__ wscale, int Cout, int Cin,
-                                  int CoutPad, int CinPad, _Float16* __restrict__ out) {
-    const size_t total = (size_t)64 * CinPad * CoutPad;
+// Pass 2: -> [tap][ci/16][hi|lo][CoutPad][16 f16] of w * s[cout] (zero padded),
+// with s = 1 / wscale[cout] recovered exactly from pass 1's output.
+// bf16 = true: the bf16 mode's image in the same layout -- hi = bf16(w) (no scale, wscale = 1), lo = 0
+__device__ __forceinline__ _Float16 bf16_bits_as_h(float v) {
+    return __builtin_bit_cast(_Float16, __builtin_bit_cast(unsigned short, (__bf16)v));
+}
+template <class Src>
+__global__ void pack_split_kernel(Src src, const float* __restrict__ w, const float* __restrict__ wscale, int Cout,
+                                  int Cin, int CoutPad, int CinPad, _Float16* __restrict__ out, bool bf16) {
+    const size_t total = (size_t)src.taps() * CinPad * CoutPad;  // one (hi, lo) pair per element
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x) {
-        const int jj = (int)(i & 15);
+        const int j = (int)(i & 15);
         size_t r = i >> 4;
         const int co = (int)(r % CoutPad); r /= CoutPad;
         const int cb = (int)(r % (CinPad / 16));
-        const int pt = (int)(r / (CinPad / 16));     // phase * 16 + tap
-        const int ci = cb * 16 + jj;
+        const int tap = (int)(r / (CinPad / 16));
+        const int ci = cb * 16 + j;
         float v = 0.0f;
-        if (co < Cout && ci < Cin)
-            v = wz_up_weight(w, (size_t)co * Cin + ci, pt >> 4, pt & 15) * (1.0f / wscale[co]);
-        const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)(v - (float)hi);
-        const size_t base = (((size_t)pt * (CinPad / 16) + cb) * 2) * CoutPad * 16;
-        out[base + (size_t)co * 16 + jj] = hi;
-        out[base + (size_t)CoutPad * 16 + (size_t)co * 16 + jj] = lo;
+        if (co < Cout && ci < Cin) v = src.at(w, (size_t)co * Cin + ci, tap) * (1.0f / wscale[co]);
+        const _Float16 hi = bf16 ? bf16_bits_as_h(v) : (_Float16)v;
+        const _Float16 lo = bf16 ? (_Float16)0.0f : (_Float16)(v - (float)hi);
+        const size_t base = (((size_t)tap * (CinPad / 16) + cb) * 2) * CoutPad * 16;
+        out[base + (size_t)co * 16 + j] = hi;
+        out[base + (size_t)CoutPad * 16 + (size_t)co * 16 + j] = lo;
     }
+}
+
+static int pack_blocks(const PackedImage& img) {   // one thread per 4-byte element, grid-stride beyond 4096 blocks
+    const size_t blocks = (img.body / 4 + 255) / 256;
+    return blocks > 4096 ? 4096 : (int)blocks;
+}
+
+// one 16-bit image at `out`: the scales behind the taps first, then the taps
+template <class Src>
+static hipError_t launch_pack16(Src src, const PackedImage& img, const float* w, int Cout, int Cin, bool bf16,
+                                void* out, hipStream_t st) {
+    const int CoutPad = ddpm3d_cout_pad(Cout), CinPad = ddpm3d_cin_pad(Cin);
+    float* wscale = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + img.body);
+    hipLaunchKernelGGL(pack_scale_kernel<Src>, dim3(CoutPad), dim3(256), 0, st, src, w, Cout, Cin, bf16, wscale);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pack_split_kernel<Src>, dim3(pack_blocks(img)), dim3(256), 0, st, src, w, wscale, Cout, Cin,
+                       CoutPad, CinPad, (_Float16*)out, bf16);
+    return hipGetLastError();
 }
 
 hipError_t ddpm3d_launch_pack_up_phase(const float* w, int Cout, int Cin, void* out, hipStream_t st) {
-    // the shipped Winograd-D image in front (the shapes that fall back run on it), the phase body behind it
+    // the shipped Winograd-D image in front (the shapes that fall back run on it), the phase image behind it
     hipError_t e = ddpm3d_launch_pack(w, Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ, out, st);
     if (e != hipSuccess) return e;
-    const int CoutPad = ddpm3d_cout_pad(Cout), CinPad = ddpm3d_cin_pad(Cin);
-    char* body = reinterpret_cast<char*>(out) + ddpm3d_packed_bytes(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ);
-    const size_t total = (size_t)64 * CinPad * CoutPad;
-    float* wscale = reinterpret_cast<float*>(body + total * 4);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pack_wz_up_scale_kernel, dim3(CoutPad), dim3(256), 0, st, w, Cout, Cin, wscale);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pack_wz_up_kernel, dim3(blocks), dim3(256), 0, st, w, wscale, Cout, Cin, CoutPad, CinPad,
-                       (_Float16*)body);
-    return hipGetLastError();
+    char* body = reinterpret_cast<char*>(out) + ddpm3d_packed_image(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ).bytes();
+    return launch_pack16(WzUpTaps{}, ddpm3d_up_phase_image(Cout, Cin), w, Cout, Cin, false, body, st);
 }
 
 hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int prec, void* out, hipStream_t st) {
-    const int CoutPad = ddpm3d_cout_pad(Cout), CinPad = ddpm3d_cin_pad(Cin);
-    const bool bf16 = prec == DDPM3D_PREC_BF16 || prec == DDPM3D_PREC_BF16_WZ;
-    if (prec == DDPM3D_PREC_F16X3_WZ || prec == DDPM3D_PREC_F16_WZ || prec == DDPM3D_PREC_BF16_WZ) {
-        // [16-bit image of 36 transformed taps][CoutPad fp32 wscale]
-        const size_t total = (size_t)36 * CinPad * CoutPad;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        float* wscale = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + total * 4);
-        if (bf16)
-            hipLaunchKernelGGL(pack_ones_kernel, dim3((CoutPad + 255) / 256), dim3(256), 0, st, wscale, CoutPad);
-        else
-            hipLaunchKernelGGL(pack_wz_scale_kernel, dim3(CoutPad), dim3(256), 0, st, w, Cout, Cin, wscale);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(pack_wz_kernel, dim3(blocks), dim3(256), 0, st, w, wscale, Cout, Cin, CoutPad, CinPad,
-                           (_Float16*)out, bf16);
+    const PackedImage img = ddpm3d_packed_image(Cout, Cin, ks, prec);
+    if (prec == DDPM3D_PREC_F32) {
+        hipLaunchKernelGGL(pack_weight_kernel, dim3(pack_blocks(img)), dim3(256), 0, st, w, Cout, Cin, img.taps,
+                           ddpm3d_cout_pad(Cout), ddpm3d_cin_pad(Cin), (float*)out);
         return hipGetLastError();
     }
-    const int taps = ks * ks * ks;
-    const size_t total = (size_t)taps * CinPad * CoutPad;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if (prec == 0) {
-        hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, taps, CoutPad,
-                           CinPad, (float*)out);
-        return hipGetLastError();
-    }
-    // PREC 1: [f16 image (total hi/lo pairs = total*4 bytes)][CoutPad fp32 wscale]
-    float* wscale = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + total * 4);
-    if (bf16)
-        hipLaunchKernelGGL(pack_ones_kernel, dim3((CoutPad + 255) / 256), dim3(256), 0, st, wscale, CoutPad);
-    else
-        hipLaunchKernelGGL(pack_x3_scale_kernel, dim3(CoutPad), dim3(256), 0, st, w, Cout, Cin * taps, wscale);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pack_x3_kernel, dim3(blocks), dim3(256), 0, st, w, wscale, Cout, Cin, taps, CoutPad,
-                       CinPad, (_Float16*)out, bf16);
-    return hipGetLastError();
+    const bool bf16 = ddpm3d_prec_bf16(prec);
+    if (ddpm3d_prec_wz(prec)) return launch_pack16(WzTaps{}, img, w, Cout, Cin, bf16, out, st);
+    return launch_pack16(PlainTaps{img.taps}, img, w, Cout, Cin, bf16, out, st);
 }
 
 // ------------------------------------------------------------- wave helpers

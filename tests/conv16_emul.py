@@ -80,7 +80,7 @@ def act_scale(bound, gain):
 
 
 def weight_scale(wmax):
-    """pack_x3_scale_kernel / pack_wz_scale_kernel (ops.hip:32, :95): s = 2^floor(log2(W_TARGET / max|w|)),
+    """pack_scale_kernel (ops.hip), whatever the weight source: s = 2^floor(log2(W_TARGET / max|w|)),
     clamped to [2^-24, 2^24]; 1 for an all-zero channel."""
     m = float(wmax)
     if not (m > 0 and m < 3.0e38):
@@ -162,7 +162,7 @@ def conv16(srcs, w, b, precision, in_mode="same", aff=None, act=False, bound=Non
     stride, pad = ((1, 2, 2) if in_mode == "stride2" else 1), k // 2
     if not wz:
         # direct kernels: operand = 16-bit(v * S) (conv3d.hip:174-185, conv1x1.hip:61 pw_operand,
-        # conv3d_skinny.hip:150-172; bf16: bf16_pack, no scale); weights = 16-bit(w * s_w) (ops.hip:72-74)
+        # conv3d_skinny.hip:150-172; bf16: bf16_pack, no scale); weights = 16-bit(w * s_w) (ops.hip pack_split_kernel)
         vs = v * Sv
         a = rnd.r16(vs) / Sv
         fl = _flip(rnd, vs, delta * Sv) / Sv
@@ -221,7 +221,7 @@ def _winograd(v, delta, Sv, w, rnd, before, use_wscale, precision, exact):
         fl.append(_flip(rnd, t[j], dt))
     tq = [q / Sv for q in tq]
     fl = [f / Sv for f in fl]
-    # weight transform wz_weight (ops.hip:88): U0 = g0, U1 = 0.5*((g0+g2)+g1), U2 = 0.5*((g0+g2)-g1), U3 = g2, fp32
+    # weight transform wz_weight (ops.hip): U0 = g0, U1 = 0.5*((g0+g2)+g1), U2 = 0.5*((g0+g2)-g1), U3 = g2, fp32
     g = [w[:, :, z].double() for z in range(3)]
     if before:
         g = [rnd.r16(x) for x in g]          # (mutation: 16-bit weights, exact transform)
@@ -236,7 +236,7 @@ def _winograd(v, delta, Sv, w, rnd, before, use_wscale, precision, exact):
         sw = torch.ones(Cout, dtype=torch.float64)
     sw4 = sw.reshape(Cout, 1, 1, 1)
     if not before:
-        U = [rnd.r16(rnd.r32(u * sw4)) / sw4 for u in U]     # pack_wz_kernel (ops.hip:128-131)
+        U = [rnd.r16(rnd.r32(u * sw4)) / sw4 for u in U]     # pack_split_kernel<WzTaps> (ops.hip)
     conv = lambda a, u: F.conv3d(a, u.unsqueeze(2), padding=(0, 1, 1))
     M = [conv(tq[j], U[j]) for j in range(4)]
     Ma = [conv(tq[j].abs(), U[j].abs()) for j in range(4)]

@@ -78,8 +78,8 @@ class Mut:
 
 
 def split(x, mut, drop_lo):
-    """hi = f16(x) (RNE), lo = f16(x - hi) (the subtraction is exact in fp32): pack_x3_kernel / pack_wz_kernel
-    (ops.hip:68-69, :128-129), conv3d.hip:177-179, conv1x1.hip:69-70, split_pair (conv3d_stage.h:29)"""
+    """hi = f16(x) (RNE), lo = f16(x - hi) (the subtraction is exact in fp32): pack_split_kernel (ops.hip),
+    conv3d.hip:177-179, conv1x1.hip:69-70, split_pair (conv3d_stage.h:29)"""
     if mut.exact:
         return x, torch.zeros_like(x)
     hi = f16(x)
@@ -195,7 +195,7 @@ def conv32(srcs, w, b, precision, in_mode="same", aff=None, act=False, bound=Non
 
 
 def _weights(wt, mut, dims):
-    """per-cout scale s = 2^floor(log2(8 / max|w|)) (pack_x3_scale_kernel / pack_wz_scale_kernel), w * s in fp32
+    """per-cout scale s = 2^floor(log2(8 / max|w|)) (pack_scale_kernel over the form's taps), w * s in fp32
     (exact), split; returned unscaled (exact)"""
     Cout = wt.shape[0]
     if mut.use_wscale and not mut.exact:
@@ -239,11 +239,11 @@ def _winograd(v, delta, Sv, w, mut):
         tlo.append(lo / Sv)
         tda.append(da / Sv)
         thf.append(hf / Sv)
-    # weight transform wz_weight (ops.hip:88): U0 = g0, U1 = 0.5*((g0+g2)+g1), U2 = 0.5*((g0+g2)-g1), U3 = g2, fp32
+    # weight transform wz_weight (ops.hip): U0 = g0, U1 = 0.5*((g0+g2)+g1), U2 = 0.5*((g0+g2)-g1), U3 = g2, fp32
     g = [w[:, :, z].double() for z in range(3)]
     g02 = rr(g[0] + g[2])
     U = [g[0], rr(0.5 * rr(g02 + g[1])), rr(0.5 * rr(g02 - g[1])), g[2]]
-    # one scale per cout over all 36 transformed taps (pack_wz_scale_kernel), then the split (pack_wz_kernel)
+    # one scale per cout over all 36 transformed taps, then the split (pack_scale_kernel, pack_split_kernel on WzTaps)
     Ust = torch.stack(U, dim=1)                                    # [Cout, 4, Cin, 3, 3]
     Uhi, Ulo, sw = _weights(Ust, mut, dims=(1, 2, 3, 4))
     conv = lambda a, u: F.conv3d(a, u.unsqueeze(2), padding=(0, 1, 1))

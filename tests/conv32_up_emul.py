@@ -6,7 +6,7 @@ On the up-sampled plane the nine (dy, dx) taps of an output voxel of parity (py,
 py = 0 reads source row i-1 at dy = 0 and row i at dy = 1, 2; py = 1 reads row i at dy = 0, 1 and row i+1 at
 dy = 2; the same along x.  So each of the four phases is a conv with a 2x2 in-plane footprint on the source grid.
 
-What rounds, and where (ops.hip wz_up_weight / pack_wz_up_scale_kernel / pack_wz_up_kernel, conv3d_wz.h PHASE):
+What rounds, and where (ops.hip wz_up_weight behind WzUpTaps, pack_scale_kernel / pack_split_kernel; conv3d_wz.h PHASE):
   * the input exactly as conv32_emul's Winograd-D form -- affine, SiLU, activation scale (gain 2), fp32 input
     transform along depth, hi/lo split -- on the SOURCE grid (each source voxel once);
   * the weights: U_j[dy][dx] as wz_weight (fp32), summed per phase over the collapsing group in fp32, added in

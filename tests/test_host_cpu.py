@@ -48,6 +48,12 @@ def test_library_exports_every_declared_symbol():
     assert lib.ddpm3d_packed_weight_bytes(128, 2, 3, 0) == 27 * 16 * 128 * 4      # Cin padded to 16
     # split-f16 image: hi+lo f16 = the same bytes, plus one fp32 output scale per padded cout
     assert lib.ddpm3d_packed_weight_bytes(128, 128, 3, 1) == 27 * 128 * 128 * 4 + 128 * 4
+    # Winograd-D image: 36 transformed taps; the phase image: that image, then 64 phase taps with scales of their own
+    for prec in (3, 4, 6):
+        assert lib.ddpm3d_packed_weight_bytes(128, 48, 3, prec) == 36 * 48 * 128 * 4 + 128 * 4
+    lib.ddpm3d_packed_up_phase_bytes.restype = ctypes.c_size_t
+    assert lib.ddpm3d_packed_up_phase_bytes(128, 48) == (36 + 64) * 48 * 128 * 4 + 2 * 128 * 4
+    assert lib.ddpm3d_packed_up_phase_bytes(96, 48) == 0 and lib.ddpm3d_packed_up_phase_bytes(128, 40) == 0
     assert lib.ddpm3d_packed_weight_bytes(8, 8, 2, 0) == 0 and lib.ddpm3d_packed_weight_bytes(8, 8, 3, 7) == 0
     lib.ddpm3d_conv_workspace_bytes.restype = ctypes.c_size_t
     # 64^3 level: 2048 tiles of 128 voxels (2x8x8) fill the chip, no split, one row per tile
