@@ -466,31 +466,6 @@ int ddpm3d_attention(const float* qkv, int N, int T, int heads, int head_channel
     return ddpm3d_attention_p(qkv, N, T, heads, head_channels, DDPM3D_PREC_F32, nullptr, 0, 0, out, stream);
 }
 
-static int step_args_ok(const float* mo, const float* x, const float* noise, const float* coef,
-                        const int64_t* t, int N, int voxels, float* sample) {
-    return mo && x && noise && coef && t && sample && N > 0 && voxels > 0;
-}
-
-int ddpm3d_p_sample_step(const float* model_out, const float* x, const float* noise, const float* coef,
-                         const int64_t* t_idx, int N, int voxels, int flags, float* sample,
-                         float* pred_xstart, void* stream) {
-    if (!step_args_ok(model_out, x, noise, coef, t_idx, N, voxels, sample))
-        return fail(DDPM3D_EINVAL, "p_sample_step: bad arguments");
-    return launched(ddpm3d_launch_sample_step(false, model_out, nullptr, x, noise, nullptr, coef, t_idx, N, voxels, flags, 0.0f,
-                                              sample, pred_xstart, (hipStream_t)stream),
-                    "p_sample_step");
-}
-
-int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise, const float* coef,
-                     const int64_t* t_idx, int N, int voxels, int flags, float eta, float* sample,
-                     float* pred_xstart, void* stream) {
-    if (!step_args_ok(model_out, x, noise, coef, t_idx, N, voxels, sample))
-        return fail(DDPM3D_EINVAL, "ddim_step: bad arguments");
-    return launched(ddpm3d_launch_sample_step(true, model_out, nullptr, x, noise, nullptr, coef, t_idx, N, voxels, flags, eta,
-                                              sample, pred_xstart, (hipStream_t)stream),
-                    "ddim_step");
-}
-
 // ------------------------------------------------------------ variational bound
 // grid.y carries the sample index of the element-wise launches
 static bool vb_shape_ok(int N, int voxels, int T) { return N > 0 && N <= 65535 && voxels > 0 && T > 0; }
@@ -585,29 +560,6 @@ int ddpm3d_ddim_reverse_step(const float* model_out, const float* x, const float
                     "ddim_reverse_step");
 }
 
-// ------------------------------------------------- DPM-Solver++ multistep step (added within ABI 13)
-static int dpm_solver_step_any(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
-                               const float* noise, const ddpm3d_noise_key* key, const float* coef, const float* scoef,
-                               const int64_t* t_idx, int N, int voxels, int T, int flags, int order, float* sample,
-                               float* pred_xstart, void* stream) {
-    const int rc = step_entry_ok("dpm_solver_step", model_out && x && coef && scoef && t_idx && sample && pred_xstart,
-                                 N, voxels, T, flags);
-    if (rc != DDPM3D_OK) return rc;
-    if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d is not 1, 2 or 3", order);
-    if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
-        return fail(DDPM3D_EINVAL, "dpm_solver_step: order %d needs %d earlier x0 predictions", order, order - 1);
-    return launched(ddpm3d_launch_dpm_solver_step(model_out, nullptr, x, x0_prev1, x0_prev2, noise, key, coef, scoef, t_idx, N,
-                                                  voxels, T, flags, order, sample, pred_xstart, (hipStream_t)stream),
-                    "dpm_solver_step");
-}
-
-int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
-                           const float* noise, const float* coef, const float* scoef, const int64_t* t_idx, int N,
-                           int voxels, int T, int flags, int order, float* sample, float* pred_xstart, void* stream) {
-    return dpm_solver_step_any(model_out, x, x0_prev1, x0_prev2, noise, nullptr, coef, scoef, t_idx, N, voxels, T,
-                               flags, order, sample, pred_xstart, stream);
-}
-
 // ------------------------------------------------- sampler noise from a counter-based key (added within ABI 13)
 // The host side of a key; `geometry`: the entry reads origin / patch / canvas (ddpm3d_noise_bits does not).
 static int noise_key_ok(const char* what, const ddpm3d_noise_key* key, int N, int voxels, bool geometry) {
@@ -650,39 +602,151 @@ int ddpm3d_noise_bits(const ddpm3d_noise_key* key, int N, int quads, uint32_t* o
     return launched(ddpm3d_launch_noise_bits(*key, N, quads, out, (hipStream_t)stream), "noise_bits");
 }
 
+// ------------------------------------------------- the nine step entries
+// ddpm3d_{p_sample,ddim,dpm_solver}_step{,_keyed,_x0}: one validate-and-launch function; each entry states its name,
+// kind and argument style and passes its arguments in the order of the widest list (dpm_solver_step_x0's, eta after
+// order), NULL or 0 for what it does not take.  The three styles keep the checks, their order and their messages of
+// the ABI steps that added them: the keyed entries check the key first, the x0 entries last.
+enum StepKind { STEP_DDPM, STEP_DDIM, STEP_SOLVER };
+enum StepStyle { STEP_PLAIN, STEP_KEYED, STEP_X0 };
+struct StepArgs {
+    const float *model_out, *xstart, *x, *x0_prev1, *x0_prev2, *noise;
+    const ddpm3d_noise_key* key;
+    const float *coef, *scoef;
+    const int64_t* t_idx;
+    int N, voxels, T, flags, order;
+    float eta;
+    float *sample, *pred_xstart;
+    void* stream;
+};
+
+static int step_entry(const char* name, StepKind kind, StepStyle style, const StepArgs& a) {
+    const bool solver = kind == STEP_SOLVER;
+    // the keyed solver entry names itself in its key check only: everything else it shares with the un-keyed entry,
+    // under that entry's name
+    const char* what = solver && style == STEP_KEYED ? "dpm_solver_step" : name;
+    if (style == STEP_KEYED && (a.key || !solver)) {            // the solver's NULL key is the ODE form
+        const int rc = noise_key_ok(name, a.key, a.N, a.voxels, true);
+        if (rc != DDPM3D_OK) return rc;
+    }
+    if (style == STEP_X0) {
+        // the pointers, the shape, the flags, the noise source, then the outputs apart from each other and from what is read
+        if (!a.xstart || !a.x || !a.coef || !a.t_idx || !a.sample) return fail(DDPM3D_EINVAL, "%s: null pointer", what);
+        if (a.N < 1 || a.N > 65535 || a.voxels < 1)
+            return fail(DDPM3D_EINVAL, "%s: bad arguments (N=%d voxels=%d)", what, a.N, a.voxels);
+        if (a.flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "%s: unknown flag bits %#x", what, a.flags);
+        if (kind == STEP_DDPM && (a.flags & DDPM3D_F_LEARN_SIGMA) && !a.model_out)
+            return fail(DDPM3D_EINVAL, "%s: F_LEARN_SIGMA reads model_out's second half: model_out is NULL", what);
+        if (a.noise && a.key)
+            return fail(DDPM3D_EINVAL, "%s: noise and key both name the noise: one of them must be NULL", what);
+        if (!a.noise && !a.key && !solver) return fail(DDPM3D_EINVAL, "%s: one of noise and key must be given", what);
+        const float *s = a.sample, *p = a.pred_xstart;
+        if (s == p || s == a.xstart || s == a.x || s == a.noise || s == a.model_out ||
+            (p && (p == a.xstart || p == a.x || p == a.noise || p == a.model_out)))
+            return fail(DDPM3D_EINVAL, "%s: sample and pred_xstart must be tensors of their own", what);
+        if (a.key) {
+            const int rc = noise_key_ok(what, a.key, a.N, a.voxels, true);
+            if (rc != DDPM3D_OK) return rc;
+        }
+        if (solver && (!a.scoef || !a.pred_xstart || a.T < 1))
+            return fail(DDPM3D_EINVAL, "%s: bad arguments (scoef, pred_xstart or T=%d)", what, a.T);
+    } else if (solver) {
+        const int rc = step_entry_ok(what, a.model_out && a.x && a.coef && a.scoef && a.t_idx && a.sample && a.pred_xstart,
+                                     a.N, a.voxels, a.T, a.flags);
+        if (rc != DDPM3D_OK) return rc;
+    } else if (!(a.model_out && a.x && (a.noise || style == STEP_KEYED) && a.coef && a.t_idx && a.sample && a.N > 0 &&
+                 a.voxels > 0)) {
+        return fail(DDPM3D_EINVAL, "%s: bad arguments", what);
+    }
+    if (!solver)
+        return launched(ddpm3d_launch_sample_step(kind == STEP_DDIM, a.model_out, a.xstart, a.x, a.noise, a.key, a.coef,
+                                                  a.t_idx, a.N, a.voxels, a.flags, a.eta, a.sample, a.pred_xstart,
+                                                  (hipStream_t)a.stream),
+                        what);
+    if (a.order < 1 || a.order > 3) return fail(DDPM3D_EINVAL, "%s: order %d is not 1, 2 or 3", what, a.order);
+    if ((a.order >= 2 && !a.x0_prev1) || (a.order == 3 && !a.x0_prev2))
+        return fail(DDPM3D_EINVAL, "%s: order %d needs %d earlier x0 predictions", what, a.order, a.order - 1);
+    if (style == STEP_X0 && (a.sample == a.x0_prev1 || a.sample == a.x0_prev2 || a.pred_xstart == a.x0_prev1 ||
+                             a.pred_xstart == a.x0_prev2))
+        return fail(DDPM3D_EINVAL, "%s: sample and pred_xstart must be tensors of their own", what);
+    return launched(ddpm3d_launch_dpm_solver_step(a.model_out, a.xstart, a.x, a.x0_prev1, a.x0_prev2, a.noise, a.key,
+                                                  a.coef, a.scoef, a.t_idx, a.N, a.voxels, a.T, a.flags, a.order,
+                                                  a.sample, a.pred_xstart, (hipStream_t)a.stream),
+                    what);
+}
+
+int ddpm3d_p_sample_step(const float* model_out, const float* x, const float* noise, const float* coef,
+                         const int64_t* t_idx, int N, int voxels, int flags, float* sample,
+                         float* pred_xstart, void* stream) {
+    return step_entry("p_sample_step", STEP_DDPM, STEP_PLAIN,
+                      {model_out, nullptr, x, nullptr, nullptr, noise, nullptr, coef, nullptr, t_idx, N, voxels, 0, flags,
+                       0, 0.0f, sample, pred_xstart, stream});
+}
+
+int ddpm3d_ddim_step(const float* model_out, const float* x, const float* noise, const float* coef,
+                     const int64_t* t_idx, int N, int voxels, int flags, float eta, float* sample,
+                     float* pred_xstart, void* stream) {
+    return step_entry("ddim_step", STEP_DDIM, STEP_PLAIN,
+                      {model_out, nullptr, x, nullptr, nullptr, noise, nullptr, coef, nullptr, t_idx, N, voxels, 0, flags,
+                       0, eta, sample, pred_xstart, stream});
+}
+
+int ddpm3d_dpm_solver_step(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
+                           const float* noise, const float* coef, const float* scoef, const int64_t* t_idx, int N,
+                           int voxels, int T, int flags, int order, float* sample, float* pred_xstart, void* stream) {
+    return step_entry("dpm_solver_step", STEP_SOLVER, STEP_PLAIN,
+                      {model_out, nullptr, x, x0_prev1, x0_prev2, noise, nullptr, coef, scoef, t_idx, N, voxels, T, flags,
+                       order, 0.0f, sample, pred_xstart, stream});
+}
+
 int ddpm3d_p_sample_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key, const float* coef,
                                const int64_t* t_idx, int N, int voxels, int flags, float* sample, float* pred_xstart,
                                void* stream) {
-    const int rc = noise_key_ok("p_sample_step_keyed", key, N, voxels, true);
-    if (rc != DDPM3D_OK) return rc;
-    if (!model_out || !x || !coef || !t_idx || !sample)
-        return fail(DDPM3D_EINVAL, "p_sample_step_keyed: bad arguments");
-    return launched(ddpm3d_launch_sample_step(false, model_out, nullptr, x, nullptr, key, coef, t_idx, N, voxels, flags, 0.0f,
-                                              sample, pred_xstart, (hipStream_t)stream),
-                    "p_sample_step_keyed");
+    return step_entry("p_sample_step_keyed", STEP_DDPM, STEP_KEYED,
+                      {model_out, nullptr, x, nullptr, nullptr, nullptr, key, coef, nullptr, t_idx, N, voxels, 0, flags, 0,
+                       0.0f, sample, pred_xstart, stream});
 }
 
 int ddpm3d_ddim_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key, const float* coef,
                            const int64_t* t_idx, int N, int voxels, int flags, float eta, float* sample,
                            float* pred_xstart, void* stream) {
-    const int rc = noise_key_ok("ddim_step_keyed", key, N, voxels, true);
-    if (rc != DDPM3D_OK) return rc;
-    if (!model_out || !x || !coef || !t_idx || !sample) return fail(DDPM3D_EINVAL, "ddim_step_keyed: bad arguments");
-    return launched(ddpm3d_launch_sample_step(true, model_out, nullptr, x, nullptr, key, coef, t_idx, N, voxels, flags, eta,
-                                              sample, pred_xstart, (hipStream_t)stream),
-                    "ddim_step_keyed");
+    return step_entry("ddim_step_keyed", STEP_DDIM, STEP_KEYED,
+                      {model_out, nullptr, x, nullptr, nullptr, nullptr, key, coef, nullptr, t_idx, N, voxels, 0, flags, 0,
+                       eta, sample, pred_xstart, stream});
 }
 
 int ddpm3d_dpm_solver_step_keyed(const float* model_out, const float* x, const float* x0_prev1, const float* x0_prev2,
                                  const ddpm3d_noise_key* key, const float* coef, const float* scoef,
                                  const int64_t* t_idx, int N, int voxels, int T, int flags, int order, float* sample,
                                  float* pred_xstart, void* stream) {
-    if (key != nullptr) {                       // a NULL key is the ODE form
-        const int rc = noise_key_ok("dpm_solver_step_keyed", key, N, voxels, true);
-        if (rc != DDPM3D_OK) return rc;
-    }
-    return dpm_solver_step_any(model_out, x, x0_prev1, x0_prev2, nullptr, key, coef, scoef, t_idx, N, voxels, T, flags,
-                               order, sample, pred_xstart, stream);
+    return step_entry("dpm_solver_step_keyed", STEP_SOLVER, STEP_KEYED,
+                      {model_out, nullptr, x, x0_prev1, x0_prev2, nullptr, key, coef, scoef, t_idx, N, voxels, T, flags,
+                       order, 0.0f, sample, pred_xstart, stream});
+}
+
+int ddpm3d_p_sample_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
+                            const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                            int flags, float* sample, float* pred_xstart, void* stream) {
+    return step_entry("p_sample_step_x0", STEP_DDPM, STEP_X0,
+                      {model_out, xstart, x, nullptr, nullptr, noise, key, coef, nullptr, t_idx, N, voxels, 0, flags, 0,
+                       0.0f, sample, pred_xstart, stream});
+}
+
+int ddpm3d_ddim_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
+                        const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
+                        int flags, float eta, float* sample, float* pred_xstart, void* stream) {
+    return step_entry("ddim_step_x0", STEP_DDIM, STEP_X0,
+                      {model_out, xstart, x, nullptr, nullptr, noise, key, coef, nullptr, t_idx, N, voxels, 0, flags, 0,
+                       eta, sample, pred_xstart, stream});
+}
+
+int ddpm3d_dpm_solver_step_x0(const float* model_out, const float* xstart, const float* x, const float* x0_prev1,
+                              const float* x0_prev2, const float* noise, const ddpm3d_noise_key* key,
+                              const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels, int T,
+                              int flags, int order, float* sample, float* pred_xstart, void* stream) {
+    return step_entry("dpm_solver_step_x0", STEP_SOLVER, STEP_X0,
+                      {model_out, xstart, x, x0_prev1, x0_prev2, noise, key, coef, scoef, t_idx, N, voxels, T, flags,
+                       order, 0.0f, sample, pred_xstart, stream});
 }
 
 int ddpm3d_q_sample_keyed(const float* x_start, const ddpm3d_noise_key* key, const float* qcoef, const int64_t* t_idx,
@@ -1270,7 +1334,7 @@ int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_reg
     return launched(ddpm3d_launch_regrid(vol, B, D, H, W, axes, out, (float*)ws, (hipStream_t)stream), "regrid");
 }
 
-// ------------------------------------------------- low-pass pull of x_start and the steps that take x0 (added within ABI 13)
+// ------------------------------------------------- low-pass pull of x_start (added within ABI 13)
 static bool pull_shape_ok(int N, int D, int H, int W) {
     return N >= 1 && N <= 65535 && baseline_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;
 }
@@ -1308,67 +1372,6 @@ int ddpm3d_xstart_pull(const float* model_out, const float* x, const float* meas
     return launched(ddpm3d_launch_xstart_pull(model_out, x, measurement, coef, t_idx, N, D, H, W, T, flags, weight,
                                               radii, taps, xstart_out, (float*)ws, (hipStream_t)stream),
                     "xstart_pull");
-}
-
-// what the three *_step_x0 entries share: the pointers, the outputs apart from each other and from what is read, the
-// flags, the noise source (`noise_count`: how many of noise and key must be given, -1 for at most one)
-static int step_x0_ok(const char* what, const float* model_out, const float* xstart, const float* x, const float* noise,
-                      const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
-                      int flags, bool reads_variance, bool ode_allowed, const float* sample, const float* pred_xstart) {
-    if (!xstart || !x || !coef || !t_idx || !sample) return fail(DDPM3D_EINVAL, "%s: null pointer", what);
-    if (N < 1 || N > 65535 || voxels < 1) return fail(DDPM3D_EINVAL, "%s: bad arguments (N=%d voxels=%d)", what, N, voxels);
-    if (flags & ~STEP_FLAGS) return fail(DDPM3D_EINVAL, "%s: unknown flag bits %#x", what, flags);
-    if (reads_variance && (flags & DDPM3D_F_LEARN_SIGMA) && !model_out)
-        return fail(DDPM3D_EINVAL, "%s: F_LEARN_SIGMA reads model_out's second half: model_out is NULL", what);
-    if (noise && key) return fail(DDPM3D_EINVAL, "%s: noise and key both name the noise: one of them must be NULL", what);
-    if (!noise && !key && !ode_allowed) return fail(DDPM3D_EINVAL, "%s: one of noise and key must be given", what);
-    if (sample == pred_xstart || sample == xstart || sample == x || sample == noise || sample == model_out ||
-        (pred_xstart && (pred_xstart == xstart || pred_xstart == x || pred_xstart == noise || pred_xstart == model_out)))
-        return fail(DDPM3D_EINVAL, "%s: sample and pred_xstart must be tensors of their own", what);
-    if (key) return noise_key_ok(what, key, N, voxels, true);
-    return DDPM3D_OK;
-}
-
-int ddpm3d_p_sample_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
-                            const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
-                            int flags, float* sample, float* pred_xstart, void* stream) {
-    const int rc = step_x0_ok("p_sample_step_x0", model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags, true,
-                              false, sample, pred_xstart);
-    if (rc != DDPM3D_OK) return rc;
-    return launched(ddpm3d_launch_sample_step(false, model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags,
-                                              0.0f, sample, pred_xstart, (hipStream_t)stream),
-                    "p_sample_step_x0");
-}
-
-int ddpm3d_ddim_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
-                        const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,
-                        int flags, float eta, float* sample, float* pred_xstart, void* stream) {
-    const int rc = step_x0_ok("ddim_step_x0", model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags, false,
-                              false, sample, pred_xstart);
-    if (rc != DDPM3D_OK) return rc;
-    return launched(ddpm3d_launch_sample_step(true, model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags, eta,
-                                              sample, pred_xstart, (hipStream_t)stream),
-                    "ddim_step_x0");
-}
-
-int ddpm3d_dpm_solver_step_x0(const float* model_out, const float* xstart, const float* x, const float* x0_prev1,
-                              const float* x0_prev2, const float* noise, const ddpm3d_noise_key* key,
-                              const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels, int T,
-                              int flags, int order, float* sample, float* pred_xstart, void* stream) {
-    const int rc = step_x0_ok("dpm_solver_step_x0", model_out, xstart, x, noise, key, coef, t_idx, N, voxels, flags,
-                              false, true, sample, pred_xstart);
-    if (rc != DDPM3D_OK) return rc;
-    if (!scoef || !pred_xstart || T < 1)
-        return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: bad arguments (scoef, pred_xstart or T=%d)", T);
-    if (order < 1 || order > 3) return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: order %d is not 1, 2 or 3", order);
-    if ((order >= 2 && !x0_prev1) || (order == 3 && !x0_prev2))
-        return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: order %d needs %d earlier x0 predictions", order, order - 1);
-    if (sample == x0_prev1 || sample == x0_prev2 || pred_xstart == x0_prev1 || pred_xstart == x0_prev2)
-        return fail(DDPM3D_EINVAL, "dpm_solver_step_x0: sample and pred_xstart must be tensors of their own");
-    return launched(ddpm3d_launch_dpm_solver_step(model_out, xstart, x, x0_prev1, x0_prev2, noise, key, coef, scoef,
-                                                  t_idx, N, voxels, T, flags, order, sample, pred_xstart,
-                                                  (hipStream_t)stream),
-                    "dpm_solver_step_x0");
 }
 
 double ddpm3d_mfma_probe_flops_per_iter(int kind) { return ddpm3d_probe_flops_per_iter(kind); }

@@ -3,6 +3,7 @@
 // sampler update.  All HBM- or latency-bound; wave64 throughout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "conv3d_params.h"
 #include "conv3d_load.h"   // affine_act, act_quad, half_pack
 #include "ops.h"
@@ -729,38 +730,31 @@ __global__ __launch_bounds__(256) void sample_step_kernel(
     }
 }
 
-template <bool DDIM, class Noise>
-static hipError_t launch_sample_step_from(const float* mo, const float* xs, const float* x, const Noise noise,
-                                          const float* coef, const int64_t* t_idx, int N, int voxels, int flags,
-                                          float eta, float* sample, float* pred_xstart, hipStream_t st) {
-    if (xs != nullptr)
-        hipLaunchKernelGGL((sample_step_kernel<DDIM, Noise, true>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x,
-                           noise, coef, t_idx, voxels, flags, eta, sample, pred_xstart);
-    else
-        hipLaunchKernelGGL((sample_step_kernel<DDIM, Noise, false>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x,
-                           noise, coef, t_idx, voxels, flags, eta, sample, pred_xstart);
-    return hipGetLastError();
+// The run-time-to-template mapping of the step launches, written once: launch(z, t...) gets the step's noise source
+// (a KeyNoise where a key is given, else a TensorNoise) and one std::true_type / std::false_type per run-time switch,
+// in the order given.
+template <class F>
+static void with_switches(F&& f) { f(); }
+template <class F, class... Rest>
+static void with_switches(F&& f, bool on, Rest... rest) {
+    if (on) with_switches([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+    else with_switches([&](auto... t) { f(std::false_type{}, t...); }, rest...);
 }
-
-template <class Noise>
-static hipError_t launch_sample_step(bool ddim, const float* mo, const float* xs, const float* x, const Noise noise,
-                                     const float* coef, const int64_t* t_idx, int N, int voxels, int flags, float eta,
-                                     float* sample, float* pred_xstart, hipStream_t st) {
-    if (ddim)
-        return launch_sample_step_from<true>(mo, xs, x, noise, coef, t_idx, N, voxels, flags, eta, sample, pred_xstart,
-                                             st);
-    return launch_sample_step_from<false>(mo, xs, x, noise, coef, t_idx, N, voxels, flags, eta, sample, pred_xstart, st);
+template <class F, class... Switches>
+static hipError_t launch_step(const float* noise, const ddpm3d_noise_key* key, F&& launch, Switches... switches) {
+    if (key != nullptr) with_switches([&](auto... t) { launch(KeyNoise{noise_key_dev(*key)}, t...); }, switches...);
+    else with_switches([&](auto... t) { launch(TensorNoise{noise}, t...); }, switches...);
+    return hipGetLastError();
 }
 
 hipError_t ddpm3d_launch_sample_step(bool ddim, const float* mo, const float* xs, const float* x, const float* noise,
                                      const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N,
                                      int voxels, int flags, float eta, float* sample, float* pred_xstart,
                                      hipStream_t st) {
-    if (key != nullptr)
-        return launch_sample_step(ddim, mo, xs, x, KeyNoise{noise_key_dev(*key)}, coef, t_idx, N, voxels, flags, eta,
-                                  sample, pred_xstart, st);
-    return launch_sample_step(ddim, mo, xs, x, TensorNoise{noise}, coef, t_idx, N, voxels, flags, eta, sample,
-                              pred_xstart, st);
+    return launch_step(noise, key, [&](auto z, auto is_ddim, auto has_x0) {
+        hipLaunchKernelGGL((sample_step_kernel<is_ddim.value, decltype(z), has_x0.value>), step_grid(N, voxels),
+                           dim3(256), 0, st, mo, xs, x, z, coef, t_idx, voxels, flags, eta, sample, pred_xstart);
+    }, ddim, xs != nullptr);
 }
 
 // ------------------------------------------------- p_mean_variance, DDIM inversion
@@ -883,30 +877,15 @@ __global__ __launch_bounds__(256) void dpm_solver_step_kernel(
     }
 }
 
-template <class Noise>
-static hipError_t launch_dpm_solver_step(const float* mo, const float* xs, const float* x, const float* m1,
-                                         const float* m2, const Noise noise, const float* coef, const float* scoef,
-                                         const int64_t* t_idx, int N, int voxels, int T, int flags, int order,
-                                         float* sample, float* pred_xstart, hipStream_t st) {
-    if (xs != nullptr)
-        hipLaunchKernelGGL((dpm_solver_step_kernel<Noise, true>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x, m1,
-                           m2, noise, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
-    else
-        hipLaunchKernelGGL((dpm_solver_step_kernel<Noise, false>), step_grid(N, voxels), dim3(256), 0, st, mo, xs, x, m1,
-                           m2, noise, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
-    return hipGetLastError();
-}
-
 hipError_t ddpm3d_launch_dpm_solver_step(const float* mo, const float* xs, const float* x, const float* m1,
                                          const float* m2, const float* noise, const ddpm3d_noise_key* key,
                                          const float* coef, const float* scoef, const int64_t* t_idx, int N, int voxels,
                                          int T, int flags, int order, float* sample, float* pred_xstart,
                                          hipStream_t st) {
-    if (key != nullptr)
-        return launch_dpm_solver_step(mo, xs, x, m1, m2, KeyNoise{noise_key_dev(*key)}, coef, scoef, t_idx, N, voxels,
-                                      T, flags, order, sample, pred_xstart, st);
-    return launch_dpm_solver_step(mo, xs, x, m1, m2, TensorNoise{noise}, coef, scoef, t_idx, N, voxels, T, flags, order,
-                                  sample, pred_xstart, st);
+    return launch_step(noise, key, [&](auto z, auto has_x0) {
+        hipLaunchKernelGGL((dpm_solver_step_kernel<decltype(z), has_x0.value>), step_grid(N, voxels), dim3(256), 0, st,
+                           mo, xs, x, m1, m2, z, coef, scoef, t_idx, voxels, T, flags, order, sample, pred_xstart);
+    }, xs != nullptr);
 }
 
 // ------------------------------------------------------- variational bound
@@ -1083,13 +1062,10 @@ __global__ __launch_bounds__(256) void vb_fold_kernel(const double* __restrict__
 
 hipError_t ddpm3d_launch_q_sample(const float* x0, const float* noise, const ddpm3d_noise_key* key, const float* qcoef,
                                   const int64_t* t_idx, int N, int voxels, int T, float* xt, hipStream_t st) {
-    if (key != nullptr)
-        hipLaunchKernelGGL(q_sample_kernel<KeyNoise>, step_grid(N, voxels), dim3(256), 0, st, x0,
-                           KeyNoise{noise_key_dev(*key)}, qcoef, t_idx, voxels, T, xt);
-    else
-        hipLaunchKernelGGL(q_sample_kernel<TensorNoise>, step_grid(N, voxels), dim3(256), 0, st, x0, TensorNoise{noise},
-                           qcoef, t_idx, voxels, T, xt);
-    return hipGetLastError();
+    return launch_step(noise, key, [&](auto z) {
+        hipLaunchKernelGGL(q_sample_kernel<decltype(z)>, step_grid(N, voxels), dim3(256), 0, st, x0, z, qcoef, t_idx,
+                           voxels, T, xt);
+    });
 }
 
 hipError_t ddpm3d_launch_vb_terms(const float* mo, const float* x_start, const float* x_t, const float* noise,

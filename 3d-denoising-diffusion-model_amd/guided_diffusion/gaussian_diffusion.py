@@ -380,53 +380,53 @@ class GaussianDiffusion:
         SpacedDiffusion, respace.py:123-128)."""
         return self._scale_timesteps(t)
 
-    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None, noise_key=None, draw=0,
-                xstart=None):
-        """One fused reverse step.  `out`: (sample, pred_xstart) tensors of x's shape to write into (the joint loop's
-        patch buffers); fresh tensors otherwise.  With `noise_key` the kernel evaluates the key's `draw` itself and
-        `noise` is not read.  With `xstart` (a guide's pulled x0, of x's shape) the step runs on the *_step_x0 entry:
-        x0 is that tensor instead of the model output's first half."""
-        lib = H.load()
-        N = x.shape[0]
-        vox = x[0].numel()
-        flags = self._flags(clip_denoised)
+    # (kind, variant) -> the C entry of a step; _step assembles every entry's argument list (_hip.EXPORTS) from one
+    # ordered description
+    _STEP_ENTRY = {(kind, variant): "ddpm3d_%s_step%s" % (name, suffix)
+                   for kind, name in (("ddpm", "p_sample"), ("ddim", "ddim"), ("solver", "dpm_solver"))
+                   for variant, suffix in (("plain", ""), ("keyed", "_keyed"), ("x0", "_x0"))}
+
+    def _step(self, kind, model_output, x, t, noise, flags, rule, hist=(), scoef=None, out=None, noise_key=None,
+              draw=0, xstart=None):
+        """One fused step of `kind` ("ddpm", "ddim" or "solver"): the tensor checks of every step call, then one launch
+        of the entry its variant names -- x0 with `xstart` (a guide's pulled x0, of x's shape: x0 is that tensor instead
+        of the model output's first half), else keyed with `noise_key` (the kernel evaluates the key's `draw` itself and
+        `noise` is not read), else plain.  `rule`: what follows flags in the entry's list ([eta] of ddim, [order] of the
+        solver); `hist`, `scoef`: the solver's (m1, m2) and its table; the solver alone takes T and may run with
+        neither noise nor key (its ODE form).  `out`: (sample, pred_xstart) tensors of x's shape to write into (the
+        joint loop's patch buffers); fresh tensors otherwise."""
+        solver = kind == "solver"
         self._model_step_output(model_output, x, flags)
         H.require_device(x, "x")
-        if noise_key is None:
-            self._check_noise(noise, x)
-        else:
+        kd = None
+        if noise_key is not None:
             kd = noise_key.desc(draw, x)
+        elif noise is not None or not solver:
+            self._check_noise(noise, x)
         if xstart is not None:
             H.require_device(xstart, "xstart")
             assert xstart.shape == x.shape and xstart.device == x.device
-        st = self._device_state(x.device)
         sample, x0 = out if out is not None else (th.empty_like(x), th.empty_like(x))
         for name, o in (("out[0] (sample)", sample), ("out[1] (pred_xstart)", x0)):
             H.require_device(o, name)
             assert o.shape == x.shape and o.device == x.device, "%s: %s on %s for x %s on %s" % (
                 name, tuple(o.shape), o.device, tuple(x.shape), x.device)
         t = t.to(device=x.device, dtype=th.int64).contiguous()
-        if xstart is not None:
-            args = (H.ptr(model_output), H.ptr(xstart), H.ptr(x), H.ptr(noise) if noise_key is None else None,
-                    kd if noise_key is not None else None, H.ptr(st["coef"]), H.ptr(t), N, vox, flags)
-            if kind == "ddpm":
-                H.check(lib.ddpm3d_p_sample_step_x0(*args, H.ptr(sample), H.ptr(x0), H.stream()))
-            else:
-                H.check(lib.ddpm3d_ddim_step_x0(*args, float(eta), H.ptr(sample), H.ptr(x0), H.stream()))
-        elif noise_key is not None and kind == "ddpm":
-            H.check(lib.ddpm3d_p_sample_step_keyed(H.ptr(model_output), H.ptr(x), kd, H.ptr(st["coef"]), H.ptr(t), N,
-                                                   vox, flags, H.ptr(sample), H.ptr(x0), H.stream()))
-        elif noise_key is not None:
-            H.check(lib.ddpm3d_ddim_step_keyed(H.ptr(model_output), H.ptr(x), kd, H.ptr(st["coef"]), H.ptr(t), N, vox,
-                                               flags, float(eta), H.ptr(sample), H.ptr(x0), H.stream()))
-        elif kind == "ddpm":
-            H.check(lib.ddpm3d_p_sample_step(H.ptr(model_output), H.ptr(x), H.ptr(noise), H.ptr(st["coef"]),
-                                             H.ptr(t), N, vox, flags, H.ptr(sample), H.ptr(x0), H.stream()))
-        else:
-            H.check(lib.ddpm3d_ddim_step(H.ptr(model_output), H.ptr(x), H.ptr(noise), H.ptr(st["coef"]),
-                                         H.ptr(t), N, vox, flags, float(eta), H.ptr(sample), H.ptr(x0),
-                                         H.stream()))
+        z = None if kd is not None else H.ptr(noise)
+        variant, source = ("x0", [z, kd]) if xstart is not None else ("plain", [z]) if kd is None else ("keyed", [kd])
+        args = ([H.ptr(model_output)] + [H.ptr(xstart)] * (variant == "x0") + [H.ptr(x)] + [H.ptr(m) for m in hist]
+                + source + [H.ptr(self._device_state(x.device)["coef"])] + [H.ptr(scoef)] * solver
+                + [H.ptr(t), x.shape[0], x[0].numel()] + [self.num_timesteps] * solver + [flags] + rule
+                + [H.ptr(sample), H.ptr(x0), H.stream()])
+        H.check(getattr(H.load(), self._STEP_ENTRY[kind, variant])(*args))
         return {"sample": sample, "pred_xstart": x0}
+
+    def _update(self, kind, model_output, x, t, noise, clip_denoised, eta=0.0, out=None, noise_key=None, draw=0,
+                xstart=None):
+        """One fused reverse step of kind "ddpm" or "ddim" (_step)."""
+        return self._step(kind, model_output, x, t, noise, self._flags(clip_denoised),
+                          [] if kind == "ddpm" else [float(eta)], out=out, noise_key=noise_key, draw=draw,
+                          xstart=xstart)
 
     @staticmethod
     def _indices(indices, progress):
@@ -529,6 +529,11 @@ class GaussianDiffusion:
         """gaussian_diffusion.py:395-439.  `noise`: optional injected randn_like draw; `noise_key`, `draw`
         (extension): the step's noise is that draw of the key, evaluated by the kernel.  `guide` (extension): a
         guidance.LowPassPull applied to the x_start prediction where the reference applies denoised_fn (:293-314)."""
+        return self._sample_step("ddpm", model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, 0.0, noise,
+                                 noise_key, draw, guide)
+
+    def _sample_step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, noise, noise_key,
+                     draw, guide):
         self._reject_hooks(denoised_fn, cond_fn)
         self._check_key(noise_key, noise)
         self._guide_measurement(guide, x.shape, model_kwargs)
@@ -536,19 +541,13 @@ class GaussianDiffusion:
         if noise is None and noise_key is None:
             noise = th.randn_like(x)
         xs = self._guided_x0_at(guide, out, x, t, clip_denoised, model_kwargs)
-        return self._update("ddpm", out, x, t, noise, clip_denoised, noise_key=noise_key, draw=draw, xstart=xs)
+        return self._update(kind, out, x, t, noise, clip_denoised, eta, noise_key=noise_key, draw=draw, xstart=xs)
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                     eta=0.0, noise=None, noise_key=None, draw=0, guide=None):
         """gaussian_diffusion.py:537-585.  `noise_key`, `draw`, `guide` as in p_sample."""
-        self._reject_hooks(denoised_fn, cond_fn)
-        self._check_key(noise_key, noise)
-        self._guide_measurement(guide, x.shape, model_kwargs)
-        out = self._call_model(model, x, t, model_kwargs)
-        if noise is None and noise_key is None:
-            noise = th.randn_like(x)
-        xs = self._guided_x0_at(guide, out, x, t, clip_denoised, model_kwargs)
-        return self._update("ddim", out, x, t, noise, clip_denoised, eta, noise_key=noise_key, draw=draw, xstart=xs)
+        return self._sample_step("ddim", model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, noise,
+                                 noise_key, draw, guide)
 
     # ------------------------------------------------------------------ loops
     def _trace_step(self, trace, res, prev, i):
@@ -559,38 +558,53 @@ class GaussianDiffusion:
             trace.add(res["pred_xstart"], prev, i if tmap is None else tmap[i], self.num_timesteps)
         return res["pred_xstart"]
 
-    def _loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-              progress, eta, step_noise, trace=None, noise_key=None, guide=None):
-        self._reject_hooks(denoised_fn, cond_fn)
-        self._check_key(noise_key, step_noise)
-        self._guide_measurement(guide, shape, model_kwargs)            # refused here, before the device is looked at
-        if device is None:
-            device = next(model.parameters()).device
-        device = th.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("sampling runs on HIP kernels only; got device %s" % device)
-        assert isinstance(shape, (tuple, list))
-        img = self._start_noise(noise, shape, device, noise_key)
-        indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
-        # grad mode and the current device are changed around the COMPUTE of a step only and are
-        # back to the caller's before every yield (the reference wraps p_sample alone in no_grad and
-        # yields outside it, gaussian_diffusion.py:524-535): an abandoned *_progressive generator
-        # leaves nothing changed.
+    def _frame(self, step, start, indices, model, shape, model_kwargs, device, progress, trace, guide=None,
+               clip_denoised=True, draws=False, step_noise=None):
+        """The frame of every *_progressive loop: from img = start(), per index i (the loop's k-th): the network, then
+        res = step(k, i, model output, img, t, z, xs), the trace row, the yield, img = res["sample"].  z: the step's
+        noise tensor where the loop `draws` one (_draw_noise, once per step), else None; xs: the guide's pulled x0, or
+        None.  Grad mode and the current device are changed around the COMPUTE of a step only and are back to the
+        caller's before every yield (the reference wraps p_sample alone in no_grad and yields outside it,
+        gaussian_diffusion.py:524-535): an abandoned generator leaves nothing changed."""
+        indices = self._indices(indices, progress)
         with th.no_grad(), th.cuda.device(device):
+            img = start()
             t_all, net = self._step_model(model, shape, model_kwargs or {}, device)
             y = self._guide_measurement(guide, shape, model_kwargs, device)
         prev = None                     # the previous step's pred_xstart, kept for `trace` only
         for k, i in enumerate(indices):
             with th.no_grad(), th.cuda.device(device):
                 out = net(img, i)
-                z = self._draw_noise(step_noise, k, img) if noise_key is None else None
+                z = self._draw_noise(step_noise, k, img) if draws else None
                 xs = self._guided_x0(guide, y, out, img, t_all[i], i, clip_denoised)
-                res = self._update(kind, out, img, t_all[i], z, clip_denoised, eta, noise_key=noise_key, draw=k + 1,
-                                   xstart=xs)
+                res = step(k, i, out, img, t_all[i], z, xs)
                 if trace is not None:
                     prev = self._trace_step(trace, res, prev, i)
             yield res
             img = res["sample"]
+
+    @staticmethod
+    def _sampling_device(model, device):
+        if device is None:
+            device = next(model.parameters()).device
+        device = th.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("sampling runs on HIP kernels only; got device %s" % device)
+        return device
+
+    def _sampler_loop(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
+                      progress, eta, step_noise, trace=None, noise_key=None, guide=None):
+        """The ddpm and ddim loops: their checks, then the frame over _update."""
+        self._reject_hooks(denoised_fn, cond_fn)
+        self._check_key(noise_key, step_noise)
+        self._guide_measurement(guide, shape, model_kwargs)            # refused here, before the device is looked at
+        device = self._sampling_device(model, device)
+        assert isinstance(shape, (tuple, list))
+        return self._frame(
+            lambda k, i, out, img, t, z, xs: self._update(kind, out, img, t, z, clip_denoised, eta,
+                                                          noise_key=noise_key, draw=k + 1, xstart=xs),
+            lambda: self._start_noise(noise, shape, device, noise_key), range(self.num_timesteps - 1, -1, -1), model,
+            shape, model_kwargs, device, progress, trace, guide, clip_denoised, noise_key is None, step_noise)
 
     @staticmethod
     def _start_noise(noise, shape, device, noise_key):
@@ -613,37 +627,38 @@ class GaussianDiffusion:
         towards the measurement's local means before the clip and the posterior mean (the reference's denoised_fn
         position, :293-314) by one ddpm3d_xstart_pull call, and pred_xstart (also `trace`'s) is the pulled one.  On the
         other steps, and with None, nothing more is launched."""
-        yield from self._loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+        yield from self._sampler_loop("ddpm", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
                               device, progress, 0.0, step_noise, trace, noise_key, guide)
+
+    @staticmethod
+    def _last_sample(steps):
+        final = None
+        for final in steps:
+            pass
+        return final["sample"]
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, step_noise=None, trace=None, noise_key=None,
                       guide=None):
         """gaussian_diffusion.py:441-485."""
-        final = None
-        for final in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn,
-                                                    model_kwargs, device, progress, step_noise, trace, noise_key,
-                                                    guide):
-            pass
-        return final["sample"]
+        return self._last_sample(self.p_sample_loop_progressive(
+            model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, step_noise, trace,
+            noise_key, guide))
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
                                      step_noise=None, trace=None, noise_key=None, guide=None):
         """gaussian_diffusion.py:659-707."""
-        yield from self._loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+        yield from self._sampler_loop("ddim", model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
                               device, progress, eta, step_noise, trace, noise_key, guide)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None, trace=None,
                          noise_key=None, guide=None):
         """gaussian_diffusion.py:625-657."""
-        final = None
-        for final in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
-                                                       cond_fn, model_kwargs, device, progress, eta,
-                                                       step_noise, trace, noise_key, guide):
-            pass
-        return final["sample"]
+        return self._last_sample(self.ddim_sample_loop_progressive(
+            model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, eta, step_noise,
+            trace, noise_key, guide))
 
     # ------------------------------------------------------ variational bound
     def _check_t(self, t, N):
@@ -877,29 +892,16 @@ class GaussianDiffusion:
         if device.type != "cuda":
             raise RuntimeError("DDIM inversion runs on HIP kernels only; got device %s" % device)
         flags = self._flags(clip_denoised)
-        indices = self._indices(range(self.num_timesteps), progress)
-        # as in _loop: grad mode and the current device change around each step's compute only
-        with th.no_grad(), th.cuda.device(device):
-            img = x_start.to(device)
-            t_all, net = self._step_model(model, x_start.shape, model_kwargs or {}, device)
-        prev = None
-        for i in indices:
-            with th.no_grad(), th.cuda.device(device):
-                res = self._reverse_step(net(img, i), img, t_all[i], flags)
-                if trace is not None:
-                    prev = self._trace_step(trace, res, prev, i)
-            yield res
-            img = res["sample"]
+        yield from self._frame(lambda k, i, out, img, t, z, xs: self._reverse_step(out, img, t, flags),
+                               lambda: x_start.to(device), range(self.num_timesteps), model, x_start.shape,
+                               model_kwargs, device, progress, trace)
 
     def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                                  device=None, progress=False, eta=0.0, trace=None):
         """DDIM inversion (extension): x_T from a clean x_start, the last sample of
         ddim_reverse_sample_loop_progressive."""
-        final = None
-        for final in self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised, denoised_fn,
-                                                               model_kwargs, device, progress, eta, trace):
-            pass
-        return final["sample"]
+        return self._last_sample(self.ddim_reverse_sample_loop_progressive(
+            model, x_start, clip_denoised, denoised_fn, model_kwargs, device, progress, eta, trace))
 
     # ------------------------------------------------- DPM-Solver++ multistep
     def _solver_step(self, model_output, x, m1, m2, z, t, flags, order, stochastic, p, noise_key=None, draw=0,
@@ -907,32 +909,9 @@ class GaussianDiffusion:
         """One ddpm3d_dpm_solver_step launch at effective order p; t: int64 on x's device.  With `noise_key` the keyed
         entry reads the key's `draw` instead of z; with `xstart` (a guide's pulled x0) the *_x0 entry takes it as the
         data prediction."""
-        if z is not None:
-            self._check_noise(z, x)
-        self._model_step_output(model_output, x, flags)
-        st = self._device_state(x.device)
-        scoef = self._solver_state(x.device, order, stochastic)
-        sample = th.empty_like(x)
-        x0 = th.empty_like(x)
-        if xstart is not None:
-            H.check(H.load().ddpm3d_dpm_solver_step_x0(H.ptr(model_output), H.ptr(xstart), H.ptr(x), H.ptr(m1),
-                                                       H.ptr(m2), H.ptr(z) if noise_key is None else None,
-                                                       None if noise_key is None else noise_key.desc(draw, x),
-                                                       H.ptr(st["coef"]), H.ptr(scoef), H.ptr(t), x.shape[0],
-                                                       x[0].numel(), self.num_timesteps, flags, p, H.ptr(sample),
-                                                       H.ptr(x0), H.stream()))
-            return {"sample": sample, "pred_xstart": x0}
-        if noise_key is not None:
-            H.check(H.load().ddpm3d_dpm_solver_step_keyed(H.ptr(model_output), H.ptr(x), H.ptr(m1), H.ptr(m2),
-                                                          noise_key.desc(draw, x), H.ptr(st["coef"]), H.ptr(scoef),
-                                                          H.ptr(t), x.shape[0], x[0].numel(), self.num_timesteps,
-                                                          flags, p, H.ptr(sample), H.ptr(x0), H.stream()))
-            return {"sample": sample, "pred_xstart": x0}
-        H.check(H.load().ddpm3d_dpm_solver_step(H.ptr(model_output), H.ptr(x), H.ptr(m1), H.ptr(m2), H.ptr(z),
-                                                H.ptr(st["coef"]), H.ptr(scoef), H.ptr(t), x.shape[0],
-                                                x[0].numel(), self.num_timesteps, flags, p, H.ptr(sample),
-                                                H.ptr(x0), H.stream()))
-        return {"sample": sample, "pred_xstart": x0}
+        return self._step("solver", model_output, x, t, z, flags, [p], (m1, m2),
+                          self._solver_state(x.device, order, stochastic), noise_key=noise_key, draw=draw,
+                          xstart=xstart)
 
     def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                            cond_fn=None, model_kwargs=None, device=None, progress=False, order=2,
@@ -955,47 +934,27 @@ class GaussianDiffusion:
         self._check_key(noise_key, step_noise)
         self._reject_hooks(denoised_fn, cond_fn)
         self._guide_measurement(guide, shape, model_kwargs)
-        if device is None:
-            device = next(model.parameters()).device
-        device = th.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("sampling runs on HIP kernels only; got device %s" % device)
+        device = self._sampling_device(model, device)
         assert isinstance(shape, (tuple, list))
         flags = self._flags(clip_denoised)
-        return self._solver_loop(model, shape, noise, flags, model_kwargs or {}, device, progress, order,
-                                 stochastic, step_noise, trace, noise_key, guide, clip_denoised)
-
-    def _solver_loop(self, model, shape, noise, flags, model_kwargs, device, progress, order, stochastic,
-                     step_noise, trace=None, noise_key=None, guide=None, clip_denoised=True):
-        indices = self._indices(range(self.num_timesteps - 1, -1, -1), progress)
-        # as in _loop: grad mode and the current device change around each step's compute only
-        with th.no_grad(), th.cuda.device(device):
-            img = self._start_noise(noise, shape, device, noise_key)
-            t_all, net = self._step_model(model, shape, model_kwargs, device)
-            y = self._guide_measurement(guide, shape, model_kwargs, device)
         key = noise_key if stochastic else None
         hist = []                       # pred_xstart of the last one or two steps, newest first
-        for k, i in enumerate(indices):
-            with th.no_grad(), th.cuda.device(device):
-                out = net(img, i)
-                z = self._draw_noise(step_noise, k, img) if stochastic and key is None else None
-                p = 1 if i == 0 else min(order, k + 1)
-                res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z,
-                                        t_all[i], flags, order, stochastic, p, key, k + 1,
-                                        self._guided_x0(guide, y, out, img, t_all[i], i, clip_denoised))
-                if trace is not None:       # prev is the newest entry of the solver's own history
-                    self._trace_step(trace, res, hist[0] if hist else None, i)
-            yield res
-            img = res["sample"]
-            hist = [res["pred_xstart"]] + hist[:1]
+
+        def step(k, i, out, img, t, z, xs):
+            p = 1 if i == 0 else min(order, k + 1)
+            res = self._solver_step(out, img, hist[0] if p >= 2 else None, hist[1] if p >= 3 else None, z, t, flags,
+                                    order, stochastic, p, key, k + 1, xs)
+            hist[:] = [res["pred_xstart"]] + hist[:1]
+            return res
+
+        return self._frame(step, lambda: self._start_noise(noise, shape, device, noise_key),
+                           range(self.num_timesteps - 1, -1, -1), model, shape, model_kwargs, device, progress, trace,
+                           guide, clip_denoised, stochastic and key is None, step_noise)
 
     def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                model_kwargs=None, device=None, progress=False, order=2, stochastic=False,
                                step_noise=None, trace=None, noise_key=None, guide=None):
         """DPM-Solver++ multistep sampling (extension): the last sample of dpm_solver_sample_loop_progressive."""
-        final = None
-        for final in self.dpm_solver_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn,
-                                                             cond_fn, model_kwargs, device, progress, order,
-                                                             stochastic, step_noise, trace, noise_key, guide):
-            pass
-        return final["sample"]
+        return self._last_sample(self.dpm_solver_sample_loop_progressive(
+            model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, order, stochastic,
+            step_noise, trace, noise_key, guide))
