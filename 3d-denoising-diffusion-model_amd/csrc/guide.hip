@@ -61,7 +61,8 @@ __global__ __launch_bounds__(SMOOTH_THREADS) void pull_pass_kernel(const PullArg
     if (LAST) {
         const float wg = p.weight * g;
         float x0 = raw(v) + wg;
-        if (p.flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);   // :296-297, after denoised_fn
+        // :296-297, after denoised_fn; a NaN stays NaN as in x.clamp(-1, 1) (step_x0's rule)
+        if (p.flags & DDPM3D_F_CLIP) x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);
         out[base + v] = x0;
     } else {
         out[base + v] = g;

@@ -638,10 +638,16 @@ hipError_t ddpm3d_launch_subsample_hw2(const float* in, int N, int D, int H, int
 // learned variance the same way.
 #pragma clang fp contract(off)
 
+// x.clamp(-1, 1): a NaN stays NaN, as in torch (fminf / fmaxf would return the bound for it, and a diverged network's
+// output would leave the step as a finite volume); every other input gives the value fminf(fmaxf(x, -1), 1) gives
+__device__ __forceinline__ float clamp_unit(float x) { return x < -1.0f ? -1.0f : (x > 1.0f ? 1.0f : x); }
+// x.clamp(min=lo), NaN kept likewise
+__device__ __forceinline__ float clamp_min(float x, float lo) { return x < lo ? lo : x; }
+
 // x0 from the model output's first half (x_start itself, or eps), then the clip
 __device__ __forceinline__ float step_x0(float xv, float e, float c_recip, float c_recipm1, int flags) {
     float x0 = (flags & DDPM3D_F_PREDICT_XSTART) ? e : c_recip * xv - c_recipm1 * e;   // :305-311, :328-333
-    if (flags & DDPM3D_F_CLIP) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                     // :296-297
+    if (flags & DDPM3D_F_CLIP) x0 = clamp_unit(x0);                                    // :296-297
     return x0;
 }
 
@@ -665,9 +671,11 @@ __device__ __forceinline__ float eps_from_x0(float xv, float x0, float c_recip, 
     return (c_recip * xv - x0) / c_recipm1;                     // :345-349
 }
 
-// A sample whose t lies outside [0, T) reads no table row and gets NaN in every per-voxel output (fminf / fmaxf
-// would turn NaN coefficients into the clip bounds, so that case is a branch of its own): a and b, b only when
-// has_b, then c and d only when has_cd.
+// The kernels that take T (p_mean_variance, ddim_reverse_step, dpm_solver_step, q_sample, vb_terms) bound t
+// themselves: a sample whose t lies outside [0, T) reads no table row and gets NaN in every per-voxel output, a and
+// b, b only when has_b, then c and d only when has_cd.  sample_step_kernel takes no T and reads row t_idx[n] as it
+// stands: t in [0, rows of coef) is its caller's duty (include/ddpm3d.h), and there this fill serves only a keyed
+// patch that leaves its canvas.
 __device__ __forceinline__ void step_nan_fill(int n, int voxels, int stride, float* a, float* b, bool has_b, float* c,
                                               float* d, bool has_cd) {
     const float nan = __builtin_nanf("");
@@ -993,9 +1001,9 @@ __global__ __launch_bounds__(VB_THREADS) void vb_terms_kernel(
                     const float cdf_plus = approx_std_normal_cdf(inv_stdv * (centered + BIN));
                     const float cdf_min = approx_std_normal_cdf(inv_stdv * (centered - BIN));
                     float lp;
-                    if (xs < -0.999f) lp = log_r(fmaxf(cdf_plus, 1e-12f));
-                    else if (xs > 0.999f) lp = log_r(fmaxf(1.0f - cdf_min, 1e-12f));
-                    else lp = log_r(fmaxf(cdf_plus - cdf_min, 1e-12f));
+                    if (xs < -0.999f) lp = log_r(clamp_min(cdf_plus, 1e-12f));
+                    else if (xs > 0.999f) lp = log_r(clamp_min(1.0f - cdf_min, 1e-12f));
+                    else lp = log_r(clamp_min(cdf_plus - cdf_min, 1e-12f));
                     term = -lp;
                 } else {
                     // normal_kl(true posterior mean, posterior_log_variance_clipped, mean, logvar)  (:723-728)

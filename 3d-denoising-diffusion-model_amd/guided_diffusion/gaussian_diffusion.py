@@ -534,6 +534,9 @@ class GaussianDiffusion:
 
     def _sample_step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta, noise, noise_key,
                      draw, guide):
+        # the step kernel behind both calls takes no T and reads table row t as it stands: t is bounded here, before
+        # the model runs and before anything touches the device (the reference raises IndexError for such a t)
+        t = self._check_t(t, x.shape[0])
         self._reject_hooks(denoised_fn, cond_fn)
         self._check_key(noise_key, noise)
         self._guide_measurement(guide, x.shape, model_kwargs)
@@ -663,7 +666,9 @@ class GaussianDiffusion:
     # ------------------------------------------------------ variational bound
     def _check_t(self, t, N):
         """User-supplied step indices: shape (N,), every entry in [0, T) -- checked on the host before anything
-        is launched (the kernels themselves turn an out-of-range t into NaN without reading past the tables)."""
+        is launched.  The kernels that take T (q_sample, p_mean_variance, ddim_reverse_step, dpm_solver_step,
+        vb_terms, xstart_pull) also bound t themselves and turn an out-of-range t into NaN without reading past the
+        tables; the DDPM / DDIM step kernel takes no T, so for p_sample and ddim_sample this check is the only one."""
         if not isinstance(t, th.Tensor):
             t = th.as_tensor(t)
         if t.dim() != 1 or t.shape[0] != N:

@@ -483,6 +483,10 @@ int ddpm3d_subsample_hw2(const float* in, int N, int D, int H, int W, int C, flo
  * fp32-applied like _extract_into_tensor, :897-910); t_idx[n] selects the row.
  * model_out is NCDHW (N, 2 or 1, voxels); x, noise, sample, pred_xstart are
  * (N, 1, voxels).  pred_xstart may be NULL.
+ * Precondition: these two entries, their _keyed forms and their _x0 forms (ddpm3d_p_sample_step*, ddpm3d_ddim_step*)
+ * take no T, and their kernel reads row t_idx[n] of coef as it stands.  Every t_idx[n] in [0, rows of coef) is the
+ * caller's duty; a value outside is a read past the table, not a NaN result (the entries that take T bound t
+ * themselves).  The Python layer checks a user's t on the host before it calls them.
  */
 enum {
     DDPM3D_C_SQRT_RECIP_ACP = 0,
@@ -1113,7 +1117,8 @@ int ddpm3d_noise_fill(const ddpm3d_noise_key* key, int N, int voxels, float* out
 int ddpm3d_noise_bits(const ddpm3d_noise_key* key, int N, int quads, uint32_t* out, void* stream);
 /* The step entries above with their noise tensor replaced by a key; everything else, bit for bit, as the un-keyed
  * entry fed with what ddpm3d_noise_fill writes for the same key.  A NULL key is refused, except by the solver step,
- * where it selects the ODE form (no noise), as a NULL noise does above. */
+ * where it selects the ODE form (no noise), as a NULL noise does above.  ddpm3d_p_sample_step_keyed and
+ * ddpm3d_ddim_step_keyed take no T: t_idx[n] in [0, rows of coef) is the caller's duty, as for the un-keyed entries. */
 int ddpm3d_p_sample_step_keyed(const float* model_out, const float* x, const ddpm3d_noise_key* key,
                                const float* coef, const int64_t* t_idx, int N, int voxels,
                                int flags, float* sample, float* pred_xstart, void* stream);
@@ -1172,6 +1177,8 @@ int ddpm3d_xstart_pull(const float* model_out, const float* x, const float* meas
  * xstart, x, coef, t_idx or sample (the solver: scoef, pred_xstart too), N outside 1..65535, voxels below 1, unknown
  * flag bits, a wrong number of noise sources, a bad key (as the keyed entries), sample or pred_xstart equal to each
  * other or to a tensor the call reads, and the solver's order and history as ddpm3d_dpm_solver_step.
+ * ddpm3d_p_sample_step_x0 and ddpm3d_ddim_step_x0 take no T: t_idx[n] in [0, rows of coef) is the caller's duty, as
+ * for ddpm3d_p_sample_step.
  */
 int ddpm3d_p_sample_step_x0(const float* model_out, const float* xstart, const float* x, const float* noise,
                             const ddpm3d_noise_key* key, const float* coef, const int64_t* t_idx, int N, int voxels,

@@ -143,6 +143,33 @@ def test_pull_containment_and_repeatability():
     assert torch.isnan(bad0[0]).all() and torch.isfinite(bad0[1:]).all()
 
 
+@pytest.mark.parametrize("radii", [(0, 0, 0), (1, 2, 3)])
+def test_pull_keeps_nan_through_the_clip(radii):
+    """A NaN in the model output (a diverged network) stays NaN through the pull's clip, as through x.clamp(-1, 1):
+    the pull equals its composition of existing entries, whose clip is torch's, NaN for NaN and bit for bit elsewhere.
+    The pointwise pull is NaN at exactly the planted voxels; a smoothing pull spreads them and leaves the rest finite."""
+    d = diffusion("learned_range")
+    shape4 = (3, 7, 9, 65)
+    x, y, mo = inputs(shape4, "learned_range", seed=3)
+    t = steps_t(d, 3)
+    planted = [(0, 0, 0, 0, 0), (1, 0, 3, 4, 5), (2, 0, 6, 8, 64)]
+    for p in planted:
+        mo[p] = float("nan")
+    pull = pull_with(radii, weight=0.8)
+    got = pull.apply(mo, x, t, d._flags(True), d, measurement=y)
+    want = composed(d, mo, x, y, t, pull, True)
+    assert torch.equal(torch.isnan(got), torch.isnan(want))
+    assert torch.equal(got.nan_to_num(7.0), want.nan_to_num(7.0))
+    assert all(bool(torch.isnan(got[p])) for p in planted)
+    count = int(torch.isnan(got).sum())
+    assert count == 3 if radii == (0, 0, 0) else 3 < count < got.numel() // 2
+    assert float(got.nan_to_num(0.0).abs().max()) <= 1.0
+    if radii == (0, 0, 0):               # the CPU reference's clip keeps them too
+        ref = gr.pulled_x0(d.coef_table(), mo.cpu(), x.cpu(), t.cpu(), y.cpu(), gr.taps_for(radii), pull.weight,
+                           False, True)
+        assert np.array_equal(np.isnan(ref.numpy()), np_(torch.isnan(got)))
+
+
 # ------------------------------------------------------------------------------------------- the *_step_x0 entries
 def _key(N, seed=7):
     return gd.NoiseKey(seed, list(range(11, 11 + N)))
