@@ -1141,12 +1141,13 @@ int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t vox
 }
 
 // ------------------------------------------------- connected components (added within ABI 13)
-static bool ccl_shape_ok(int D, int H, int W) {
+// a volume the dense kernels index with 32-bit voxel and row numbers: 1 or more each, D * H and D * H * W <= 2^31 - 1
+static bool volume_shape_ok(int D, int H, int W) {
     return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H <= 0x7fffffff && (int64_t)D * H * W <= 0x7fffffff;
 }
 
 size_t ddpm3d_label_components_workspace_bytes(int D, int H, int W) {
-    return ccl_shape_ok(D, H, W) ? ddpm3d_ccl_workspace_bytes(D, H, W) : 0;
+    return volume_shape_ok(D, H, W) ? ddpm3d_ccl_workspace_bytes(D, H, W) : 0;
 }
 
 int ddpm3d_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity, int D, int H,
@@ -1154,7 +1155,7 @@ int ddpm3d_label_components(const float* vol, const uint8_t* keep, float thresho
     if (!vol || !roots || !status) return fail(DDPM3D_EINVAL, "label_components: null pointer");
     if (connectivity != 6 && connectivity != 18 && connectivity != 26)
         return fail(DDPM3D_EINVAL, "label_components: connectivity %d (6, 18 or 26)", connectivity);
-    if (!ccl_shape_ok(D, H, W))
+    if (!volume_shape_ok(D, H, W))
         return fail(DDPM3D_EINVAL, "label_components: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= "
                                    "2^31 - 1)", D, H, W);
     if (threshold != threshold) return fail(DDPM3D_EINVAL, "label_components: the threshold is NaN");
@@ -1173,7 +1174,7 @@ int ddpm3d_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int 
     if (vol == out) return fail(DDPM3D_EINVAL, "sphere_mean: out must not be vol (every voxel is read by its neighbours)");
     if (B < 1 || B > DDPM3D_MAX_DRAWS)
         return fail(DDPM3D_EINVAL, "sphere_mean: B=%d volumes (1..%d)", B, DDPM3D_MAX_DRAWS);
-    if (D < 1 || H < 1 || W < 1 || (int64_t)D * H > 0x7fffffff || (int64_t)D * H * W > 0x7fffffff)
+    if (!volume_shape_ok(D, H, W))
         return fail(DDPM3D_EINVAL, "sphere_mean: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)",
                     D, H, W);
     if (r0 < 0 || r0 > R || r1 < 0 || r1 > R)
@@ -1193,12 +1194,8 @@ int ddpm3d_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int 
 }
 
 // ------------------------------------------------- baseline denoisers (added within ABI 13)
-static bool baseline_shape_ok(int D, int H, int W) {
-    return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H <= 0x7fffffff && (int64_t)D * H * W <= 0x7fffffff;
-}
-
 size_t ddpm3d_gauss_smooth_workspace_bytes(int D, int H, int W) {
-    return baseline_shape_ok(D, H, W) ? (((size_t)D * H * W * sizeof(float) + 15) & ~(size_t)15) : 0;
+    return volume_shape_ok(D, H, W) ? (((size_t)D * H * W * sizeof(float) + 15) & ~(size_t)15) : 0;
 }
 
 // the radii (0..DDPM3D_SMOOTH_MAX_RADIUS) and the host tap tables (positive, finite, symmetric) of a Gaussian entry
@@ -1223,7 +1220,7 @@ int ddpm3d_gauss_smooth(const float* vol, int D, int H, int W, int r0, int r1, i
                         const float* taps1, const float* taps2, float* out, void* ws, size_t ws_bytes, void* stream) {
     if (!vol || !out || !taps0 || !taps1 || !taps2) return fail(DDPM3D_EINVAL, "gauss_smooth: null pointer");
     if (vol == out) return fail(DDPM3D_EINVAL, "gauss_smooth: out must not be vol (every voxel is read by its neighbours)");
-    if (!baseline_shape_ok(D, H, W))
+    if (!volume_shape_ok(D, H, W))
         return fail(DDPM3D_EINVAL, "gauss_smooth: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)",
                     D, H, W);
     const int radii[3] = {r0, r1, r2};
@@ -1242,7 +1239,7 @@ int ddpm3d_nlm(const float* vol, int D, int H, int W, int s0, int s1, int s2, in
     const int S = DDPM3D_NLM_MAX_SEARCH, P = DDPM3D_NLM_MAX_PATCH;
     if (!vol || !out) return fail(DDPM3D_EINVAL, "nlm: null pointer");
     if (vol == out) return fail(DDPM3D_EINVAL, "nlm: out must not be vol (every voxel is read by its neighbours)");
-    if (!baseline_shape_ok(D, H, W))
+    if (!volume_shape_ok(D, H, W))
         return fail(DDPM3D_EINVAL, "nlm: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)", D, H, W);
     if (s0 < 0 || s0 > S || s1 < 0 || s1 > S || s2 < 0 || s2 > S)
         return fail(DDPM3D_EINVAL, "nlm: search radii s0=%d s1=%d s2=%d (0..%d)", s0, s1, s2, S);
@@ -1336,7 +1333,7 @@ int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_reg
 
 // ------------------------------------------------- low-pass pull of x_start (added within ABI 13)
 static bool pull_shape_ok(int N, int D, int H, int W) {
-    return N >= 1 && N <= 65535 && baseline_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;
+    return N >= 1 && N <= 65535 && volume_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;
 }
 
 size_t ddpm3d_xstart_pull_workspace_bytes(int N, int D, int H, int W) {

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include "ddpm3d.h"
+#include "ops.h"   // DynLdsOnce / ddpm3d_allow_dynamic_lds
 
 #define DDPM3D_CONV_CK 16      // input channels staged per LDS tile
 #define DDPM3D_REDUCE_VOX 16   // voxels per workgroup (= per statistics row) of the split-K reduce
@@ -234,23 +235,6 @@ static inline bool ddpm3d_up_phase_geom(int D, int H, int W, const ConvCfg& c, U
     g.tilesY = (Hl + g.TY - 1) / g.TY;
     g.tilesZ = (D + TZ - 1) / TZ;
     return 4LL * g.tilesX * g.tilesY * g.tilesZ == (long long)c.tilesX * c.tilesY * c.tilesZ;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: raise it once
-// per (kernel instantiation, device), not once per process (a process that drives two GPUs would
-// otherwise fail its first > 64 KB launch on the second one).  `done` = one flag word per kernel.
-struct DynLdsOnce { unsigned long long mask[4]; };   // 256 devices
-static inline hipError_t ddpm3d_allow_dynamic_lds(DynLdsOnce& done, const void* kernel, int bytes) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    dev &= 255;
-    unsigned long long& w = done.mask[dev >> 6];
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (__atomic_load_n(&w, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) __atomic_fetch_or(&w, bit, __ATOMIC_RELEASE);
-    return e;
 }
 
 hipError_t ddpm3d_launch_conv(const ConvK& k, const ConvCfg& c, hipStream_t st);

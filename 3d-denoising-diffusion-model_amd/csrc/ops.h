@@ -8,6 +8,23 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // the same for a kernel whose pointers need different (power-of-two) alignments
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: raise it once
+// per (kernel instantiation, device), not once per process (a process that drives two GPUs would
+// otherwise fail its first > 64 KB launch on the second one).  `done` = one flag word per kernel.
+struct DynLdsOnce { unsigned long long mask[4]; };   // 256 devices
+static inline hipError_t ddpm3d_allow_dynamic_lds(DynLdsOnce& done, const void* kernel, int bytes) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    dev &= 255;
+    unsigned long long& w = done.mask[dev >> 6];
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (__atomic_load_n(&w, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) __atomic_fetch_or(&w, bit, __ATOMIC_RELEASE);
+    return e;
+}
+
 hipError_t ddpm3d_launch_pack(const float* w, int Cout, int Cin, int ks, int prec, void* out, hipStream_t st);
 hipError_t ddpm3d_launch_pack_up_phase(const float* w, int Cout, int Cin, void* out, hipStream_t st);
 hipError_t ddpm3d_launch_gn_finalize(const double* st0, int C0, int rows0, const double* st1, int C1,
@@ -123,8 +140,6 @@ hipError_t ddpm3d_launch_label_components(const float* vol, const uint8_t* keep,
 // entries lie in -1..DDPM3D_PEAK_MAX_RADIUS)
 hipError_t ddpm3d_launch_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int H, int W, int r0, int r1,
                                      const int32_t* half_w, float* out, hipStream_t st);
-// the tile (TD, TH; TW = 64) and the LDS bytes that launch uses for radii (r0, r1, rw) with or without keep
-void ddpm3d_sphere_mean_tile(int r0, int r1, int rw, bool keep, int* TD, int* TH, size_t* lds_bytes);
 // smooth.hip: the separable Gaussian of one volume, passes along W, H, D (the caller has checked the shape, the radii
 // (D, H, W order, 0..DDPM3D_SMOOTH_MAX_RADIUS), the three host tap tables and the workspace of one volume)
 hipError_t ddpm3d_launch_gauss_smooth(const float* vol, int D, int H, int W, const int* radii, const float* const* taps,
@@ -139,8 +154,6 @@ hipError_t ddpm3d_launch_xstart_pull(const float* mo, const float* x, const floa
 // is exp(-max(fma(sum of squared patch differences, k1, -k2), 0)), k1 = 1 / (n_p h^2), k2 = 2 sigma^2 / h^2
 hipError_t ddpm3d_launch_nlm(const float* vol, int D, int H, int W, const int* search, const int* patch, float k1,
                              float k2, float* out, hipStream_t st);
-// the tile (TD, TH; TW = 64) and the LDS bytes that launch uses for halos (R0, R1, R2), R_a = s_a + p_a
-void ddpm3d_nlm_tile(int R0, int R1, int R2, int* TD, int* TH, size_t* lds_bytes);
 // regrid.hip: B volumes of one shape onto another grid, passes along W, H, D with the tables of axes[] (D, H, W order)
 // in device memory (the caller has checked the shapes, the taps, the ratios and the workspace); stage[] gets the voxels
 // per volume after the W, the H and the D pass, of which the first two, times B, are the workspace's two buffers

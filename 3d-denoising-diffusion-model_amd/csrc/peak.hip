@@ -1,29 +1,21 @@
 // Sphere-mean map for SUVpeak (definitions in include/ddpm3d.h): out[b][v] = mean of vol[b] over the
-// footprint voxels around v that lie inside the volume and are kept.  One dense pass.  A workgroup of four waves owns
-// an output tile of TD x TH x 64 voxels, stages the tile plus its halo in LDS (zeros outside the volume and where
-// keep == 0; with keep also one flag byte per voxel) and sums the footprint's row runs from there: lane = x, so every
-// LDS read of a wave is 64 consecutive words.  The footprint travels in the kernel arguments as the list of its
-// present rows (dz, dy, half-width), which a workgroup copies to LDS once, so each row's half-width is a scalar.  Taps
-// are added in one order whatever the tile: the same bits on every run, and row b does not depend on B.  No atomics;
-// plain vector stores.
+// footprint voxels around v that lie inside the volume and are kept.  One dense pass on the halo-tile frame of
+// halo_tile.h (tiles, staging, grid and launch are there): the halo is staged with zeros outside the volume and where
+// keep == 0, with keep also one flag byte per voxel, and the footprint's row runs are summed from LDS.  The footprint
+// travels in the kernel arguments as the list of its present rows (dz, dy, half-width), which a workgroup copies to LDS
+// once, so each row's half-width is a scalar.  Taps are added in one order whatever the tile: the same bits on every
+// run, and row b does not depend on B.  No atomics; plain vector stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <atomic>
 #include "ddpm3d.h"
-#include "ops.h"
+#include "halo_tile.h"
 
 namespace {
 
-constexpr int PEAK_THREADS = 256;
-constexpr int PEAK_TW = 64;                                   // one wave spans the tile along W
 constexpr int PEAK_SIDE = 2 * DDPM3D_PEAK_MAX_RADIUS + 1;
 constexpr size_t PEAK_LDS_FOUR = 40 * 1024;                   // a tile this small leaves room for four workgroups per CU
-constexpr int PEAK_STAGE_ROWS = 8;                            // rows a wave has in flight while staging
-constexpr size_t PEAK_LDS_ALL = 160 * 1024;                   // the LDS of a CU
-constexpr size_t PEAK_LDS_PLAIN = 64 * 1024;                  // what a launch may use without raising the kernel's limit
 constexpr size_t PEAK_LDS_STATIC = sizeof(int) * PEAK_SIDE * PEAK_SIDE;   // the row list
-// tiles in order of preference: the first that fits PEAK_LDS_FOUR, else the first that fits PEAK_LDS_ALL
-constexpr int PEAK_TILES[5][2] = {{8, 8}, {4, 8}, {4, 4}, {2, 4}, {1, 4}};
+constexpr int PEAK_TILES[5][2] = {{8, 8}, {4, 8}, {4, 4}, {2, 4}, {1, 4}};   // in order of preference (halo_pick)
 
 struct PeakArgs {
     int D, H, W;
@@ -35,79 +27,70 @@ struct PeakArgs {
 };
 
 constexpr size_t peak_lds_bytes(int TD, int TH, int r0, int r1, int rw, bool keep) {
-    const size_t n = (size_t)(TD + 2 * r0) * (TH + 2 * r1) * (PEAK_TW + 2 * rw);
+    const size_t n = halo_words(TD, TH, r0, r1, rw);
     return n * sizeof(float) + (keep ? (n + 3) / 4 * 4 : 0);       // dynamic; the row list is static on top
 }
 static_assert(peak_lds_bytes(PEAK_TILES[4][0], PEAK_TILES[4][1], DDPM3D_PEAK_MAX_RADIUS, DDPM3D_PEAK_MAX_RADIUS,
-                             DDPM3D_PEAK_MAX_RADIUS, true) + PEAK_LDS_STATIC <= PEAK_LDS_ALL,
+                             DDPM3D_PEAK_MAX_RADIUS, true) + PEAK_LDS_STATIC <= HALO_LDS_ALL,
               "the smallest tile of the largest footprint fits a CU's LDS");
 
 // grid: x = tiles along W x tiles along H, y = tiles along D (strided: an extent may exceed a grid's y range),
 // z = volume b.  A wave owns the TD outputs above one another at (y, lane): TD independent sums, so that TD (and
 // with the +-k pair 2 TD) LDS reads are in flight before the first add waits.  Every output adds its taps in the order
-// of the row list (dz, dy ascending), then dx = 0, -1, +1, -2, +2, ...
+// of the row list (dz, dy ascending), then dx = 0, -1, +1, -2, +2, ...  Six waves per SIMD is what the small tiles of a
+// footprint along W alone can fill (21 KB of LDS a workgroup); the register allocator is held to it.
 template <bool KEEP, int TD>
-__global__ __launch_bounds__(PEAK_THREADS) void sphere_mean_kernel(const float* __restrict__ vol,
-                                                                   const uint8_t* __restrict__ keep,
-                                                                   float* __restrict__ out, const PeakArgs a) {
+__global__ __launch_bounds__(HALO_THREADS) __attribute__((amdgpu_waves_per_eu(6)))
+void sphere_mean_kernel(const float* __restrict__ vol, const uint8_t* __restrict__ keep, float* __restrict__ out,
+                        const PeakArgs a) {
     extern __shared__ float lds[];
     __shared__ int s_rows[PEAK_SIDE * PEAK_SIDE];
-    const int LW = PEAK_TW + 2 * a.rw, LH = a.TH + 2 * a.r1, LD = TD + 2 * a.r0;
-    const int slab = LH * LW;                                 // words per staged plane
+    const HaloFrame f = halo_frame(TD, a.TH, a.r0, a.r1, a.rw, a.D, a.H, a.W);
+    const auto [LW, LH, LD, slab, lane, wave, tiles_w, tiles_d, tx0, ty0, plane] = f;   // the compute loop's names
+    const int64_t x = tx0 + lane;
     float* __restrict__ sx = lds;
     uint8_t* __restrict__ sk = reinterpret_cast<uint8_t*>(lds + (size_t)LD * slab);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tiles_w = (int)(((int64_t)a.W + PEAK_TW - 1) / PEAK_TW);
-    const int tiles_d = (int)(((int64_t)a.D + TD - 1) / TD);
-    // 64-bit coordinates: an extent may be 2^31 - 1, and a tile or its halo reaches past it
-    const int64_t tx0 = (int64_t)(blockIdx.x % tiles_w) * PEAK_TW;
-    const int64_t ty0 = (int64_t)(blockIdx.x / tiles_w) * a.TH;
-    const int64_t x = tx0 + lane;
-    const int64_t plane = (int64_t)a.H * a.W;
     const int64_t base = (int64_t)blockIdx.z * a.D * plane;
-    for (int i = threadIdx.x; i < a.n_rows; i += PEAK_THREADS) s_rows[i] = a.rows[i];
+    for (int i = threadIdx.x; i < a.n_rows; i += HALO_THREADS) s_rows[i] = a.rows[i];
 
     for (int tz = blockIdx.y; tz < tiles_d; tz += gridDim.y) {
         const int64_t tz0 = (int64_t)tz * TD;
-        // stage: a wave takes PEAK_STAGE_ROWS consecutive rows of the tile plus halo at a time, a lane the words lane
-        // and (the tail of 2 rw words) lane + 64 of each; all loads of the batch are issued before the first is used
+        // stage with zeros outside the volume and where keep == 0; a word is the value and, with keep, its flag
         const int64_t gx0 = tx0 - a.rw + lane, gx1 = gx0 + 64;
         const bool x0_in = gx0 >= 0 && gx0 < a.W, x1_in = lane < 2 * a.rw && gx1 < a.W;
-        for (int row0 = wave * PEAK_STAGE_ROWS; row0 < LD * LH; row0 += PEAK_THREADS / 64 * PEAK_STAGE_ROWS) {
-            float v0[PEAK_STAGE_ROWS], v1[PEAK_STAGE_ROWS];
-            uint8_t k0[PEAK_STAGE_ROWS], k1[PEAK_STAGE_ROWS];
-#pragma unroll
-            for (int r = 0; r < PEAK_STAGE_ROWS; ++r) {
-                const int row = row0 + r;
-                const int64_t gz = tz0 - a.r0 + row / LH, gy = ty0 - a.r1 + row % LH;
-                const bool row_in = row < LD * LH && gz >= 0 && gz < a.D && gy >= 0 && gy < a.H;
-                const int64_t at = gz * plane + gy * a.W;
-                v0[r] = row_in && x0_in ? vol[base + at + gx0] : 0.0f;
-                v1[r] = row_in && x1_in ? vol[base + at + gx1] : 0.0f;
-                if (KEEP) {
-                    k0[r] = row_in && x0_in ? keep[at + gx0] : 0;
-                    k1[r] = row_in && x1_in ? keep[at + gx1] : 0;
+        struct Word { float v; uint8_t k; };
+        halo_stage<Word>(
+            f, 2 * a.rw,
+            [&](int row, Word& w0, Word& w1) {
+                const int64_t gz = tz0 - a.r0 + row / f.LH, gy = f.ty0 - a.r1 + row % f.LH;
+                const bool row_in = (row < f.LD * f.LH) & (gz >= 0) & (gz < a.D) & (gy >= 0) & (gy < a.H);
+                const int64_t at = gz * f.plane + gy * a.W;
+                if (KEEP) {                                   // one test per word covers the value and its flag
+                    w0 = w1 = Word{0.0f, 0};
+                    if (row_in & x0_in) {
+                        w0.v = vol[base + at + gx0];
+                        w0.k = keep[at + gx0];
+                    }
+                    if (row_in & x1_in) {
+                        w1.v = vol[base + at + gx1];
+                        w1.k = keep[at + gx1];
+                    }
+                } else {
+                    w0.v = row_in && x0_in ? vol[base + at + gx0] : 0.0f;
+                    w1.v = row_in && x1_in ? vol[base + at + gx1] : 0.0f;
                 }
-            }
-#pragma unroll
-            for (int r = 0; r < PEAK_STAGE_ROWS; ++r) {
-                const int row = row0 + r;
-                if (row >= LD * LH) break;
+            },
+            [&](int at, const Word& w) {
                 // with keep a select, not a product: an unkept NaN does not get in
-                sx[row * LW + lane] = !KEEP || k0[r] ? v0[r] : 0.0f;
-                if (KEEP) sk[row * LW + lane] = k0[r] ? 1 : 0;
-                if (lane < 2 * a.rw) {
-                    sx[row * LW + 64 + lane] = !KEEP || k1[r] ? v1[r] : 0.0f;
-                    if (KEEP) sk[row * LW + 64 + lane] = k1[r] ? 1 : 0;
-                }
-            }
-        }
+                sx[at] = !KEEP || w.k ? w.v : 0.0f;
+                if (KEEP) sk[at] = w.k ? 1 : 0;
+            });
         __syncthreads();
 
         // the whole footprint of every voxel of the tile lies inside the volume: n is the tap count
         const bool inner = tz0 >= a.r0 && a.D - tz0 >= TD + a.r0 && ty0 >= a.r1 && a.H - ty0 >= a.TH + a.r1 &&
-                           tx0 >= a.rw && a.W - tx0 >= PEAK_TW + a.rw;
-        for (int oy = wave; oy < a.TH; oy += PEAK_THREADS / 64) {
+                           tx0 >= a.rw && a.W - tx0 >= HALO_TW + a.rw;
+        for (int oy = wave; oy < a.TH; oy += HALO_THREADS / 64) {
             const int64_t y = ty0 + oy;
             if (y >= a.H) break;                              // the same for all lanes of the wave
             float acc[TD];
@@ -161,49 +144,20 @@ __global__ __launch_bounds__(PEAK_THREADS) void sphere_mean_kernel(const float* 
     }
 }
 
+HaloPick peak_tile(int r0, int r1, int rw, bool keep) {
+    return halo_pick(PEAK_TILES, PEAK_LDS_FOUR, PEAK_LDS_STATIC,
+                     [=](int TD, int TH) { return peak_lds_bytes(TD, TH, r0, r1, rw, keep); });
+}
+
+template <bool KEEP, int TD>
+constexpr auto peak_launch = halo_launch<sphere_mean_kernel<KEEP, TD>, const float*, const uint8_t*, float*, PeakArgs>;
 template <bool KEEP>
-hipError_t peak_launch(const float* vol, const uint8_t* keep, float* out, const PeakArgs& a, dim3 grid, size_t lds_bytes,
-                       hipStream_t st) {
-    void (*fn)(const float*, const uint8_t*, float*, const PeakArgs) =
-        a.TD == 8 ? sphere_mean_kernel<KEEP, 8> : a.TD == 4 ? sphere_mean_kernel<KEEP, 4>
-        : a.TD == 2 ? sphere_mean_kernel<KEEP, 2> : sphere_mean_kernel<KEEP, 1>;
-    if (lds_bytes + PEAK_LDS_STATIC > PEAK_LDS_PLAIN) {
-        // raise this instantiation's limit to all a CU has, once per device (bit d of the mask), not per launch
-        static std::atomic<unsigned long long> raised[4];
-        std::atomic<unsigned long long>& mask = raised[a.TD == 8 ? 0 : a.TD == 4 ? 1 : a.TD == 2 ? 2 : 3];
-        int device = 0;
-        hipError_t e = hipGetDevice(&device);
-        if (e != hipSuccess) return e;
-        const unsigned long long bit = device < 64 ? 1ull << device : 0;   // beyond 64 devices: set it every time
-        if (!(mask.load(std::memory_order_acquire) & bit)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(PEAK_LDS_ALL - PEAK_LDS_STATIC));
-            if (e != hipSuccess) return e;
-            mask.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    hipLaunchKernelGGL(fn, grid, dim3(PEAK_THREADS), lds_bytes, st, vol, keep, out, a);
-    return hipGetLastError();
+constexpr auto peak_launch_td(int TD) {
+    return TD == 8 ? peak_launch<KEEP, 8> : TD == 4 ? peak_launch<KEEP, 4> : TD == 2 ? peak_launch<KEEP, 2>
+                                                                                       : peak_launch<KEEP, 1>;
 }
 
 }  // namespace
-
-void ddpm3d_sphere_mean_tile(int r0, int r1, int rw, bool keep, int* TD, int* TH, size_t* lds_bytes) {
-    const size_t budgets[2] = {PEAK_LDS_FOUR, PEAK_LDS_ALL};
-    for (size_t budget : budgets) {
-        for (const auto& t : PEAK_TILES) {
-            const size_t need = peak_lds_bytes(t[0], t[1], r0, r1, rw, keep);
-            if (need + PEAK_LDS_STATIC <= budget) {
-                *TD = t[0];
-                *TH = t[1];
-                *lds_bytes = need;
-                return;
-            }
-        }
-    }
-    *TD = *TH = 0;                                            // not reached for radii within DDPM3D_PEAK_MAX_RADIUS
-    *lds_bytes = 0;
-}
 
 hipError_t ddpm3d_launch_sphere_mean(const float* vol, const uint8_t* keep, int B, int D, int H, int W, int r0, int r1,
                                      const int32_t* half_w, float* out, hipStream_t st) {
@@ -217,13 +171,9 @@ hipError_t ddpm3d_launch_sphere_mean(const float* vol, const uint8_t* keep, int 
         a.taps += 2 * w + 1;
     }
     for (int i = a.n_rows; i < PEAK_SIDE * PEAK_SIDE; ++i) a.rows[i] = 0;
-    size_t lds_bytes = 0;
-    ddpm3d_sphere_mean_tile(r0, r1, a.rw, keep != nullptr, &a.TD, &a.TH, &lds_bytes);
-    if (lds_bytes == 0) return hipErrorInvalidValue;
-    // H * W <= 2^31 - 1, so the x extent fits; the y extent is capped and the kernel strides over the tiles along D
-    const int64_t tiles_hw = (((int64_t)W + PEAK_TW - 1) / PEAK_TW) * (((int64_t)H + a.TH - 1) / a.TH);
-    const int tiles_d = (int)(((int64_t)D + a.TD - 1) / a.TD);
-    const dim3 grid((unsigned)tiles_hw, (unsigned)(tiles_d < 65535 ? tiles_d : 65535), (unsigned)B);
-    return keep ? peak_launch<true>(vol, keep, out, a, grid, lds_bytes, st)
-                : peak_launch<false>(vol, keep, out, a, grid, lds_bytes, st);
+    const HaloPick tile = peak_tile(r0, r1, a.rw, keep != nullptr);
+    if (tile.lds_bytes == 0) return hipErrorInvalidValue;    // not reached for radii within DDPM3D_PEAK_MAX_RADIUS
+    a.TD = tile.TD, a.TH = tile.TH;
+    const auto launch = keep ? peak_launch_td<true>(a.TD) : peak_launch_td<false>(a.TD);
+    return launch(halo_grid(B, D, H, W, a.TD, a.TH), tile.lds_bytes, PEAK_LDS_STATIC, st, vol, keep, out, a);
 }
