@@ -2,9 +2,10 @@
 // (unet.py:1015-1044, :1687-1694; ResBlock :236-256; AttentionBlock :296-305; Downsample / Upsample
 // :102-105, :129-136) compiled ONCE per (model, N, D, H, W) into a flat list of this library's own per-op
 // calls -- every buffer carved out of ONE caller-provided device arena -- and replayed by
-// ddpm3d_unet_forward.  The same plan the Python host builds (guided_diffusion/engine.py: _Plan), for
-// hosts that are not Python: same calls, same arguments, same order, hence bit-identical results
-// (tests/test_gpu_model.py::test_native_plan_equals_python_plan).  Host code only: no kernel lives here.
+// ddpm3d_unet_forward.  This is the only planner: the Python host (guided_diffusion/engine.py: _Plan) reads the
+// list with ddpm3d_unet_plan_steps and issues the same calls itself, launch by launch -- same calls, same
+// arguments, same order, hence bit-identical results (tests/test_gpu_plan_golden.py).  Host code only: no
+// kernel lives here.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -26,43 +27,37 @@ struct Act {                 // an NDHWC activation of the plan, with the GroupN
     long long voxels() const { return (long long)D * H * W; }
 };
 
-enum StepKind { S_CONV, S_FINALIZE, S_ABSMAX, S_PAD, S_POOL, S_ATTN };
-
-struct Step {
-    int kind;
-    ddpm3d_conv_desc conv;                       // S_CONV
-    ddpm3d_conv_skip skip; bool has_skip;        // S_CONV: the ResBlock tail as one ddpm3d_conv3d_skip call
-    // S_FINALIZE
-    size_t st0, st1; int C0, rows0, C1, rows1; double count; const float *gamma, *beta; int film, film_off;
-    size_t A, B, bound; bool has_ab;
-    // S_ABSMAX / S_PAD (input edge; x pointer patched per call)
-    size_t per_sample; int two; size_t dst; int C, Cpad, vox;
-    // S_POOL
-    size_t src, pA, pB; int act, D, H, W, io;
-    // S_ATTN
-    size_t qkv, qb; int T, heads, ch, prec; bool has_qb;
+struct Step {                // one call of the list: its public record, and the descriptors a conv record points at
+    ddpm3d_plan_step rec;
+    ddpm3d_conv_desc conv;
+    ddpm3d_conv_skip skip;
 };
+
+Step new_step(int kind) {
+    Step st;
+    memset(&st, 0, sizeof(st));
+    st.rec.kind = kind;
+    return st;
+}
 
 struct Planner {
     const ddpm3d_unet_desc& m;
     int N, D, H, W;
-    char* base;                                   // arena (NULL while sizing)
-    size_t top = 0;
+    char* base;                                   // arena (never dereferenced here)
+    size_t end;                                   // its size, rounded down to 256 (while sizing: far away)
+    size_t top = 0, tail = 0;                     // bytes used at the front / at the end
     std::map<std::pair<size_t, int>, std::vector<size_t>> pool;   // (bytes, esize) -> free activation buffers
     std::vector<Step> steps;
-    std::vector<int> film_steps, bias_steps;      // finalize steps / conv steps whose film pointer is per call
-    std::vector<int> bias_offs;
     std::vector<int> ws_steps;                    // conv steps that use the shared split-K workspace
     size_t ws_bytes = 0, ws_off = 0;
-    int first_step = -1, last_step = -1, absmax_step = -1, pad_step = -1;
     size_t in_absmax = 0;
     int half_esize;                               // 2 in the f16 / bf16 modes
     bool scaled, f16;
     char err[256] = "";
     int code = DDPM3D_EINVAL;                     // what a failed build returns (DDPM3D_E2BIG: split the batch)
 
-    Planner(const ddpm3d_unet_desc& d, int n, int dd, int hh, int ww, char* b)
-        : m(d), N(n), D(dd), H(hh), W(ww), base(b) {
+    Planner(const ddpm3d_unet_desc& d, int n, int dd, int hh, int ww, char* b, size_t arena_bytes)
+        : m(d), N(n), D(dd), H(hh), W(ww), base(b), end(arena_bytes & ~(size_t)255) {
         half_esize = (m.arithmetic == DDPM3D_PREC_F16 || m.arithmetic == DDPM3D_PREC_BF16) ? 2 : 4;
         f16 = m.arithmetic == DDPM3D_PREC_F16;
         scaled = m.arithmetic == DDPM3D_PREC_F16X3 || m.arithmetic == DDPM3D_PREC_F16;
@@ -74,11 +69,22 @@ struct Planner {
         va_end(ap);
         return false;
     }
-    size_t alloc(size_t bytes) {                  // 256-byte aligned bump allocation
-        const size_t o = (top + 255) & ~(size_t)255;
+    // Two bump regions in one arena.  Activations and the split-K workspace grow from the front at page (4 KiB)
+    // alignment: the conv kernels run measurably slower on activations that start inside a page (published network,
+    // bf16, 1x64^3: 7.17 against 7.14 ms per forward) -- what one allocation per tensor gave
+    // the Python planner for free.  Their sizes are multiples of a page at every level that matters, so this costs
+    // no padding there.  The many small buffers (statistics rows, GroupNorm coefficients, bounds) are packed at 256
+    // bytes from the end downwards, so that they never push an activation off its page boundary.
+    size_t alloc_act(size_t bytes) {
+        const size_t o = (top + 4095) & ~(size_t)4095;
         top = o + bytes;
         return o;
     }
+    size_t alloc(size_t bytes) {
+        tail += (bytes + 255) & ~(size_t)255;
+        return end - tail;
+    }
+    size_t need() const { return ((top + 255) & ~(size_t)255) + tail; }
     void* at(size_t off) const { return base + off; }
 
     Act new_act(int C, int d, int h, int w, bool fp32 = false) {
@@ -88,7 +94,7 @@ struct Planner {
         const size_t b = a.bytes(N);
         auto& fr = pool[{b, a.esize}];
         if (!fr.empty()) { a.off = fr.back(); fr.pop_back(); }
-        else a.off = alloc(b);
+        else a.off = alloc_act(b);
         return a;
     }
     void release(const Act& a) { pool[{a.bytes(N), a.esize}].push_back(a.off); }
@@ -100,21 +106,23 @@ struct Planner {
         if (!gamma && !(scaled || force_bound)) return true;
         if (s1 && s1->voxels() != s0->voxels()) return fail("concat of tensors with different spatial size");
         const int Cn = s0->C + (s1 ? s1->C : 0);
-        Step st;
-        memset(&st, 0, sizeof(st));
-        st.kind = S_FINALIZE;
-        st.st0 = s0->stats_off; st.C0 = s0->C; st.rows0 = s0->rows;
-        st.st1 = s1 ? s1->stats_off : 0; st.C1 = s1 ? s1->C : 0; st.rows1 = s1 ? s1->rows : 0;
-        st.count = (double)s0->voxels();
-        st.gamma = gamma; st.beta = beta;
-        st.has_ab = gamma != nullptr;
-        if (gamma) { st.A = alloc((size_t)N * Cn * 4); st.B = alloc((size_t)N * Cn * 4); }
-        st.bound = alloc((size_t)N * 32 * 2 * 4);
-        st.film = film_off >= 0;
-        st.film_off = film_off >= 0 ? film_off : 0;
-        if (st.film) film_steps.push_back((int)steps.size());
+        Step st = new_step(DDPM3D_STEP_FINALIZE);
+        ddpm3d_plan_step& r = st.rec;
+        r.in[0] = at(s0->stats_off); r.n[0] = s0->C; r.n[1] = s0->rows;
+        if (s1) { r.in[1] = at(s1->stats_off); r.n[2] = s1->C; r.n[3] = s1->rows; }
+        r.n[4] = N; r.n[5] = 32;
+        r.count = (double)s0->voxels(); r.eps = 1e-5f;
+        r.in[2] = gamma; r.in[3] = beta;
+        *A = *B = 0;
+        if (gamma) {
+            *A = alloc((size_t)N * Cn * 4); *B = alloc((size_t)N * Cn * 4);
+            r.out[0] = at(*A); r.out[1] = at(*B);
+        }
+        *bound = alloc((size_t)N * 32 * 2 * 4);
+        r.out[2] = at(*bound);
+        if (film_off >= 0) { r.flags = DDPM3D_STEP_FILM; r.film_off = film_off; }
         steps.push_back(st);
-        *A = st.A; *B = st.B; *bound = st.bound; *has = true;
+        *has = true;
         return true;
     }
 
@@ -136,7 +144,7 @@ struct Planner {
         size_t xbound = 0; int xbound_first = 0; bool has_xbound = false;
         bool* fused = nullptr;
     };
-    bool conv_step(const ddpm3d_conv_weights& pc, ConvArgs a, int* step_index = nullptr) {
+    bool conv_step(const ddpm3d_conv_weights& pc, ConvArgs a) {
         ddpm3d_conv_desc d;
         memset(&d, 0, sizeof(d));
         const bool wz = pc.w_packed_wz && !a.planar && (a.in_mode == DDPM3D_IN_SAME || a.in_mode == DDPM3D_IN_UP);
@@ -209,14 +217,13 @@ struct Planner {
             d.stats_rows = rows;
         }
         if (need) { ws_steps.push_back((int)steps.size()); if (need > ws_bytes) ws_bytes = need; }
-        Step st;
-        memset(&st, 0, sizeof(st));
-        st.kind = S_CONV;
+        // (rec.conv / rec.skip are set once the list has stopped growing: ddpm3d_unet_plan_create)
+        Step st = new_step(DDPM3D_STEP_CONV);
         st.conv = d;
-        st.skip = sk;
-        st.has_skip = a.skip_w != nullptr;
-        if (a.bias_per_n) { bias_steps.push_back((int)steps.size()); bias_offs.push_back(a.film_off); }
-        if (step_index) *step_index = (int)steps.size();
+        st.skip = sk;                              // all zero where the step is a plain ddpm3d_conv3d call
+        st.rec.flags = (a.planar ? DDPM3D_STEP_X | DDPM3D_STEP_LOW_RES : 0) | (a.ncdhw_out ? DDPM3D_STEP_OUT : 0) |
+                       (a.bias_per_n ? DDPM3D_STEP_FILM_BIAS : 0);
+        st.rec.film_off = a.bias_per_n ? a.film_off : 0;
         steps.push_back(st);
         return true;
     }
@@ -240,12 +247,12 @@ struct Planner {
         if (e.updown == DDPM3D_UPDOWN_DOWN && e.conv1.w_packed_wz && !s1) {
             // h_upd(in_rest(x)) as a pass of its own: conv1 then reads a plain tensor and runs its Winograd-D form
             pooled = new_act(s0->C, d, h, w, true);
-            Step st;
-            memset(&st, 0, sizeof(st));
-            st.kind = S_POOL;
-            st.src = s0->off; st.pA = A1; st.pB = B1; st.act = DDPM3D_ACT_SILU;
-            st.D = d; st.H = h; st.W = w; st.C = s0->C; st.dst = pooled.off;
-            st.io = (s0->esize == 2 ? DDPM3D_IO_SRC0_BF16 : 0) | ((s0->esize == 2 && f16) ? DDPM3D_IO_HALF_IS_F16 : 0);
+            Step st = new_step(DDPM3D_STEP_POOL_ACT);
+            ddpm3d_plan_step& r = st.rec;
+            r.in[0] = at(s0->off); r.in[1] = at(A1); r.in[2] = at(B1);
+            r.n[0] = DDPM3D_ACT_SILU; r.n[1] = 1; r.n[2] = N; r.n[3] = d; r.n[4] = h; r.n[5] = w; r.n[6] = s0->C;
+            r.out[0] = at(pooled.off);
+            r.n[7] = (s0->esize == 2 ? DDPM3D_IO_SRC0_BF16 : 0) | ((s0->esize == 2 && f16) ? DDPM3D_IO_HALF_IS_F16 : 0);
             steps.push_back(st);
             c1.src0 = &pooled; c1.aff = false; c1.act = DDPM3D_ACT_NONE; c1.in_mode = DDPM3D_IN_SAME;
             use_pooled = true;
@@ -312,12 +319,13 @@ struct Planner {
         size_t qA, qB, qb; bool hasq;
         if (!finalize(&qkv, nullptr, nullptr, nullptr, -1, m.arithmetic != DDPM3D_PREC_F32, &qA, &qB, &qb, &hasq)) return false;
         Act a = new_act(Cn, x->D, x->H, x->W, true);
-        Step st;
-        memset(&st, 0, sizeof(st));
-        st.kind = S_ATTN;
-        st.qkv = qkv.off; st.T = (int)x->voxels(); st.heads = e.heads; st.ch = ch;
-        st.prec = m.arithmetic == DDPM3D_PREC_F32 ? DDPM3D_PREC_F32 : DDPM3D_PREC_F16X3;
-        st.qb = qb; st.has_qb = hasq; st.dst = a.off;
+        Step st = new_step(DDPM3D_STEP_ATTENTION);
+        ddpm3d_plan_step& r = st.rec;
+        r.in[0] = at(qkv.off); r.n[0] = N; r.n[1] = x->voxels(); r.n[2] = e.heads; r.n[3] = ch;
+        r.n[4] = m.arithmetic == DDPM3D_PREC_F32 ? DDPM3D_PREC_F32 : DDPM3D_PREC_F16X3;
+        if (hasq) r.in[1] = (const float*)at(qb) + 1;
+        r.n[5] = 32; r.n[6] = 2;
+        r.out[0] = at(a.off);
         steps.push_back(st);
         release(qkv);
         Act y = new_act(Cn, x->D, x->H, x->W);
@@ -356,33 +364,45 @@ struct Planner {
         return fail("unknown layer kind %d", e.kind);
     }
 
+    // range of the network input (it carries no statistics): max |x| [, max |low_res|] per sample
+    void absmax_step(size_t per_sample, int flags) {
+        Step st = new_step(DDPM3D_STEP_ABSMAX);
+        st.rec.flags = flags;
+        st.rec.n[0] = N; st.rec.n[1] = (int64_t)per_sample;
+        st.rec.out[0] = at(in_absmax);
+        if (scaled) steps.push_back(st);
+    }
+
     bool build() {
+        // the block tables are what the loops below index `layers` and the skip stack with: refuse a table that
+        // does not cover exactly n_layers, or that pops more skips than the encoder pushes, before any indexing
+        long long covered = m.n_middle_layers;
+        bool tables = m.n_input_blocks >= 0 && m.n_middle_layers >= 0 && m.n_output_blocks >= 0;
+        for (int b = 0; tables && b < m.n_input_blocks; ++b) { tables = m.input_block_layers[b] >= 0; covered += m.input_block_layers[b]; }
+        for (int b = 0; tables && b < m.n_output_blocks; ++b) { tables = m.output_block_layers[b] >= 0; covered += m.output_block_layers[b]; }
+        if (!tables || covered != m.n_layers) return fail("the block sizes cover %lld of %d layers", covered, m.n_layers);
+        if (m.n_output_blocks > m.n_input_blocks + 1)
+            return fail("%d output blocks for %d input blocks: nothing left on the skip stack", m.n_output_blocks, m.n_input_blocks + 1);
         Act h = new_act(m.first.Cout, D, H, W);
         Act xin;
         if (m.planar) {
             in_absmax = alloc((size_t)N * 2 * 4);
-            Step st;
-            memset(&st, 0, sizeof(st));
-            st.kind = S_ABSMAX; st.per_sample = (size_t)D * H * W; st.two = 1; st.dst = in_absmax;
-            if (scaled) { absmax_step = (int)steps.size(); steps.push_back(st); }
+            absmax_step((size_t)D * H * W, DDPM3D_STEP_X | DDPM3D_STEP_LOW_RES);
             ConvArgs c;
             c.out = &h; c.planar = true; c.bound = in_absmax; c.bound_count = 2; c.bound_stride = 1; c.has_bound = true;
-            if (!conv_step(m.first, c, &first_step)) return false;
+            if (!conv_step(m.first, c)) return false;
         } else {
             xin = new_act(m.cin_pad, D, H, W, true);
             in_absmax = alloc((size_t)N * 4);
-            Step st;
-            memset(&st, 0, sizeof(st));
-            st.kind = S_ABSMAX; st.per_sample = (size_t)m.in_channels * D * H * W; st.two = 0; st.dst = in_absmax;
-            if (scaled) { absmax_step = (int)steps.size(); steps.push_back(st); }
-            Step sp;
-            memset(&sp, 0, sizeof(sp));
-            sp.kind = S_PAD; sp.C = m.in_channels; sp.Cpad = m.cin_pad; sp.vox = D * H * W; sp.dst = xin.off;
-            pad_step = (int)steps.size();
+            absmax_step((size_t)m.in_channels * D * H * W, DDPM3D_STEP_X);
+            Step sp = new_step(DDPM3D_STEP_PAD);
+            sp.rec.flags = DDPM3D_STEP_X;
+            sp.rec.n[0] = N; sp.rec.n[1] = m.in_channels; sp.rec.n[2] = D * H * W; sp.rec.n[3] = m.cin_pad;
+            sp.rec.out[0] = at(xin.off);
             steps.push_back(sp);
             ConvArgs c;
             c.src0 = &xin; c.out = &h; c.bound = in_absmax; c.bound_count = 1; c.bound_stride = 1; c.has_bound = true;
-            if (!conv_step(m.first, c, &first_step)) return false;
+            if (!conv_step(m.first, c)) return false;
         }
         std::vector<Act> hs;
         hs.push_back(h);
@@ -408,20 +428,20 @@ struct Planner {
             for (int i = 0; i < m.output_block_layers[b]; ++i) {
                 if (!layer(m.layers[li++], &s0, two ? &s1 : nullptr, &h)) return false;
                 release(s0);
-                if (two) release(s1);
+                // (without a middle block the first output block reads ONE tensor as input and as skip)
+                if (two && s1.off != s0.off) release(s1);
                 s0 = h;
                 two = false;
             }
         }
-        if (li != m.n_layers) return fail("the block sizes cover %d of %d layers", li, m.n_layers);
         size_t A, B, bnd; bool has;
         if (!finalize(&h, nullptr, m.out_gamma, m.out_beta, -1, false, &A, &B, &bnd, &has)) return false;
         ConvArgs c;
         c.src0 = &h; c.A = A; c.B = B; c.aff = true; c.act = DDPM3D_ACT_SILU; c.ncdhw_out = true; c.want_stats = false;
         c.bound = bnd; c.bound_count = 32; c.bound_stride = 2; c.has_bound = has;
-        if (!conv_step(m.out, c, &last_step)) return false;
+        if (!conv_step(m.out, c)) return false;
         release(h);
-        if (ws_bytes) ws_off = alloc(ws_bytes);
+        if (ws_bytes) ws_off = alloc_act(ws_bytes);
         for (int i : ws_steps) { steps[i].conv.workspace = at(ws_off); steps[i].conv.workspace_bytes = ws_bytes; }
         return true;
     }
@@ -432,11 +452,8 @@ thread_local char g_unet_err[256] = "";
 }  // namespace
 
 struct ddpm3d_unet_plan {
-    std::vector<Step> steps;
-    std::vector<int> film_steps, bias_steps, bias_offs;
-    int first_step, last_step, absmax_step, pad_step;
-    int N, planar, out_channels;
-    char* base;
+    std::vector<Step> steps;     // never resized: the conv records point into it
+    int planar;
 };
 
 extern "C" {
@@ -455,9 +472,9 @@ size_t ddpm3d_unet_plan_bytes(const ddpm3d_unet_desc* m, int N, int D, int H, in
     if (!desc_ok(m, N, D, H, W)) { snprintf(g_unet_err, sizeof(g_unet_err), "unet_plan_bytes: bad description"); return 0; }
     // sizing pass: the same planning against a base that is never dereferenced (non-null, so that the per-op
     // validation sees what it will see at run time)
-    Planner p(*m, N, D, H, W, reinterpret_cast<char*>(4096));
+    Planner p(*m, N, D, H, W, reinterpret_cast<char*>(4096), (size_t)1 << 46);
     if (!p.build()) { snprintf(g_unet_err, sizeof(g_unet_err), "%s", p.err); return 0; }
-    return (p.top + 255) & ~(size_t)255;
+    return p.need();
 }
 
 int ddpm3d_unet_plan_create(const ddpm3d_unet_desc* m, int N, int D, int H, int W, void* arena, size_t arena_bytes,
@@ -466,26 +483,64 @@ int ddpm3d_unet_plan_create(const ddpm3d_unet_desc* m, int N, int D, int H, int 
         snprintf(g_unet_err, sizeof(g_unet_err), "unet_plan_create: bad description, or an arena that is not 256-byte aligned");
         return DDPM3D_EINVAL;
     }
-    Planner p(*m, N, D, H, W, static_cast<char*>(arena));
-    if (!p.build()) { snprintf(g_unet_err, sizeof(g_unet_err), "%s", p.err); return p.code; }
-    if (p.top > arena_bytes) {
-        snprintf(g_unet_err, sizeof(g_unet_err), "unet_plan_create: the plan needs %zu bytes, the arena has %zu", p.top, arena_bytes);
+    // (the small buffers are carved from the arena's end: size the plan before any address is formed)
+    const size_t need = ddpm3d_unet_plan_bytes(m, N, D, H, W);
+    if (need > arena_bytes) {
+        snprintf(g_unet_err, sizeof(g_unet_err), "unet_plan_create: the plan needs %zu bytes, the arena has %zu", need, arena_bytes);
         return DDPM3D_EINVAL;
     }
+    Planner p(*m, N, D, H, W, static_cast<char*>(arena), arena_bytes);
+    if (!p.build()) { snprintf(g_unet_err, sizeof(g_unet_err), "%s", p.err); return p.code; }
     ddpm3d_unet_plan* pl = new (std::nothrow) ddpm3d_unet_plan();
     if (!pl) return DDPM3D_EINVAL;
     pl->steps.swap(p.steps);
-    pl->film_steps.swap(p.film_steps);
-    pl->bias_steps.swap(p.bias_steps);
-    pl->bias_offs.swap(p.bias_offs);
-    pl->first_step = p.first_step; pl->last_step = p.last_step; pl->absmax_step = p.absmax_step; pl->pad_step = p.pad_step;
-    pl->N = N; pl->planar = m->planar; pl->out_channels = m->out.Cout;
-    pl->base = static_cast<char*>(arena);
+    for (Step& s : pl->steps)
+        if (s.rec.kind == DDPM3D_STEP_CONV) { s.rec.conv = &s.conv; s.rec.skip = s.skip.w_packed ? &s.skip : nullptr; }
+    pl->planar = m->planar;
     *plan = pl;
     return DDPM3D_OK;
 }
 
 void ddpm3d_unet_plan_destroy(ddpm3d_unet_plan* plan) { delete plan; }
+
+int ddpm3d_unet_plan_steps(ddpm3d_unet_plan* pl, ddpm3d_plan_step* out, int capacity) {
+    if (!pl) { snprintf(g_unet_err, sizeof(g_unet_err), "unet_plan_steps: no plan"); return DDPM3D_EINVAL; }
+    const int n = (int)pl->steps.size();
+    for (int i = 0; out && i < n && i < capacity; ++i) out[i] = pl->steps[i].rec;
+    return n;
+}
+
+// one call of the list, with what belongs to this forward patched in (ddpm3d.h: DDPM3D_STEP_* flags)
+static int issue(const ddpm3d_plan_step& s, const float* x, const float* low_res, const float* film_rows, int film_stride,
+                 float* out, void* stream) {
+    const bool film = s.flags & DDPM3D_STEP_FILM;
+    const float* lr = (s.flags & DDPM3D_STEP_LOW_RES) ? low_res : nullptr;
+    switch (s.kind) {
+        case DDPM3D_STEP_CONV: {
+            ddpm3d_conv_desc& d = *s.conv;
+            if (s.flags & DDPM3D_STEP_X) d.src0 = x;
+            if (s.flags & DDPM3D_STEP_LOW_RES) d.src1 = low_res;
+            if (s.flags & DDPM3D_STEP_OUT) d.out = out;
+            if (s.flags & DDPM3D_STEP_FILM_BIAS) { d.bias = film_rows + s.film_off; d.bias_stride_n = film_stride; }
+            return s.skip ? ddpm3d_conv3d_skip(&d, s.skip, stream) : ddpm3d_conv3d(&d, stream);
+        }
+        case DDPM3D_STEP_FINALIZE:
+            return ddpm3d_gn_finalize((const double*)s.in[0], (int)s.n[0], (int)s.n[1], (const double*)s.in[1], (int)s.n[2],
+                                      (int)s.n[3], (int)s.n[4], (int)s.n[5], s.count, s.eps, (const float*)s.in[2],
+                                      (const float*)s.in[3], film ? film_rows : nullptr, film ? film_stride : 0, s.film_off,
+                                      (float*)s.out[0], (float*)s.out[1], (float*)s.out[2], stream);
+        case DDPM3D_STEP_ABSMAX: return ddpm3d_absmax(x, lr, (int)s.n[0], (size_t)s.n[1], (float*)s.out[0], stream);
+        case DDPM3D_STEP_PAD:
+            return ddpm3d_ncdhw_to_ndhwc_pad(x, (int)s.n[0], (int)s.n[1], (int)s.n[2], (int)s.n[3], (float*)s.out[0], stream);
+        case DDPM3D_STEP_POOL_ACT:
+            return ddpm3d_pool_act(s.in[0], (const float*)s.in[1], (const float*)s.in[2], (int)s.n[0], (int)s.n[1], (int)s.n[2],
+                                   (int)s.n[3], (int)s.n[4], (int)s.n[5], (int)s.n[6], s.out[0], (int)s.n[7], stream);
+        case DDPM3D_STEP_ATTENTION:
+            return ddpm3d_attention_p((const float*)s.in[0], (int)s.n[0], (int)s.n[1], (int)s.n[2], (int)s.n[3], (int)s.n[4],
+                                      (const float*)s.in[1], (int)s.n[5], (int)s.n[6], (float*)s.out[0], stream);
+    }
+    return DDPM3D_EINVAL;
+}
 
 int ddpm3d_unet_forward(ddpm3d_unet_plan* pl, const float* x, const float* low_res, const float* film_rows,
                         int film_stride, float* out, void* stream) {
@@ -493,43 +548,8 @@ int ddpm3d_unet_forward(ddpm3d_unet_plan* pl, const float* x, const float* low_r
         snprintf(g_unet_err, sizeof(g_unet_err), "unet_forward: null argument");
         return DDPM3D_EINVAL;
     }
-    char* b = pl->base;
-    if (pl->planar) {
-        pl->steps[pl->first_step].conv.src0 = x;
-        pl->steps[pl->first_step].conv.src1 = low_res;
-    }
-    for (size_t i = 0; i < pl->bias_steps.size(); ++i) {
-        ddpm3d_conv_desc& d = pl->steps[pl->bias_steps[i]].conv;
-        d.bias = film_rows + pl->bias_offs[i];
-        d.bias_stride_n = film_stride;
-    }
-    pl->steps[pl->last_step].conv.out = out;
     for (const Step& s : pl->steps) {
-        int rc = DDPM3D_OK;
-        switch (s.kind) {
-            case S_CONV:
-                rc = s.has_skip ? ddpm3d_conv3d_skip(&s.conv, &s.skip, stream) : ddpm3d_conv3d(&s.conv, stream);
-                break;
-            case S_FINALIZE:
-                rc = ddpm3d_gn_finalize((const double*)(b + s.st0), s.C0, s.rows0, s.C1 ? (const double*)(b + s.st1) : nullptr,
-                                        s.C1, s.rows1, pl->N, 32, s.count, 1e-5f, s.gamma, s.beta,
-                                        s.film ? film_rows : nullptr, s.film ? film_stride : 0, s.film_off,
-                                        s.has_ab ? (float*)(b + s.A) : nullptr, s.has_ab ? (float*)(b + s.B) : nullptr,
-                                        (float*)(b + s.bound), stream);
-                break;
-            case S_ABSMAX:
-                rc = ddpm3d_absmax(x, s.two ? low_res : nullptr, pl->N, s.per_sample, (float*)(b + s.dst), stream);
-                break;
-            case S_PAD: rc = ddpm3d_ncdhw_to_ndhwc_pad(x, pl->N, s.C, s.vox, s.Cpad, (float*)(b + s.dst), stream); break;
-            case S_POOL:
-                rc = ddpm3d_pool_act(b + s.src, (const float*)(b + s.pA), (const float*)(b + s.pB), s.act, 1, pl->N, s.D, s.H,
-                                     s.W, s.C, b + s.dst, s.io, stream);
-                break;
-            case S_ATTN:
-                rc = ddpm3d_attention_p((const float*)(b + s.qkv), pl->N, s.T, s.heads, s.ch, s.prec,
-                                        s.has_qb ? (const float*)(b + s.qb) + 1 : nullptr, 32, 2, (float*)(b + s.dst), stream);
-                break;
-        }
+        const int rc = issue(s.rec, x, low_res, film_rows, film_stride, out, stream);
         if (rc != DDPM3D_OK) {
             snprintf(g_unet_err, sizeof(g_unet_err), "unet_forward: %s", ddpm3d_last_error());
             return rc;

@@ -94,6 +94,18 @@ class UnetDesc(C.Structure):
                 ("arithmetic", C.c_int32)]
 
 
+STEP_CONV, STEP_FINALIZE, STEP_ABSMAX, STEP_PAD, STEP_POOL_ACT, STEP_ATTENTION = range(6)
+# ddpm3d_plan_step.flags: the arguments that belong to the forward call, not to the plan
+STEP_X, STEP_LOW_RES, STEP_OUT, STEP_FILM, STEP_FILM_BIAS = 1, 2, 4, 8, 16
+
+
+class PlanStep(C.Structure):
+    """struct ddpm3d_plan_step: one call of a plan's launch list (ddpm3d_unet_plan_steps)"""
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("film_off", C.c_int32), ("reserved", C.c_int32),
+                ("conv", _fp), ("skip", _fp), ("in_", _fp * 4), ("out", _fp * 3), ("n", C.c_int64 * 8),
+                ("count", C.c_double), ("eps", C.c_float)]
+
+
 # DDPM3D_EM_*: columns of a ddpm3d_error_moments record
 (EM_N, EM_SUM_E, EM_SUM_ABS_E, EM_SUM_SQ_E, EM_SUM_Y, EM_SUM_SQ_Y, EM_MIN_Y, EM_MAX_Y, EM_COVER_1, EM_COVER_2,
  EM_REC) = range(11)
@@ -177,6 +189,7 @@ EXPORTS = {
                                           C.POINTER(_fp)]),
     "ddpm3d_unet_forward": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     "ddpm3d_unet_plan_destroy": (None, [_fp]),
+    "ddpm3d_unet_plan_steps": (C.c_int, [_fp, C.POINTER(PlanStep), C.c_int]),
     "ddpm3d_unet_last_error": (C.c_char_p, []),
     "ddpm3d_gn_finalize": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_double, C.c_float, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),

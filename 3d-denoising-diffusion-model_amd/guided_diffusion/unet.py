@@ -236,8 +236,8 @@ class UNetModel_noatt(nn.Module):
         # replay one captured hipGraph per forward instead of ~230 launches issued from Python (engine.py:
         # _Plan._replay); same kernels and arguments, bit-identical results.  DDPM3D_STEP_GRAPH=0/1 overrides.
         self.step_graph = os.environ.get("DDPM3D_STEP_GRAPH", "0") == "1"
-        # run on the C-level launch plan (ddpm3d_unet_plan_create / ddpm3d_unet_forward) instead of engine.py's
-        # Python one: the same calls in the same order, bit-identical.  DDPM3D_NATIVE_PLAN=0/1 overrides.
+        # let the library replay its launch plan (ddpm3d_unet_forward) instead of issuing the plan's launches from
+        # engine.py: the same calls in the same order, bit-identical.  DDPM3D_NATIVE_PLAN=0/1 overrides.
         self.native_plan = os.environ.get("DDPM3D_NATIVE_PLAN", "0") == "1"
 
     # ---- precision switches (unet.py:999-1013) -------------------------------
@@ -279,12 +279,15 @@ class UNetModel_noatt(nn.Module):
             with torch.cuda.device(p0.device):
                 self._engine = UNetEngine(self.topology, params, self.model_channels,
                                           self.use_scale_shift_norm, p0.device, self.conv_precision,
-                                          in_channels=self.in_channels, planar=self._planar(),
-                                          winograd=self.dims == 3, step_graph=self.step_graph)
+                                          step_graph=self.step_graph, **self.engine_args())
             self._engine_key = key
         self._engine.step_graph = self.step_graph
         self._engine.native_plan = self.native_plan
         return self._engine
+
+    def engine_args(self):
+        """what of the model's construction shapes its engine (and the library's description of it)"""
+        return dict(in_channels=self.in_channels, planar=self._planar(), winograd=self.dims == 3)
 
     PLANAR_INPUT = False   # SuperRes models: the first conv reads x and low_res as two planes
 

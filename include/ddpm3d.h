@@ -299,9 +299,10 @@ int ddpm3d_conv_skip_fused(const ddpm3d_conv_desc* conv2, const ddpm3d_conv_skip
  * A UNet forward -- UNetModel[_noatt] / SuperResModel[_noatt].forward, unet.py:1015-1044, :687-716, :1687-1694;
  * ResBlock :236-256, AttentionBlock :296-305, Downsample / Upsample :102-105, :129-136, TimestepEmbedSequential
  * :72-78 -- compiled ONCE per (model, N, D, H, W) into a flat list of the per-op calls of this header, every
- * intermediate buffer carved out of ONE caller-provided device arena, and replayed by ddpm3d_unet_forward: what the
- * Python host's launch plan (guided_diffusion/engine.py) does, for hosts that are not Python.  Same calls, same
- * arguments, same order: bit-identical to the Python plan.  The timestep path (timestep_embedding, time_embed, the
+ * intermediate buffer carved out of ONE caller-provided device arena.  This is the only planner; the list has two
+ * replayers.  ddpm3d_unet_forward issues it in one call, for hosts that are not Python; the Python host
+ * (guided_diffusion/engine.py) reads it with ddpm3d_unet_plan_steps and issues the same calls one by one, so that it
+ * can time each.  Same calls, same arguments, same order: bit-identical.  The timestep path (timestep_embedding, time_embed, the
  * fused emb_layers Linear: "film rows") stays with the caller, who evaluates it for all steps of a schedule at once.
  *
  * The description borrows every pointer (packed weights, biases, GroupNorm parameters: device memory that must
@@ -354,7 +355,9 @@ typedef struct ddpm3d_unet_desc {
 typedef struct ddpm3d_unet_plan ddpm3d_unet_plan;
 /* bytes of device arena a plan of this model and shape needs (0 = refused: ddpm3d_unet_last_error) */
 size_t ddpm3d_unet_plan_bytes(const ddpm3d_unet_desc* model, int N, int D, int H, int W);
-/* arena: 256-byte aligned device memory of at least that size, owned by the caller, private to the plan */
+/* arena: 256-byte aligned device memory of at least that size, owned by the caller, private to the plan.  Activations
+ * sit at multiples of 4 KiB from its start (the convs run measurably faster on page-aligned tensors), so give it page
+ * alignment, as hipMalloc does; the small per-step buffers are packed from its end. */
 int ddpm3d_unet_plan_create(const ddpm3d_unet_desc* model, int N, int D, int H, int W, void* arena, size_t arena_bytes,
                             ddpm3d_unet_plan** plan);
 /* x (and low_res when planar): (N, 1 or in_channels, D, H, W) fp32; film_rows: row n at film_rows + n * film_stride
@@ -364,6 +367,45 @@ int ddpm3d_unet_forward(ddpm3d_unet_plan* plan, const float* x, const float* low
                         int film_stride, float* out, void* stream);
 void ddpm3d_unet_plan_destroy(ddpm3d_unet_plan* plan);
 const char* ddpm3d_unet_last_error(void);
+
+/* A created plan's launch list, one record per call, for a host that replays the calls itself (to time or to
+ * instrument them).  A record holds every argument of the per-op entry it stands for, device pointers resolved into
+ * the arena: pointers the call reads in `in`, pointers it writes in `out`, integers in `n`, each in the entry's own
+ * argument order --
+ *   CONV       ddpm3d_conv3d(conv, stream), or ddpm3d_conv3d_skip(conv, skip, stream) where skip != NULL; both point
+ *              at the plan's own descriptors, which live as long as the plan
+ *   FINALIZE   ddpm3d_gn_finalize(in[0], n[0], n[1], in[1], n[2], n[3], n[4], n[5], count, eps, in[2], in[3],
+ *                                 film, film_stride, film_off, out[0], out[1], out[2], stream)
+ *   ABSMAX     ddpm3d_absmax(x, low_res or NULL, n[0], n[1], out[0], stream)
+ *   PAD        ddpm3d_ncdhw_to_ndhwc_pad(x, n[0], n[1], n[2], n[3], out[0], stream)
+ *   POOL_ACT   ddpm3d_pool_act(in[0], in[1], in[2], n[0], n[1], n[2], n[3], n[4], n[5], n[6], out[0], n[7], stream)
+ *   ATTENTION  ddpm3d_attention_p(in[0], n[0], n[1], n[2], n[3], n[4], in[1], n[5], n[6], out[0], stream)
+ * -- and `flags` says which arguments belong to the forward call rather than to the plan: */
+enum { DDPM3D_STEP_CONV = 0, DDPM3D_STEP_FINALIZE = 1, DDPM3D_STEP_ABSMAX = 2, DDPM3D_STEP_PAD = 3,
+       DDPM3D_STEP_POOL_ACT = 4, DDPM3D_STEP_ATTENTION = 5 };
+enum {
+    DDPM3D_STEP_X = 1,          /* reads the call's x: conv->src0 (planar first conv), x of ABSMAX / PAD            */
+    DDPM3D_STEP_LOW_RES = 2,    /* reads the call's low_res: conv->src1, ABSMAX's second tensor                     */
+    DDPM3D_STEP_OUT = 4,        /* the last conv: conv->out = the call's out                                        */
+    DDPM3D_STEP_FILM = 8,       /* FINALIZE with film = the call's film_rows, film_stride                           */
+    DDPM3D_STEP_FILM_BIAS = 16  /* conv->bias = film_rows + film_off, conv->bias_stride_n = film_stride             */
+};
+typedef struct ddpm3d_plan_step {
+    int32_t kind;               /* DDPM3D_STEP_CONV ...                                                             */
+    int32_t flags;
+    int32_t film_off;
+    int32_t reserved;
+    ddpm3d_conv_desc* conv;
+    const ddpm3d_conv_skip* skip;
+    const void* in[4];
+    void* out[3];
+    int64_t n[8];
+    double count;
+    float eps;
+} ddpm3d_plan_step;
+/* Copies the first min(count, capacity) records to `out` and returns the count (out == NULL: only counts);
+ * negative = no plan.  ddpm3d_unet_forward issues exactly these calls in this order. */
+int ddpm3d_unet_plan_steps(ddpm3d_unet_plan* plan, ddpm3d_plan_step* out, int capacity);
 
 /*
  * GroupNorm32 statistics -> affine coefficients (nn.py:93-100: 32 groups,

@@ -156,6 +156,15 @@ def test_sampler_loop_f16x3_vs_reference_golden(golden):
     assert rel_err(out.cpu().numpy(), golden("sampler.npz")["ddpm10_32/sample"]) < 1e-3
 
 
+def _residual_stream_io(plan):
+    """io_dtype of every conv step of a plan that writes the residual stream: an NDHWC tensor that convs read (the
+    tiny network has no attention, so that is every conv but the last, which stores the NCDHW output)"""
+    import guided_diffusion._hip as H
+    convs = [a[0]._obj for fn, a in plan.steps if fn.__name__ in ("ddpm3d_conv3d", "ddpm3d_conv3d_skip")]
+    assert convs[-1].out_layout == H.OUT_NCDHW and not convs[-1].io_dtype & H.IO_OUT_BF16
+    return [d.io_dtype for d in convs[:-1]]
+
+
 def test_convert_to_fp16_ddim_psnr(golden):
     """BASELINE config 4 shape of run (DDIM respaced sampler, half-precision conv operands) on the
     tiny net: model.convert_to_fp16() as scripts/test.py:33-34 calls it.  Judged by PSNR against
@@ -172,10 +181,16 @@ def test_convert_to_fp16_ddim_psnr(golden):
     psnr = 10 * np.log10(4.0 / mse)            # data range [-1, 1]
     assert psnr > 35.0, psnr
     # the torso's tensors are STORED in f16 too, as the reference's --use_fp16 does (unet.py:1035)
+    import guided_diffusion._hip as H
     plan = model.engine().plan(*[shape[0]] + list(shape[2:]))
-    assert plan.half_dtype == torch.float16 and any(b.dtype == torch.float16 for b in plan.keep
-                                                    if isinstance(b, torch.Tensor))
-    assert set(model.state_dict()) == set(build(TINY)[0].state_dict())   # parameters stay fp32 / same keys
+    stream = _residual_stream_io(plan)
+    assert plan.half_dtype == torch.float16 and stream
+    assert all(io & H.IO_OUT_BF16 and io & H.IO_HALF_IS_F16 for io in stream)
+    # (the f16x3 plan of the same network stores nothing in 16 bits)
+    plain = build(TINY)[0]
+    stream32 = _residual_stream_io(plain.engine().plan(*[shape[0]] + list(shape[2:])))
+    assert stream32 and not any(io & (H.IO_OUT_BF16 | H.IO_HALF_IS_F16) for io in stream32)
+    assert set(model.state_dict()) == set(plain.state_dict())   # parameters stay fp32 / same keys
     assert all(v.dtype == torch.float32 for v in model.state_dict().values())
 
 
@@ -199,8 +214,11 @@ def test_bf16_mode_ddim_psnr(golden):
     assert psnr > 30.0, psnr            # measured 35.7 dB
     assert all(v.dtype == torch.float32 for v in model.state_dict().values())
     # the plan really stores the residual stream in bf16
+    import guided_diffusion._hip as H
     plan = next(iter(model.engine().plans.values()))
-    assert plan.half_dtype == torch.bfloat16 and any(b.dtype == torch.bfloat16 for b in plan.keep if isinstance(b, torch.Tensor))
+    stream = _residual_stream_io(plan)
+    assert plan.half_dtype == torch.bfloat16 and stream
+    assert all(io & H.IO_OUT_BF16 and not io & H.IO_HALF_IS_F16 for io in stream)
 
 
 def test_p_sample_loop_api_and_determinism():
@@ -475,9 +493,10 @@ def test_step_graph_replay_equals_eager_launches():
     ("published f16", None, (1, 1, 8, 32, 32), [251], "f16"),
 ])
 def test_native_plan_equals_python_plan(tag, over, shape, t, precision):
-    """The whole-network level of the C ABI (ddpm3d_unet_plan_create / ddpm3d_unet_forward: libddpm3d compiles the
-    launch list itself, into one caller-provided arena -- SURVEY 8b's `unet_forward(handle, ...)`) against the
-    Python host's plan of the same model: the same per-op calls in the same order, so the outputs are BITWISE
+    """The planner and its two replayers: the whole-network level of the C ABI (ddpm3d_unet_plan_create /
+    ddpm3d_unet_forward: libddpm3d compiles the launch list into one caller-provided arena and replays it -- SURVEY
+    8b's `unet_forward(handle, ...)`) against the Python host's launch-by-launch replay of the list of the same
+    model: the same per-op calls in the same order, so the outputs are BITWISE
     equal, per architecture variant and arithmetic; also through the sampler's fast path (one film row shared
     by the batch), with the step graph on top, and for a second shape of the same model."""
     model, diff = build(PUBLISHED if over is None else dict(TINY, **over), "10", precision=precision)
@@ -514,7 +533,7 @@ def test_native_plan_equals_python_plan(tag, over, shape, t, precision):
 
 def test_native_plan_runs_the_2d_network_and_refuses_bad_arenas():
     """create_model_and_diffusion's 2-D RGB network (ordinary multi-channel input, padded at the edge) through the
-    C-level plan, bitwise equal to the Python plan; and the C entry points refuse a NULL / undersized arena."""
+    library's replay, bitwise equal to the Python replay; and the C entry points refuse a NULL / undersized arena."""
     import ctypes as C
     import guided_diffusion._hip as H
     from guided_diffusion import script_util as su

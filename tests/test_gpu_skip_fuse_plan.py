@@ -1,8 +1,8 @@
 """
-Routing of ddpm3d_conv3d_skip by the two planners, on the published network in the f16x3 mode: the Python plan
-(engine.py) and the native one (csrc/unet_plan.hip) run the tail of every ResBlock with a 1x1 skip conv as ONE step
-wherever the library takes its fused form (ddpm3d_conv_skip_fused) and as the two shipped steps elsewhere, so their
-forwards stay bitwise equal; DDPM3D_SKIP_FUSE=0 restores the two-step list in both.  The fused and the two-step
+Routing of ddpm3d_conv3d_skip by the planner and its two replayers, on the published network in the f16x3 mode: the
+plan (csrc/unet_plan.hip), replayed from Python (engine.py) and by the library, runs the tail of every ResBlock with a
+1x1 skip conv as ONE step wherever the library takes its fused form (ddpm3d_conv_skip_fused) and as the two shipped
+steps elsewhere, and the two forwards are bitwise equal; DDPM3D_SKIP_FUSE=0 restores the two-step list.  The fused and the two-step
 forwards differ in rounding only: by at most twice the two-step forward's own distance from the exact-f32 forward of
 the same inputs.
 """
@@ -102,7 +102,7 @@ def test_both_planners_fuse_where_the_library_does_and_the_override_restores(run
     for n, _ in steps:
         expand += ["ddpm3d_conv3d", "ddpm3d_conv3d"] if n == "ddpm3d_conv3d_skip" else [n]
     assert [n for n, _ in steps0] == expand
-    # ---- the two planners agree bit for bit under either routing; the routings differ in rounding only
+    # ---- the two replayers agree bit for bit under either routing; the routings differ in rounding only
     assert torch.isfinite(r["py"]).all()
     assert torch.equal(r["py"], r["nat"]) and torch.equal(r["py0"], r["nat0"])
     assert not torch.equal(r["py"], r["py0"])

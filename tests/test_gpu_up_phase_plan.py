@@ -1,7 +1,7 @@
 """
-Routing of the phase form (DDPM3D_HINT_UP_PHASE) by the two planners: the Python plan (engine.py) and the native one
-(csrc/unet_plan.hip) give conv1 of every up-ResBlock -- and nothing else -- the phase image and the hint, so their
-forwards stay bitwise equal; DDPM3D_UP_PHASE=0 restores the 36-tap routing in both.
+Routing of the phase form (DDPM3D_HINT_UP_PHASE) by the planner and its two replayers: the plan (csrc/unet_plan.hip),
+replayed from Python (engine.py) and by the library, gives conv1 of every up-ResBlock -- and nothing else -- the phase
+image and the hint, and the two forwards are bitwise equal; DDPM3D_UP_PHASE=0 restores the 36-tap routing.
 """
 
 import ctypes as C

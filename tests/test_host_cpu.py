@@ -287,7 +287,7 @@ def test_integration_doc_binds_the_current_abi():
 
 
 def test_unet_desc_struct_layouts_match_the_header():
-    """The ctypes mirrors of ddpm3d_conv_weights / ddpm3d_layer / ddpm3d_unet_desc have the field order, sizes and
+    """The ctypes mirrors of ddpm3d_conv_weights / ddpm3d_layer / ddpm3d_unet_desc / ddpm3d_plan_step have the field order, sizes and
     offsets a C compiler gives the header's structs (checked against a tiny C program compiled here with gcc)."""
     import subprocess
     import tempfile
@@ -304,6 +304,10 @@ int main(void) {
     printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(ddpm3d_unet_desc), offsetof(ddpm3d_unet_desc, layers),
            offsetof(ddpm3d_unet_desc, input_block_layers), offsetof(ddpm3d_unet_desc, output_block_layers),
            offsetof(ddpm3d_unet_desc, first), offsetof(ddpm3d_unet_desc, out), offsetof(ddpm3d_unet_desc, arithmetic));
+    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(ddpm3d_plan_step), offsetof(ddpm3d_plan_step, flags),
+           offsetof(ddpm3d_plan_step, film_off), offsetof(ddpm3d_plan_step, reserved), offsetof(ddpm3d_plan_step, conv),
+           offsetof(ddpm3d_plan_step, skip), offsetof(ddpm3d_plan_step, in), offsetof(ddpm3d_plan_step, out),
+           offsetof(ddpm3d_plan_step, n), offsetof(ddpm3d_plan_step, count), offsetof(ddpm3d_plan_step, eps));
     return 0;
 }
 """
@@ -321,6 +325,10 @@ int main(void) {
     assert [int(v) for v in out[2].split()] == [ctypes.sizeof(U), U.layers.offset, U.input_block_layers.offset,
                                                 U.output_block_layers.offset, U.first.offset, U.out.offset,
                                                 U.arithmetic.offset]
+    S = _hip.PlanStep
+    assert [int(v) for v in out[3].split()] == [ctypes.sizeof(S), S.flags.offset, S.film_off.offset, S.reserved.offset,
+                                                S.conv.offset, S.skip.offset, S.in_.offset, S.out.offset, S.n.offset,
+                                                S.count.offset, S.eps.offset]
 
 
 def test_no_wide_store_is_followed_by_a_write_of_its_data_registers():
