@@ -4,7 +4,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
-#include "conv3d_params.h"
+#include "conv3d_select.h"
 #include "ddpm3d.h"
 #include "ops.h"
 #include "noise.h"
@@ -81,10 +81,9 @@ size_t ddpm3d_conv_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout
     return ddpm3d_conv_cfg(N, D, H, W, Cin, Cout, ksize, precision).workspace_bytes;
 }
 
-// Validation and routing shared by ddpm3d_conv3d and ddpm3d_conv_kernel_family: fills the launch record and
-// says which kernel takes the call.
-enum { ROUTE_GENERAL = 0, ROUTE_SKINNY = 1, ROUTE_PW = 2 };
-static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& route, bool for_launch) {
+// Validation shared by ddpm3d_conv3d and the queries: the checks in their order, the launch record, and -- from
+// ddpm3d_conv_select, which alone decides it -- the kernel instance that takes the call.  skip_cx: conv3d_select.h.
+static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, ConvSel& s, bool for_launch, int skip_cx = 0) {
     if (!d) return fail(DDPM3D_EINVAL, "conv3d: null descriptor");
     if (d->N <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0 || d->Cin <= 0)
         return fail(DDPM3D_EINVAL, "conv3d: non-positive shape N=%d D=%d H=%d W=%d Cin=%d Cout=%d", d->N, d->D,
@@ -148,24 +147,20 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
     k.CinPad = ddpm3d_cin_pad(d->Cin); k.CoutPad = ddpm3d_cout_pad(d->Cout);
     k.in_mode = d->in_mode; k.act = d->act; k.bias_stride_n = d->bias_stride_n;
     k.res_mode = d->res_mode; k.out_layout = d->out_layout;
-    k.tilesZ = c.tilesZ; k.tilesY = c.tilesY; k.tilesX = c.tilesX;
     k.stats_rows = c.stats_rows;
     k.reduce_vox = c.reduce_vox;
-    k.hint = d->kernel_hint;
     // DDPM3D_HINT_UP_PHASE: w_packed is the phase image; the phase form where the low-resolution grid tiles like the
     // output grid, else the shipped path on the Winograd-D image the buffer starts with (hint bit dropped)
-    bool phase = false;
-    if (d->kernel_hint & DDPM3D_HINT_UP_PHASE) {
-        if (d->precision != DDPM3D_PREC_F16X3_WZ || d->in_mode != DDPM3D_IN_UP)
-            return fail(DDPM3D_EINVAL, "conv3d: DDPM3D_HINT_UP_PHASE needs precision F16X3_WZ and in_mode UP");
-        UpPhaseGeom g;
-        phase = ddpm3d_up_phase_geom(d->D, d->H, d->W, c, g) && d->res_mode != DDPM3D_RES_POOL;
-        if (!phase) k.hint &= ~DDPM3D_HINT_UP_PHASE;
-    }
+    if ((d->kernel_hint & DDPM3D_HINT_UP_PHASE) && (d->precision != DDPM3D_PREC_F16X3_WZ || d->in_mode != DDPM3D_IN_UP))
+        return fail(DDPM3D_EINVAL, "conv3d: DDPM3D_HINT_UP_PHASE needs precision F16X3_WZ and in_mode UP");
+    s = ddpm3d_conv_select(*d, c, skip_cx);
+    k.tilesZ = s.tilesZ; k.tilesY = s.tilesY; k.tilesX = s.tilesX;
+    k.hint = s.hint;
     // the image this call reads: the phase image behind the Winograd-D one, else the buffer's (first) image
-    const PackedImage front = ddpm3d_packed_image(d->Cout, d->Cin, d->ksize, d->precision);
-    const PackedImage img = phase ? ddpm3d_up_phase_image(d->Cout, d->Cin) : front;
-    k.w = (const float*)((const char*)d->w_packed + (phase ? front.bytes() : (size_t)0));
+    const bool phase = s.kernel == CONV_WZ && s.variant == WZV_UP;
+    const PackedImage img = phase ? ddpm3d_up_phase_image(d->Cout, d->Cin)
+                                  : ddpm3d_packed_image(d->Cout, d->Cin, d->ksize, d->precision);
+    k.w = (const float*)((const char*)d->w_packed + s.w_offset);
     k.io = d->io_dtype;
     if (d->io_dtype & ~(DDPM3D_IO_SRC0_BF16 | DDPM3D_IO_SRC1_BF16 | DDPM3D_IO_OUT_BF16 | DDPM3D_IO_RES_BF16 |
                         DDPM3D_IO_HALF_IS_F16))
@@ -213,29 +208,19 @@ static int conv_prepare(const ddpm3d_conv_desc* d, ConvK& k, ConvCfg& c, int& ro
     if (d->stats && !aligned16(d->stats)) return fail(DDPM3D_EINVAL, "conv3d: stats must be 16-byte aligned");
     if (d->stats && d->out_layout != DDPM3D_OUT_NDHWC)
         return fail(DDPM3D_EINVAL, "conv3d: statistics only with NDHWC output");
-    const long long blocks = (long long)k.N * k.tilesZ * k.tilesY * k.tilesX;
+    const long long blocks = (long long)k.N * c.tilesZ * c.tilesY * c.tilesX;    // (the tiles the shape rule counted)
     if (blocks > 0x7fffffffLL) return fail(DDPM3D_EINVAL, "conv3d: grid too large");
-    // one or two output channels (the network's last layer): its own kernel (conv3d_skinny.hip)
-    if (d->ksize == 3 && d->Cout <= 2 && d->in_mode == DDPM3D_IN_SAME && d->C1 == 0 && !d->stats &&
-        d->res_mode == DDPM3D_RES_NONE &&
-        ddpm3d_skinny_ok(k.CinPad, d->precision, !(d->io_dtype & DDPM3D_IO_SRC0_BF16) ? 0
-                                                  : ((d->io_dtype & DDPM3D_IO_HALF_IS_F16) ? 2 : 1)))
-        route = ROUTE_SKINNY;
-    else
-        route = ddpm3d_pw_ok(k, c, d->ksize) ? ROUTE_PW : ROUTE_GENERAL;
     return DDPM3D_OK;
 }
 
 int ddpm3d_conv3d(const ddpm3d_conv_desc* d, void* stream) {
     ConvK k;
     ConvCfg c;
-    int route = ROUTE_GENERAL;
-    const int ok = conv_prepare(d, k, c, route, true);
+    ConvSel s;
+    const int ok = conv_prepare(d, k, c, s, true);
     if (ok != DDPM3D_OK) return ok;
-    if (route == ROUTE_SKINNY)
-        return launched(ddpm3d_launch_conv_skinny(k, d->precision, (hipStream_t)stream), "conv3d (skinny)");
-    const int rc = route == ROUTE_PW ? launched(ddpm3d_launch_conv_pw(k, c, (hipStream_t)stream), "conv3d (1x1)")
-                                     : launched(ddpm3d_launch_conv(k, c, (hipStream_t)stream), "conv3d");
+    const int rc = launched(ddpm3d_launch_conv(k, s, (hipStream_t)stream),
+                            s.kernel == CONV_SKINNY ? "conv3d (skinny)" : s.kernel == CONV_PW ? "conv3d (1x1)" : "conv3d");
     if (rc != DDPM3D_OK || c.S == 1) return rc;
     return launched(ddpm3d_launch_splitk_reduce(k, (hipStream_t)stream), "conv3d split-K reduce");
 }
@@ -248,7 +233,7 @@ static int base_prec(int p) {
          : p == DDPM3D_PREC_BF16_WZ ? DDPM3D_PREC_BF16 : p;
 }
 static int skip_prepare(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk, ddpm3d_conv_desc& sd, ConvK& k, ConvCfg& c,
-                        bool& fused, bool for_launch) {
+                        ConvSel& s, bool& fused, bool for_launch) {
     fused = false;
     if (!d || !sk) return fail(DDPM3D_EINVAL, "conv3d_skip: null descriptor");
     if (d->res_mode != DDPM3D_RES_NONE || d->res)
@@ -272,18 +257,19 @@ static int skip_prepare(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk, d
     sd.io_dtype = sk->io_dtype | (d->io_dtype & (DDPM3D_IO_OUT_BF16 | DDPM3D_IO_HALF_IS_F16));
     ConvK ks;
     ConvCfg cs;
-    int route_s = ROUTE_GENERAL, route = ROUTE_GENERAL;
-    int ok = conv_prepare(&sd, ks, cs, route_s, false);
+    ConvSel ss;
+    int ok = conv_prepare(&sd, ks, cs, ss, false);
     if (ok != DDPM3D_OK) return ok;
     if (for_launch && (!sk->src0 || !sk->w_packed || !sk->bias)) return fail(DDPM3D_EINVAL, "conv3d_skip: null buffer");
-    // the fused form: f16x3 Winograd-D conv2 on a plain fp32 input, the default issue order; a skip conv that conv1x1.hip
-    // would take (whole 32-channel blocks), fp32 tensors throughout; and the level is one the measured rule admits
+    // the fused form exists for: f16x3 Winograd-D conv2 on a plain fp32 input, the default issue order; a skip conv that
+    // conv1x1.hip would take (whole 32-channel blocks), fp32 tensors throughout.  Whether such a pair runs it is
+    // ddpm3d_conv_select's decision (the measured rule)
     const int cand = d->precision == DDPM3D_PREC_F16X3_WZ && d->in_mode == DDPM3D_IN_SAME && d->io_dtype == 0 &&
                      sk->io_dtype == 0 && !(d->kernel_hint & (DDPM3D_HINT_UP_PHASE | DDPM3D_HINT_WZ_ORDER_MASK)) &&
-                     route_s == ROUTE_PW && aligned16(sk->bias);
-    ok = conv_prepare(d, k, c, route, for_launch && cand);
+                     ss.kernel == CONV_PW && aligned16(sk->bias);
+    ok = conv_prepare(d, k, c, s, for_launch && cand, cand ? sd.Cin : 0);
     if (ok != DDPM3D_OK) return ok;
-    fused = cand && route == ROUTE_GENERAL && ddpm3d_skip_fuse_rule(d->N, d->D, d->H, d->W, sd.Cin, d->Cout, c);
+    fused = s.kernel == CONV_WZ && s.variant == WZV_SKIP;
     if (!fused) return DDPM3D_OK;
     k.sk_src0 = sk->src0; k.sk_src1 = sk->src1; k.sk_C0 = sk->C0; k.sk_C1 = sk->C1;
     k.sk_src0_bytes = ks.src0_bytes; k.sk_src1_bytes = ks.src1_bytes;
@@ -298,11 +284,12 @@ int ddpm3d_conv3d_skip(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk, vo
     ddpm3d_conv_desc sd;
     ConvK k;
     ConvCfg c;
+    ConvSel s;
     bool fused = false;
-    const int ok = skip_prepare(d, sk, sd, k, c, fused, true);
+    const int ok = skip_prepare(d, sk, sd, k, c, s, fused, true);
     if (ok != DDPM3D_OK) return ok;
     if (fused) {
-        const int rc = launched(ddpm3d_launch_conv(k, c, (hipStream_t)stream), "conv3d_skip");
+        const int rc = launched(ddpm3d_launch_conv(k, s, (hipStream_t)stream), "conv3d_skip");
         if (rc != DDPM3D_OK || c.S == 1) return rc;
         return launched(ddpm3d_launch_splitk_reduce(k, (hipStream_t)stream), "conv3d_skip split-K reduce");
     }
@@ -320,15 +307,16 @@ int ddpm3d_conv_skip_fused(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk
     ddpm3d_conv_desc sd;
     ConvK k;
     ConvCfg c;
+    ConvSel s;
     bool fused = false;
-    return skip_prepare(d, sk, sd, k, c, fused, false) == DDPM3D_OK && fused ? 1 : 0;
+    return skip_prepare(d, sk, sd, k, c, s, fused, false) == DDPM3D_OK && fused ? 1 : 0;
 }
 
 int ddpm3d_conv_plan(const ddpm3d_conv_desc* d, int* stats_rows, size_t* workspace_bytes, int* split) {
     ConvK k;
     ConvCfg c;
-    int route = ROUTE_GENERAL;
-    const int ok = conv_prepare(d, k, c, route, false);
+    ConvSel s;
+    const int ok = conv_prepare(d, k, c, s, false);
     if (ok != DDPM3D_OK) return ok;
     if (stats_rows) *stats_rows = c.stats_rows;
     if (workspace_bytes) *workspace_bytes = c.workspace_bytes;
@@ -340,15 +328,38 @@ int ddpm3d_conv_kernel_family(const ddpm3d_conv_desc* d, char* name, int name_le
     if (!name || name_len <= 0) return fail(DDPM3D_EINVAL, "conv_kernel_family: no buffer");
     ConvK k;
     ConvCfg c;
-    int route = ROUTE_GENERAL;
-    const int ok = conv_prepare(d, k, c, route, false);   // (the split-K workspace may be attached later)
+    ConvSel s;
+    const int ok = conv_prepare(d, k, c, s, false);   // (the split-K workspace may be attached later)
     if (ok != DDPM3D_OK) return ok;
     const int tile = 1 << c.TXL;    // 8: 8x8x2 / 8x4x4 tiles, 4: 4x4x8
     int n;
-    if (route == ROUTE_SKINNY) n = snprintf(name, (size_t)name_len, "conv3d_p%d_k3_skinny", d->precision);
-    else if (route == ROUTE_PW) n = snprintf(name, (size_t)name_len, "conv1x1_p%d_t%d", d->precision, tile);
+    if (s.kernel == CONV_SKINNY) n = snprintf(name, (size_t)name_len, "conv3d_p%d_k3_skinny", d->precision);
+    else if (s.kernel == CONV_PW) n = snprintf(name, (size_t)name_len, "conv1x1_p%d_t%d", d->precision, tile);
     else n = snprintf(name, (size_t)name_len, "conv3d_p%d_k%d_wn%d_t%d", d->precision, d->ksize, c.WN, tile);
     if (n < 0 || n >= name_len) return fail(DDPM3D_EINVAL, "conv_kernel_family: buffer of %d bytes is too short", name_len);
+    return DDPM3D_OK;
+}
+
+int ddpm3d_conv_kernel_instance(const ddpm3d_conv_desc* d, const ddpm3d_conv_skip* sk, char* name, int name_len) {
+    if (!name || name_len <= 0) return fail(DDPM3D_EINVAL, "conv_kernel_instance: no buffer");
+    ddpm3d_conv_desc sd;
+    ConvK k;
+    ConvCfg c;
+    ConvSel s;
+    bool fused = false;
+    int ok = sk ? skip_prepare(d, sk, sd, k, c, s, fused, false) : conv_prepare(d, k, c, s, false);
+    if (ok == DDPM3D_OK && sk && !fused) {
+        // two calls: conv2 as the entry issues it, with the 1x1 conv's output as its residual
+        static const float unattached = 0.0f;
+        ddpm3d_conv_desc d2 = *d;
+        d2.res = d->out ? d->out : &unattached;
+        d2.res_mode = DDPM3D_RES_SAME;
+        if (d->io_dtype & DDPM3D_IO_OUT_BF16) d2.io_dtype |= DDPM3D_IO_RES_BF16;
+        ok = conv_prepare(&d2, k, c, s, false);
+    }
+    if (ok != DDPM3D_OK) return ok;
+    const int n = ddpm3d_conv_sel_name(s, name, (size_t)name_len);
+    if (n < 0 || n >= name_len) return fail(DDPM3D_EINVAL, "conv_kernel_instance: buffer of %d bytes is too short", name_len);
     return DDPM3D_OK;
 }
 

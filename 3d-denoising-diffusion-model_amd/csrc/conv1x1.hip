@@ -23,13 +23,14 @@
 //              never waits for a younger load than it needs
 //   epilogue   conv_epilogue (bias, residual, 16-bit stores, split-K slabs) per 32-cout accumulator
 //
-// Eligibility (ddpm3d_pw_ok, checked by the C ABI): ksize 1, input mode SAME, no affine / activation
+// Eligibility (ddpm3d_pw_ok, conv3d_select.h): ksize 1, input mode SAME, no affine / activation
 // prologue, no statistics, Cout % 128 == 0, Cin % 32 == 0 (and C0 % 32 == 0 for a concat), both sources
 // of one element width, precision F16X3 / F16 / BF16.  Everything else stays on conv3d.hip's form.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "conv3d_load.h"
 #include "conv3d_epilogue.h"
+#include "conv3d_select.h"   // ConvSel; DDPM3D_PW_WIDE: conv_epilogue's 16-byte store form
 
 namespace {
 
@@ -43,9 +44,6 @@ namespace {
 #endif
 #ifndef DDPM3D_PW_WGS
 #define DDPM3D_PW_WGS 2          // workgroups per CU the register budget is held to
-#endif
-#ifndef DDPM3D_PW_WIDE
-#define DDPM3D_PW_WIDE 1         // conv_epilogue's 16-byte store form
 #endif
 constexpr int pw_depth(int prec) { return prec == 1 ? DDPM3D_PW_DEPTH_X3 : DDPM3D_PW_DEPTH_ONE; }
 
@@ -270,28 +268,26 @@ __global__ __launch_bounds__(256, DDPM3D_PW_WGS) void conv3d_pw_kernel(const Con
 }
 
 template <int PREC, int S16, int TXL, int TYL>
-hipError_t pw_launch(const ConvK& k, hipStream_t st) {
+hipError_t pw_launch(const ConvK& k, const ConvSel& s, hipStream_t st) {
     constexpr int NP = PREC == 1 ? 2 : 1;
-    const int gx = k.N * k.tilesZ * k.tilesY * k.tilesX, gy = k.CoutPad / 128;
-    hipLaunchKernelGGL((conv3d_pw_kernel<PREC, S16, TXL, TYL, DDPM3D_PW_WIDE != 0>), dim3(gx, gy, k.ksplit), dim3(256),
-                       pw_depth(PREC) * 512 * NP * 16, st, k);
+    hipLaunchKernelGGL((conv3d_pw_kernel<PREC, S16, TXL, TYL, DDPM3D_PW_WIDE != 0>), dim3(s.grid[0], s.grid[1], s.grid[2]),
+                       dim3(256), pw_depth(PREC) * 512 * NP * 16, st, k);
     return hipGetLastError();
 }
 
 template <int PREC>
-hipError_t pw_launch_prec(const ConvK& k, const ConvCfg& c, hipStream_t st) {
-    const bool s16 = (k.io & DDPM3D_IO_SRC0_BF16) != 0;
-    if (c.TXL == 3) return s16 ? pw_launch<PREC, 1, 3, 3>(k, st) : pw_launch<PREC, 0, 3, 3>(k, st);
-    return s16 ? pw_launch<PREC, 1, 2, 2>(k, st) : pw_launch<PREC, 0, 2, 2>(k, st);
+hipError_t pw_launch_prec(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    if (s.TX == 8) return s.src16 ? pw_launch<PREC, 1, 3, 3>(k, s, st) : pw_launch<PREC, 0, 3, 3>(k, s, st);
+    return s.src16 ? pw_launch<PREC, 1, 2, 2>(k, s, st) : pw_launch<PREC, 0, 2, 2>(k, s, st);
 }
 
 }  // namespace
 
-hipError_t ddpm3d_launch_conv_pw(const ConvK& k, const ConvCfg& c, hipStream_t st) {
-    switch (c.PREC) {
-        case 1: return pw_launch_prec<1>(k, c, st);
-        case 2: return pw_launch_prec<2>(k, c, st);
-        case 5: return pw_launch_prec<5>(k, c, st);
+hipError_t ddpm3d_launch_conv_pw(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    switch (s.arith) {
+        case 1: return pw_launch_prec<1>(k, s, st);
+        case 2: return pw_launch_prec<2>(k, s, st);
+        case 5: return pw_launch_prec<5>(k, s, st);
     }
     return hipErrorInvalidValue;
 }

@@ -13,8 +13,9 @@
 //   split-K        blockIdx.z owns a range of the ci-chunks (low-res levels)
 //
 // This file: the direct form (all shapes and input modes), the split-K reduce and the
-// dispatcher.  The 3x3x3 layers that carry the network's FLOPs run the Winograd-along-depth
-// form instead (conv3d_wz.h, staging in conv3d_stage.h).
+// launchers.  The 3x3x3 layers that carry the network's FLOPs run the Winograd-along-depth
+// form instead (conv3d_wz.h, staging in conv3d_stage.h).  Which instance a call runs is decided in
+// conv3d_select.h: a launcher maps that record to the instantiation and does no shape arithmetic.
 //
 // Arithmetic modes (template PREC), same fp32 inputs, outputs and
 // accumulators:
@@ -36,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include "conv3d_load.h"
 #include "conv3d_epilogue.h"  // LdsGeom, conv_epilogue
+#include "conv3d_select.h"
 
 // PIPEM = 1: IN_SAME / IN_UP inputs, staging software-pipelined; 0: IN_POOL / IN_PLANAR2;
 // 2: IN_STRIDE2 (stride (1,2,2): the halo tile is laid out in the source grid, rows 2 voxels apart).
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(256, (PIPEM == 2 ? 1 : (TXL == 2 ? 2 : 3))) void co
 
 // This file is compiled once per arithmetic mode (-DDDPM3D_PREC_ONLY=0|1|2|5, and 3 = the
 // Winograd-D kernels of every mode; see the Makefile) so the instantiations build in parallel; the
-// mode-independent parts below (split-K reduction, dispatcher) live in the PREC 0 object only.
+// mode-independent parts below (split-K reduction, the launcher of all kernels) live in the PREC 0 object only.
 #ifndef DDPM3D_PREC_ONLY
 #error "compile with -DDDPM3D_PREC_ONLY=0, 1, 2, 3 or 5"
 #endif
@@ -463,21 +465,20 @@ hipError_t ddpm3d_launch_splitk_reduce(const ConvK& k, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t ddpm3d_launch_conv_p0(const ConvK& k, const ConvCfg& c, hipStream_t st);
-hipError_t ddpm3d_launch_conv_p1(const ConvK& k, const ConvCfg& c, hipStream_t st);
-hipError_t ddpm3d_launch_conv_p2(const ConvK& k, const ConvCfg& c, hipStream_t st);
-hipError_t ddpm3d_launch_conv_p5(const ConvK& k, const ConvCfg& c, hipStream_t st);
-hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvCfg& c, hipStream_t st);
+hipError_t ddpm3d_launch_conv_p0(const ConvK& k, const ConvSel& s, hipStream_t st);
+hipError_t ddpm3d_launch_conv_p1(const ConvK& k, const ConvSel& s, hipStream_t st);
+hipError_t ddpm3d_launch_conv_p2(const ConvK& k, const ConvSel& s, hipStream_t st);
+hipError_t ddpm3d_launch_conv_p5(const ConvK& k, const ConvSel& s, hipStream_t st);
 
-hipError_t ddpm3d_launch_conv(const ConvK& k, const ConvCfg& c, hipStream_t st) {
-    switch (c.PREC) {
-        case 0: return ddpm3d_launch_conv_p0(k, c, st);
-        case 1: return ddpm3d_launch_conv_p1(k, c, st);
-        case 2: return ddpm3d_launch_conv_p2(k, c, st);
-        case 3:
-        case 4:
-        case 6: return ddpm3d_launch_conv_wz(k, c, st);
-        case 5: return ddpm3d_launch_conv_p5(k, c, st);
+hipError_t ddpm3d_launch_conv(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    if (s.kernel == CONV_WZ) return ddpm3d_launch_conv_wz(k, s, st);
+    if (s.kernel == CONV_PW) return ddpm3d_launch_conv_pw(k, s, st);
+    if (s.kernel == CONV_SKINNY) return ddpm3d_launch_conv_skinny(k, s, st);
+    switch (s.arith) {      // the direct kernels, one object per arithmetic
+        case 0: return ddpm3d_launch_conv_p0(k, s, st);
+        case 1: return ddpm3d_launch_conv_p1(k, s, st);
+        case 2: return ddpm3d_launch_conv_p2(k, s, st);
+        case 5: return ddpm3d_launch_conv_p5(k, s, st);
     }
     return hipErrorInvalidValue;
 }
@@ -487,117 +488,47 @@ hipError_t ddpm3d_launch_conv(const ConvK& k, const ConvCfg& c, hipStream_t st) 
 // Winograd-D forms of the f16x3 / f16 / bf16 3x3x3 conv, an object of their own (conv3d_p3.o;
 // eligibility is checked by the C ABI)
 #include "conv3d_wz.h"
-#ifndef DDPM3D_WZ_T84
-#define DDPM3D_WZ_T84 1     // measurement builds: 0 = 8x8x2 tiles wherever 8x4x4 ones would be taken
-#endif
-hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvCfg& c, hipStream_t st) {
-    const int gy = k.CoutPad / 128;
-    const int gx = k.N * k.tilesZ * k.tilesY * k.tilesX;
+static_assert(WZ_F16X3 == 0 && WZ_F16 == 1 && WZ_BF16 == 2 && WZ_F16X3_UP == 2 + WZV_UP && WZ_F16X3_SKIP == 2 + WZV_SKIP, "ddpm3d_wz_mode");
+
+// One kernel, eighteen instantiations.  Measured and dropped in r02 (profiles/r02_layer_ab_*.txt,
+// r02_wzp_plane_pair_*.txt): a wave-specialised persistent form (compute waves + loader waves, tile
+// walk, epilogue hand-off through LDS); a 128-row wave tile with one wave per SIMD (plain, and with the staging
+// interleaved into the tap loop); a plane-pair form (8x8x4 tiles, two anti-phase halves of two transformed planes
+// each, half the L2 weight stream) -- 0-15 % behind this one or equal to it.
+// r03: the plane-pair form rebuilt for the one-MFMA modes (f16, bf16), where the L2 weight stream was suspected to be
+// the bound, at weight-ring depths 3 / 4 / 5 / 6 / 8, bit-identical: 15-30 % SLOWER than this form on
+// the 64^3 and 64x32x32 layers, equal below (profiles/r03_layer_ab_plane_pair_{bf16,f16}.txt) -- with a third of the
+// MFMAs its tap phase (72 MFMAs) is shorter than the other half's staging phase, so the anti-phase halves wait for
+// each other.  Not kept (the form is commit 8797410's conv3d_wzp.h with the weight-ring depth made a template
+// parameter).  Every instantiation is ~1 MB of code object to load at the first launch.
+template <int MODE, int IL, int TX, int TY>
+static hipError_t wz_launch(const ConvK& k, const ConvSel& s, hipStream_t st) {
 #ifdef DDPM3D_WZ_STAMPS
     constexpr size_t stamp_lds = 4 * WZ_NSTAMP * 8;     // measurement build: the stamps sit behind the image
 #else
     constexpr size_t stamp_lds = 0;
 #endif
-    constexpr size_t lds = (size_t)WzGeom::BUF + stamp_lds;
-    // One kernel form.  Measured and dropped in r02 (profiles/r02_layer_ab_*.txt, r02_wzp_plane_pair_*.txt,
-    // DESIGN.md 3.1b): a wave-specialised persistent form (compute waves + loader waves, tile walk,
-    // epilogue hand-off through LDS); a 128-row wave tile with one wave per SIMD (plain, and with the
-    // staging interleaved into the tap loop); a plane-pair form (8x8x4 tiles, two anti-phase halves of
-    // two transformed planes each, half the L2 weight stream) -- 0-15 % behind this one or equal to it.
-    // r03: the plane-pair form rebuilt for the one-MFMA modes (f16, bf16), where the L2 weight stream
-    // was suspected to be the bound, at weight-ring depths 3 / 4 / 5 / 6 / 8, bit-identical:
-    // 15-30 % SLOWER than this form on the 64^3 and 64x32x32 layers, equal below
-    // (profiles/r03_layer_ab_plane_pair_{bf16,f16}.txt) -- with a third of the MFMAs its tap phase
-    // (72 MFMAs) is shorter than the other half's staging phase, so the anti-phase halves wait for each
-    // other.  Not kept (the form is commit 8797410's conv3d_wzp.h with the weight-ring depth made a template
-    // parameter).
-    // f16x3: the issue order of a tap (conv3d_wz.h, IL): one order for every shape since r03
-    // (profiles/r03_layer_ab_wz_issue_order.txt; r02 had picked between 0 and 1 by shape).
-    if (k.sk_w != nullptr) {
-        // ddpm3d_conv3d_skip's fused form (conv3d_wz.h SKIP; api.hip has checked the arithmetic, the input mode and the
-        // hints): the tile forms and the grids of the plain f16x3 launches below
-        if (c.PREC != DDPM3D_PREC_F16X3_WZ) return hipErrorInvalidValue;
-        constexpr size_t slds4 = (size_t)WzGeomT<4>::BUF + stamp_lds, slds84 = (size_t)WzGeomT<8, 4>::BUF + stamp_lds;
-        if (c.TXL == 2)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_SKIP, 4, 4>), dim3(gx, gy, k.ksplit), dim3(256), slds4, st, k);
-        else if (DDPM3D_WZ_T84 && k.H % 8 == 0 && k.D % 4 == 0) {
-            ConvK k2 = k;
-            k2.tilesY = 2 * k.tilesY;
-            k2.tilesZ = k.tilesZ / 2;
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_SKIP, 4, 8, 4>), dim3(gx, gy, k.ksplit), dim3(256), slds84, st, k2);
-        } else
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_SKIP, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds, st, k);
-        return hipGetLastError();
-    }
-    if (k.hint & DDPM3D_HINT_UP_PHASE) {
-        // an IN_UP conv as four 2x2 phase convs on the low-resolution source (conv3d_wz.h PHASE; api.hip keeps the bit
-        // only where ddpm3d_up_phase_geom holds): 4 phases x the low-resolution tiles = the grid the shape rule counted
-        UpPhaseGeom g;
-        if (c.PREC != DDPM3D_PREC_F16X3_WZ || !ddpm3d_up_phase_geom(k.D, k.H, k.W, c, g)) return hipErrorInvalidValue;
-        ConvK k2 = k;
-        k2.tilesX = g.tilesX; k2.tilesY = g.tilesY; k2.tilesZ = g.tilesZ;
-        const dim3 grid(4 * k.N * g.tilesZ * g.tilesY * g.tilesX, gy, k.ksplit);
-        constexpr size_t plds4 = (size_t)WzGeomT<4>::BUF + stamp_lds, plds84 = (size_t)WzGeomT<8, 4>::BUF + stamp_lds;
-        if (g.TX == 4)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_UP, 4, 4, 4>), grid, dim3(256), plds4, st, k2);
-        else if (g.TY == 4)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_UP, 4, 8, 4>), grid, dim3(256), plds84, st, k2);
-        else
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3_UP, 4, 8, 8>), grid, dim3(256), lds, st, k2);
-        return hipGetLastError();
-    }
-    if (c.TXL == 2) {
-        // 4x4x8 tiles (the levels below 8x8: r03).  One issue order; the image is 56 KB
-        constexpr size_t lds4 = (size_t)WzGeomT<4>::BUF + stamp_lds;
-        if (c.PREC == DDPM3D_PREC_F16_WZ)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16, 0, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds4, st, k);
-        else if (c.PREC == DDPM3D_PREC_BF16_WZ)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_BF16, 0, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds4, st, k);
-        else
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 4, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds4, st, k);
-        return hipGetLastError();
-    }
-    // 8x4x4 tiles (two z-pairs per workgroup; r03) where they tile the volume like the 8x8x2 grid the shape rule
-    // counted (H % 8 == 0, D % 4 == 0: same number of tiles, so statistics rows and workspace are unchanged); the
-    // default issue order only
-    if (DDPM3D_WZ_T84 && k.H % 8 == 0 && k.D % 4 == 0 && !(k.hint & DDPM3D_HINT_WZ_ORDER_MASK)) {
-        ConvK k2 = k;
-        k2.tilesY = 2 * k.tilesY;
-        k2.tilesZ = k.tilesZ / 2;
-        constexpr size_t lds84 = (size_t)WzGeomT<8, 4>::BUF + stamp_lds;
-        if (c.PREC == DDPM3D_PREC_F16_WZ)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16, 0, 8, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds84, st, k2);
-        else if (c.PREC == DDPM3D_PREC_BF16_WZ)
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_BF16, 0, 8, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds84, st, k2);
-        else
-            hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 4, 8, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds84, st, k2);
-        return hipGetLastError();
-    }
-    if (c.PREC == DDPM3D_PREC_F16_WZ)
-        hipLaunchKernelGGL(conv3d_wz_kernel<WZ_F16>, dim3(gx, gy, k.ksplit), dim3(256), lds, st, k);
-    else if (c.PREC == DDPM3D_PREC_BF16_WZ)
-        hipLaunchKernelGGL(conv3d_wz_kernel<WZ_BF16>, dim3(gx, gy, k.ksplit), dim3(256), lds, st, k);
-    else {
-        // kernel_hint bits 12..14: force an issue order (A/B measurements; identical arithmetic), 0 = the default.
-        // Built: 0, 1 (r02's two), 2, 4 (r03); 3, 5, 6 of conv3d_wz.h were measured and are not instantiated
-        // (every instantiation is ~1 MB of code object to load at the first launch)
-        int order = (k.hint & DDPM3D_HINT_WZ_ORDER_MASK) >> DDPM3D_HINT_WZ_ORDER_SHIFT;
-        if (order == 0) order = 5;   // (value = IL + 1): weight loads first, reads behind, wave priority 1
-        switch (order - 1) {
-            case 0: hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 0>), dim3(gx, gy, k.ksplit), dim3(256), lds, st, k); break;
-            case 1: hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 1>), dim3(gx, gy, k.ksplit), dim3(256), lds, st, k); break;
-            case 2: hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 2>), dim3(gx, gy, k.ksplit), dim3(256), lds, st, k); break;
-            case 4: hipLaunchKernelGGL((conv3d_wz_kernel<WZ_F16X3, 4>), dim3(gx, gy, k.ksplit), dim3(256), lds, st, k); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
+    constexpr size_t lds = (size_t)WzGeomT<TX, TY>::BUF + stamp_lds;
+    hipLaunchKernelGGL((conv3d_wz_kernel<MODE, IL, TX, TY>), dim3(s.grid[0], s.grid[1], s.grid[2]), dim3(256), lds, st, k);
     return hipGetLastError();
+}
+
+hipError_t ddpm3d_launch_conv_wz(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    const int mode = ddpm3d_wz_mode(s);
+#define WZ(M_, IL_, TX_, TY_) \
+    if (mode == M_ && s.order == IL_ && s.TX == TX_ && s.TY == TY_) return wz_launch<M_, IL_, TX_, TY_>(k, s, st);
+#define WZ_TILES(M_, IL_) WZ(M_, IL_, 8, 8) WZ(M_, IL_, 8, 4) WZ(M_, IL_, 4, 4)
+    WZ_TILES(WZ_F16X3, 4) WZ(WZ_F16X3, 0, 8, 8) WZ(WZ_F16X3, 1, 8, 8) WZ(WZ_F16X3, 2, 8, 8)
+    WZ_TILES(WZ_F16, 0) WZ_TILES(WZ_BF16, 0) WZ_TILES(WZ_F16X3_UP, 4) WZ_TILES(WZ_F16X3_SKIP, 4)
+#undef WZ_TILES
+#undef WZ
+    return hipErrorInvalidValue;
 }
 #else   // the direct kernels of one arithmetic mode
 
 // ---------------------------------------------------------------- dispatch
 template <int PREC, int PIPE, int KS, int WN, int MT, int TXL, int TYL>
-static hipError_t launch_cfg(const ConvK& k, int grid_x, int grid_y, hipStream_t st) {
+static hipError_t launch_cfg(const ConvK& k, const ConvSel& s, hipStream_t st) {
     constexpr int TX = 1 << TXL, TY = 1 << TYL, TZ = (4 / WN) * MT * 32 / (TX * TY);
     constexpr int PAD = KS / 2, SXY = PIPE == 2 ? 2 : 1;
     constexpr int HX = SXY * (TX - 1) + KS, HY = SXY * (TY - 1) + KS, HZ = TZ + 2 * PAD;
@@ -608,29 +539,21 @@ static hipError_t launch_cfg(const ConvK& k, int grid_x, int grid_y, hipStream_t
             once, reinterpret_cast<const void*>(&conv3d_kernel<PREC, PIPE, KS, WN, MT, TXL, TYL>), (int)lds_bytes);
         if (attr != hipSuccess) return attr;
     }
-    hipLaunchKernelGGL((conv3d_kernel<PREC, PIPE, KS, WN, MT, TXL, TYL>), dim3(grid_x, grid_y, k.ksplit), dim3(256),
+    hipLaunchKernelGGL((conv3d_kernel<PREC, PIPE, KS, WN, MT, TXL, TYL>), dim3(s.grid[0], s.grid[1], s.grid[2]), dim3(256),
                        lds_bytes, st, k);
     return hipGetLastError();
 }
 
 #define DDPM3D_CAT2(a, b) a##b
 #define DDPM3D_CAT(a, b) DDPM3D_CAT2(a, b)
-hipError_t DDPM3D_CAT(ddpm3d_launch_conv_p, DDPM3D_PREC_ONLY)(const ConvK& k, const ConvCfg& c, hipStream_t st) {
-    const int gx = k.N * k.tilesZ * k.tilesY * k.tilesX;
-    const int gy = (k.CoutPad + 32 * c.WN - 1) / (32 * c.WN);
-    const int pipe = k.in_mode == DDPM3D_IN_STRIDE2 ? 2 : ((k.in_mode == DDPM3D_IN_SAME || k.in_mode == DDPM3D_IN_UP) ? 1 : 0);
-#define CASE(P_, PI_, KS_, WN_, MT_, TXL_, TYL_)                                                      \
-    if (pipe == PI_ && c.KS == KS_ && c.WN == WN_ && c.MT == MT_ && c.TXL == TXL_ && c.TYL == TYL_)   \
-        return launch_cfg<P_, PI_, KS_, WN_, MT_, TXL_, TYL_>(k, gx, gy, st);
-#define CASES(P_, PI_)                                                                          \
-    CASE(P_, PI_, 3, 4, 4, 3, 3) CASE(P_, PI_, 3, 2, 2, 3, 3) CASE(P_, PI_, 3, 1, 1, 3, 3)      \
-    CASE(P_, PI_, 3, 4, 4, 2, 2) CASE(P_, PI_, 3, 2, 2, 2, 2) CASE(P_, PI_, 3, 1, 1, 2, 2)      \
-    CASE(P_, PI_, 1, 4, 4, 3, 3) CASE(P_, PI_, 1, 2, 2, 3, 3) CASE(P_, PI_, 1, 1, 1, 3, 3)      \
-    CASE(P_, PI_, 1, 4, 4, 2, 2) CASE(P_, PI_, 1, 2, 2, 2, 2) CASE(P_, PI_, 1, 1, 1, 2, 2)
-    CASES(DDPM3D_PREC_ONLY, 1) CASES(DDPM3D_PREC_ONLY, 0)
-    // stride-(1,2,2) 3x3x3 convs (Downsample with use_conv)
-    CASE(DDPM3D_PREC_ONLY, 2, 3, 4, 4, 3, 3) CASE(DDPM3D_PREC_ONLY, 2, 3, 2, 2, 3, 3) CASE(DDPM3D_PREC_ONLY, 2, 3, 1, 1, 3, 3)
-    CASE(DDPM3D_PREC_ONLY, 2, 3, 4, 4, 2, 2) CASE(DDPM3D_PREC_ONLY, 2, 3, 2, 2, 2, 2) CASE(DDPM3D_PREC_ONLY, 2, 3, 1, 1, 2, 2)
+hipError_t DDPM3D_CAT(ddpm3d_launch_conv_p, DDPM3D_PREC_ONLY)(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    // <PREC, PIPEM, KS, WN, MT = WN, TXL, TYL = TXL>: every WN on 8x8 and 4x4 tiles, per pipe mode and kernel size
+#define CASE(PI_, KS_, WN_, TXL_)                                               \
+    if (s.pipe == PI_ && s.KS == KS_ && s.WN == WN_ && s.TX == (1 << TXL_))     \
+        return launch_cfg<DDPM3D_PREC_ONLY, PI_, KS_, WN_, WN_, TXL_, TXL_>(k, s, st);
+#define CASES(PI_, KS_) CASE(PI_, KS_, 4, 3) CASE(PI_, KS_, 2, 3) CASE(PI_, KS_, 1, 3) CASE(PI_, KS_, 4, 2) CASE(PI_, KS_, 2, 2) CASE(PI_, KS_, 1, 2)
+    CASES(1, 3) CASES(1, 1) CASES(0, 3) CASES(0, 1)
+    CASES(2, 3)     // stride-(1,2,2) 3x3x3 convs (Downsample with use_conv)
 #undef CASES
 #undef CASE
     return hipErrorInvalidValue;

@@ -84,9 +84,18 @@ static inline void ddpm3d_conv_cfg_split(ConvCfg& c, int S, int N, int D, int H,
     }
 }
 
-// One rule, used by the launcher, by ddpm3d_conv_stats_rows /
+// 8x8 tiles in (H, W), else 4x4 (the levels below 8x8)
+static inline bool ddpm3d_tile8(int H, int W, int ksize) {
+#ifdef DDPM3D_FORCE_T4_3X3   // measurement only: 4x4x8 tiles for every 3x3x3 layer (r03: slower, see DESIGN 3.1b)
+    if (ksize == 3) return false;
+#endif
+    return H >= 8 && W >= 8;
+}
+
+// One rule, used by the C entries (api.hip), by ddpm3d_conv_stats_rows /
 // ddpm3d_conv_workspace_bytes and by the weight packer: how a conv of this
 // shape is tiled and whether its reduction dimension is split over workgroups.
+// (The kernel instance and its 128-voxel tile form: conv3d_select.h; the tile COUNT is fixed here.)
 //
 // Split-K: a low-resolution level has few 128-voxel tiles (64x4x4 -> 8), so
 // without it a 512->512 conv occupies 32 of 256 CUs.  The Cin chunks are dealt
@@ -102,11 +111,7 @@ static inline ConvCfg ddpm3d_conv_cfg(int N, int D, int H, int W, int Cin, int C
                           prec == DDPM3D_PREC_BF16_WZ;
     c.KS = ksize;
     c.WN = Cout > 64 ? 4 : (Cout > 32 ? 2 : 1);
-#ifdef DDPM3D_FORCE_T4_3X3   // measurement only: 4x4x8 tiles for every 3x3x3 layer (r03: slower, see DESIGN 3.1b)
-    if (H >= 8 && W >= 8 && ksize != 3) { c.TXL = 3; c.TYL = 3; } else { c.TXL = 2; c.TYL = 2; }
-#else
-    if (H >= 8 && W >= 8) { c.TXL = 3; c.TYL = 3; } else { c.TXL = 2; c.TYL = 2; }
-#endif
+    c.TXL = c.TYL = ddpm3d_tile8(H, W, ksize) ? 3 : 2;
     c.MT = c.WN;  // 128-voxel tile (a 256-voxel tile, 8 accumulators per wave, measured 2.2x slower: r01)
     const int TX = 1 << c.TXL, TY = 1 << c.TYL, TZ = (4 / c.WN) * c.MT * 32 / (TX * TY);
     c.tilesX = (W + TX - 1) / TX;
@@ -219,41 +224,6 @@ static inline PackedImage ddpm3d_up_phase_image(int Cout, int Cin) { return Pack
 static inline size_t ddpm3d_up_phase_bytes(int Cout, int Cin) {
     return ddpm3d_packed_image(Cout, Cin, 3, DDPM3D_PREC_F16X3_WZ).bytes() + ddpm3d_up_phase_image(Cout, Cin).bytes();
 }
-// Tile form on the LOW-resolution grid (H/2 x W/2), chosen like the launcher chooses the output grid's
-// (8x4x4 where H/2 % 8 == 0 and D % 4 == 0, else 8x8x2, 4x4x8 below 8x8), ragged edges included.  The form is
-// taken only where four phases x the low-resolution tiles are exactly the tiles the shape rule counted on
-// the output grid: statistics rows (one per workgroup), workspace and split then are what ddpm3d_conv_cfg
-// reports.  false = the shipped path.
-struct UpPhaseGeom { int TX, TY, tilesX, tilesY, tilesZ; };
-static inline bool ddpm3d_up_phase_geom(int D, int H, int W, const ConvCfg& c, UpPhaseGeom& g) {
-    if (((H | W) & 1) || c.KS != 3 || c.WN != 4 || c.MT != 4) return false;
-    const int Hl = H / 2, Wl = W / 2;
-    if (Hl >= 8 && Wl >= 8) { g.TX = 8; g.TY = (Hl % 8 == 0 && D % 4 == 0) ? 4 : 8; }
-    else { g.TX = 4; g.TY = 4; }
-    const int TZ = 128 / (g.TX * g.TY);
-    g.tilesX = (Wl + g.TX - 1) / g.TX;
-    g.tilesY = (Hl + g.TY - 1) / g.TY;
-    g.tilesZ = (D + TZ - 1) / TZ;
-    return 4LL * g.tilesX * g.tilesY * g.tilesZ == (long long)c.tilesX * c.tilesY * c.tilesZ;
-}
-
-hipError_t ddpm3d_launch_conv(const ConvK& k, const ConvCfg& c, hipStream_t st);
-hipError_t ddpm3d_launch_splitk_reduce(const ConvK& k, hipStream_t st);
-hipError_t ddpm3d_launch_conv_skinny(const ConvK& k, int prec, hipStream_t st);   // conv3d_skinny.hip
-hipError_t ddpm3d_launch_conv_pw(const ConvK& k, const ConvCfg& c, hipStream_t st);   // conv1x1.hip
-// the 1x1x1 convs on raw inputs (ResBlock skip connections) that conv1x1.hip's register-fed GEMM takes;
-// k is the filled launch record (chunks_per_split included)
-// (r03 kept the split-f16 form above 1024 workgroups -- the three 256 -> 128 skip convs at 64^3 -- on conv3d.hip's
-// kernel, 0.110 against 0.120 ms; with the lean epilogue (conv3d_epilogue.h, r04) a 1x1 workgroup is 7 k cycles
-// shorter and the order is the other way round, 0.108 against 0.115: profiles/r04_lib_ab_conv1x1_cut_lean_epilogue.txt)
-static inline bool ddpm3d_pw_ok(const ConvK& k, const ConvCfg& c, int ksize) {
-    const bool s0 = (k.io & DDPM3D_IO_SRC0_BF16) != 0, s1 = (k.io & DDPM3D_IO_SRC1_BF16) != 0;
-    return ksize == 1 && (c.PREC == 1 || c.PREC == 2 || c.PREC == 5) && c.WN == 4 && c.MT == 4 &&
-           k.in_mode == DDPM3D_IN_SAME && k.affA == nullptr && k.act == 0 && k.stats == nullptr &&
-           k.Cout % 128 == 0 && k.Cin % 32 == 0 && k.C0 % 32 == 0 && (k.C1 == 0 || s0 == s1) &&
-           (k.ksplit == 1 || k.chunks_per_split % 2 == 0);
-}
-bool ddpm3d_skinny_ok(int CinPad, int prec, int src16);   // src16: 0 fp32, 1 bf16, 2 f16
 
 // GroupNorm partial sums are STORED in fp64 (r03).  With fp32 sums the variance E[x^2] - mean^2 loses
 // |mean|^2 / var x 1e-7 of its value to cancellation -- invisible on normalised data, 1e-2 on a tensor

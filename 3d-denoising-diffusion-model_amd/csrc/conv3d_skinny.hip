@@ -19,15 +19,13 @@
 // column with a 10/8 x 10/8 x (ZSEG+2)/ZSEG halo, from L2 mostly.  Bound: HBM (the input tensor,
 // Cin * 4 bytes per voxel; the output is Cout * 4).
 #include "conv3d_stage.h"
+#include "conv3d_select.h"
 
 namespace {
 
 constexpr int SK_TX = 8, SK_HX = 10, SK_HALO = SK_HX * SK_HX;   // 8x8 outputs, 10x10 halo voxels
 constexpr int SK_COLS = 64;                                      // 27 * Cout padded to two MFMA column tiles
 constexpr int SK_PSTRIDE = SK_COLS + 1;                          // P row stride in floats
-#ifndef SK_MIN_WGS
-#define SK_MIN_WGS 512
-#endif
 
 // one plane of a lane's halo voxel: per k-step its 8 channels (two 16-byte quads of fp32, or one of bf16)
 template <int NCH, int B16>
@@ -256,34 +254,20 @@ static hipError_t sk_launch(const ConvK& k, dim3 grid, int zseg, int zsegs, hipS
     return hipGetLastError();
 }
 
-// Instantiated: Cin = 32, 64, 128 channels (base widths); fp32 sources in the f16x3 / f16 arithmetic, bf16
-// sources in the bf16 mode and f16 sources in the f16 mode (the modes whose residual stream is 16-bit).
-// Anything else stays on the general kernel (api.hip asks here).  src16: 0 fp32, 1 bf16, 2 f16.
-bool ddpm3d_skinny_ok(int CinPad, int prec, int src16) {
-    if (CinPad != 32 && CinPad != 64 && CinPad != 128) return false;
-    if (prec == DDPM3D_PREC_BF16) return src16 == 1;
-    if (prec == DDPM3D_PREC_F16) return src16 == 0 || src16 == 2;
-    return prec == DDPM3D_PREC_F16X3 && src16 == 0;
-}
-
+// Instantiated (ddpm3d_skinny_ok, conv3d_select.h): Cin = 32, 64, 128; per arithmetic the source types listed there.
 template <int MODE, int B16>
-static hipError_t sk_launch_mode(const ConvK& k, dim3 grid, int zseg, int zsegs, hipStream_t st) {
-    if (k.CinPad == 32) return sk_launch<MODE, 2, B16>(k, grid, zseg, zsegs, st);
-    if (k.CinPad == 64) return sk_launch<MODE, 4, B16>(k, grid, zseg, zsegs, st);
-    return sk_launch<MODE, 8, B16>(k, grid, zseg, zsegs, st);
+static hipError_t sk_launch_mode(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    const dim3 grid(s.grid[0]);
+    if (s.nch == 2) return sk_launch<MODE, 2, B16>(k, grid, s.TZ, s.tilesZ, st);
+    if (s.nch == 4) return sk_launch<MODE, 4, B16>(k, grid, s.TZ, s.tilesZ, st);
+    if (s.nch == 8) return sk_launch<MODE, 8, B16>(k, grid, s.TZ, s.tilesZ, st);
+    return hipErrorInvalidValue;
 }
 
-hipError_t ddpm3d_launch_conv_skinny(const ConvK& k, int prec, hipStream_t st) {
-    // depth segments: as long as possible (less halo) while the grid still fills the chip twice over
-    const int tiles = k.N * ((k.H + 7) / 8) * ((k.W + 7) / 8);
-    int zseg = k.D;
-    while (zseg > 4 && (long long)tiles * ((k.D + zseg - 1) / zseg) < SK_MIN_WGS) zseg = (zseg + 1) / 2;
-    const int zsegs = (k.D + zseg - 1) / zseg;
-    const dim3 grid(tiles * zsegs);
-    if (prec == DDPM3D_PREC_F16) {
-        if (k.io & DDPM3D_IO_SRC0_BF16) return sk_launch_mode<WZ_F16, 2>(k, grid, zseg, zsegs, st);   // f16 source
-        return sk_launch_mode<WZ_F16, 0>(k, grid, zseg, zsegs, st);
-    }
-    if (prec == DDPM3D_PREC_BF16) return sk_launch_mode<WZ_BF16, 1>(k, grid, zseg, zsegs, st);
-    return sk_launch_mode<WZ_F16X3, 0>(k, grid, zseg, zsegs, st);
+hipError_t ddpm3d_launch_conv_skinny(const ConvK& k, const ConvSel& s, hipStream_t st) {
+    if (s.arith == WZ_F16 && s.src16 == 2) return sk_launch_mode<WZ_F16, 2>(k, s, st);     // f16 source
+    if (s.arith == WZ_F16 && s.src16 == 0) return sk_launch_mode<WZ_F16, 0>(k, s, st);
+    if (s.arith == WZ_BF16 && s.src16 == 1) return sk_launch_mode<WZ_BF16, 1>(k, s, st);
+    if (s.arith == WZ_F16X3 && s.src16 == 0) return sk_launch_mode<WZ_F16X3, 0>(k, s, st);
+    return hipErrorInvalidValue;
 }

@@ -184,6 +184,7 @@ EXPORTS = {
     "ddpm3d_conv_plan": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "ddpm3d_conv3d_skip": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvSkip), _fp]),
     "ddpm3d_conv_skip_fused": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvSkip)]),
+    "ddpm3d_conv_kernel_instance": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvSkip), C.c_char_p, C.c_int]),
     "ddpm3d_unet_plan_bytes": (C.c_size_t, [C.POINTER(UnetDesc), C.c_int, C.c_int, C.c_int, C.c_int]),
     "ddpm3d_unet_plan_create": (C.c_int, [C.POINTER(UnetDesc), C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_size_t,
                                           C.POINTER(_fp)]),
@@ -325,6 +326,13 @@ def conv_plan(desc):
     rows, ws, split = C.c_int(0), C.c_size_t(0), C.c_int(0)
     check(load().ddpm3d_conv_plan(C.byref(desc), C.byref(rows), C.byref(ws), C.byref(split)))
     return rows.value, ws.value, split.value
+
+
+def conv_instance(desc, skip=None):
+    """the kernel instance ddpm3d_conv3d (skip None) or ddpm3d_conv3d_skip runs, e.g. "conv3d_wz_kernel<0,4,8,4>" """
+    name = C.create_string_buffer(96)
+    check(load().ddpm3d_conv_kernel_instance(C.byref(desc), None if skip is None else C.byref(skip), name, 96))
+    return name.value.decode()
 
 
 def stream():

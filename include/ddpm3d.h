@@ -293,6 +293,15 @@ typedef struct ddpm3d_conv_skip {
 } ddpm3d_conv_skip;
 int ddpm3d_conv3d_skip(const ddpm3d_conv_desc* conv2, const ddpm3d_conv_skip* skip, void* stream);
 int ddpm3d_conv_skip_fused(const ddpm3d_conv_desc* conv2, const ddpm3d_conv_skip* skip);
+/* Which kernel INSTANCE the call runs (ABI 13, additive): the kernel template's name with every template argument
+ * written out as an integer, defaults included, bools as 0 / 1, no blanks -- "conv3d_wz_kernel<0,4,8,4>",
+ * "conv3d_kernel<1,1,3,2,2,3,3>", "conv3d_pw_kernel<1,0,3,3,1>", "conv3d_skinny_kernel<0,8,0>".  It is the name a
+ * kernel trace prints for the launch, less its return type, "(anonymous namespace)::", the parameter list and the
+ * blanks, with true / false read as 1 / 0.  skip == NULL: ddpm3d_conv3d(desc); else ddpm3d_conv3d_skip(desc, skip) --
+ * the fused launch, or conv2's launch of the two calls.  Refuses what ddpm3d_conv_kernel_family (with a skip: what
+ * ddpm3d_conv_skip_fused) refuses, launches nothing, and only prints the selection the launch would use; a forced
+ * issue order that is not built (3, 5, 6) is named although its launch fails. */
+int ddpm3d_conv_kernel_instance(const ddpm3d_conv_desc* desc, const ddpm3d_conv_skip* skip, char* name, int name_len);
 
 /*
  * ---- The whole network (ABI 12; SURVEY 8b's `unet_forward(handle, ...)` granularity) ----------------------------

@@ -107,7 +107,7 @@ def conv3d(srcs, w, b, out_dhw, in_mode=H.IN_SAME, aff=None, act=H.ACT_NONE, res
     H.check(lib.ddpm3d_conv_kernel_family(C.byref(d), name, 64))
     H.check(lib.ddpm3d_conv3d(C.byref(d), H.stream()))
     torch.cuda.synchronize()
-    LAST_PLAN.update(split=split, rows=rows, family=name.value.decode())
+    LAST_PLAN.update(split=split, rows=rows, family=name.value.decode(), instance=H.conv_instance(d))
     return out, stats, rows
 
 

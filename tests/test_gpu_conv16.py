@@ -60,6 +60,7 @@ class Case:
     name: str
     prec: int                 # 2, 4 (f16) / 5, 6 (bf16)
     family: str               # ddpm3d_conv_kernel_family's answer the case claims
+    wz: str = "8,8"           # Winograd-D: the tile (TX, TY) of the instance the case is meant for (t4 families: 4,4)
     N: int = 1
     D: int = 5
     H: int = 8
@@ -115,10 +116,30 @@ WZ8, WZ4 = "conv3d_p%d_k3_wn4_t8", "conv3d_p%d_k3_wn4_t4"
 PW8, PW4 = "conv1x1_p%d_t8", "conv1x1_p%d_t4"
 K18, K14 = "conv3d_p%d_k1_wn4_t8", "conv3d_p%d_k1_wn4_t4"
 SK = "conv3d_p%d_k3_skinny"
-R8 = dict(D=5, H=8, W=10)           # 8x8x2 tiles, odd D, ragged W
-R84 = dict(D=8, H=8, W=12)          # 8x4x4 tiles (H % 8 == 0, D % 4 == 0), ragged W
-R4 = dict(D=9, H=4, W=6)            # 4x4x8 tiles, D not a multiple of 8, ragged W
+R8 = dict(D=5, H=8, W=10, wz="8,8")     # 8x8x2 tiles, odd D, ragged W
+R84 = dict(D=8, H=8, W=12, wz="8,4")    # 8x4x4 tiles (H % 8 == 0, D % 4 == 0), ragged W
+R4 = dict(D=9, H=4, W=6, wz="4,4")      # 4x4x8 tiles, D not a multiple of 8, ragged W
 FS = dict(split=2, expect_split=True)
+
+
+def claimed_instance(c):
+    """ddpm3d_conv_kernel_instance's answer the case claims, spelled from what it says of itself: the kernel and tile
+    width of its family, its arithmetic, input mode and source storage, and for the Winograd-D form the tile `wz`
+    (also test_gpu_conv32.py's cases, whose sources are fp32)"""
+    fam, src = c.family, getattr(c, "src", ("f32",))
+    txl = {"8": 3, "4": 2}[fam.rsplit("_t", 1)[-1]] if "_t" in fam else 3
+    if fam.endswith("skinny"):      # <arithmetic, Cin / 16, source type: 0 fp32, 1 bf16, 2 f16>
+        return "conv3d_skinny_kernel<%d,%d,%d>" % ({1: 0, 2: 1, 5: 2}[c.prec], sum(c.C) // 16,
+                                                  0 if src[0] == "f32" else 2 if c.prec in E.F16_MODES else 1)
+    if fam.startswith("conv1x1"):   # <PREC, 16-bit sources, TXL, TYL, wide stores>
+        return "conv3d_pw_kernel<%d,%d,%d,%d,1>" % (c.prec, src[0] == "h", txl, txl)
+    if c.prec in (3, 4, 6):         # <arithmetic, issue order, TX, TY>
+        return "conv3d_wz_kernel<%d,%d,%s>" % ({3: 0, 4: 1, 6: 2}[c.prec], 4 if c.prec == 3 else 0,
+                                              "4,4" if txl == 2 else c.wz)
+    wn = int(fam.split("_wn")[1][0])
+    pipe = {"same": 1, "up": 1, "stride2": 2}.get(c.in_mode, 0)
+    return "conv3d_kernel<%d,%d,%d,%d,%d,%d,%d>" % (c.prec, pipe, c.k, wn, wn, txl, txl)
+
 
 CASES = []
 for geo, fam in ((R8, WZ8), (R84, WZ8), (R4, WZ4)):
@@ -145,7 +166,7 @@ CASES += [
     Case("wz_x300_bf16", 6, WZ8 % 6, xscale=300.0, aff=False, act=False, **R8),
     Case("direct_x300_bf16", 5, "conv3d_p5_k3_wn4_t4", xscale=300.0, aff=False, act=False, D=6, H=4, W=4),
     # the network's 8x8 and 4x4 level shapes (rule's split), and 4x4 with a forced split
-    *_both("wz_level_8x8", 4, WZ8, D=16, H=8, W=8, C=(384,), Cout=384, res_mode="same", expect_split=True),
+    *_both("wz_level_8x8", 4, WZ8, D=16, H=8, W=8, wz="8,4", C=(384,), Cout=384, res_mode="same", expect_split=True),
     *_both("wz_level_4x4", 4, WZ4, D=16, H=4, W=4, C=(512,), Cout=512, expect_split=True),
     *_both("wz_level_4x4_forced", 4, WZ4, D=16, H=4, W=4, C=(256,), Cout=128, split=4, expect_split=True),
     # the direct kernel: the planar first conv on 8x8 and 4x4 tiles, 8x8 / 4x4 tiles with a partial cout tile,
@@ -305,6 +326,7 @@ def test_conv16_kernel_vs_emulation(hc, c):
     out, stats, plan = run_gpu(hc, c, t)
     # the route the case claims, and nothing else
     assert plan["family"] == c.family, (plan["family"], c.family)
+    assert plan["instance"] == claimed_instance(c), (plan["instance"], claimed_instance(c))
     assert (plan["split"] > 1) == c.expect_split, plan
     if c.split:
         assert plan["split"] == c.split

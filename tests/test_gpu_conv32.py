@@ -62,6 +62,8 @@ class Case:
     name: str
     prec: int                 # 0 (f32), 1 (f16x3), 3 (f16x3 Winograd-D)
     family: str               # ddpm3d_conv_kernel_family's answer the case claims
+    wz: str = "8,8"           # Winograd-D: the tile (TX, TY) of the instance the case is meant for (t4 families: 4,4)
+    inst: str = ""            # ddpm3d_conv_kernel_instance's answer, where it is not test_gpu_conv16.claimed_instance's
     N: int = 1
     D: int = 5
     H: int = 8
@@ -94,9 +96,9 @@ def _modes(name, precs, family_fmt, **kw):
 
 D8, D4 = "conv3d_p%d_k3_wn4_t8", "conv3d_p%d_k3_wn4_t4"
 K18, K14 = "conv3d_p%d_k1_wn4_t8", "conv3d_p%d_k1_wn4_t4"
-R8 = dict(D=5, H=8, W=10)           # 8x8 tiles (Winograd-D: 8x8x2), odd D, ragged W
-R84 = dict(D=8, H=8, W=12)          # Winograd-D 8x4x4 tiles (H % 8 == 0, D % 4 == 0), ragged W
-R4 = dict(D=9, H=4, W=6)            # 4x4 tiles (Winograd-D: 4x4x8), D not a multiple of 8, ragged W
+R8 = dict(D=5, H=8, W=10, wz="8,8")     # 8x8 tiles (Winograd-D: 8x8x2), odd D, ragged W
+R84 = dict(D=8, H=8, W=12, wz="8,4")    # Winograd-D 8x4x4 tiles (H % 8 == 0, D % 4 == 0), ragged W
+R4 = dict(D=9, H=4, W=6, wz="4,4")      # 4x4 tiles (Winograd-D: 4x4x8), D not a multiple of 8, ragged W
 FS = dict(split=2, expect_split=True)
 NOIN = dict(aff=False, act=False)
 DIRECT = (0, 1)
@@ -177,7 +179,7 @@ CASES += [
 ]
 # ---- the published level shapes, the rule's split (384 -> 384 @ 16x8x8, 512 -> 512 @ 16x4x4), and a forced one
 CASES += [
-    *_modes("level_8x8", (0, 3), D8, D=16, H=8, W=8, C=(384,), Cout=384, res_mode="same", expect_split=True),
+    *_modes("level_8x8", (0, 3), D8, D=16, H=8, W=8, wz="8,4", C=(384,), Cout=384, res_mode="same", expect_split=True),
     *_modes("level_4x4", (0, 3), D4, D=16, H=4, W=4, C=(512,), Cout=512, expect_split=True),
     *_modes("level_4x4_forced", (0, 3), D4, D=16, H=4, W=4, C=(256,), Cout=128, split=4, expect_split=True),
 ]
@@ -333,6 +335,7 @@ def test_conv32_kernel_vs_emulation(hc, c):
     out, got, stats, plan = run_gpu(hc, c, t)
     # the route the case claims, and nothing else
     assert plan["family"] == c.family, (plan["family"], c.family)
+    assert plan["instance"] == G16.claimed_instance(c), (plan["instance"], G16.claimed_instance(c))
     assert (plan["split"] > 1) == c.expect_split, plan
     if c.split:
         assert plan["split"] == c.split

@@ -38,6 +38,7 @@ U = G.U
 @dataclass
 class Case:
     name: str
+    wz: str = "8,8"           # the tile (TX, TY) of the Winograd-D instance the case is meant for
     N: int = 1
     D: int = 5
     H: int = 8
@@ -69,7 +70,7 @@ CASES += [
     Case("skip_two_samples_1e6", N=2, mags=((1e-6, 1.0), (1.0, 1e-6)), **G.R8),
     Case("skip_x_alternating_max", alt_max_x=True, **G.R84),
     # the published network's (512 + 512) -> 512 ResBlock at 64x4x4, the rule's 16-way split
-    Case("skip_published_1024_512_64x4x4", D=64, H=4, W=4, Cx=(512, 512), Cout=512, expect_split=True),
+    Case("skip_published_1024_512_64x4x4", D=64, H=4, W=4, wz="4,4", Cx=(512, 512), Cout=512, expect_split=True),
 ]
 
 
@@ -141,6 +142,7 @@ def run(hc, c, t, prec2=3, half=None, two_calls=False):
     if half is not None:
         sk.io_dtype = H.IO_SRC0_BF16 | (H.IO_SRC1_BF16 if len(xs) > 1 else 0)
     fused = bool(lib.ddpm3d_conv_skip_fused(C.byref(d), C.byref(sk)))
+    instance = H.conv_instance(d, sk)
     # statistics rows, workspace and split: what ddpm3d_conv_plan reports for the conv2 descriptor
     rows, need, split = H.conv_plan(d)
     if not c.split:
@@ -175,7 +177,7 @@ def run(hc, c, t, prec2=3, half=None, two_calls=False):
         H.check(lib.ddpm3d_conv3d(C.byref(d), H.stream()))
     torch.cuda.synchronize()
     del keep
-    return out.cpu(), stats.cpu(), dict(fused=fused, rows=rows, split=split, split1=split1)
+    return out.cpu(), stats.cpu(), dict(fused=fused, rows=rows, split=split, split1=split1, instance=instance)
 
 
 def _bits(t):
@@ -187,6 +189,7 @@ def test_skip_kernel_vs_emulation(hc, c):
     t = _inputs(c.name)
     out, stats, info = run(hc, c, t)
     assert info["fused"], info
+    assert info["instance"] == "conv3d_wz_kernel<4,4,%s>" % c.wz, (info, c.wz)      # <mode 4: skip, issue order, TX, TY>
     if c.expect_split is not None:
         assert (info["split"] > 1) == c.expect_split, info
     if c.split:
@@ -247,19 +250,22 @@ def test_skip_error_against_fp64_within_twice_f32(hc, c):
                            for i in bad.nonzero()[:6].tolist()]
 
 
+# (conv2's instance of the two calls: the plain f16x3 Winograd-D form, or precision 1's direct kernel)
 FALLBACK = [
-    ("bf16_io", Case("skip_fallback_bf16_io", Cx=(32, 32), **G.R84), dict(half=torch.bfloat16)),
-    ("bf16_io_split", Case("skip_fallback_bf16_io_split", Cx=(64,), **G.R8, **G.FS), dict(half=torch.bfloat16)),
-    ("precision_1", Case("skip_fallback_p1", Cx=(32, 32), **G.R8), dict(prec2=1)),
-    ("precision_1_split", Case("skip_fallback_p1_split", Cx=(64,), **G.R4, **G.FS), dict(prec2=1)),
+    ("bf16_io", Case("skip_fallback_bf16_io", Cx=(32, 32), **G.R84), dict(half=torch.bfloat16), "conv3d_wz_kernel<0,4,8,4>"),
+    ("bf16_io_split", Case("skip_fallback_bf16_io_split", Cx=(64,), **G.R8, **G.FS), dict(half=torch.bfloat16),
+     "conv3d_wz_kernel<0,4,8,8>"),
+    ("precision_1", Case("skip_fallback_p1", Cx=(32, 32), **G.R8), dict(prec2=1), "conv3d_kernel<1,1,3,4,4,3,3>"),
+    ("precision_1_split", Case("skip_fallback_p1_split", Cx=(64,), **G.R4, **G.FS), dict(prec2=1),
+     "conv3d_kernel<1,1,3,4,4,2,2>"),
 ]
 
 
-@pytest.mark.parametrize("c,kw", [f[1:] for f in FALLBACK], ids=[f[0] for f in FALLBACK])
-def test_skip_fallback_is_the_two_shipped_calls(hc, c, kw):
+@pytest.mark.parametrize("c,kw,inst", [f[1:] for f in FALLBACK], ids=[f[0] for f in FALLBACK])
+def test_skip_fallback_is_the_two_shipped_calls(hc, c, kw, inst):
     t = c.inputs()
     out, stats, info = run(hc, c, t, **kw)
-    assert not info["fused"]
+    assert not info["fused"] and info["instance"] == inst, (info, inst)
     out2, stats2, info2 = run(hc, c, t, two_calls=True, **kw)
     assert info2["rows"] == info["rows"] and info2["split"] == info["split"]
     assert torch.isfinite(out.float()).all()

@@ -36,9 +36,12 @@ pytestmark = pytest.mark.gpu
 
 U = G.U
 FAM = "conv3d_p3_k3_wn4_t8"
-T882 = dict(D=5, H=16, W=28)      # source 5 x 8 x 14: 8x8x2 tiles, odd D, ragged W
-T844 = dict(D=8, H=16, W=28)      # source 8 x 8 x 14: 8x4x4 tiles, ragged W
-T448 = dict(D=7, H=8, W=12)       # source 7 x 4 x 6: 4x4x8 tiles, odd D, ragged W
+PHASE, PLAIN = "conv3d_wz_kernel<3,4,%s>", "conv3d_wz_kernel<0,4,%s>"     # <mode: 3 phase / 0 plain f16x3, issue order, TX, TY>
+# (inst: the phase instance on the SOURCE grid's tile form; wz: the plain instance's tile, which the unhinted call runs)
+T882 = dict(D=5, H=16, W=28, inst=PHASE % "8,8", wz="8,8")      # source 5 x 8 x 14: 8x8x2 tiles, odd D, ragged W
+T844 = dict(D=8, H=16, W=28, inst=PHASE % "8,4", wz="8,4")      # source 8 x 8 x 14: 8x4x4 tiles, ragged W
+T448 = dict(D=7, H=8, W=12, inst=PHASE % "4,4", wz="8,8")       # source 7 x 4 x 6: 4x4x8 tiles, odd D, ragged W
+D64 = dict(D=64, wz="8,4")        # the published levels: depth 64, H % 8 == 0
 
 
 def _case(name, **kw):
@@ -52,7 +55,7 @@ for geo, g in ((T882, "t8x8x2"), (T844, "t8x4x4"), (T448, "t4x4x8")):
                   _case("%s_resid%s" % (g, sk), res_mode="same", **geo, **sp),
                   _case("%s_resid_up%s" % (g, sk), res_mode="up", **geo, **sp)]
 CASES += [
-    _case("d1", D=1, H=16, W=16, res_mode="same"),
+    _case("d1", D=1, H=16, W=16, inst=PHASE % "8,8", res_mode="same"),
     _case("concat_resid_up", C=(16, 16), res_mode="up", **T882),
     # (64 input channels: the rule splits them in two)
     _case("concat_rule_split_resid_up", C=(32, 32), res_mode="up", expect_split=True, **T844),
@@ -62,15 +65,15 @@ CASES += [
     _case("alternating_max", alt_max=True, **G.NOIN, **T844),
     _case("alternating_max_t4", alt_max=True, **G.NOIN, **T448),
     # conv1 of the published network's four up-ResBlocks at 1 x 64^3 (rule's split: 8, 2, none, none)
-    _case("published_384_64x8x8", D=64, H=8, W=8, C=(384,), Cout=384, expect_split=True),
-    _case("published_256_64x16x16", D=64, H=16, W=16, C=(256,), Cout=256, expect_split=True),
-    _case("published_128_64x32x32", D=64, H=32, W=32, C=(128,), Cout=128),
-    _case("published_128_64x64x64", D=64, H=64, W=64, C=(128,), Cout=128),
+    _case("published_384_64x8x8", H=8, W=8, inst=PHASE % "4,4", C=(384,), Cout=384, expect_split=True, **D64),
+    _case("published_256_64x16x16", H=16, W=16, inst=PHASE % "8,4", C=(256,), Cout=256, expect_split=True, **D64),
+    _case("published_128_64x32x32", H=32, W=32, inst=PHASE % "8,4", C=(128,), Cout=128, **D64),
+    _case("published_128_64x64x64", H=64, W=64, inst=PHASE % "8,4", C=(128,), Cout=128, **D64),
 ]
 # shapes whose low-resolution grid does not tile like the output grid: the hinted call runs the 36-tap path
 FALLBACK = [
-    _case("fallback_w24", D=4, H=16, W=24),
-    _case("fallback_d1_8x8", D=1, H=8, W=8, res_mode="up"),
+    _case("fallback_w24", D=4, H=16, W=24, inst=PLAIN % "8,4"),
+    _case("fallback_d1_8x8", D=1, H=8, W=8, inst=PLAIN % "8,8", res_mode="up"),
 ]
 
 
@@ -144,6 +147,7 @@ def test_up_phase_kernel_vs_emulation(hc, c):
     t = _inputs(c.name)
     out, got, stats, plan = run_gpu(hc, c, t)
     assert plan["family"] == c.family, (plan["family"], c.family)
+    assert plan["instance"] == c.inst, (plan["instance"], c.inst)
     assert (plan["split"] > 1) == c.expect_split, plan
     if c.split:
         assert plan["split"] == c.split
@@ -153,6 +157,7 @@ def test_up_phase_kernel_vs_emulation(hc, c):
     # the phase form ran: the unhinted call on the same inputs rounds its weights differently
     out36, got36, _, plan36 = run_gpu(hc, c, t, phase=False)
     assert plan36["split"] == plan["split"] and plan36["rows"] == plan["rows"]
+    assert plan36["instance"] == G.G16.claimed_instance(c), (plan36["instance"], c.wz)
     assert not torch.equal(out.view(torch.int32), out36.view(torch.int32))
     assert torch.isfinite(got).all()
     # ---- against the emulation of the phase arithmetic
@@ -189,7 +194,7 @@ def test_up_phase_fallback_is_the_shipped_path(hc, c):
     t = _inputs(c.name)
     out, _, stats, plan = run_gpu(hc, c, t)
     out36, _, stats36, plan36 = run_gpu(hc, c, t, phase=False)
-    assert plan == plan36
+    assert plan == plan36 and plan["instance"] == c.inst, (plan, plan36, c.inst)
     assert torch.equal(out.view(torch.int32), out36.view(torch.int32))
     assert torch.equal(stats.view(torch.int64), stats36.view(torch.int64))
 

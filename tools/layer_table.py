@@ -2,7 +2,7 @@
 """
 Per-launch table of one UNet forward of the published architecture (BASELINE config 2 shape):
 layer shape, input mode, kernel family, split-K factor, time (HIP events, averaged over --reps
-instrumented forwards) and algorithmic TFLOP/s.  Run on the GPU box:
+instrumented forwards), algorithmic TFLOP/s and the kernel instance (ddpm3d_conv_kernel_instance).  Run on the GPU box:
 
     python tools/layer_table.py [--size 64] [--batch 1] [--precision f16x3] > gpurun_out/layers.txt
 
@@ -58,7 +58,8 @@ def main():
     assert all(len(r) == len(steps) for r in runs)
     ms = [sum(r[i] for r in runs) / len(runs) for i in range(len(steps))]
     print("# published architecture, %dx1x%d^3, conv arithmetic %s, %d instrumented forwards" % (B, S, a.precision, a.reps))
-    print("%3s  %-24s %-6s %-12s %-14s %2s  %8s %8s" % ("#", "kernel family", "input", "Cin->Cout", "D x H x W", "S", "ms", "TFLOP/s"))
+    print("%3s  %-24s %-6s %-12s %-14s %2s  %8s %8s  %s" % ("#", "kernel family", "input", "Cin->Cout", "D x H x W", "S", "ms", "TFLOP/s",
+                                                         "kernel instance"))
     tot = 0.0
     for j, i in enumerate(steps):
         tag, fl = plan.conv_meta[i]
@@ -75,9 +76,10 @@ def main():
         vox = d.D * d.H * d.W
         ws = lib.ddpm3d_conv_workspace_bytes(d.N, d.D, d.H, d.W, d.Cin, d.Cout, d.ksize, d.precision)
         split = ws // (d.N * vox * d.Cout * 4) if ws else 1
-        print("%3d  %-24s %-6s %-12s %-14s %2d  %8.3f %8.1f" % (
+        inst = H.conv_instance(d, args[1]._obj if fn is lib.ddpm3d_conv3d_skip else None)
+        print("%3d  %-24s %-6s %-12s %-14s %2d  %8.3f %8.1f  %s" % (
             j, tag, IN_MODES.get(d.in_mode, "?"), "%d->%d" % (d.Cin, d.Cout), "%dx%dx%d" % (d.D, d.H, d.W),
-            split, ms[j], fl / ms[j] / 1e9))
+            split, ms[j], fl / ms[j] / 1e9, inst))
     fl_tot = sum(f for _, f in plan.conv_meta.values())
     print("# total %.3f ms, %.1f GFLOP, %.1f TFLOP/s" % (tot, fl_tot / 1e9, fl_tot / tot / 1e9))
 
