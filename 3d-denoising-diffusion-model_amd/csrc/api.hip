@@ -1102,27 +1102,27 @@ int ddpm3d_msssim3d(const float* est, const float* target, const uint8_t* mask, 
 
 // ------------------------------------------------- per-region moments (added within ABI 13)
 // Checks the host side of a region index; *chunks receives the number of chunks all regions are cut into.
-static int roi_index_check(int B, const ddpm3d_roi_index* ix, int64_t* chunks) {
+static int roi_index_check(const char* what, int B, const ddpm3d_roi_index* ix, int64_t* chunks) {
     if (!ix || !ix->offsets || !ix->d_offsets || !ix->d_chunks || !ix->d_index)
-        return fail(DDPM3D_EINVAL, "roi_moments: null pointer in the region index");
+        return fail(DDPM3D_EINVAL, "%s: null pointer in the region index", what);
     if (B < 1 || B > DDPM3D_MAX_DRAWS)
-        return fail(DDPM3D_EINVAL, "roi_moments: B=%d estimates (1..%d)", B, DDPM3D_MAX_DRAWS);
+        return fail(DDPM3D_EINVAL, "%s: B=%d estimates (1..%d)", what, B, DDPM3D_MAX_DRAWS);
     if (ix->regions < 1 || ix->regions > DDPM3D_ROI_MAX_REGIONS)
-        return fail(DDPM3D_EINVAL, "roi_moments: %d regions (1..%d)", ix->regions, DDPM3D_ROI_MAX_REGIONS);
+        return fail(DDPM3D_EINVAL, "%s: %d regions (1..%d)", what, ix->regions, DDPM3D_ROI_MAX_REGIONS);
     if (ix->entries < 0 || ix->entries > EM_MAX_VOXELS)
-        return fail(DDPM3D_EINVAL, "roi_moments: entries=%lld (0..2^40)", (long long)ix->entries);
+        return fail(DDPM3D_EINVAL, "%s: entries=%lld (0..2^40)", what, (long long)ix->entries);
     if (ix->offsets[0] != 0)
-        return fail(DDPM3D_EINVAL, "roi_moments: offsets[0]=%lld, not 0", (long long)ix->offsets[0]);
+        return fail(DDPM3D_EINVAL, "%s: offsets[0]=%lld, not 0", what, (long long)ix->offsets[0]);
     int64_t n = 0;
     for (int r = 0; r < ix->regions; ++r) {
         const int64_t len = ix->offsets[r + 1] - ix->offsets[r];
         if (len < 0 || ix->offsets[r + 1] > ix->entries)
-            return fail(DDPM3D_EINVAL, "roi_moments: offsets[%d]=%lld after %lld (non-decreasing, at most entries=%lld)",
+            return fail(DDPM3D_EINVAL, "%s: offsets[%d]=%lld after %lld (non-decreasing, at most entries=%lld)", what,
                         r + 1, (long long)ix->offsets[r + 1], (long long)ix->offsets[r], (long long)ix->entries);
         n += (len + DDPM3D_ROI_CHUNK - 1) / DDPM3D_ROI_CHUNK;
     }
     if (ix->offsets[ix->regions] != ix->entries)
-        return fail(DDPM3D_EINVAL, "roi_moments: offsets end at %lld, not at entries=%lld",
+        return fail(DDPM3D_EINVAL, "%s: offsets end at %lld, not at entries=%lld", what,
                     (long long)ix->offsets[ix->regions], (long long)ix->entries);
     *chunks = n;                                  // at most 2^40 / 4096 + 4096: a grid's x extent
     return DDPM3D_OK;
@@ -1133,7 +1133,7 @@ static size_t roi_ws_bytes(int B, int64_t chunks) {
 
 size_t ddpm3d_roi_moments_workspace_bytes(int B, const ddpm3d_roi_index* index) {
     int64_t chunks = 0;
-    return roi_index_check(B, index, &chunks) == DDPM3D_OK ? roi_ws_bytes(B, chunks) : 0;
+    return roi_index_check("roi_moments", B, index, &chunks) == DDPM3D_OK ? roi_ws_bytes(B, chunks) : 0;
 }
 
 int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t voxels, const ddpm3d_roi_index* index,
@@ -1142,13 +1142,32 @@ int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t vox
     if (voxels <= 0 || voxels > EM_MAX_VOXELS)
         return fail(DDPM3D_EINVAL, "roi_moments: voxels=%lld (1..2^40)", (long long)voxels);
     int64_t chunks = 0;
-    int rc = roi_index_check(B, index, &chunks);
+    int rc = roi_index_check("roi_moments", B, index, &chunks);
     if (rc != DDPM3D_OK) return rc;
     rc = ws_ok("roi_moments", roi_ws_bytes(B, chunks), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_roi_moments(est, target, B, voxels, *index, chunks, (double*)ws, out,
                                               (hipStream_t)stream),
                     "roi_moments");
+}
+
+// ------------------------------------------------- per-region co-occurrence matrices (added within ABI 13)
+int ddpm3d_roi_texture(const float* est, int B, int D, int H, int W, const ddpm3d_roi_index* index,
+                       const int16_t* region_of, const float* lo, const float* inv_w, int levels, uint64_t* glcm,
+                       uint64_t* hist, uint64_t* counts, void* stream) {
+    if (!est || !region_of || !lo || !inv_w || !glcm || !hist || !counts)
+        return fail(DDPM3D_EINVAL, "roi_texture: null pointer");
+    if (D < 1 || H < 1 || W < 1 || D > 65535 || H > 65535 || W > 65535 || (int64_t)D * H * W > 0x7fffffff)
+        return fail(DDPM3D_EINVAL, "roi_texture: bad volume (D=%d H=%d W=%d; 1..65535 each, D * H * W <= 2^31 - 1)",
+                    D, H, W);
+    if (levels < 2 || levels > DDPM3D_TEX_MAX_LEVELS)
+        return fail(DDPM3D_EINVAL, "roi_texture: %d grey levels (2..%d)", levels, DDPM3D_TEX_MAX_LEVELS);
+    int64_t chunks = 0;
+    const int rc = roi_index_check("roi_texture", B, index, &chunks);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_roi_texture(est, B, D, H, W, *index, chunks, region_of, lo, inv_w, levels, glcm,
+                                              hist, counts, (hipStream_t)stream),
+                    "roi_texture");
 }
 
 // ------------------------------------------------- connected components (added within ABI 13)

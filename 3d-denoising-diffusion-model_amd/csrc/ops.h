@@ -130,6 +130,11 @@ struct ddpm3d_roi_index;
 hipError_t ddpm3d_launch_roi_moments(const float* est, const float* target, int B, int64_t voxels,
                                      const ddpm3d_roi_index& ix, int64_t chunks, double* ws, double* out,
                                      hipStream_t st);
+// texture.hip: per-region co-occurrence matrices, histograms and side counters over the same index; zeroes the three
+// outputs on `st` first (the caller has checked the descriptor's host side, the shape and the level count)
+hipError_t ddpm3d_launch_roi_texture(const float* est, int B, int D, int H, int W, const ddpm3d_roi_index& ix,
+                                     int64_t chunks, const int16_t* region_of, const float* lo, const float* inv_w,
+                                     int levels, uint64_t* glcm, uint64_t* hist, uint64_t* counts, hipStream_t st);
 // ccl.hip: connected components of vol > threshold (the caller has checked the shape, the connectivity and the
 // workspace; the workspace query takes valid shapes only)
 size_t ddpm3d_ccl_workspace_bytes(int D, int H, int W);

@@ -120,6 +120,9 @@ MSSSIM_MAX_SCALES = 5   # DDPM3D_MSSSIM_MAX_SCALES: scales of ddpm3d_msssim3d
 # DDPM3D_ROI_*: columns of a ddpm3d_roi_moments record, and the limits of a region index
 (ROI_N, ROI_SUM_X, ROI_SUM_SQ_X, ROI_MIN_X, ROI_MAX_X, ROI_SUM_E, ROI_SUM_ABS_E, ROI_SUM_SQ_E, ROI_REC) = range(9)
 ROI_MAX_REGIONS, ROI_CHUNK = 4096, 4096
+# DDPM3D_TEX_*: the most grey levels of ddpm3d_roi_texture and the columns of its side counters
+TEX_MAX_LEVELS = 64
+(TEX_N, TEX_BELOW, TEX_ABOVE, TEX_PAIRS, TEX_REC) = range(5)
 CCL_TILE = (8, 8, 64)   # DDPM3D_CCL_TILE_D / _H / _W: the brick one workgroup of ddpm3d_label_components labels in LDS
 PEAK_MAX_RADIUS = 8     # DDPM3D_PEAK_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_sphere_mean's footprint
 SMOOTH_MAX_RADIUS = 16  # DDPM3D_SMOOTH_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_gauss_smooth's taps
@@ -248,6 +251,8 @@ EXPORTS = {
                                   _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_roi_moments_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(RoiIndex)]),
     "ddpm3d_roi_moments": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.POINTER(RoiIndex), _fp, C.c_size_t, _fp, _fp]),
+    "ddpm3d_roi_texture": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(RoiIndex), _fp, _fp, _fp, C.c_int, _fp, _fp, _fp,
+                                     _fp]),
     "ddpm3d_label_components_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ddpm3d_label_components": (C.c_int, [_fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp,
                                           C.c_size_t, _fp, _fp]),

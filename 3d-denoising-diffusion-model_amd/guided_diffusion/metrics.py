@@ -35,6 +35,11 @@ pred_xstart, one call of ddpm3d_trace_moments (csrc/trace.hip) per step and no h
 records(); trace_figures turns pooled records into PSNR, NRMSE, MAE, bias, mean, std, delta_rms and clipped per step
 on the host.
 
+Per-region texture: roi_texture is one call of ddpm3d_roi_texture (csrc/texture.hip) that builds the
+grey-level co-occurrence matrix, the grey-level histogram and the side counters of every region of a region index,
+texture_figures takes Haralick's figures from them on the host as IBSI defines them (contrast, joint entropy, inverse
+difference moment, ...), roi_report(..., texture=...) adds them to both of its blocks.
+
 Credible intervals: interval_figures scores two per-voxel quantile maps of
 uncertainty.draw_quantiles against the target: the share of voxels the interval covers and its mean width.
 """
@@ -480,9 +485,24 @@ class RoiIndex:
         self._dev = torch.tensor([offsets, chunks], dtype=torch.int64).to(self.device)
         self.desc = H.RoiIndex(len(self.labels), offsets[-1], self._host, H.ptr(self._dev[0]), H.ptr(self._dev[1]),
                                H.ptr(index))
+        self._region_of = None
 
     def __len__(self):
         return len(self.labels)
+
+    def region_of(self):
+        """The dense map ddpm3d_roi_texture reads: a device int16 tensor of the volume's shape holding ordinal + 1 of
+        the voxel's region in this index, 0 for a voxel of none.  Built on first use with torch ops from `index` and
+        `counts` and cached: it costs 2 bytes per voxel for as long as the index lives."""
+        if self._region_of is None:
+            with torch.cuda.device(self.device):
+                ordinal = torch.repeat_interleave(
+                    torch.arange(1, len(self.labels) + 1, dtype=torch.int16, device=self.device),
+                    torch.tensor(self.counts, dtype=torch.int64, device=self.device))
+                dense = torch.zeros(self.voxels, dtype=torch.int16, device=self.device)
+                dense[self.index] = ordinal
+                self._region_of = dense.view(self.shape)
+        return self._region_of
 
 
 def roi_index(labels, keep=None):
@@ -515,10 +535,8 @@ def roi_index(labels, keep=None):
         return RoiIndex(labels.shape, found.tolist(), counts.tolist(), at[order].contiguous())
 
 
-def roi_moments(estimate, index, target=None):
-    """ddpm3d_roi_moments of a (D, H, W) or (K, D, H, W) estimate over a region index: one launch, one
-    device-to-host copy.  -> the R records of the regions, each a list of H.ROI_REC floats (columns H.ROI_*; the
-    three error columns are 0 without a target); a list of K such lists for a (K, D, H, W) estimate."""
+def _roi_moments_device(estimate, index, target=None):
+    """roi_moments' checks and launch: the (K, R, H.ROI_REC) fp64 records, still on the device"""
     H.require_device(estimate, "estimate")
     if estimate.dim() not in (3, 4) or tuple(estimate.shape[-3:]) != index.shape or estimate.device != index.device:
         raise ValueError("roi_moments: estimate of shape %s on %s against an index of a %s volume on %s"
@@ -538,7 +556,14 @@ def roi_moments(estimate, index, target=None):
         out = torch.empty((K, len(index), H.ROI_REC), dtype=torch.float64, device=index.device)
         H.check(lib.ddpm3d_roi_moments(H.ptr(estimate), H.ptr(target), K, index.voxels, index.desc, H.ptr(ws),
                                        ws.numel() * 8, H.ptr(out), H.stream()))
-        rec = out.cpu().tolist()                       # the one device-to-host copy (it waits for the stream)
+    return out
+
+
+def roi_moments(estimate, index, target=None):
+    """ddpm3d_roi_moments of a (D, H, W) or (K, D, H, W) estimate over a region index: one launch, one
+    device-to-host copy.  -> the R records of the regions, each a list of H.ROI_REC floats (columns H.ROI_*; the
+    three error columns are 0 without a target); a list of K such lists for a (K, D, H, W) estimate."""
+    rec = _roi_moments_device(estimate, index, target).cpu().tolist()   # the one device-to-host copy (it waits)
     return rec if estimate.dim() == 4 else rec[0]
 
 
@@ -556,7 +581,7 @@ def _region(rec):
 
 
 def roi_figures(records, target_records=None, labels=None, background=None, draw_records=None, *, spacing=None,
-                peaks=None, target_peaks=None, draw_peaks=None):
+                peaks=None, target_peaks=None, draw_peaks=None, texture=None, target_texture=None, draw_texture=None):
     """Records to figures, on the host: {label: figures} for the R records of one estimate (roi_moments' return).
     Per region n, mean, std (population), min, max, cov = std / mean.  With target_records, the target's own records
     (roi_moments(target, index)) beside records taken against that target: mean_bias, mean_bias_rel, max_bias_rel,
@@ -568,7 +593,10 @@ def roi_figures(records, target_records=None, labels=None, background=None, draw
     three numbers): volume_ml = n s0 s1 s2 / 1000 (the MTV of a lesion), tlg = volume_ml * mean and, with
     target_records, tlg_bias_rel; peaks (R values, roi_peak's return): peak and, with target_peaks, peak_bias_rel =
     (peak - target peak) / target peak; draw_peaks (K >= 2 lists of R values): draw_peaks and peak_std (sample std,
-    ddof = 1)."""
+    ddof = 1); texture (R dicts, texture_figures' return): texture and, with target_texture (the target's own R
+    dicts), texture_rel = (f - target's f) / target's f per figure, None where either is None or the denominator is
+    0; draw_texture (K >= 2 lists of R dicts): draw_texture and texture_std (sample std per figure, ddof = 1, over
+    the draws where it is defined)."""
     R = len(records)
     labels = list(range(R)) if labels is None else [int(v) for v in labels]
     if len(labels) != R or (target_records is not None and len(target_records) != R):
@@ -582,6 +610,10 @@ def roi_figures(records, target_records=None, labels=None, background=None, draw
         raise ValueError("roi_figures: peaks and target_peaks must hold %d values" % R)
     if draw_peaks is not None and (len(draw_peaks) < 2 or any(len(d) != R for d in draw_peaks)):
         raise ValueError("roi_figures: draw_peaks must be K >= 2 lists of %d values" % R)
+    if any(t is not None and len(t) != R for t in (texture, target_texture)):
+        raise ValueError("roi_figures: texture and target_texture must hold %d dicts" % R)
+    if draw_texture is not None and (len(draw_texture) < 2 or any(len(d) != R for d in draw_texture)):
+        raise ValueError("roi_figures: draw_texture must be K >= 2 lists of %d dicts" % R)
     voxel_ml = None if spacing is None else math.prod(_check_spacing(spacing, "roi_figures")) / 1000.0
     figs = [_region(r) for r in records]
     tfigs = None if target_records is None else [_region(r) for r in target_records]
@@ -633,12 +665,20 @@ def roi_figures(records, target_records=None, labels=None, background=None, draw
                 K = len(draw_peaks)
                 centre = math.fsum(f["draw_peaks"]) / K
                 f["peak_std"] = math.sqrt(math.fsum((v - centre) ** 2 for v in f["draw_peaks"]) / (K - 1))
+        if texture is not None:
+            f["texture"] = texture[i]
+            if target_texture is not None:
+                f["texture_rel"] = _texture_rel(texture[i], target_texture[i])
+        if draw_texture is not None:
+            f["draw_texture"] = [d[i] for d in draw_texture]
+            f["texture_std"] = _texture_std(f["draw_texture"])
         out[label] = f
     return out
 
 
 def roi_report(estimate, target, index, labels=None, background=None, draws=None, *, spacing=None, volume_mm3=None,
-               keep=None, draw_peaks=None, footprint=None, target_peaks=None):
+               keep=None, draw_peaks=None, footprint=None, target_peaks=None, texture=None, draw_texture=None,
+               target_texture=None):
     """Region figures of one (D, H, W) estimate against the target: {label: {"n", "target": the target's own n,
     mean, std, min, max, cov, "estimate": roi_figures of the estimate}}.  labels names the regions (default: the
     index's own labels); draws is a (K, D, H, W) device tensor of K >= 2 posterior draws or their K lists of records
@@ -648,8 +688,22 @@ def roi_report(estimate, target, index, labels=None, background=None, draws=None
     draws given as a tensor, or draw_peaks (K lists of roi_peak's values, for draws given as records), add draw_peaks
     and peak_std.  A caller that reports several estimates against one target passes the footprint it already has
     (sphere_footprint of the same spacing; volume_mm3 is then not given) and the target's peaks (roi_peak(target,
-    ...)) so that neither is computed again."""
+    ...)) so that neither is computed again.
+    With texture = {"bin_width": w, "levels": 64, "lower": 0.0} (fixed bin size: the same bins for the target and every
+    estimate, so that their figures are comparable; levels and lower are optional) both blocks gain "texture"
+    (texture_figures of roi_texture) and the estimate "texture_rel" against the target's; draws given as a tensor, or
+    draw_texture (K lists of texture_figures' R dicts, for draws given as records), add draw_texture and texture_std;
+    target_texture passes the target's own figures when the caller has them already.  Without texture the return is
+    what it was."""
     labels = index.labels if labels is None else labels
+    if texture is None and not (draw_texture is None and target_texture is None):
+        raise ValueError("roi_report: draw_texture and target_texture need texture")
+    if texture is not None:
+        if not isinstance(texture, dict) or set(texture) - {"levels", "bin_width", "lower"} or \
+                texture.get("bin_width") is None:
+            raise ValueError("roi_report: texture must be a dict with bin_width and optionally levels and lower "
+                             "(got %r)" % (texture,))
+        _check_texture("roi_report", texture.get("levels", 64), texture["bin_width"], texture.get("lower", 0.0))
     if spacing is None and not (volume_mm3 is None and keep is None and draw_peaks is None and footprint is None
                                 and target_peaks is None):
         raise ValueError("roi_report: volume_mm3, keep, draw_peaks, footprint and target_peaks need a spacing")
@@ -666,6 +720,13 @@ def roi_report(estimate, target, index, labels=None, background=None, draws=None
         tmore = dict(spacing=spacing, peaks=tpeaks)
         more = dict(spacing=spacing, peaks=roi_peak(estimate, index, footprint, keep=keep), target_peaks=tpeaks,
                     draw_peaks=draw_peaks)
+    if texture is not None:
+        ttex = texture_figures(roi_texture(target, index, **texture)) if target_texture is None else target_texture
+        if draw_texture is None and isinstance(draws, torch.Tensor):
+            draw_texture = texture_figures(roi_texture(draws, index, **texture))
+        tmore = dict(tmore, texture=ttex)
+        more = dict(more, texture=texture_figures(roi_texture(estimate, index, **texture)), target_texture=ttex,
+                    draw_texture=draw_texture)
     trec = roi_moments(target, index)
     if isinstance(draws, torch.Tensor):
         draws = roi_moments(draws, index)
@@ -673,6 +734,156 @@ def roi_report(estimate, target, index, labels=None, background=None, draws=None
                       background=background, draw_records=draws, **more)
     tgt = roi_figures(trec, labels=labels, **tmore)
     return {label: {"n": tgt[label]["n"], "target": tgt[label], "estimate": est[label]} for label in labels}
+
+
+# ----------------------------------------------------------------- per-region texture
+TEXTURE_DIRECTIONS = 13
+# what keeps the region's maximum inside the top bin of fixed-bin-number discretisation: with inv_w = levels (1 - 8 u)
+# / (max - min) rounded to fp32 (u = 2^-24), the fp32 product (max - min) * inv_w is at most levels (1 - 8 u)(1 + u)^2 <
+# levels (1 - 2 u), which lies below the fp32 predecessor of `levels`
+_FBN_SHRINK = 1.0 - 2.0 ** -21
+
+
+class RoiTexture:
+    """roi_texture's return: the integer matrices of ddpm3d_roi_texture as numpy int64 arrays, `glcm` (K, R, levels,
+    levels), `hist` (K, R, levels) and `counts` (K, R, H.TEX_REC; columns H.TEX_*), the discretisation `lo` and
+    `inv_w` (K, R) float32, `levels`, the index's `labels`, and `batched`: whether the estimate was a (K, D, H, W)
+    stack (K = 1 otherwise)."""
+
+    def __init__(self, glcm, hist, counts, lo, inv_w, levels, labels, batched):
+        self.glcm, self.hist, self.counts, self.lo, self.inv_w = glcm, hist, counts, lo, inv_w
+        self.levels, self.labels, self.batched = levels, labels, batched
+
+
+def _check_texture(what, levels, bin_width, lower):
+    """(levels, bin_width or None, lower) of a texture request, refused on the host"""
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 2 <= levels <= H.TEX_MAX_LEVELS:
+        raise ValueError("%s: levels must be an integer in 2..%d (got %r)" % (what, H.TEX_MAX_LEVELS, levels))
+    number = lambda v: (not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+                        and math.isfinite(v))
+    if bin_width is not None and not (number(bin_width) and bin_width > 0 and 1.0 / float(bin_width) < 3.0e38):
+        raise ValueError("%s: bin_width must be a positive finite number or None (got %r)" % (what, bin_width))
+    if not number(lower):
+        raise ValueError("%s: lower must be a finite number (got %r)" % (what, lower))
+    return levels, None if bin_width is None else float(bin_width), float(lower)
+
+
+def roi_texture(estimate, index, *, levels=64, bin_width=None, lower=0.0):
+    """The grey-level co-occurrence matrices, grey-level histograms and side counters of every region of the index
+    in a (D, H, W) or (K, D, H, W) estimate: one call of ddpm3d_roi_texture (csrc/texture.hip; include/ddpm3d.h has
+    the definition: 13 directions at distance 1, merged, symmetric) and one device-to-host copy.  A value x of region
+    r gets the grey level min(max(floor((x - lo) * inv_w), 0), levels - 1) in fp32.  With bin_width (fixed bin size,
+    what IBSI recommends for SUV) lo = lower and inv_w = 1 / bin_width for every region and estimate, so that the
+    figures of several volumes are comparable.  Without it (fixed bin number) lo is the region's own minimum in that
+    estimate and inv_w = levels (1 - 2^-21) / (max - min), 0 for a flat region, both from one ddpm3d_roi_moments
+    launch and kept on the device: the factor keeps the maximum inside the top bin instead of on its upper edge.
+    Uses index.region_of().  -> RoiTexture"""
+    levels, bin_width, lower = _check_texture("roi_texture", levels, bin_width, lower)
+    H.require_device(estimate, "estimate")
+    if estimate.dim() not in (3, 4) or tuple(estimate.shape[-3:]) != index.shape or estimate.device != index.device:
+        raise ValueError("roi_texture: estimate of shape %s on %s against an index of a %s volume on %s"
+                         % (tuple(estimate.shape), estimate.device, index.shape, index.device))
+    K = int(estimate.shape[0]) if estimate.dim() == 4 else 1
+    if not 1 <= K <= H.MAX_DRAWS:
+        raise ValueError("roi_texture: %d estimates (1..%d)" % (K, H.MAX_DRAWS))
+    if max(index.shape) > 65535 or index.voxels > 2 ** 31 - 1:
+        raise ValueError("roi_texture: a volume of %s (every extent at most 65535, at most 2^31 - 1 voxels)"
+                         % (index.shape,))
+    lib = H.load()
+    R, D, Hh, W = len(index), index.shape[0], index.shape[1], index.shape[2]
+    sizes = [K * R * levels * levels, K * R * levels, K * R * H.TEX_REC, K * R]
+    with torch.cuda.device(index.device):
+        # one buffer, so that one copy brings everything back: the three outputs, then lo and inv_w as 2 K R floats
+        buf = torch.empty(sum(sizes), dtype=torch.int64, device=index.device)
+        glcm, hist, counts, tail = torch.split(buf, sizes)
+        params = tail.view(torch.float32).view(2, K, R)
+        if bin_width is not None:
+            params[0] = float(np.float32(lower))
+            params[1] = float(np.float32(1.0 / bin_width))
+        else:
+            rec = _roi_moments_device(estimate, index)
+            mn, mx = rec[..., H.ROI_MIN_X], rec[..., H.ROI_MAX_X]
+            some = mx > mn
+            params[0] = torch.where(rec[..., H.ROI_N] > 0, mn, torch.zeros_like(mn)).to(torch.float32)
+            params[1] = torch.where(some, (levels * _FBN_SHRINK) / torch.where(some, mx - mn, torch.ones_like(mn)),
+                                    torch.zeros_like(mn)).to(torch.float32)
+        H.check(lib.ddpm3d_roi_texture(H.ptr(estimate), K, D, Hh, W, index.desc, H.ptr(index.region_of()),
+                                       H.ptr(params[0]), H.ptr(params[1]), levels, H.ptr(glcm), H.ptr(hist),
+                                       H.ptr(counts), H.stream()))
+        host = buf.cpu().numpy()                       # the one device-to-host copy (it waits for the stream)
+    glcm, hist, counts, tail = np.split(host, np.cumsum(sizes)[:-1])
+    params = tail.view(np.float32).reshape(2, K, R)
+    return RoiTexture(glcm.reshape(K, R, levels, levels), hist.reshape(K, R, levels), counts.reshape(K, R, H.TEX_REC),
+                      params[0].copy(), params[1].copy(), levels, list(index.labels), estimate.dim() == 4)
+
+
+TEXTURE_FIGURES = ("joint_entropy", "angular_second_moment", "contrast", "dissimilarity", "inverse_difference",
+                   "inverse_difference_moment", "joint_average", "joint_variance", "correlation", "hist_entropy",
+                   "hist_uniformity", "p10", "p50", "p90", "clamped")
+
+
+def _texture_region(glcm, hist, counts, lo, inv_w, levels):
+    """The figures of one region from its integer matrices, in fp64 (p = C / sum C, i and j 0-based)"""
+    n, pairs = int(counts[H.TEX_N]), int(counts[H.TEX_PAIRS])
+    out = {"n": n, "pairs": pairs}
+    if pairs == 0:
+        out.update({k: None for k in TEXTURE_FIGURES})
+        return out
+    p = glcm.astype(np.float64) / float(glcm.sum())
+    i = np.arange(levels, dtype=np.float64)[:, None]
+    j = np.arange(levels, dtype=np.float64)[None, :]
+    d = np.abs(i - j)
+    some = p > 0
+    out["joint_entropy"] = float(-np.sum(p[some] * np.log2(p[some])))
+    out["angular_second_moment"] = float(np.sum(p * p))
+    out["contrast"] = float(np.sum(d * d * p))
+    out["dissimilarity"] = float(np.sum(d * p))
+    out["inverse_difference"] = float(np.sum(p / (1.0 + d)))
+    out["inverse_difference_moment"] = float(np.sum(p / (1.0 + d * d)))
+    mu = float(np.sum(i * p))
+    var = float(np.sum((i - mu) ** 2 * p))
+    out["joint_average"], out["joint_variance"] = mu, var
+    out["correlation"] = None if var == 0 else (float(np.sum(i * j * p)) - mu * mu) / var
+    q = hist.astype(np.float64) / n
+    out["hist_entropy"] = float(-np.sum(q[q > 0] * np.log2(q[q > 0])))
+    out["hist_uniformity"] = float(np.sum(q * q))
+    cum = np.cumsum(hist.astype(np.int64))
+    for pct in (10, 50, 90):                           # the first bin whose cumulative count reaches pct % of n
+        g = int(np.argmax(cum * 100 >= pct * n))
+        out["p%d" % pct] = None if inv_w == 0 else float(lo) + (g + 0.5) / float(inv_w)
+    out["clamped"] = (int(counts[H.TEX_BELOW]) + int(counts[H.TEX_ABOVE])) / n
+    return out
+
+
+def texture_figures(result):
+    """Haralick's figures as IBSI defines them, from roi_texture's integer matrices, on the host in fp64: per region a
+    dict with n (counted voxels), pairs, and from p = C / sum C: joint_entropy = -sum p log2 p,
+    angular_second_moment = sum p^2, contrast = sum (i - j)^2 p, dissimilarity = sum |i - j| p, inverse_difference =
+    sum p / (1 + |i - j|), inverse_difference_moment = sum p / (1 + (i - j)^2), joint_average mu = sum i p,
+    joint_variance = sum (i - mu)^2 p, correlation = (sum i j p - mu^2) / variance (None for variance 0); from the
+    histogram q = hist / n: hist_entropy, hist_uniformity = sum q^2 and p10, p50, p90 in the volume's units (lo +
+    (g + 0.5) / inv_w for the first bin g whose cumulative count reaches that share of n; None for inv_w = 0); and
+    clamped, the share of counted voxels outside the bins.  Every figure of a region without pairs is None.  -> a list
+    of R dicts, K such lists for a (K, D, H, W) estimate."""
+    rows = [[_texture_region(result.glcm[k, r], result.hist[k, r], result.counts[k, r], result.lo[k, r],
+                             result.inv_w[k, r], result.levels) for r in range(result.glcm.shape[1])]
+            for k in range(result.glcm.shape[0])]
+    return rows if result.batched else rows[0]
+
+
+def _texture_rel(f, t):
+    """(f - t) / t per figure; None where either is None or t is 0"""
+    return {k: None if f[k] is None or t[k] is None else _ratio(f[k] - t[k], t[k]) for k in f}
+
+
+def _texture_std(draws):
+    """the sample std (ddof = 1) per figure over the draws where it is defined; None with fewer than two"""
+    out = {}
+    for k in draws[0]:
+        v = [d[k] for d in draws if d[k] is not None]
+        centre = math.fsum(v) / len(v) if v else 0.0
+        out[k] = math.sqrt(math.fsum((x - centre) ** 2 for x in v) / (len(v) - 1)) if len(v) >= 2 else None
+    return out
 
 
 # ----------------------------------------------------------------- SUVpeak, MTV, TLG (DESIGN.md 3.12)

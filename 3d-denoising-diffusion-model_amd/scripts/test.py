@@ -86,6 +86,16 @@ non-local means (guided_diffusion/metrics.py gaussian_smooth, nlm) and score
 the two like the input and the written volume: the entry "baselines" of
 metrics_<name>.json and, with regions, "gaussian" and "nlm" beside "input" in
 every region.  The filtered volumes are not written;
+`--roi_texture_bin W` (the fixed bin width in the target's units, e.g. 0.25 for
+SUV; needs `--target_samples` and regions; `--roi_texture_levels N`, 2..64,
+default 64, and `--roi_texture_lower L`, default 0) adds "texture" to every
+region's target, input, baseline and denoised figures: contrast, joint entropy,
+inverse difference moment and the other second-order figures of the region's
+grey-level co-occurrence matrix as IBSI defines them (13 directions at distance
+1, merged; guided_diffusion/metrics.py roi_texture, texture_figures), with
+"texture_rel" against the target's and, with `--num_draws`, their spread over
+the draws: whether the texture inside a lesion survives, which a smoothing
+filter's first-order figures do not show;
 `--msssim_scales N` (1..5; needs `--target_samples` and every extent to be at
 least 11 after N - 1 halvings) adds "msssim", the multi-scale SSIM over N
 scales (guided_diffusion/metrics.py msssim3d), to the "denoised", "input" and
@@ -228,6 +238,11 @@ def create_argparser():
     parser.add_argument("--consistency_weight", type=float, default=None, metavar="W")
     parser.add_argument("--consistency_stop_t", type=int, default=None, metavar="T")
     parser.add_argument("--draw_quantiles", type=float, nargs="+", default=None, metavar="Q")
+    # per-region texture (grey-level co-occurrence figures, IBSI): the fixed bin width in the target's units (e.g. 0.25
+    # for SUV; giving it turns the feature on), the number of grey levels (default 64) and the first bin's lower edge
+    parser.add_argument("--roi_texture_bin", type=float, default=None, metavar="W")
+    parser.add_argument("--roi_texture_levels", type=int, default=None, metavar="N")
+    parser.add_argument("--roi_texture_lower", type=float, default=None, metavar="L")
     return parser
 
 
@@ -252,6 +267,7 @@ def main(argv=None):
     _check_regrid(parser, args)
     _check_consistency(parser, args)
     args.peak = _check_spacing(parser, args)
+    args.texture = _check_texture(parser, args)
     args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
     vol = _plan_regrid(parser, args, vol)
@@ -453,6 +469,34 @@ def _check_segmentation(parser, args):
         parser.error("--roi_threshold must be a finite number (got %r)" % args.roi_threshold)
     if args.roi_threshold_frac is not None and not 0.0 < args.roi_threshold_frac < 1.0:
         parser.error("--roi_threshold_frac must lie in (0, 1) (got %r)" % args.roi_threshold_frac)
+
+
+def _check_texture(parser, args):
+    """--roi_texture_bin / _levels / _lower, checked before any file is read: None without the first, else
+    roi_report's texture= dict"""
+    if args.roi_texture_bin is None:
+        for flag, value in (("--roi_texture_levels", args.roi_texture_levels),
+                            ("--roi_texture_lower", args.roi_texture_lower)):
+            if value is not None:
+                parser.error("%s needs --roi_texture_bin: the bin width is what turns the texture figures on" % flag)
+        return None
+    levels = 64 if args.roi_texture_levels is None else args.roi_texture_levels
+    lower = 0.0 if args.roi_texture_lower is None else args.roi_texture_lower
+    if not (np.isfinite(args.roi_texture_bin) and args.roi_texture_bin > 0):
+        parser.error("--roi_texture_bin must be a positive finite number (got %r)" % args.roi_texture_bin)
+    if not 2 <= levels <= _hip.TEX_MAX_LEVELS:
+        parser.error("--roi_texture_levels must be in 2..%d (got %d)" % (_hip.TEX_MAX_LEVELS, levels))
+    if not np.isfinite(lower):
+        parser.error("--roi_texture_lower must be a finite number (got %r)" % lower)
+    if not args.target_samples:
+        parser.error("--roi_texture_bin needs --target_samples: its figures are taken per region against the target")
+    if not (args.roi_labels or _segmenting(args)):
+        parser.error("--roi_texture_bin needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
+    try:                                       # what roi_texture itself would refuse later (a width whose inverse overflows)
+        metrics._check_texture("--roi_texture_bin", int(levels), float(args.roi_texture_bin), float(lower))
+    except ValueError as e:
+        parser.error(str(e))
+    return {"bin_width": float(args.roi_texture_bin), "levels": int(levels), "lower": float(lower)}
 
 
 def _check_spacing(parser, args):
@@ -760,13 +804,21 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
     if peak is not None:                       # the footprint and the target's peaks once, for both reports
         more = {"spacing": peak["spacing"], "keep": keep, "footprint": peak["footprint"],
                 "target_peaks": metrics.roi_peak(tgt, index, peak["footprint"], keep=keep)}
+    texture = getattr(args, "texture", None)
+    if texture is not None:                    # the target's own figures once, for every report
+        more.update(texture=texture,
+                    target_texture=metrics.texture_figures(metrics.roi_texture(tgt, index, **texture)))
     records = draw_found = None
     if draws is not None:
         records, draw_found = [], []
         if peak is not None:
             more["draw_peaks"] = []
+        if texture is not None:
+            more["draw_texture"] = []
         for d in draws:
             records.append(metrics.roi_moments(d, index))
+            if texture is not None:
+                more["draw_texture"].append(metrics.texture_figures(metrics.roi_texture(d, index, **texture)))
             if peak is not None:
                 more["draw_peaks"].append(metrics.roi_peak(d, index, peak["footprint"], keep=keep))
             if seg is not None:
@@ -776,9 +828,9 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
                 draw_found.append({"n_found": found["n_found"], "false_positives": found["false_positives"]})
     den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records, **more)
     inp_rep = metrics.roi_report(inp, tgt, index, background=background,
-                                 **{k: v for k, v in more.items() if k != "draw_peaks"})
+                                 **{k: v for k, v in more.items() if k not in ("draw_peaks", "draw_texture")})
     base_rep = {name: metrics.roi_report(x, tgt, index, background=background,
-                                         **{k: v for k, v in more.items() if k != "draw_peaks"})
+                                         **{k: v for k, v in more.items() if k not in ("draw_peaks", "draw_texture")})
                 for name, x in (baselines or {}).items()}
     regions = {str(label): {"n": den_rep[label]["n"], "target": den_rep[label]["target"],
                             "input": inp_rep[label]["estimate"],
@@ -788,18 +840,27 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
     show = lambda v: "n/a" if v is None else "%.5g" % v
     for label in index.labels[:20]:
         r = regions[str(label)]
-        logger.log("  region %d (%d voxels): mean %s target, %s input, %s denoised; max %s / %s / %s%s%s"
+        logger.log("  region %d (%d voxels): mean %s target, %s input, %s denoised; max %s / %s / %s%s%s%s"
                    % (label, r["n"], show(r["target"]["mean"]), show(r["input"]["mean"]), show(r["denoised"]["mean"]),
                       show(r["target"]["max"]), show(r["input"]["max"]), show(r["denoised"]["max"]),
                       "; mean over draws +- %s" % show(r["denoised"]["mean_std"]) if records else "",
                       "; peak %s / %s / %s" % (show(r["target"]["peak"]), show(r["input"]["peak"]),
-                                               show(r["denoised"]["peak"])) if peak is not None else ""))
+                                               show(r["denoised"]["peak"])) if peak is not None else "",
+                      "".join("; %s %s / %s / %s" % ((k,) + tuple(show(r[w]["texture"][k])
+                                                                  for w in ("target", "input", "denoised")))
+                              for k in ("contrast", "joint_entropy")) if texture is not None else ""))
     if len(index.labels) > 20:
         logger.log("  (%d more regions in the metrics file)" % (len(index.labels) - 20))
     spaced = {}
     if peak is not None:
         spaced = {"voxel_spacing": list(args.voxel_spacing), "peak_volume_mm3": peak["footprint"].volume_mm3,
                   "peak_taps": peak["footprint"].taps}
+    if texture is not None:
+        spaced["texture"] = dict(texture, directions=metrics.TEXTURE_DIRECTIONS)
+        if any((r["target"]["texture"]["clamped"] or 0.0) > 0.05 for r in regions.values()):
+            logger.log("  WARNING: more than 5 %% of a region of the target falls outside the grey levels: choose "
+                       "--roi_texture_bin (and --roi_texture_levels / --roi_texture_lower) so that %d bins span the "
+                       "target's values" % texture["levels"])
     if seg is None:
         return {"labels": args.roi_labels, "background": background, "regions": regions, **spaced}
     return {"labels": labels_path, "background": None, "threshold": seg["threshold"],

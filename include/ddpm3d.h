@@ -966,6 +966,41 @@ size_t ddpm3d_roi_moments_workspace_bytes(int B, const ddpm3d_roi_index* index);
 int ddpm3d_roi_moments(const float* est, const float* target, int B, int64_t voxels, const ddpm3d_roi_index* index,
                        void* ws, size_t ws_bytes, double* out, void* stream);
 /*
+ * Per-region texture: grey-level co-occurrence matrices (GLCM; Haralick, Shanmugam, Dinstein, IEEE Trans SMC 1973)
+ * as the Image Biomarker Standardisation Initiative defines them (Zwanenburg et al., Radiology 2020; 295: 328;
+ * "3D, merged", distance 1), over the same region index (added within ABI 13; the reference has no metric code).
+ *   est        [B][D][H][W] fp32, W innermost, B in 1..DDPM3D_MAX_DRAWS
+ *   region_of  DEVICE int16 [D][H][W]: ordinal + 1 of the voxel's region in `index`, 0 for a voxel of none
+ *   lo, inv_w  DEVICE fp32 [B][R]: the first bin's lower edge and 1 / bin width of estimate b in region r
+ *   levels     grey levels, 2..DDPM3D_TEX_MAX_LEVELS
+ * Discretisation: a voxel value x of estimate b in region r gets the grey level
+ *   g = min(max((int)floorf((x - lo[b][r]) * inv_w[b][r]), 0), levels - 1),
+ * the subtraction and the product each rounded to fp32 (the comparisons are made on the floored float, so any value is
+ * safe, +-inf included); a voxel whose (x - lo) * inv_w is NaN is not counted at all.
+ * Co-occurrence: the 13 direction vectors (dz, dy, dx) in {-1, 0, 1}^3 lexicographically above (0, 0, 0).  An
+ * unordered pair {v, v + d} counts iff both voxels lie inside the volume, v is an entry of region r, region_of[v + d]
+ * = r + 1 and both are counted voxels; it adds 1 to C[g_v][g_u] and 1 to C[g_u][g_v], so C is symmetric, sums to
+ * twice the pairs and holds all 13 directions.
+ *   glcm    [B][R][levels][levels] uint64 out (device memory)
+ *   hist    [B][R][levels] uint64 out: the counted voxels per grey level
+ *   counts  [B][R][DDPM3D_TEX_REC] uint64 out: N counted voxels, BELOW / ABOVE the counted voxels whose unclamped bin
+ *           is < 0 / >= levels, PAIRS
+ * The entry zeroes the three outputs itself on `stream`, then one launch: a workgroup serves consecutive chunks of
+ * DDPM3D_ROI_CHUNK entries of one region for one estimate, keeps the matrix and the histogram in LDS as 32-bit
+ * counters, tests every neighbour's coordinates against the extents before any load (no load leaves the volume,
+ * whatever region_of holds; an index value outside [0, D * H * W) is skipped), finds a pair from its lower voxel only
+ * and adds its non-zero cells to the outputs with 64-bit integer atomics.  Integer sums have one right answer: the
+ * same bits on every run and for every launch geometry, and row b does not depend on B.  No floating-point atomics.
+ * Enqueue-only: it allocates nothing and does not synchronise.  Returns DDPM3D_EINVAL before any launch for a NULL
+ * pointer or a NULL pointer inside index, B outside 1..DDPM3D_MAX_DRAWS, an extent outside 1..65535 or D * H * W above
+ * 2^31 - 1, levels outside 2..DDPM3D_TEX_MAX_LEVELS, and an index that ddpm3d_roi_moments would refuse.
+ */
+#define DDPM3D_TEX_MAX_LEVELS 64
+enum { DDPM3D_TEX_N = 0, DDPM3D_TEX_BELOW = 1, DDPM3D_TEX_ABOVE = 2, DDPM3D_TEX_PAIRS = 3, DDPM3D_TEX_REC = 4 };
+int ddpm3d_roi_texture(const float* est, int B, int D, int H, int W, const ddpm3d_roi_index* index,
+                       const int16_t* region_of, const float* lo, const float* inv_w, int levels,
+                       uint64_t* glcm, uint64_t* hist, uint64_t* counts, void* stream);
+/*
  * Connected-component labelling of a thresholded volume (added within ABI 13; the reference has no such code): the
  * mechanical lesion definition of PET, "voxels above an SUV threshold, grouped into connected components", whose
  * labels feed the region index above.
