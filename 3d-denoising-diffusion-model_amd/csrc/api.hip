@@ -1170,6 +1170,111 @@ int ddpm3d_roi_texture(const float* est, int B, int D, int H, int W, const ddpm3
                     "roi_texture");
 }
 
+// ------------------------------------------------- radial spectra and shell correlation (added within ABI 13)
+static bool spec_shape_ok(int B, int D, int H, int W) {
+    const int lim = DDPM3D_SPEC_MAX_EXTENT;
+    return B >= 1 && B <= DDPM3D_MAX_DRAWS && D >= 2 && H >= 2 && W >= 2 && D <= lim && H <= lim && W <= lim;
+}
+static int spec_shape_check(const char* what, int B, int D, int H, int W) {
+    if (B < 1 || B > DDPM3D_MAX_DRAWS)
+        return fail(DDPM3D_EINVAL, "%s: B=%d volumes (1..%d)", what, B, DDPM3D_MAX_DRAWS);
+    if (!spec_shape_ok(B, D, H, W))
+        return fail(DDPM3D_EINVAL, "%s: bad volume (D=%d H=%d W=%d; 2..%d each)", what, D, H, W,
+                    DDPM3D_SPEC_MAX_EXTENT);
+    return DDPM3D_OK;
+}
+static int spec_axes_check(const char* what, const ddpm3d_dft_axis* axes, int D, int H, int W) {
+    if (!axes) return fail(DDPM3D_EINVAL, "%s: null pointer", what);
+    const int n[3] = {D, H, W}, rows[3] = {D, H, W / 2 + 1};
+    for (int a = 0; a < 3; ++a) {
+        if (!axes[a].cos_t || !axes[a].sin_t) return fail(DDPM3D_EINVAL, "%s: null table in axes[%d]", what, a);
+        if (axes[a].n != n[a] || axes[a].rows != rows[a])
+            return fail(DDPM3D_EINVAL, "%s: axes[%d] is %d rows of n=%d, the shape wants %d rows of n=%d", what, a,
+                        axes[a].rows, axes[a].n, rows[a], n[a]);
+    }
+    return DDPM3D_OK;
+}
+
+size_t ddpm3d_dft3_workspace_bytes(int B, int D, int H, int W) {
+    return spec_shape_ok(B, D, H, W) ? ddpm3d_dft_workspace_bytes(B, D, H, W) : 0;
+}
+
+static int dft3_entry(const char* what, const float* vol, const float* pivot, int B, int D, int H, int W,
+                      const ddpm3d_dft_axis* axes, void* ws, size_t ws_bytes, float* re, float* im, int only,
+                      void* stream) {
+    if (!vol || !re || !im) return fail(DDPM3D_EINVAL, "%s: null pointer", what);
+    int rc = spec_shape_check(what, B, D, H, W);
+    if (rc != DDPM3D_OK) return rc;
+    rc = spec_axes_check(what, axes, D, H, W);
+    if (rc != DDPM3D_OK) return rc;
+    rc = ws_ok(what, ddpm3d_dft_workspace_bytes(B, D, H, W), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_dft3(vol, pivot, B, D, H, W, axes, ws, re, im, only, (hipStream_t)stream), what);
+}
+
+int ddpm3d_dft3(const float* vol, const float* pivot, int B, int D, int H, int W, const ddpm3d_dft_axis axes[3],
+                void* ws, size_t ws_bytes, float* re, float* im, void* stream) {
+    return dft3_entry("dft3", vol, pivot, B, D, H, W, axes, ws, ws_bytes, re, im, -1, stream);
+}
+
+int ddpm3d_dft3_pass(int pass, const float* vol, const float* pivot, int B, int D, int H, int W,
+                     const ddpm3d_dft_axis axes[3], void* ws, size_t ws_bytes, float* re, float* im, void* stream) {
+    if (pass < 0 || pass > 2) return fail(DDPM3D_EINVAL, "dft3_pass: pass %d (0 = W, 1 = H, 2 = D)", pass);
+    return dft3_entry("dft3_pass", vol, pivot, B, D, H, W, axes, ws, ws_bytes, re, im, pass, stream);
+}
+
+size_t ddpm3d_shell_sums_workspace_bytes(int B, const ddpm3d_roi_index* shells) {
+    int64_t chunks = 0;
+    return roi_index_check("shell_sums", B, shells, &chunks) == DDPM3D_OK ? ddpm3d_sp_workspace_bytes(B, chunks) : 0;
+}
+
+int ddpm3d_shell_sums(const float* xre, const float* xim, const float* yre, const float* yim, int B, int D, int H,
+                      int W, const ddpm3d_roi_index* shells, void* ws, size_t ws_bytes, double* out, void* stream) {
+    if (!xre || !xim || !out) return fail(DDPM3D_EINVAL, "shell_sums: null pointer");
+    if ((yre == nullptr) != (yim == nullptr))
+        return fail(DDPM3D_EINVAL, "shell_sums: yre and yim must both be given or both be NULL");
+    int rc = spec_shape_check("shell_sums", B, D, H, W);
+    if (rc != DDPM3D_OK) return rc;
+    int64_t chunks = 0;
+    rc = roi_index_check("shell_sums", B, shells, &chunks);
+    if (rc != DDPM3D_OK) return rc;
+    rc = ws_ok("shell_sums", ddpm3d_sp_workspace_bytes(B, chunks), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_shell_sums(xre, xim, yre, yim, B, D, H, W, *shells, chunks, (double*)ws, out,
+                                             (hipStream_t)stream),
+                    "shell_sums");
+}
+
+size_t ddpm3d_shell_spectrum_workspace_bytes(int B, int D, int H, int W, const ddpm3d_roi_index* shells,
+                                             int with_target) {
+    int64_t chunks = 0;
+    if (!spec_shape_ok(B, D, H, W) || roi_index_check("shell_spectrum", B, shells, &chunks) != DDPM3D_OK ||
+        shells->entries != (int64_t)D * H * (W / 2 + 1))
+        return 0;
+    return ddpm3d_spectrum_workspace_bytes(B, D, H, W, chunks, with_target != 0);
+}
+
+int ddpm3d_shell_spectrum(const float* est, const float* est_pivot, const float* target, const float* target_pivot,
+                          int B, int D, int H, int W, const ddpm3d_dft_axis axes[3], const ddpm3d_roi_index* shells,
+                          void* ws, size_t ws_bytes, double* out, void* stream) {
+    if (!est || !out) return fail(DDPM3D_EINVAL, "shell_spectrum: null pointer");
+    int rc = spec_shape_check("shell_spectrum", B, D, H, W);
+    if (rc != DDPM3D_OK) return rc;
+    rc = spec_axes_check("shell_spectrum", axes, D, H, W);
+    if (rc != DDPM3D_OK) return rc;
+    int64_t chunks = 0;
+    rc = roi_index_check("shell_spectrum", B, shells, &chunks);
+    if (rc != DDPM3D_OK) return rc;
+    if (shells->entries != (int64_t)D * H * (W / 2 + 1))
+        return fail(DDPM3D_EINVAL, "shell_spectrum: the shell index has %lld entries, the half spectrum %lld",
+                    (long long)shells->entries, (long long)D * H * (W / 2 + 1));
+    rc = ws_ok("shell_spectrum", ddpm3d_spectrum_workspace_bytes(B, D, H, W, chunks, target != nullptr), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_shell_spectrum(est, est_pivot, target, target ? target_pivot : nullptr, B, D, H, W,
+                                                 axes, *shells, chunks, ws, out, (hipStream_t)stream),
+                    "shell_spectrum");
+}
+
 // ------------------------------------------------- connected components (added within ABI 13)
 // a volume the dense kernels index with 32-bit voxel and row numbers: 1 or more each, D * H and D * H * W <= 2^31 - 1
 static bool volume_shape_ok(int D, int H, int W) {

@@ -135,6 +135,22 @@ hipError_t ddpm3d_launch_roi_moments(const float* est, const float* target, int 
 hipError_t ddpm3d_launch_roi_texture(const float* est, int B, int D, int H, int W, const ddpm3d_roi_index& ix,
                                      int64_t chunks, const int16_t* region_of, const float* lo, const float* inv_w,
                                      int levels, uint64_t* glcm, uint64_t* hist, uint64_t* counts, hipStream_t st);
+// spectrum.hip: the windowed 3-D DFT as three MFMA GEMM passes, the per-shell sums over a shell index cut into
+// `chunks` chunks, and the driver of both (the caller has checked the shapes, the axis tables, the descriptor's host
+// side and the workspaces; the workspace queries take valid shapes only).  only = 0, 1, 2 runs pass W, H or D alone, -1 all.
+struct ddpm3d_dft_axis;
+size_t ddpm3d_dft_workspace_bytes(int B, int D, int H, int W);
+hipError_t ddpm3d_launch_dft3(const float* vol, const float* pivot, int B, int D, int H, int W,
+                              const ddpm3d_dft_axis* axes, void* ws, float* re, float* im, int only, hipStream_t st);
+size_t ddpm3d_sp_workspace_bytes(int B, int64_t chunks);
+hipError_t ddpm3d_launch_shell_sums(const float* xre, const float* xim, const float* yre, const float* yim, int B,
+                                    int D, int H, int W, const ddpm3d_roi_index& ix, int64_t chunks, double* ws,
+                                    double* out, hipStream_t st);
+size_t ddpm3d_spectrum_workspace_bytes(int B, int D, int H, int W, int64_t chunks, int with_target);
+hipError_t ddpm3d_launch_shell_spectrum(const float* est, const float* est_pivot, const float* target,
+                                        const float* target_pivot, int B, int D, int H, int W,
+                                        const ddpm3d_dft_axis* axes, const ddpm3d_roi_index& ix, int64_t chunks,
+                                        void* ws, double* out, hipStream_t st);
 // ccl.hip: connected components of vol > threshold (the caller has checked the shape, the connectivity and the
 // workspace; the workspace query takes valid shapes only)
 size_t ddpm3d_ccl_workspace_bytes(int D, int H, int W);

@@ -152,6 +152,17 @@ class RoiIndex(C.Structure):
                 ("d_offsets", C.c_void_p), ("d_chunks", C.c_void_p), ("d_index", C.c_void_p)]
 
 
+SPEC_MAX_EXTENT = 2048  # DDPM3D_SPEC_MAX_EXTENT: the largest extent per axis of ddpm3d_dft3
+# DDPM3D_SP_*: columns of a ddpm3d_shell_sums record (column 5 is padding)
+(SP_N, SP_SUM_XX, SP_SUM_YY, SP_SUM_XY, SP_SUM_EE) = range(5)
+SP_REC = 6
+
+
+class DftAxis(C.Structure):
+    """struct ddpm3d_dft_axis: transform length, table rows and the device cos / sin tables [rows][n]"""
+    _fields_ = [("n", C.c_int32), ("rows", C.c_int32), ("cos_t", C.c_void_p), ("sin_t", C.c_void_p)]
+
+
 class NoiseKeyDesc(C.Structure):
     """struct ddpm3d_noise_key: seed, device stream ids [N], draw, device origins [N][3] or NULL, and the patch and
     canvas extents (D, H, W order) the origins refer to"""
@@ -253,6 +264,15 @@ EXPORTS = {
     "ddpm3d_roi_moments": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.POINTER(RoiIndex), _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_roi_texture": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(RoiIndex), _fp, _fp, _fp, C.c_int, _fp, _fp, _fp,
                                      _fp]),
+    "ddpm3d_dft3_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ddpm3d_dft3": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.POINTER(DftAxis), _fp, C.c_size_t, _fp, _fp, _fp]),
+    "ddpm3d_dft3_pass": (C.c_int, [C.c_int, _fp, _fp] + [C.c_int] * 4 + [C.POINTER(DftAxis), _fp, C.c_size_t, _fp, _fp,
+                                   _fp]),
+    "ddpm3d_shell_sums_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(RoiIndex)]),
+    "ddpm3d_shell_sums": (C.c_int, [_fp] * 4 + [C.c_int] * 4 + [C.POINTER(RoiIndex), _fp, C.c_size_t, _fp, _fp]),
+    "ddpm3d_shell_spectrum_workspace_bytes": (C.c_size_t, [C.c_int] * 4 + [C.POINTER(RoiIndex), C.c_int]),
+    "ddpm3d_shell_spectrum": (C.c_int, [_fp] * 4 + [C.c_int] * 4 + [C.POINTER(DftAxis), C.POINTER(RoiIndex), _fp,
+                                        C.c_size_t, _fp, _fp]),
     "ddpm3d_label_components_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ddpm3d_label_components": (C.c_int, [_fp, _fp, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp,
                                           C.c_size_t, _fp, _fp]),

@@ -40,6 +40,12 @@ grey-level co-occurrence matrix, the grey-level histogram and the side counters 
 texture_figures takes Haralick's figures from them on the host as IBSI defines them (contrast, joint entropy, inverse
 difference moment, ...), roi_report(..., texture=...) adds them to both of its blocks.
 
+Radial spectra and Fourier shell correlation: spectrum_plan builds the per-axis DFT tables (window
+folded in) and the frequency shells of a volume shape and spacing on the host and, on first use, the shell index on
+the device; dft3 is ddpm3d_dft3 (csrc/spectrum.hip: three MFMA GEMM passes), shell_spectrum one call of
+ddpm3d_shell_spectrum and one copy of its per-shell records, spectrum_figures turns them into power spectra, the FSC,
+the power ratio and the resolutions at FSC = 0.5 and 1/7 on the host.  evaluate does not take a plan: its parameter list is pinned as it is.
+
 Credible intervals: interval_figures scores two per-voxel quantile maps of
 uncertainty.draw_quantiles against the target: the share of voxels the interval covers and its mean width.
 """
@@ -1221,3 +1227,238 @@ def detection(target_labels, estimate_labels):
     return {"n_target": n_target, "n_estimate": n_estimate, "found": found, "overlap": over, "n_found": n_found,
             "n_missed": n_target - n_found, "false_positives": n_estimate - n_hit,
             "sensitivity": n_found / n_target if n_target else None}
+
+
+# ----------------------------------------------------------------- radial spectra, shell correlation
+SPECTRUM_WINDOWS = ("hann", "none")
+FSC_THRESHOLDS = (("0.5", 0.5), ("0.143", 1.0 / 7.0))
+RATIO_HALF = 0.25           # the power ratio at which the amplitude ratio is 1/2
+
+
+def _window(name, n):
+    x = np.arange(n, dtype=np.float64)
+    return np.sin(np.pi * (x + 0.5) / n) ** 2 if name == "hann" else np.ones(n)
+
+
+def _dft_tables(n, rows, w):
+    """(C, S) in fp64: C[k][x] = w[x] cos(2 pi ((k x) mod n) / n), S[k][x] = -w[x] sin(same); the integer mod keeps
+    the argument reduction exact"""
+    kx = (np.arange(rows, dtype=np.int64)[:, None] * np.arange(n, dtype=np.int64)[None, :]) % n
+    ang = 2.0 * np.pi * kx.astype(np.float64) / n
+    return w[None, :] * np.cos(ang), -w[None, :] * np.sin(ang)
+
+
+def _shell_of(r2, xp):
+    """the largest integer s with s^2 <= r2 (fp64 array of numpy or torch, xp): the sqrt only proposes, the integer
+    comparisons decide (s^2 is exact in fp64 for every s a plan allows)"""
+    s = xp.floor(xp.sqrt(r2))
+    s = xp.where((s + 1.0) * (s + 1.0) <= r2, s + 1.0, s)
+    return xp.where(s * s > r2, s - 1.0, s)
+
+
+class SpectrumPlan:
+    """spectrum_plan's return.  Host side (numpy, fp64 unless noted): `shape` (D, H, W), `spacing`, `window`,
+    `shell_width` (cycles/mm), `windows` (three vectors), `cos` / `sin` (the fp32 tables per axis, as uploaded), `q`
+    (three tables), `shells` S, `n_reported`, `frequency` (the S shell centres, cycles/mm), `weight_sq` = sum of w^2
+    over the volume.  The device side (tables, shell index, window vectors) is built on first use per device."""
+
+    def __init__(self, shape, spacing, window, shell_width, windows, q, shells, n_reported):
+        self.shape, self.spacing, self.window, self.shell_width = shape, spacing, window, shell_width
+        self.windows, self.q, self.shells, self.n_reported = windows, q, shells, n_reported
+        self.rows = (shape[0], shape[1], shape[2] // 2 + 1)
+        tables = [_dft_tables(n, r, w) for n, r, w in zip(shape, self.rows, windows)]
+        self.cos = [np.ascontiguousarray(c, dtype=np.float32) for c, _ in tables]
+        self.sin = [np.ascontiguousarray(s, dtype=np.float32) for _, s in tables]
+        self.frequency = (np.arange(shells, dtype=np.float64) + 0.5) * shell_width
+        self.weight_sq = float(np.prod([np.sum(w * w) for w in windows]))
+        self.voxels = int(math.prod(shape))
+        self.coeffs = shape[0] * shape[1] * self.rows[2]
+        self._device = {}
+
+    def shell_numbers(self):
+        """the shell of every half-spectrum coefficient, numpy int64 (D, H, W / 2 + 1)"""
+        r2 = (self.q[0][:, None, None] + self.q[1][None, :, None]) + self.q[2][None, None, :]
+        return _shell_of(r2, np).astype(np.int64)
+
+    def on(self, device):
+        """the device side for `device`: (axes descriptor array, shell RoiIndex, [wD, wH, wW] fp64 tensors)"""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("a spectrum plan's tables live on the GPU: this package runs on HIP kernels only "
+                               "(got %s)" % device)
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._device:
+            with torch.cuda.device(device):
+                keep = [torch.from_numpy(np.stack([c, s])).to(device) for c, s in zip(self.cos, self.sin)]
+                axes = (H.DftAxis * 3)(*[H.DftAxis(n, r, H.ptr(t[0]), H.ptr(t[1]))
+                                         for n, r, t in zip(self.shape, self.rows, keep)])
+                q = [torch.from_numpy(v).to(device) for v in self.q]
+                r2 = (q[0][:, None, None] + q[1][None, :, None]) + q[2][None, None, :]
+                found = roi_index((_shell_of(r2, torch) + 1.0).to(torch.int64))
+                counts = [0] * self.shells                      # a shell no coefficient falls into stays, empty
+                for label, n in zip(found.labels, found.counts):
+                    counts[label - 1] = n
+                index = RoiIndex(r2.shape, range(1, self.shells + 1), counts, found.index)
+                wins = [torch.from_numpy(w).to(device) for w in self.windows]
+            self._device[key] = (axes, index, wins, keep)
+        return self._device[key][:3]
+
+    def pivot(self, volume):
+        """the window-weighted mean sum w v / sum w of each (K, D, H, W) volume: a device fp32 tensor (K), no sync"""
+        wins = self.on(volume.device)[2]
+        t = torch.matmul(volume, wins[2].to(torch.float32)).to(torch.float64)      # (K, D, H)
+        t = torch.matmul(torch.matmul(t, wins[1]), wins[0])
+        return (t / float(np.prod([w.sum() for w in self.windows]))).to(torch.float32).contiguous()
+
+
+def spectrum_plan(shape, spacing, window="hann", shell_width=None):
+    """The plan of dft3 / shell_spectrum for (D, H, W) volumes of `spacing` mm per voxel (same order): the per-axis
+    window (`hann`: sin^2(pi (x + 1/2) / n), never 0; `none`), the DFT tables with the window folded in, and the
+    radial shells of width `shell_width` cycles/mm (default 1 / the longest edge in mm).  All of it is built on the
+    host in fp64; nothing touches a device before the plan is first used."""
+    try:
+        shape = tuple(int(v) for v in shape)
+    except (TypeError, ValueError):
+        shape = ()
+    if len(shape) != 3 or not all(2 <= n <= H.SPEC_MAX_EXTENT for n in shape):
+        raise ValueError("spectrum_plan: the shape must be three extents in 2..%d (got %r)" % (H.SPEC_MAX_EXTENT, shape))
+    spacing = _check_spacing(spacing, "spectrum_plan")
+    if window not in SPECTRUM_WINDOWS:
+        raise ValueError("spectrum_plan: window %r (one of %s)" % (window, ", ".join(SPECTRUM_WINDOWS)))
+    edges = [n * s for n, s in zip(shape, spacing)]
+    if shell_width is None:
+        shell_width = 1.0 / max(edges)
+    shell_width = float(shell_width)
+    if not (math.isfinite(shell_width) and shell_width > 0):
+        raise ValueError("spectrum_plan: the shell width must be positive and finite, in cycles/mm (got %r)"
+                         % shell_width)
+    q = []
+    for a, (n, edge) in enumerate(zip(shape, edges)):
+        k = np.arange(n // 2 + 1 if a == 2 else n, dtype=np.int64)
+        folded = np.where(2 * k <= n, k, k - n).astype(np.float64)         # k folded to (-n/2, n/2]
+        q.append((folded / (edge * shell_width)) ** 2)
+    top = (q[0].max() + q[1].max()) + q[2].max()
+    if not top < float(2 * H.ROI_MAX_REGIONS) ** 2:
+        raise ValueError("spectrum_plan: a shell width of %g cycles/mm gives more than %d shells"
+                         % (shell_width, H.ROI_MAX_REGIONS))
+    shells = int(_shell_of(np.float64(top), np)) + 1
+    if shells > H.ROI_MAX_REGIONS:
+        raise ValueError("spectrum_plan: a shell width of %g cycles/mm gives %d shells (at most %d)"
+                         % (shell_width, shells, H.ROI_MAX_REGIONS))
+    nyquist = min(1.0 / (2.0 * s) for s in spacing)
+    n_reported = sum(1 for s in range(shells) if (s + 1) * shell_width <= nyquist)
+    return SpectrumPlan(shape, spacing, window, shell_width, [_window(window, n) for n in shape], q, shells,
+                        n_reported)
+
+
+def _spectrum_stack(volume, plan, what):
+    H.require_device(volume, what)
+    if volume.dim() not in (3, 4) or tuple(volume.shape[-3:]) != plan.shape:
+        raise ValueError("%s of shape %s against a plan for %s volumes" % (what, tuple(volume.shape), plan.shape))
+    K = int(volume.shape[0]) if volume.dim() == 4 else 1
+    if not 1 <= K <= H.MAX_DRAWS:
+        raise ValueError("%s: %d volumes (1..%d)" % (what, K, H.MAX_DRAWS))
+    return K
+
+
+def dft3(volume, plan, pivot=None):
+    """ddpm3d_dft3 of a (D, H, W) or (K, D, H, W) device volume: numpy.fft.rfftn(w (v - pivot)) with the plan's
+    window, as two fp32 device tensors (re, im) of shape (..., D, H, W / 2 + 1).  pivot: None (0) or a device fp32
+    tensor of K values."""
+    K = _spectrum_stack(volume, plan, "volume")
+    if pivot is not None:
+        H.require_device(pivot, "pivot")
+        if pivot.numel() != K or pivot.device != volume.device:
+            raise ValueError("dft3: a pivot of %d values for %d volumes" % (pivot.numel(), K))
+    axes = plan.on(volume.device)[0]
+    lib = H.load()
+    D, Hh, W = plan.shape
+    need = lib.ddpm3d_dft3_workspace_bytes(K, D, Hh, W)
+    with torch.cuda.device(volume.device):
+        ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=volume.device)
+        out = torch.empty((2,) + tuple(volume.shape[:-1]) + (plan.rows[2],), dtype=torch.float32,
+                          device=volume.device)
+        H.check(lib.ddpm3d_dft3(H.ptr(volume), H.ptr(pivot), K, D, Hh, W, axes, H.ptr(ws), ws.numel() * 4,
+                                H.ptr(out[0]), H.ptr(out[1]), H.stream()))
+    return out[0], out[1]
+
+
+def _shell_spectrum_device(estimate, plan, target=None):
+    K = _spectrum_stack(estimate, plan, "estimate")
+    if target is not None:
+        H.require_device(target, "target")
+        if tuple(target.shape) != plan.shape or target.device != estimate.device:
+            raise ValueError("shell_spectrum: target of shape %s on %s, estimate on %s, plan for %s"
+                             % (tuple(target.shape), target.device, estimate.device, plan.shape))
+    axes, index, _ = plan.on(estimate.device)
+    lib = H.load()
+    D, Hh, W = plan.shape
+    need = lib.ddpm3d_shell_spectrum_workspace_bytes(K, D, Hh, W, index.desc, int(target is not None))
+    with torch.cuda.device(estimate.device):
+        pe = plan.pivot(estimate.reshape((K,) + plan.shape))
+        pt = None if target is None else plan.pivot(target[None])
+        ws = torch.empty(max(need, 16) // 8, dtype=torch.float64, device=estimate.device)
+        out = torch.empty((K, plan.shells, H.SP_REC), dtype=torch.float64, device=estimate.device)
+        H.check(lib.ddpm3d_shell_spectrum(H.ptr(estimate), H.ptr(pe), H.ptr(target), H.ptr(pt), K, D, Hh, W, axes,
+                                          index.desc, H.ptr(ws), ws.numel() * 8, H.ptr(out), H.stream()))
+    return out
+
+
+def shell_spectrum(estimate, plan, target=None):
+    """The per-shell records of a (D, H, W) or (K, D, H, W) estimate (and of a (D, H, W) target): one call of
+    ddpm3d_shell_spectrum and one device-to-host copy.  The pivots are the window-weighted means.  -> a numpy float64
+    array (K, S, H.SP_REC), columns H.SP_* (the Y, XY and EE columns are 0 without a target)."""
+    return _shell_spectrum_device(estimate, plan, target).cpu().numpy()   # the one device-to-host copy (it waits)
+
+
+def _first_crossing(curve, threshold, frequency):
+    """1 / f where `curve` first falls below the threshold among shells >= 1, linear between shell centres; (None,
+    True) if it never does, (None, False) if an undefined shell comes first"""
+    for s in range(1, len(curve)):
+        if curve[s] is None:
+            return None, False
+        if curve[s] < threshold:
+            if s == 1 or curve[s - 1] is None:
+                return 1.0 / frequency[s], False
+            a, b = curve[s - 1], curve[s]
+            f = frequency[s - 1] + (a - threshold) / (a - b) * (frequency[s] - frequency[s - 1])
+            return 1.0 / f, False
+    return None, True
+
+
+def spectrum_figures(records, plan):
+    """The figures of shell records (K, S, H.SP_REC) or (S, H.SP_REC), on the host in fp64, over the plan's reported
+    shells (those wholly below the smallest axis Nyquist): per estimate a dict of lists `frequency` (cycles/mm), `n`,
+    `power`, `power_target`, `power_error` (sum / (V sum w^2)), `fsc` = XY / sqrt(XX YY), `ratio` = XX / YY,
+    `error_rel` = EE / YY (None for a zero denominator or a non-finite sum), and the summaries `fsc_resolution_mm`
+    {"0.5", "0.143", "to_nyquist"} (1 / f at the first crossing below the threshold among shells >= 1, linear between
+    shell centres; None, with to_nyquist true, for a curve that never crosses) and `ratio_half_mm` (the first crossing
+    of `ratio` below 0.25).  A list of K dicts for three-dimensional records."""
+    rec = np.asarray(records, dtype=np.float64)
+    if rec.ndim not in (2, 3) or rec.shape[-2:] != (plan.shells, H.SP_REC):
+        raise ValueError("spectrum_figures: records of shape %s for a plan of %d shells" % (rec.shape, plan.shells))
+    norm = plan.voxels * plan.weight_sq
+    freq = [float(f) for f in plan.frequency[:plan.n_reported]]
+
+    def div(a, b):
+        return None if not (math.isfinite(a) and math.isfinite(b)) or b == 0 else a / b
+
+    def one(r):
+        r = r[:plan.n_reported].tolist()
+        fig = {"frequency": freq, "n": [int(v[H.SP_N]) for v in r]}
+        for key, col in (("power", H.SP_SUM_XX), ("power_target", H.SP_SUM_YY), ("power_error", H.SP_SUM_EE)):
+            fig[key] = [v[col] / norm if math.isfinite(v[col]) else None for v in r]
+        fig["fsc"] = [None if not (math.isfinite(v[H.SP_SUM_XX]) and math.isfinite(v[H.SP_SUM_YY]))
+                      else div(v[H.SP_SUM_XY], math.sqrt(v[H.SP_SUM_XX] * v[H.SP_SUM_YY])) for v in r]
+        fig["ratio"] = [div(v[H.SP_SUM_XX], v[H.SP_SUM_YY]) for v in r]
+        fig["error_rel"] = [div(v[H.SP_SUM_EE], v[H.SP_SUM_YY]) for v in r]
+        res, open_end = {}, False
+        for name, thr in FSC_THRESHOLDS:
+            res[name], never = _first_crossing(fig["fsc"], thr, freq)
+            open_end = open_end or never
+        res["to_nyquist"] = open_end
+        fig["fsc_resolution_mm"] = res
+        fig["ratio_half_mm"] = _first_crossing(fig["ratio"], RATIO_HALF, freq)[0]
+        return fig
+
+    return one(rec) if rec.ndim == 2 else [one(r) for r in rec]

@@ -101,6 +101,14 @@ least 11 after N - 1 halvings) adds "msssim", the multi-scale SSIM over N
 scales (guided_diffusion/metrics.py msssim3d), to the "denoised", "input" and
 baseline rows of metrics_<name>.json, and "msssim_scales" and
 "msssim_weights" beside them;
+`--spectrum True` (needs `--target_samples` and `--voxel_spacing`, which then
+needs no regions) adds "spectrum" to the same rows: per radial frequency shell
+the power of estimate, target and error, the Fourier shell correlation, the
+power ratio to the target, and the resolutions in mm at FSC = 0.5 and 1/7 and
+at amplitude ratio 1/2 (guided_diffusion/metrics.py shell_spectrum, one launch
+for all rows and the `--num_draws` draws); `--spectrum_window hann|none`; the
+one-shot blends are transformed over [1, n - 1) of each axis, where their
+written zeros are no edge; the file gains a top-level "spectrum" block;
 `--trace True` (any path, any sampler, no other flag needed) records how every
 reverse step's pred_xstart moves (guided_diffusion/metrics.py StepTrace: one
 small reduction per step on the GPU, nothing waits inside the loop) and writes
@@ -211,7 +219,10 @@ def create_argparser():
                     roi_labels="", roi_background=-1,
                     # lesion labels made from the target instead (not in the reference): connected components of the
                     # voxels above --roi_threshold / --roi_threshold_frac, specks below roi_min_voxels dropped
-                    roi_connectivity=26, roi_min_voxels=1)
+                    roi_connectivity=26, roi_min_voxels=1,
+                    # radial power spectra and Fourier shell correlation of every metric row (not in the reference;
+                    # needs --target_samples and --voxel_spacing), and their window: hann or none
+                    spectrum=False, spectrum_window="hann")
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
@@ -266,6 +277,7 @@ def main(argv=None):
     _check_segmentation(parser, args)
     _check_regrid(parser, args)
     _check_consistency(parser, args)
+    _check_spectrum(parser, args)
     args.peak = _check_spacing(parser, args)
     args.texture = _check_texture(parser, args)
     args.baselines = _check_baselines(parser, args)
@@ -346,7 +358,71 @@ def _load_target(parser, args):
                      "after %d halvings); it allows at most %d"
                      % (tuple(vol.shape), args.msssim_scales, 2 * metrics.SSIM_RADIUS + 1, args.msssim_scales - 1,
                         metrics.msssim_max_scales(vol.shape)))
+    if args.spectrum:
+        lo, hi = _spectrum_box(args, vol.shape)
+        if not all(2 <= b - a <= _hip.SPEC_MAX_EXTENT for a, b in zip(lo, hi)):
+            parser.error("--spectrum: the transformed box of a %s volume has extents %s; each must be in 2..%d"
+                         % (tuple(vol.shape), tuple(b - a for a, b in zip(lo, hi)), _hip.SPEC_MAX_EXTENT))
     return vol, target
+
+
+def _check_spectrum(parser, args):
+    """--spectrum / --spectrum_window, checked before any file is read (and before --voxel_spacing, which this flag
+    frees from needing regions)"""
+    if not args.spectrum:
+        return
+    if args.spectrum_window not in metrics.SPECTRUM_WINDOWS:
+        parser.error("--spectrum_window must be one of %s (got %r)"
+                     % (", ".join(metrics.SPECTRUM_WINDOWS), args.spectrum_window))
+    if not args.target_samples:
+        parser.error("--spectrum needs --target_samples: the shell correlation is taken against the full-dose target")
+    if args.voxel_spacing is None:
+        parser.error("--spectrum needs --voxel_spacing: its frequencies are in cycles/mm")
+    rows = 2 + (args.baseline_gaussian_fwhm is not None) + (args.baseline_nlm_h is not None)
+    if rows + (args.num_draws if args.num_draws > 1 else 0) > _hip.MAX_DRAWS:
+        parser.error("--spectrum transforms the %d rows and the --num_draws draws in one launch of at most %d "
+                     "volumes (got %d draws)" % (rows, _hip.MAX_DRAWS, args.num_draws))
+
+
+def _spectrum_box(args, shape):
+    """(lo, hi) per axis of `shape`: the one-shot blends write zeros on the outermost planes (Hann weight 0), which
+    would be an edge, so every row is transformed over [1, n - 1); the joint path over the whole volume"""
+    if args.joint_patches:
+        return [0] * 3, list(shape)
+    return [1] * 3, [n - 1 for n in shape]
+
+
+def _spectrum_block(args, tgt, rows, draws, n_draws):
+    """--spectrum: one metrics.shell_spectrum over the stack of `rows` ({name: (H, W, Z) device volume}, "denoised"
+    among them) and the n_draws stitched draws (any iterable: each is cut into the stack as it comes, none is held)
+    against tgt, all cut to the box -> ({name: figures}, the file's top-level block); the "denoised" figures carry
+    the draws' summaries.  Memory on this device: the stack of len(rows) + n_draws boxed volumes, and the driver's
+    workspace of 2 (len(rows) + n_draws) + 4 half-spectrum planes of the same size."""
+    s0, s1, s2 = args.voxel_spacing
+    lo, hi = _spectrum_box(args, tgt.shape)
+    cut = lambda t: t[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+    box = tuple(b - a for a, b in zip(lo, hi))
+    plan = metrics.spectrum_plan(box, (s1, s2, s0), window=args.spectrum_window)
+    stack = th.empty((len(rows) + n_draws,) + box, dtype=th.float32, device=tgt.device)
+    filled = 0
+    for source in (rows.values(), draws):
+        for v in source:
+            stack[filled] = cut(v)
+            filled += 1
+    assert filled == stack.shape[0], (filled, tuple(stack.shape))
+    figs = metrics.spectrum_figures(metrics.shell_spectrum(stack, plan, cut(tgt).contiguous()), plan)
+    out = dict(zip(rows, figs))
+    if n_draws:
+        out["denoised"] = {**out["denoised"],
+                           "draws": [{"fsc_resolution_mm": f["fsc_resolution_mm"], "ratio_half_mm": f["ratio_half_mm"]}
+                                     for f in figs[len(rows):]]}
+    for name, f in out.items():
+        res = f["fsc_resolution_mm"]
+        mm = lambda v: "not reached" if v is None else "%.3f mm" % v
+        logger.log("  %-8s spectrum: FSC 0.5 at %s, FSC 1/7 at %s, amplitude ratio 1/2 at %s"
+                   % (name, mm(res["0.5"]), mm(res["0.143"]), mm(f["ratio_half_mm"])))
+    return out, {"window": plan.window, "shell_width": plan.shell_width, "shells": plan.shells,
+                 "n_reported": plan.n_reported, "box": [[a, b] for a, b in zip(lo, hi)]}
 
 
 def _load_roi(parser, args, vol):
@@ -515,8 +591,8 @@ def _check_spacing(parser, args):
         parser.error("--voxel_spacing needs --target_samples: its figures are taken per region against the target")
     if not (args.roi_labels or _segmenting(args)):
         if (args.baseline_gaussian_fwhm is not None or args.model_spacing is not None
-                or args.consistency_fwhm is not None):
-            return None                        # the spacing serves the Gaussian baseline, the regridding or the guidance
+                or args.consistency_fwhm is not None or args.spectrum):
+            return None         # the spacing serves the Gaussian baseline, the regridding, the guidance or the spectrum
         parser.error("--voxel_spacing needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
     s0, s1, s2 = args.voxel_spacing
     try:
@@ -940,6 +1016,17 @@ def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, r
         logger.log("  %-8s vs target: PSNR %.3f dB  NRMSE %.5f  SSIM %.5f  MAE %.5g  bias %.5g  (L = %.6g, %d voxels)"
                    % (name, r["psnr"], r["nrmse"], r["ssim"], r["mae"], r["bias"], r["data_range"], r["n_voxels"]))
         log_msssim(name, r)
+    if args.spectrum:
+        # the K stitched draws come one volume at a time; they are held only where the region block needs them again
+        n_draws = args.num_draws if draws is not None and args.num_draws > 1 else 0
+        draws = [] if draws is None else (list(draws) if roi is not None else draws)
+        figs, report["spectrum"] = _spectrum_block(
+            args, tgt, {"input": inp, "denoised": den, **{name: x for name, (x, _) in filtered.items()}}, draws,
+            n_draws)
+        report["input"]["spectrum"], report["denoised"]["spectrum"] = figs["input"], figs["denoised"]
+        for name in filtered:
+            report["baselines"][name]["spectrum"] = figs[name]
+        draws = iter(draws) if roi is not None and draws else None
     if roi is not None:
         keep = None if weight is None else live.to(th.uint8).contiguous()
         report["roi"] = _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=out_path,

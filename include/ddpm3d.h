@@ -1001,6 +1001,75 @@ int ddpm3d_roi_texture(const float* est, int B, int D, int H, int W, const ddpm3
                        const int16_t* region_of, const float* lo, const float* inv_w, int levels,
                        uint64_t* glcm, uint64_t* hist, uint64_t* counts, void* stream);
 /*
+ * Radial power spectra and Fourier shell correlation (added within ABI 13; the reference has no metric code;
+ * DESIGN.md 3.21).  A volume is [D][H][W] fp32, W innermost.  Per axis a of extent n the caller builds two fp32 tables
+ * in fp64, rounded once, ddpm3d_dft_axis:
+ *   cos_t[k][x] =  w_a[x] cos(2 pi ((k x) mod n) / n),   sin_t[k][x] = -w_a[x] sin(2 pi ((k x) mod n) / n)
+ * DEVICE [rows][n], rows = W / 2 + 1 on the W axis (half spectrum) and n on D and H; w_a is the axis' window (1 for
+ * none).  axes[] is in D, H, W order.
+ * ddpm3d_dft3: with w = w_D w_H w_W and the pivot p_b (device [B], NULL: 0),
+ *   X_b[kd][kh][kw] = sum w(d, h, x) (v_b(d, h, x) - p_b) exp(-2 pi i (kd d / D + kh h / H + kw x / W)),
+ * unnormalised, numpy.fft.rfftn(w (v - p)); re and im are [B][D][H][W / 2 + 1] fp32 planes.  Three launches of one
+ * LDS-tiled GEMM kernel on the exact fp32-input MFMA (32x32x2), passes W (real -> complex, v - p formed once in fp32
+ * in the operand load), H and D (complex -> complex as one real GEMM with K = 2n: [C | -S; S | C] against [Xr; Xi]);
+ * fp32 split-complex intermediates; pass W writes (re, im), pass H the workspace, pass D (re, im) again.  Every
+ * coefficient is a k-ordered fp32 fma chain per pass: the same bits on every run, and volume b does not depend on B.
+ * To first order a coefficient is within ((W + 2) + (2H + 2) + (2D + 2)) 2^-24 sum |w (v - p)| of its exact value.
+ * ws: ddpm3d_dft3_workspace_bytes(B, D, H, W) bytes, 16-byte aligned.
+ *
+ * ddpm3d_shell_sums: `shells` is a ddpm3d_roi_index whose regions are the S frequency shells and whose d_index holds
+ * flat half-spectrum coefficient indices in [0, D H (W / 2 + 1)), ascending within a shell (a value outside that range
+ * is skipped).  x is [B][coeffs] (re and im planes), y [coeffs] or both NULL.  out[B][S][DDPM3D_SP_REC] doubles, sums
+ * over the FULL spectrum evaluated on the half spectrum: a coefficient with 0 < kw and 2 kw != W (kw = index mod
+ * (W / 2 + 1)) counts twice, every other once:
+ *   N = coefficients, SUM_XX = sum |X|^2, SUM_YY = sum |Y|^2, SUM_XY = sum Re(X conj Y), SUM_EE = sum |X - Y|^2
+ * (the last three 0 without y; the sixth column is 0).  Every term is widened to fp64 and formed and added in fp64
+ * without contraction, in ddpm3d_roi_moments' frame: one workgroup per (chunk of DDPM3D_ROI_CHUNK, estimate) writes a
+ * record, a second launch folds them in a fixed order.  No atomics: the same bits on every run, and row b does not
+ * depend on B.  ws: ddpm3d_shell_sums_workspace_bytes(B, shells) bytes, 16-byte aligned.
+ *
+ * ddpm3d_shell_spectrum: the driver.  The target's transform once (target NULL: none, and target_pivot is ignored),
+ * the B estimates' transforms one volume at a time, then one ddpm3d_shell_sums; shells->entries must be
+ * D H (W / 2 + 1).  Its records carry the bits of ddpm3d_dft3 + ddpm3d_shell_sums.  ws:
+ * ddpm3d_shell_spectrum_workspace_bytes(B, D, H, W, shells, with_target) bytes, 16-byte aligned.
+ *
+ * All three only enqueue: no allocation, no synchronisation.  The workspace queries never shrink as an extent grows
+ * and answer 0 for what the entry refuses.  DDPM3D_EINVAL before any launch for a NULL required pointer (vol, axes
+ * and their tables, re, im, xre, xim, est, out, ws), yre and yim not both set or both NULL, B outside
+ * 1..DDPM3D_MAX_DRAWS, an extent outside 2..DDPM3D_SPEC_MAX_EXTENT, axes[a].n or .rows that do not match the shape,
+ * every index ddpm3d_roi_moments refuses, entries other than D H (W / 2 + 1) (driver), and a workspace that is too
+ * small (a target without room for it included) or misaligned.
+ */
+#define DDPM3D_SPEC_MAX_EXTENT 2048
+enum {
+    DDPM3D_SP_N = 0,
+    DDPM3D_SP_SUM_XX = 1,
+    DDPM3D_SP_SUM_YY = 2,
+    DDPM3D_SP_SUM_XY = 3,
+    DDPM3D_SP_SUM_EE = 4,
+    DDPM3D_SP_REC = 6           /* doubles per record; column 5 is 0 */
+};
+typedef struct ddpm3d_dft_axis {
+    int32_t n, rows;
+    const float* cos_t;
+    const float* sin_t;
+} ddpm3d_dft_axis;
+size_t ddpm3d_dft3_workspace_bytes(int B, int D, int H, int W);
+int ddpm3d_dft3(const float* vol, const float* pivot, int B, int D, int H, int W, const ddpm3d_dft_axis axes[3],
+                void* ws, size_t ws_bytes, float* re, float* im, void* stream);
+/* one pass of ddpm3d_dft3 alone, for timing: pass 0 (W) reads vol and writes (re, im), 1 (H) reads (re, im) and writes
+ * the workspace, 2 (D) reads the workspace and writes (re, im), each over whatever its input holds; same refusals */
+int ddpm3d_dft3_pass(int pass, const float* vol, const float* pivot, int B, int D, int H, int W,
+                     const ddpm3d_dft_axis axes[3], void* ws, size_t ws_bytes, float* re, float* im, void* stream);
+size_t ddpm3d_shell_sums_workspace_bytes(int B, const ddpm3d_roi_index* shells);
+int ddpm3d_shell_sums(const float* xre, const float* xim, const float* yre, const float* yim, int B, int D, int H,
+                      int W, const ddpm3d_roi_index* shells, void* ws, size_t ws_bytes, double* out, void* stream);
+size_t ddpm3d_shell_spectrum_workspace_bytes(int B, int D, int H, int W, const ddpm3d_roi_index* shells,
+                                             int with_target);
+int ddpm3d_shell_spectrum(const float* est, const float* est_pivot, const float* target, const float* target_pivot,
+                          int B, int D, int H, int W, const ddpm3d_dft_axis axes[3], const ddpm3d_roi_index* shells,
+                          void* ws, size_t ws_bytes, double* out, void* stream);
+/*
  * Connected-component labelling of a thresholded volume (added within ABI 13; the reference has no such code): the
  * mechanical lesion definition of PET, "voxels above an SUV threshold, grouped into connected components", whose
  * labels feed the region index above.
