@@ -1466,6 +1466,93 @@ int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_reg
     return launched(ddpm3d_launch_regrid(vol, B, D, H, W, axes, out, (float*)ws, (hipStream_t)stream), "regrid");
 }
 
+// ------------------------------------------------- maximum-intensity and ray-sum projections (added within ABI 13)
+static bool project_counts_ok(int angles, int bins, int samples) {
+    return angles >= 1 && angles <= DDPM3D_PROJECT_MAX_ANGLES && bins >= 1 && bins <= DDPM3D_PROJECT_MAX_BINS &&
+           samples >= 1 && samples <= DDPM3D_PROJECT_MAX_BINS;
+}
+static int project_counts_check(const char* what, int angles, int bins, int samples) {
+    if (!project_counts_ok(angles, bins, samples))
+        return fail(DDPM3D_EINVAL, "%s: angles=%d (1..%d), bins=%d and samples=%d (1..%d each)", what, angles,
+                    DDPM3D_PROJECT_MAX_ANGLES, bins, samples, DDPM3D_PROJECT_MAX_BINS);
+    return DDPM3D_OK;
+}
+static bool finite_f32(float v) { return v - v == 0.0f; }
+static bool positive_finite(double v) { return v > 0.0 && v - v == 0.0; }
+
+int ddpm3d_project_table_fill(int H, int W, double s1, double s2, double pitch, int bins, double step, int samples,
+                              const double* angles_deg, int angles, ddpm3d_project_table* table) {
+    if (!angles_deg || !table) return fail(DDPM3D_EINVAL, "project_table_fill: null pointer");
+    if (H < 1 || W < 1) return fail(DDPM3D_EINVAL, "project_table_fill: bad slice (H=%d W=%d; 1 or more each)", H, W);
+    if (!positive_finite(s1) || !positive_finite(s2) || !positive_finite(pitch) || !positive_finite(step))
+        return fail(DDPM3D_EINVAL, "project_table_fill: spacing (%g, %g), pitch %g, step %g (positive and finite, mm)",
+                    s1, s2, pitch, step);
+    const int rc = project_counts_check("project_table_fill", angles, bins, samples);
+    if (rc != DDPM3D_OK) return rc;
+    ddpm3d_project_table t;
+    memset(&t, 0, sizeof t);
+    t.angles = angles, t.bins = bins, t.samples = samples, t.step = (float)step;
+    const double mid_u = 0.5 * (bins - 1), mid_j = 0.5 * (samples - 1);
+    for (int k = 0; k < angles; ++k) {
+        const double deg = angles_deg[k];
+        if (deg - deg != 0.0) return fail(DDPM3D_EINVAL, "project_table_fill: angles_deg[%d]=%g is not finite", k, deg);
+        // exactly 0 or +-1 at multiples of 90 degrees
+        const double turn = fmod(deg, 360.0), quarter = turn / 90.0;
+        double c, s;
+        if (quarter == floor(quarter)) {
+            static const double qc[4] = {1.0, 0.0, -1.0, 0.0}, qs[4] = {0.0, 1.0, 0.0, -1.0};
+            const int q = ((int)quarter % 4 + 4) % 4;
+            c = qc[q], s = qs[q];
+        } else {
+            const double rad = turn * (3.14159265358979323846 / 180.0);
+            c = cos(rad), s = sin(rad);
+        }
+        // h' = (a s + r c) / s1 + (H - 1) / 2 and w' = (a c - r s) / s2 + (W - 1) / 2 with a = (u - mid_u) pitch and
+        // r = (j - mid_j) step, as origin + u * (per-u increment) + j * (per-j increment)
+        const double hu = pitch * s / s1, hj = step * c / s1, wu = pitch * c / s2, wj = -step * s / s2;
+        const double v[6] = {0.5 * (H - 1) - mid_u * hu - mid_j * hj, hu, hj,
+                             0.5 * (W - 1) - mid_u * wu - mid_j * wj, wu, wj};
+        for (int i = 0; i < 6; ++i) {
+            t.coef[k][i] = (float)v[i];
+            if (!finite_f32(t.coef[k][i]))
+                return fail(DDPM3D_EINVAL, "project_table_fill: entry %d of angle %d (%g degrees) is not finite in "
+                                           "fp32", i, k, deg);
+        }
+    }
+    if (!finite_f32(t.step)) return fail(DDPM3D_EINVAL, "project_table_fill: the step %g is not finite in fp32", step);
+    *table = t;
+    return DDPM3D_OK;
+}
+
+int ddpm3d_project(const float* vol, int B, int D, int H, int W, const ddpm3d_project_table* table, int mode,
+                   float* out, void* stream) {
+    if (!vol || !out || !table) return fail(DDPM3D_EINVAL, "project: null pointer");
+    if (B < 1 || B > DDPM3D_MAX_DRAWS) return fail(DDPM3D_EINVAL, "project: B=%d volumes (1..%d)", B, DDPM3D_MAX_DRAWS);
+    if (mode != DDPM3D_PROJECT_MAX && mode != DDPM3D_PROJECT_SUM)
+        return fail(DDPM3D_EINVAL, "project: mode %d (DDPM3D_PROJECT_MAX = %d or DDPM3D_PROJECT_SUM = %d)", mode,
+                    DDPM3D_PROJECT_MAX, DDPM3D_PROJECT_SUM);
+    const int rc = project_counts_check("project", table->angles, table->bins, table->samples);
+    if (rc != DDPM3D_OK) return rc;
+    const int64_t lim = 0x7fffffff;
+    // H - 1 and W - 1 must be fp32 numbers: the counting rule compares against them
+    if (D < 1 || H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || (int64_t)H * W > lim ||
+        (int64_t)D * H * W > lim || (int64_t)B * D * H * W > lim)
+        return fail(DDPM3D_EINVAL, "project: bad volumes (B=%d D=%d H=%d W=%d; 1 or more each, H and W <= 2^24, "
+                                   "B * D * H * W <= 2^31 - 1)", B, D, H, W);
+    // B * angles * bins <= 2^30, D <= 2^31 - 1: no overflow
+    const int64_t out_voxels = (int64_t)B * table->angles * table->bins * D;
+    if (out_voxels > lim)
+        return fail(DDPM3D_EINVAL, "project: %lld outputs (B * angles * D * bins <= 2^31 - 1)", (long long)out_voxels);
+    if (!finite_f32(table->step)) return fail(DDPM3D_EINVAL, "project: the table's step is not finite");
+    for (int k = 0; k < table->angles; ++k)
+        for (int i = 0; i < 6; ++i)
+            if (!finite_f32(table->coef[k][i]))
+                return fail(DDPM3D_EINVAL, "project: entry %d of the table's angle %d is not finite", i, k);
+    if (ranges_overlap(vol, (size_t)B * D * H * W * sizeof(float), out, (size_t)out_voxels * sizeof(float)))
+        return fail(DDPM3D_EINVAL, "project: out overlaps vol");
+    return launched(ddpm3d_launch_project(vol, B, D, H, W, *table, mode, out, (hipStream_t)stream), "project");
+}
+
 // ------------------------------------------------- low-pass pull of x_start (added within ABI 13)
 static bool pull_shape_ok(int N, int D, int H, int W) {
     return N >= 1 && N <= 65535 && volume_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;

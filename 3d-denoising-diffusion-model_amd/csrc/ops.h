@@ -175,6 +175,11 @@ hipError_t ddpm3d_launch_xstart_pull(const float* mo, const float* x, const floa
 // is exp(-max(fma(sum of squared patch differences, k1, -k2), 0)), k1 = 1 / (n_p h^2), k2 = 2 sigma^2 / h^2
 hipError_t ddpm3d_launch_nlm(const float* vol, int D, int H, int W, const int* search, const int* patch, float k1,
                              float k2, float* out, hipStream_t st);
+// project.hip: the maximum (mode DDPM3D_PROJECT_MAX) or the line integral (DDPM3D_PROJECT_SUM) along the table's rays
+// through every slice of B volumes, out [B][angles][D][bins] (the caller has checked the shape, the table and the mode)
+struct ddpm3d_project_table;
+hipError_t ddpm3d_launch_project(const float* vol, int B, int D, int H, int W, const ddpm3d_project_table& table,
+                                 int mode, float* out, hipStream_t st);
 // regrid.hip: B volumes of one shape onto another grid, passes along W, H, D with the tables of axes[] (D, H, W order)
 // in device memory (the caller has checked the shapes, the taps, the ratios and the workspace); stage[] gets the voxels
 // per volume after the W, the H and the D pass, of which the first two, times B, are the workspace's two buffers

@@ -180,6 +180,16 @@ class RegridAxis(C.Structure):
                 ("count", C.c_void_p), ("weights", C.c_void_p)]
 
 
+PROJECT_MAX_ANGLES, PROJECT_MAX_BINS = 64, 4096     # DDPM3D_PROJECT_MAX_ANGLES / _BINS (bins and samples per ray)
+PROJECT_MAX, PROJECT_SUM = 0, 1                     # DDPM3D_PROJECT_MAX / _SUM: the modes of ddpm3d_project
+
+
+class ProjectTable(C.Structure):
+    """struct ddpm3d_project_table: angles, bins, samples, the step in mm and per angle {h0, hu, hj, w0, wu, wj}"""
+    _fields_ = [("angles", C.c_int32), ("bins", C.c_int32), ("samples", C.c_int32), ("step", C.c_float),
+                ("coef", (C.c_float * 6) * PROJECT_MAX_ANGLES)]
+
+
 LAYER_RES, LAYER_ATTN, LAYER_DOWNCONV, LAYER_UPCONV = 1, 2, 3, 4
 UPDOWN = {None: 0, "down": 1, "up": 2}
 
@@ -283,6 +293,9 @@ EXPORTS = {
     "ddpm3d_nlm": (C.c_int, [_fp] + [C.c_int] * 9 + [C.c_float, C.c_float, _fp, _fp]),
     "ddpm3d_regrid_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
     "ddpm3d_regrid": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(RegridAxis), _fp, _fp, C.c_size_t, _fp]),
+    "ddpm3d_project_table_fill": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double,
+                                            C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(ProjectTable)]),
+    "ddpm3d_project": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(ProjectTable), C.c_int, _fp, _fp]),
     "ddpm3d_noise_fill": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_noise_bits": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_p_sample_step_keyed": (C.c_int, [_fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,

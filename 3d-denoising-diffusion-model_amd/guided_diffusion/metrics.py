@@ -46,6 +46,11 @@ the device; dft3 is ddpm3d_dft3 (csrc/spectrum.hip: three MFMA GEMM passes), she
 ddpm3d_shell_spectrum and one copy of its per-shell records, spectrum_figures turns them into power spectra, the FSC,
 the power ratio and the resolutions at FSC = 0.5 and 1/7 on the host.  evaluate does not take a plan: its parameter list is pinned as it is.
 
+Rotating maximum-intensity and ray-sum projections: projection_plan folds a slice geometry, a
+detector and a list of angles into the six fp32 numbers per angle ddpm3d_project reads (ddpm3d_project_table_fill, on
+the host), project is one launch of ddpm3d_project (csrc/project.hip) over a volume or a stack: the MIP ("max") or
+the line integral ("sum") of every ray through every slice, rotated about the D axis.
+
 Credible intervals: interval_figures scores two per-voxel quantile maps of
 uncertainty.draw_quantiles against the target: the share of voxels the interval covers and its mean width.
 """
@@ -1462,3 +1467,92 @@ def spectrum_figures(records, plan):
         return fig
 
     return one(rec) if rec.ndim == 2 else [one(r) for r in rec]
+
+
+# ----------------------------------------------------------------- rotating MIP and ray sums
+PROJECTION_MODES = {"max": H.PROJECT_MAX, "sum": H.PROJECT_SUM}
+
+
+class ProjectionPlan:
+    """projection_plan's return: `shape` (D, H, W), `spacing`, `angles_deg` (a tuple), `pitch` and `step` (mm),
+    `bins` U and `samples` R, `table` (the H.ProjectTable ddpm3d_project reads, on the host) and `coef`, its angles
+    as a numpy float32 array (A, 6): h0, hu, hj, w0, wu, wj."""
+
+    def __init__(self, shape, spacing, angles_deg, pitch, bins, step, samples, table):
+        self.shape, self.spacing, self.angles_deg = shape, spacing, angles_deg
+        self.pitch, self.bins, self.step, self.samples, self.table = pitch, bins, step, samples, table
+        self.coef = np.ctypeslib.as_array(table.coef)[:len(angles_deg)].astype(np.float32)
+
+
+def _count(value, what):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= value <= H.PROJECT_MAX_BINS:
+        raise ValueError("projection_plan: %s must be an integer in 1..%d (got %r)" % (what, H.PROJECT_MAX_BINS, value))
+    return int(value)
+
+
+def projection_default_bins(shape, spacing, pitch=None):
+    """the bin (and sample) count projection_plan chooses for a (D, H, W) shape: ceil(hypot(H s1, W s2) / pitch), the
+    slice's diagonal, so that no angle clips it; pitch defaults to min(s1, s2)"""
+    pitch = min(spacing[1], spacing[2]) if pitch is None else pitch
+    return int(math.ceil(math.hypot(shape[1] * spacing[1], shape[2] * spacing[2]) / pitch))
+
+
+def projection_plan(shape, spacing, angles_deg, pitch=None, bins=None, step=None, samples=None):
+    """The plan of project for (D, H, W) volumes of `spacing` = (s0, s1, s2) mm per voxel (same order): parallel rays
+    through every (H, W) slice, rotated about the D axis by each of `angles_deg` (1..64 of them), `bins` detector bins
+    `pitch` mm apart and `samples` samples `step` mm apart per ray, all centred on the slice.  The defaults are
+    pitch = step = min(s1, s2) and bins = samples = ceil(hypot(H s1, W s2) / pitch), so that no angle clips the
+    slice.  ddpm3d_project_table_fill folds it into six fp32 numbers per angle on the host; nothing touches a device.
+    -> ProjectionPlan"""
+    try:
+        shape = tuple(int(v) for v in shape)
+    except (TypeError, ValueError):
+        shape = ()
+    if len(shape) != 3 or not all(n >= 1 for n in shape):
+        raise ValueError("projection_plan: the shape must be three extents of 1 or more (got %r)" % (shape,))
+    spacing = _check_spacing(spacing, "projection_plan")
+    try:
+        angles = tuple(float(a) for a in angles_deg)
+    except (TypeError, ValueError):
+        angles = ()
+    if not 1 <= len(angles) <= H.PROJECT_MAX_ANGLES or not all(math.isfinite(a) for a in angles):
+        raise ValueError("projection_plan: angles_deg must be 1..%d finite angles in degrees (got %r)"
+                         % (H.PROJECT_MAX_ANGLES, angles_deg))
+    pitch = min(spacing[1], spacing[2]) if pitch is None else _positive(pitch, "projection_plan: the pitch")
+    step = min(spacing[1], spacing[2]) if step is None else _positive(step, "projection_plan: the step")
+    if bins is None or samples is None:
+        default = projection_default_bins(shape, spacing, pitch)
+        if default > H.PROJECT_MAX_BINS:
+            raise ValueError("projection_plan: the diagonal of a %d x %d slice at %g x %g mm is %d bins of %g mm: bins "
+                             "and samples are limited to %d" % (shape[1], shape[2], spacing[1], spacing[2], default,
+                                                                pitch, H.PROJECT_MAX_BINS))
+        bins = default if bins is None else bins
+        samples = default if samples is None else samples
+    bins, samples = _count(bins, "bins"), _count(samples, "samples")
+    table = H.ProjectTable()
+    H.check(H.load().ddpm3d_project_table_fill(shape[1], shape[2], spacing[1], spacing[2], pitch, bins, step, samples,
+                                               (ctypes.c_double * len(angles))(*angles), len(angles),
+                                               ctypes.byref(table)))
+    return ProjectionPlan(shape, spacing, angles, pitch, bins, step, samples, table)
+
+
+def project(volume, plan, mode="max"):
+    """The projections of a device float32 (D, H, W) or (K, D, H, W) tensor along the plan's rays: one call of
+    ddpm3d_project (csrc/project.hip), no host copy.  mode "max": the largest bilinear sample along each ray, 0 where
+    the ray misses the slice (the rotating MIP); "sum": step times the sum of the samples, the line integral in
+    value * mm.  -> a device tensor (A, D, U) or (K, A, D, U)."""
+    if not isinstance(plan, ProjectionPlan):
+        raise ValueError("project: plan must be projection_plan's return (got %r)" % (plan,))
+    if mode not in PROJECTION_MODES:
+        raise ValueError("project: mode %r (one of %s)" % (mode, ", ".join(PROJECTION_MODES)))
+    K = _spectrum_stack(volume, plan, "volume")
+    D, Hh, W = plan.shape
+    A = len(plan.angles_deg)
+    if K * D * Hh * W > 2 ** 31 - 1 or K * A * D * plan.bins > 2 ** 31 - 1:
+        raise ValueError("project: %d voxels in and %d out (at most 2^31 - 1 each)"
+                         % (K * D * Hh * W, K * A * D * plan.bins))
+    with torch.cuda.device(volume.device):
+        out = torch.empty(tuple(volume.shape[:-3]) + (A, D, plan.bins), dtype=torch.float32, device=volume.device)
+        H.check(H.load().ddpm3d_project(H.ptr(volume), K, D, Hh, W, ctypes.byref(plan.table),
+                                        PROJECTION_MODES[mode], H.ptr(out), H.stream()))
+    return out

@@ -109,6 +109,16 @@ at amplitude ratio 1/2 (guided_diffusion/metrics.py shell_spectrum, one launch
 for all rows and the `--num_draws` draws); `--spectrum_window hann|none`; the
 one-shot blends are transformed over [1, n - 1) of each axis, where their
 written zeros are no edge; the file gains a top-level "spectrum" block;
+`--mip_angles N` (1..64; needs `--voxel_spacing`, which then needs neither a
+target nor regions) writes mip_<name>.npz beside the .npz: the rotating
+maximum-intensity projection about the input file's axis 0 at the angles
+k 360 / N (guided_diffusion/metrics.py project, DESIGN.md 3.22, one launch for
+all rows), each (N, D, U) float32: "denoised" and "input", with
+`--target_samples` "target" and "error" (the MIP of |denoised - target|), with
+`--num_draws` "std", with baselines "gaussian" and "nlm", and "angles_deg" and
+"pitch_mm"; .tif input also gets mip_<name>.tif, the denoised stack; the
+one-shot paths project [1, n - 1) of each axis, `--joint_patches` the whole
+volume;
 `--trace True` (any path, any sampler, no other flag needed) records how every
 reverse step's pred_xstart moves (guided_diffusion/metrics.py StepTrace: one
 small reduction per step on the GPU, nothing waits inside the loop) and writes
@@ -254,6 +264,9 @@ def create_argparser():
     parser.add_argument("--roi_texture_bin", type=float, default=None, metavar="W")
     parser.add_argument("--roi_texture_levels", type=int, default=None, metavar="N")
     parser.add_argument("--roi_texture_lower", type=float, default=None, metavar="L")
+    # rotating maximum-intensity projections about the input file's axis 0, at the angles k * 360 / N, written as
+    # mip_<name>.npz (needs --voxel_spacing, which then needs neither a target nor regions)
+    parser.add_argument("--mip_angles", type=int, default=None, metavar="N")
     return parser
 
 
@@ -278,10 +291,12 @@ def main(argv=None):
     _check_regrid(parser, args)
     _check_consistency(parser, args)
     _check_spectrum(parser, args)
+    _check_mip(parser, args)
     args.peak = _check_spacing(parser, args)
     args.texture = _check_texture(parser, args)
     args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
+    vol = _plan_mip(parser, args, vol)
     vol = _plan_regrid(parser, args, vol)
     _plan_consistency(parser, args)
     roi = _load_roi(parser, args, vol)
@@ -423,6 +438,86 @@ def _spectrum_block(args, tgt, rows, draws, n_draws):
                    % (name, mm(res["0.5"]), mm(res["0.143"]), mm(f["ratio_half_mm"])))
     return out, {"window": plan.window, "shell_width": plan.shell_width, "shells": plan.shells,
                  "n_reported": plan.n_reported, "box": [[a, b] for a, b in zip(lo, hi)]}
+
+
+def _check_mip(parser, args):
+    """--mip_angles, checked before any file is read (and before --voxel_spacing, which this flag frees from needing a
+    target or regions)"""
+    if args.mip_angles is None:
+        return
+    if not 1 <= args.mip_angles <= _hip.PROJECT_MAX_ANGLES:
+        parser.error("--mip_angles must be in 1..%d (got %d)" % (_hip.PROJECT_MAX_ANGLES, args.mip_angles))
+    if args.voxel_spacing is None:
+        parser.error("--mip_angles needs --voxel_spacing: the detector's pitch and the ray step are in mm")
+
+
+def _mip_box(args, shape):
+    """(lo, hi) per axis of the file's (D, H, W): the box _spectrum_box cuts, for the same reason"""
+    return _spectrum_box(args, shape)
+
+
+def _plan_mip(parser, args, vol):
+    """--mip_angles: the projected box and its default detector from the volume's shape, on the host and before the
+    model is built; the volume is read now if --target_samples has not done so.  -> the (D, H, W) volume (None without
+    the flag and without a target, as before)."""
+    if args.mip_angles is None:
+        return vol
+    if vol is None:
+        if not os.path.isfile(args.base_samples):
+            parser.error("--base_samples: no such file: %r" % args.base_samples)
+        vol = patches.load_volume(args.base_samples)
+    lo, hi = _mip_box(args, vol.shape)
+    box = tuple(b - a for a, b in zip(lo, hi))
+    if min(box) < 1:
+        parser.error("--mip_angles: the projected box of a %s volume has extents %s; each must be at least 1"
+                     % (tuple(vol.shape), box))
+    bins = metrics.projection_default_bins(box, args.voxel_spacing)
+    if bins > _hip.PROJECT_MAX_BINS:
+        parser.error("--mip_angles: the diagonal of the projected %d x %d slices at %g x %g mm takes %d bins; at most "
+                     "%d" % (box[1], box[2], args.voxel_spacing[1], args.voxel_spacing[2], bins,
+                             _hip.PROJECT_MAX_BINS))
+    return vol
+
+
+def _write_mip(args, out_path, native, target, result, std):
+    """--mip_angles N: mip_<name>.npz beside the .npz, the maximum-intensity projections about the file's axis 0 at
+    the angles k 360 / N of every row, each (N, D, U) float32 with rows along the file's axis 0: "denoised" and
+    "input"; with --target_samples "target" and "error" (the MIP of |denoised - target|); with --num_draws "std"; with
+    baselines "gaussian" and "nlm"; "angles_deg" and "pitch_mm".  One metrics.project over the stack of rows, cut to
+    _mip_box.  native and target are (D, H, W) host arrays, result and std (H, W, Z) host arrays.  For .tif input also
+    mip_<name>.tif, the denoised stack.  -> the .npz's path"""
+    dev = dist_util.dev()
+
+    def dhw(a, permute=False):
+        t = th.as_tensor(a).to(device=dev, dtype=th.float32)
+        return t.permute(2, 0, 1) if permute else t                          # (H, W, Z) -> (D, H, W)
+
+    rows = {"denoised": dhw(result, True), "input": dhw(native)}
+    if target is not None:
+        rows["target"] = dhw(target)
+        rows["error"] = (rows["denoised"] - rows["target"]).abs()
+    if std is not None:
+        rows["std"] = dhw(std, True)
+    for name, (x, _) in _baseline_volumes(args, rows["input"].permute(1, 2, 0).contiguous()).items():
+        rows[name] = x.permute(2, 0, 1)
+    lo, hi = _mip_box(args, native.shape)
+    box = tuple(b - a for a, b in zip(lo, hi))
+    angles = [k * 360.0 / args.mip_angles for k in range(args.mip_angles)]
+    plan = metrics.projection_plan(box, args.voxel_spacing, angles)
+    stack = th.empty((len(rows),) + box, dtype=th.float32, device=dev)
+    for k, v in enumerate(rows.values()):
+        stack[k] = v[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+    images = metrics.project(stack, plan, mode="max").cpu().numpy()
+    name = _base_name(args.base_samples)
+    path = os.path.join(os.path.dirname(out_path), "mip_%s.npz" % name)
+    np.savez(path, **{row: images[k] for k, row in enumerate(rows)}, angles_deg=np.asarray(angles, dtype=np.float64),
+             pitch_mm=np.float64(plan.pitch))
+    logger.log(f"saved {args.mip_angles} maximum-intensity projections of {', '.join(rows)} to {path}")
+    if args.base_samples.lower().endswith((".tif", ".tiff")):
+        from guided_diffusion import tiff_io
+        tiff_io.imwrite(path.replace(".npz", ".tif"), images[0])
+        logger.log(f"Saved TIFF: {path.replace('.npz', '.tif')}")
+    return path
 
 
 def _load_roi(parser, args, vol):
@@ -586,13 +681,14 @@ def _check_spacing(parser, args):
     if not all(np.isfinite(v) and v > 0 for v in args.voxel_spacing):
         parser.error("--voxel_spacing must be three positive finite numbers (got %s)" % (args.voxel_spacing,))
     if not args.target_samples:
-        if args.model_spacing is not None or args.consistency_fwhm is not None:
-            return None                        # the spacing serves the regridding or the guidance alone
+        if args.model_spacing is not None or args.consistency_fwhm is not None or args.mip_angles is not None:
+            return None                        # the spacing serves the regridding, the guidance or the MIP alone
         parser.error("--voxel_spacing needs --target_samples: its figures are taken per region against the target")
     if not (args.roi_labels or _segmenting(args)):
         if (args.baseline_gaussian_fwhm is not None or args.model_spacing is not None
-                or args.consistency_fwhm is not None or args.spectrum):
-            return None         # the spacing serves the Gaussian baseline, the regridding, the guidance or the spectrum
+                or args.consistency_fwhm is not None or args.spectrum or args.mip_angles is not None):
+            # the spacing serves the Gaussian baseline, the regridding, the guidance, the spectrum or the MIP
+            return None
         parser.error("--voxel_spacing needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
     s0, s1, s2 = args.voxel_spacing
     try:
@@ -1321,6 +1417,8 @@ def _write_outputs(args, native, target, roi, result, std=None, weight=None, dra
             if x is not None:
                 tiff_io.imwrite(path, x.transpose(2, 0, 1).astype(np.float32))       # (H,W,Z) -> (Z,H,W)
                 logger.log(f"Saved TIFF: {path}")
+    if args.mip_angles is not None:
+        _write_mip(args, out_path, native, target, result, std)
     mpath = _write_metrics(args, out_path, target, native, result, std=std, weight=weight, roi=roi, draws=draws,
                            quantiles=qmaps)
     if trace is not None:

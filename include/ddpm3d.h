@@ -1215,6 +1215,71 @@ size_t ddpm3d_regrid_workspace_bytes(int B, int D, int H, int W, int Do, int Ho,
 int ddpm3d_regrid(const float* vol, int B, int D, int H, int W, const ddpm3d_regrid_axis axes[3] /* D, H, W */,
                   float* out, void* ws, size_t ws_bytes, void* stream);
 /*
+ * Rotating maximum-intensity and ray-sum projections (added within ABI 13; the reference has no such code; DESIGN.md
+ * 3.22): the library's image output, and the parallel-beam X-ray transform of every axial slice.  B fp32 volumes
+ * [D][H][W], W innermost, B in 1..DDPM3D_MAX_DRAWS; the rotation is about D, so every ray stays in one (H, W) slice
+ * and a sample is a bilinear interpolant.  With the spacing (s1, s2) mm along H and W, the detector pitch p mm and
+ * bin count U, the step delta mm and R samples per ray, and (c, s) = (cos, sin) of the angle, bin u and sample j sit at
+ *   a = (u - (U - 1) / 2) p,   r = (j - (R - 1) / 2) delta                      (mm, about the slice's centre)
+ *   w' = (a c - r s) / s2 + (W - 1) / 2,   h' = (a s + r c) / s1 + (H - 1) / 2  (voxel indices, continuous)
+ * ddpm3d_project_table_fill folds this on the host, in fp64, into six numbers per angle, each rounded to fp32 once:
+ * coef[k] = {h0, hu, hj, w0, wu, wj}, origin, per-u and per-j increment of h' and of w' (c and s are exactly 0 or +-1
+ * at multiples of 90 degrees).  The device forms h' = fma(u, hu, fma(j, hj, h0)) and w' = fma(u, wu, fma(j, wj, w0)).
+ * The table is a HOST struct, read during the call only: it travels in the kernel arguments.
+ *
+ * A sample COUNTS iff 0 <= h' <= H - 1 and 0 <= w' <= W - 1.  With y = floor(h'), x = floor(w'), fy = h' - y,
+ * fx = w' - x (both exact), y1 = min(y + 1, H - 1), x1 = min(x + 1, W - 1) its value is, in fp32,
+ *   top = fma(fx, v[y][x1] - v[y][x], v[y][x]),  bot = fma(fx, v[y1][x1] - v[y1][x], v[y1][x]),
+ *   v = fma(fy, bot - top, top)
+ * so a NaN in any of the four corners makes the sample NaN, and a NaN sample makes its ray's output NaN in both modes.
+ *   DDPM3D_PROJECT_MAX: the largest counted sample, 0.0f where none counts (the MIP)
+ *   DDPM3D_PROJECT_SUM: acc = fma(delta, v_j, acc) over the counted samples in ascending j, from acc = 0: the line
+ *                       integral in value * mm
+ * out: [B][angles][D][U] fp32.  One launch; a thread owns one ray, so there are no atomics, the bits are the same on
+ * every run, and row b does not depend on B.  There is no keep mask: a caller who wants planes left out hands in the
+ * cut box.
+ *
+ * Error bound, against an fp64 evaluation of the same fp32 table (u = 2^-24; second-order terms are covered by a
+ * factor 1 + 2^-20 on the whole).  Per counted sample:
+ *   coordinates: t = fma(j, hj, h0) and h' = fma(u, hu, t) round once each, so |h' - h'_ref| <= e_h = u (|t| + |h'|),
+ *     likewise e_w; the fractions are exact.  A stage whose exact value is an fp32 number does not round; where both
+ *     are, the coordinate is EXACT and its e is 0 (multiples of 90 degrees with dyadic p / s and delta / s ratios).
+ *     The interpolant is continuous and bilinear per cell, so this moves the sample by at most e_h G_h + e_w G_w, with
+ *     G_h (G_w) the largest |difference| of two voxels adjacent along H (W) among the corners of the sample's cell and
+ *     of the cells that touch it (e is far below a voxel, but may carry the sample across a grid line)
+ *   lerp: the two differences, the two inner fmas, the outer difference and the outer fma round once each:
+ *     at most 6 u A, with A the largest |voxel| among the same corners
+ *   E_j = e_h G_h + e_w G_w + 6 u A
+ * max:  |out - ref| <= max over the counted j of E_j
+ * sum:  n counted samples, g_n = n u / (1 - n u) for the chain's n roundings:
+ *       |out - ref| <= delta ((1 + g_n) sum_j E_j + g_n sum_j |v_j|)
+ * A sample whose coordinate is not exact and lies within max(2^-12 voxel, e) of a face of the counting box (0 or
+ * H - 1, 0 or W - 1) may count on the device and not in the reference, or the reverse; an output with such a sample
+ * is AMBIGUOUS and outside the bound, the analogue of ddpm3d_nlm's cutoff clause (e < 2^-12 while
+ * |t| + |coordinate| < 4096).  Where the coordinates are exact nothing is ambiguous.
+ *
+ * ddpm3d_project_table_fill returns DDPM3D_EINVAL for a NULL pointer, H or W below 1, a spacing, pitch or step that is
+ * not positive and finite, bins or samples outside 1..DDPM3D_PROJECT_MAX_BINS, an angle count outside
+ * 1..DDPM3D_PROJECT_MAX_ANGLES, an angle that is not finite and a table entry that is not finite in fp32; it touches no
+ * device.  ddpm3d_project returns DDPM3D_EINVAL before any launch for a NULL pointer, out overlapping vol, B outside
+ * 1..DDPM3D_MAX_DRAWS, table->angles outside 1..DDPM3D_PROJECT_MAX_ANGLES, table->bins or table->samples outside
+ * 1..DDPM3D_PROJECT_MAX_BINS, an extent below 1, H or W above 2^24 (H - 1 and W - 1 are compared in fp32), more than
+ * 2^31 - 1 voxels in (B D H W) or out (B angles D U), a table entry or a step that is not finite, and an unknown
+ * mode.
+ */
+#define DDPM3D_PROJECT_MAX_ANGLES 64
+#define DDPM3D_PROJECT_MAX_BINS 4096
+enum { DDPM3D_PROJECT_MAX = 0, DDPM3D_PROJECT_SUM = 1 };
+typedef struct ddpm3d_project_table {
+    int32_t angles, bins, samples;                  /* A, U, R */
+    float   step;                                   /* delta, mm */
+    float   coef[DDPM3D_PROJECT_MAX_ANGLES][6];     /* per angle: h0, hu, hj, w0, wu, wj */
+} ddpm3d_project_table;
+int ddpm3d_project_table_fill(int H, int W, double s1, double s2, double pitch, int bins, double step, int samples,
+                              const double* angles_deg, int angles, ddpm3d_project_table* table);
+int ddpm3d_project(const float* vol, int B, int D, int H, int W, const ddpm3d_project_table* table, int mode,
+                   float* out, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
