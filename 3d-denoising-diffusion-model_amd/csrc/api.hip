@@ -1553,6 +1553,36 @@ int ddpm3d_project(const float* vol, int B, int D, int H, int W, const ddpm3d_pr
     return launched(ddpm3d_launch_project(vol, B, D, H, W, *table, mode, out, (hipStream_t)stream), "project");
 }
 
+// ------------------------------------------------- squared Euclidean distance transform (added within ABI 13)
+int ddpm3d_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int invert, double s0, double s1, double s2,
+                       float* out, void* stream) {
+    if (!mask || !out) return fail(DDPM3D_EINVAL, "distance_sq: null pointer");
+    if (K < 1 || D < 1 || H < 1 || W < 1)
+        return fail(DDPM3D_EINVAL, "distance_sq: bad volumes (K=%d D=%d H=%d W=%d; 1 or more each)", K, D, H, W);
+    const int lim = DDPM3D_EDT_MAX_EXTENT;
+    if (D > lim || H > lim || W > lim)
+        return fail(DDPM3D_EINVAL, "distance_sq: a %d x %d x %d volume (every extent is at most %d)", D, H, W, lim);
+    const int64_t top = 0x7fffffff, voxels = (int64_t)D * H * W;
+    if (voxels > top) return fail(DDPM3D_EINVAL, "distance_sq: %lld voxels per volume (at most 2^31 - 1)", (long long)voxels);
+    const int64_t cols = DDPM3D_EDT_COLUMNS;
+    if ((int64_t)K * D * H > top || (int64_t)K * D * ((W + cols - 1) / cols) > top ||
+        (int64_t)K * (((int64_t)H * W + cols - 1) / cols) > top)
+        return fail(DDPM3D_EINVAL, "distance_sq: K=%d volumes of %d x %d x %d are more workgroups than one launch "
+                                   "takes", K, D, H, W);
+    const double sd[3] = {s0, s1, s2};
+    float sf[3];
+    for (int a = 0; a < 3; ++a) {
+        sf[a] = positive_finite(sd[a]) ? (float)sd[a] : 0.0f;
+        if (!(sf[a] > 0.0f) || !finite_f32(sf[a]))
+            return fail(DDPM3D_EINVAL, "distance_sq: spacing (%g, %g, %g) mm (positive and finite, also in fp32)", s0,
+                        s1, s2);
+    }
+    if (invert != 0 && invert != 1) return fail(DDPM3D_EINVAL, "distance_sq: invert=%d (0 or 1)", invert);
+    if (ranges_overlap(mask, (size_t)K * voxels, out, (size_t)K * voxels * sizeof(float)))
+        return fail(DDPM3D_EINVAL, "distance_sq: out overlaps mask");
+    return launched(ddpm3d_launch_distance_sq(mask, K, D, H, W, invert, sf, out, (hipStream_t)stream), "distance_sq");
+}
+
 // ------------------------------------------------- low-pass pull of x_start (added within ABI 13)
 static bool pull_shape_ok(int N, int D, int H, int W) {
     return N >= 1 && N <= 65535 && volume_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;

@@ -180,6 +180,11 @@ hipError_t ddpm3d_launch_nlm(const float* vol, int D, int H, int W, const int* s
 struct ddpm3d_project_table;
 hipError_t ddpm3d_launch_project(const float* vol, int B, int D, int H, int W, const ddpm3d_project_table& table,
                                  int mode, float* out, hipStream_t st);
+// edt.hip: the squared distance in mm^2 from every foreground voxel ((mask != 0) != invert) of K volumes to the nearest
+// background voxel of its volume, s[] the fp32 spacings along D, H, W; three launches, the last two in place on out
+// (the caller has checked the shape, the spacings and invert)
+hipError_t ddpm3d_launch_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int invert, const float s[3],
+                                     float* out, hipStream_t st);
 // regrid.hip: B volumes of one shape onto another grid, passes along W, H, D with the tables of axes[] (D, H, W order)
 // in device memory (the caller has checked the shapes, the taps, the ratios and the workspace); stage[] gets the voxels
 // per volume after the W, the H and the D pass, of which the first two, times B, are the workspace's two buffers

@@ -124,6 +124,8 @@ ROI_MAX_REGIONS, ROI_CHUNK = 4096, 4096
 TEX_MAX_LEVELS = 64
 (TEX_N, TEX_BELOW, TEX_ABOVE, TEX_PAIRS, TEX_REC) = range(5)
 CCL_TILE = (8, 8, 64)   # DDPM3D_CCL_TILE_D / _H / _W: the brick one workgroup of ddpm3d_label_components labels in LDS
+# DDPM3D_EDT_COLUMNS / _MAX_EXTENT: the columns a workgroup of ddpm3d_distance_sq stages in LDS, the longest line
+EDT_COLUMNS, EDT_MAX_EXTENT = 16, 1024
 PEAK_MAX_RADIUS = 8     # DDPM3D_PEAK_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_sphere_mean's footprint
 SMOOTH_MAX_RADIUS = 16  # DDPM3D_SMOOTH_MAX_RADIUS: the largest per-axis radius, in voxels, of ddpm3d_gauss_smooth's taps
 NLM_MAX_SEARCH, NLM_MAX_PATCH = 5, 2    # DDPM3D_NLM_MAX_SEARCH / _PATCH: ddpm3d_nlm's largest window radii per axis
@@ -296,6 +298,7 @@ EXPORTS = {
     "ddpm3d_project_table_fill": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double,
                                             C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(ProjectTable)]),
     "ddpm3d_project": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(ProjectTable), C.c_int, _fp, _fp]),
+    "ddpm3d_distance_sq": (C.c_int, [_fp] + [C.c_int] * 5 + [C.c_double] * 3 + [_fp, _fp]),
     "ddpm3d_noise_fill": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_noise_bits": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_p_sample_step_keyed": (C.c_int, [_fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,

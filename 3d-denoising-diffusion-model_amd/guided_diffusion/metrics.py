@@ -51,6 +51,12 @@ detector and a list of angles into the six fp32 numbers per angle ddpm3d_project
 the host), project is one launch of ddpm3d_project (csrc/project.hip) over a volume or a stack: the MIP ("max") or
 the line integral ("sum") of every ray through every slice, rotated about the D axis.
 
+Distances and lesion boundaries: distance_sq is one call of ddpm3d_distance_sq (csrc/edt.hip), the
+exact squared Euclidean distance transform on anisotropic voxels; surface, boundary_target and boundary turn two such
+transforms into Dice, Hausdorff, HD95 and ASSD figures of an estimate's segmentation against the target's, whole and
+per target region, with one device-to-host copy; edge_profile reduces every volume over shells of a given width
+inside and outside the labelled regions' boundary (roi_index, roi_moments).
+
 Credible intervals: interval_figures scores two per-voxel quantile maps of
 uncertainty.draw_quantiles against the target: the share of voxels the interval covers and its mean width.
 """
@@ -1556,3 +1562,221 @@ def project(volume, plan, mode="max"):
         H.check(H.load().ddpm3d_project(H.ptr(volume), K, D, Hh, W, ctypes.byref(plan.table),
                                         PROJECTION_MODES[mode], H.ptr(out), H.stream()))
     return out
+
+
+# ----------------------------------------------------------------- distances, lesion boundaries
+PERCENTILE = 0.95           # of hd95_mm and surface_p95_mm
+EDGE_MAX_SHELLS = 64        # inside + outside of edge_profile
+
+
+def _mask_u8(mask, what):
+    """a device uint8 or bool tensor (D, H, W) or (K, D, H, W) -> contiguous uint8 (a bool tensor's bytes are 0 / 1)"""
+    if not (isinstance(mask, torch.Tensor) and mask.is_cuda):
+        raise RuntimeError("%s must live on the GPU: this package runs on HIP kernels only "
+                           "(got %s)" % (what, getattr(mask, "device", type(mask))))
+    if mask.dtype not in (torch.uint8, torch.bool) or mask.dim() not in (3, 4):
+        raise ValueError("%s must be a uint8 or bool tensor (D, H, W) or (K, D, H, W), got %s of shape %s"
+                         % (what, mask.dtype, tuple(mask.shape)))
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def distance_sq(mask, spacing, invert=False):
+    """The squared distance in mm^2 from every foreground voxel of a device uint8 or bool tensor (D, H, W) or
+    (K, D, H, W) to the nearest background voxel of its volume, 0 on the background and +inf in a volume without
+    background: scipy.ndimage.distance_transform_edt(mask, sampling=spacing) ** 2.  Foreground is mask != 0, or
+    mask == 0 with invert.  `spacing` = (s0, s1, s2) mm along D, H, W.  One call of ddpm3d_distance_sq
+    (csrc/edt.hip), no host copy.  -> a device float32 tensor of the mask's shape."""
+    spacing = _check_spacing(spacing, "distance_sq")
+    m = _mask_u8(mask, "distance_sq: mask")
+    K = int(m.shape[0]) if m.dim() == 4 else 1
+    D, Hh, W = (int(v) for v in m.shape[-3:])
+    if max(D, Hh, W) > H.EDT_MAX_EXTENT:
+        raise ValueError("distance_sq: a %d x %d x %d volume (every extent is at most %d)"
+                         % (D, Hh, W, H.EDT_MAX_EXTENT))
+    with torch.cuda.device(m.device):
+        out = torch.empty(tuple(m.shape), dtype=torch.float32, device=m.device)
+        H.check(H.load().ddpm3d_distance_sq(H.ptr(m), K, D, Hh, W, 1 if invert else 0, spacing[0], spacing[1],
+                                            spacing[2], H.ptr(out), H.stream()))
+    return out
+
+
+def surface(mask):
+    """The voxels of a device uint8 or bool mask (D, H, W) with at least one of the 6 face neighbours outside the mask;
+    a neighbour beyond the volume counts as outside: mask & ~scipy.ndimage.binary_erosion(mask) with the default
+    structure and border_value=0.  torch ops on the device.  -> a device bool tensor (D, H, W)."""
+    m = _mask_u8(mask, "surface: mask")
+    if m.dim() != 3:
+        raise ValueError("surface: mask of shape %s (want (D, H, W))" % (tuple(m.shape),))
+    with torch.cuda.device(m.device):
+        m = (m != 0).to(torch.uint8)
+        p = torch.nn.functional.pad(m, (1, 1, 1, 1, 1, 1))
+        inner = (p[:-2, 1:-1, 1:-1] & p[2:, 1:-1, 1:-1] & p[1:-1, :-2, 1:-1] & p[1:-1, 2:, 1:-1]
+                 & p[1:-1, 1:-1, :-2] & p[1:-1, 1:-1, 2:])
+        return (m & ~inner & 1).bool()
+
+
+def _percentile_at(n):
+    """numpy.percentile's method "linear" at PERCENTILE over n sorted values -> (lo, hi, t): lerp of v[lo], v[hi]"""
+    pos = PERCENTILE * (n - 1)
+    lo = int(math.floor(pos))
+    return lo, min(lo + 1, n - 1), pos - lo
+
+
+def _lerp(a, b, t):
+    """numpy's _lerp: a + (b - a) t, from the far end for t >= 0.5"""
+    return b - (b - a) * (1.0 - t) if t >= 0.5 else a + (b - a) * t
+
+
+class BoundaryTarget:
+    """boundary_target's return, the target's side of boundary: `spacing`, the foreground `fg` (device bool) and its
+    voxel count `n_fg`, `dist` (device fp32: mm from every voxel to the target's nearest surface voxel), `roi` (the
+    RoiIndex of the surface voxels, labelled by region) and `n_surface`."""
+
+    def __init__(self, spacing, fg, n_fg, dist, roi):
+        self.spacing, self.fg, self.n_fg, self.dist, self.roi = spacing, fg, n_fg, dist, roi
+        self.n_surface = roi.offsets[-1]
+        self.where = [_percentile_at(self.n_surface)] + [_percentile_at(n) for n in roi.counts]
+        starts = [0] + roi.offsets[:-1]                                     # of the whole set, then of every region
+        at = [s + w[0] for s, w in zip(starts, self.where)] + [s + w[1] for s, w in zip(starts, self.where)]
+        dev = roi.device
+        self._at = torch.tensor(at, dtype=torch.int64).to(dev)
+        self._ordinal = torch.repeat_interleave(torch.arange(len(roi), dtype=torch.int64, device=dev),
+                                                torch.tensor(roi.counts, dtype=torch.int64).to(dev))
+
+
+def boundary_target(target_labels, spacing):
+    """The part of boundary that depends on the target alone, for a caller that scores several estimates: the surface
+    of target_labels > 0, one distance_sq call on its complement, and the region index of the surface voxels.
+    -> BoundaryTarget"""
+    _check_labels(target_labels, "target_labels")
+    spacing = _check_spacing(spacing, "boundary")
+    with torch.cuda.device(target_labels.device):
+        fg = target_labels > 0
+        n_fg = int(fg.sum())
+        if n_fg == 0:
+            raise ValueError("boundary: the target has no foreground")
+        surf = surface(fg)
+        dist = distance_sq(surf, spacing, invert=True).sqrt_()
+        roi = roi_index(torch.where(surf, target_labels, torch.zeros_like(target_labels)))
+    return BoundaryTarget(spacing, fg, n_fg, dist, roi)
+
+
+def boundary(target_labels, estimate_labels, spacing, index=None):
+    """Where the estimate's segmentation put the lesion boundaries against the target's, both device integer label
+    volumes (D, H, W) as segment returns them.  Surfaces are surface() of labels > 0; a directed distance is the
+    distance in mm from a surface voxel of one to the nearest surface voxel of the other (two distance_sq calls, on
+    the complement of each surface; `index` = boundary_target(target_labels, spacing) hands the target's in).  Given
+    the index, the rest is torch ops, roi_moments over the target's surface voxels and ONE device-to-host copy.
+    -> {"dice", "jaccard" (of the foregrounds), "hd_mm" (the larger of the two directed maxima), "hd95_mm" (the larger
+    of the two directed 95th percentiles, numpy's method "linear"), "assd_mm" (the sum of all directed distances over
+    the count of both surfaces), "n_surface_target", "n_surface_estimate", "regions": {target label: {"surface_mean_mm",
+    "surface_p95_mm", "surface_max_mm"}}}.  A region's figures are DIRECTED: from that lesion's surface voxels to the
+    estimate's surface of ANY component, not only of the component that overlaps it.  When the estimate has no
+    foreground, dice and jaccard are 0 and every distance is None (decided on the host from the counts in the copy)."""
+    tgt = boundary_target(target_labels, spacing) if index is None else index
+    if not isinstance(tgt, BoundaryTarget):
+        raise ValueError("boundary: index must be boundary_target's return (got %r)" % (index,))
+    _check_labels(target_labels, "target_labels")
+    _check_labels(estimate_labels, "estimate_labels")
+    spacing = _check_spacing(spacing, "boundary")
+    if (tuple(estimate_labels.shape) != tgt.roi.shape or tuple(target_labels.shape) != tgt.roi.shape
+            or estimate_labels.device != tgt.roi.device or spacing != tgt.spacing):
+        raise ValueError("boundary: estimate labels of shape %s on %s at %s mm against a target of shape %s on %s at "
+                         "%s mm" % (tuple(estimate_labels.shape), estimate_labels.device, spacing, tgt.roi.shape,
+                                    tgt.roi.device, tgt.spacing))
+    R = len(tgt.roi)
+    with torch.cuda.device(tgt.roi.device):
+        e_fg = estimate_labels > 0
+        e_surf = surface(e_fg)
+        to_e = distance_sq(e_surf, spacing, invert=True).sqrt_()         # +inf everywhere without an estimate surface
+        # target -> estimate: the values at the target's surface voxels, sorted as a whole and within each region
+        v = to_e.reshape(-1).index_select(0, tgt.roi.index)
+        whole, order = torch.sort(v)
+        by_region = whole.index_select(0, torch.sort(tgt._ordinal.index_select(0, order), stable=True).indices)
+        n_pick = 1 + R
+        at = tgt._at
+        picks_t = torch.cat([whole.index_select(0, at[0:1]), by_region.index_select(0, at[1:n_pick]),
+                             whole.index_select(0, at[n_pick:n_pick + 1]),
+                             by_region.index_select(0, at[n_pick + 1:])]).double()
+        rec = _roi_moments_device(to_e, tgt.roi)[0]                      # (R, H.ROI_REC) fp64, fixed-order sums
+        # estimate -> target: the estimate's surface count stays on the device, so the whole volume is sorted
+        n_e = e_surf.sum()
+        last = (n_e - 1).clamp(min=0)
+        pos = PERCENTILE * last.double()
+        lo = pos.floor().long()
+        ranked = torch.sort(tgt.dist.masked_fill(~e_surf, math.inf).reshape(-1)).values
+        picks_e = ranked.index_select(0, torch.stack([lo, torch.minimum(lo + 1, last), last])).double()
+        sum_e = tgt.dist.masked_fill(~e_surf, 0.0).sum(dtype=torch.float64)
+        head = torch.stack([e_fg.sum(), (e_fg & tgt.fg).sum(), n_e]).double()
+        got = torch.cat([head, sum_e.reshape(1), picks_e, picks_t,
+                         rec[:, H.ROI_SUM_X], rec[:, H.ROI_MAX_X]]).cpu().tolist()   # the one device-to-host copy
+    n_efg, both, n_es = (int(x) for x in got[:3])
+    sum_e, e_lo, e_hi, e_max = got[3:7]
+    t = got[7:7 + 2 * n_pick]
+    sums, maxima = got[7 + 2 * n_pick:7 + 2 * n_pick + R], got[7 + 2 * n_pick + R:]
+    out = {"dice": 2.0 * both / (tgt.n_fg + n_efg), "jaccard": both / (tgt.n_fg + n_efg - both),
+           "hd_mm": None, "hd95_mm": None, "assd_mm": None, "n_surface_target": tgt.n_surface,
+           "n_surface_estimate": n_es, "regions": {}}
+    p95 = [_lerp(t[i], t[n_pick + i], tgt.where[i][2]) for i in range(n_pick)]
+    for r, label in enumerate(tgt.roi.labels):
+        out["regions"][label] = ({"surface_mean_mm": sums[r] / tgt.roi.counts[r], "surface_p95_mm": p95[1 + r],
+                                  "surface_max_mm": maxima[r]} if n_efg else
+                                 {"surface_mean_mm": None, "surface_p95_mm": None, "surface_max_mm": None})
+    if n_efg:
+        pos = PERCENTILE * (n_es - 1)
+        out["hd_mm"] = max(max(maxima), e_max)
+        out["hd95_mm"] = max(p95[0], _lerp(e_lo, e_hi, pos - math.floor(pos)))
+        out["assd_mm"] = (math.fsum(sums) + sum_e) / (tgt.n_surface + n_es)
+    return out
+
+
+def edge_profile(volumes, labels, spacing, width_mm, inside=3, outside=5, keep=None):
+    """The mean of every volume in shells of width_mm around the boundary of labels > 0 (a device integer (D, H, W)
+    tensor): the activity profile across the lesion edge, which shows spill-out.  `volumes` is a dict of name ->
+    device float32 (D, H, W) tensor.  d_in = sqrt(distance_sq(fg)) and d_out = sqrt(distance_sq(fg, invert=True));
+    inside shell i (0 .. inside - 1) holds the foreground voxels with i W < d_in <= (i + 1) W, outside shell o the
+    background voxels with o W < d_out <= (o + 1) W; voxels with keep == 0 (an optional device uint8 tensor) are
+    dropped.  The shells become a label volume, and roi_index and one roi_moments call reduce every volume over it.
+    -> {"width_mm", "inside", "outside", "rows": [{"distance_mm" (the shell's centre, negative inside), "n", "mean":
+    {name: mean or None}}]}, rows from the innermost shell outward."""
+    _check_labels(labels, "labels")
+    spacing = _check_spacing(spacing, "edge_profile")
+    width = _positive(width_mm, "edge_profile: width_mm")
+    for name, v in (("inside", inside), ("outside", outside)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("edge_profile: %s must be an integer of 0 or more (got %r)" % (name, v))
+    inside, outside = int(inside), int(outside)
+    if not 1 <= inside + outside <= EDGE_MAX_SHELLS:
+        raise ValueError("edge_profile: inside + outside = %d shells (1..%d)" % (inside + outside, EDGE_MAX_SHELLS))
+    if not isinstance(volumes, dict) or not volumes:
+        raise ValueError("edge_profile: volumes must be a dict of name -> device float32 (D, H, W) tensor")
+    names = list(volumes)
+    for name in names:
+        H.require_device(volumes[name], "edge_profile: volume %r" % (name,))
+        if tuple(volumes[name].shape) != tuple(labels.shape) or volumes[name].device != labels.device:
+            raise ValueError("edge_profile: volume %r of shape %s, labels of shape %s"
+                             % (name, tuple(volumes[name].shape), tuple(labels.shape)))
+    with torch.cuda.device(labels.device):
+        fg = labels > 0
+        edges = torch.arange(max(inside, outside) + 1, dtype=torch.float64, device=labels.device) * width
+        b_in = torch.bucketize(distance_sq(fg, spacing).double().sqrt_(), edges)      # i + 1 in shell i, 0 at d = 0
+        b_out = torch.bucketize(distance_sq(fg, spacing, invert=True).double().sqrt_(), edges)
+        zero = torch.zeros_like(b_in)
+        shells = (torch.where((b_in >= 1) & (b_in <= inside), inside + 1 - b_in, zero)
+                  + torch.where((b_out >= 1) & (b_out <= outside), inside + b_out, zero)).int()
+        try:
+            index = roi_index(shells, keep=keep)
+        except ValueError as e:
+            if "no labelled voxel" not in str(e):
+                raise
+            index = None
+        rec = [] if index is None else roi_moments(torch.stack([volumes[n] for n in names]), index)
+    at = {} if index is None else {label: r for r, label in enumerate(index.labels)}
+    rows = []
+    for j in range(1, inside + outside + 1):
+        r = at.get(j)
+        n = 0 if r is None else int(rec[0][r][H.ROI_N])
+        rows.append({"distance_mm": (j - inside - 0.5) * width, "n": n,
+                     "mean": {name: (rec[k][r][H.ROI_SUM_X] / n if n else None) for k, name in enumerate(names)}})
+    return {"width_mm": width, "inside": inside, "outside": outside, "rows": rows}

@@ -119,6 +119,21 @@ all rows), each (N, D, U) float32: "denoised" and "input", with
 "pitch_mm"; .tif input also gets mip_<name>.tif, the denoised stack; the
 one-shot paths project [1, n - 1) of each axis, `--joint_patches` the whole
 volume;
+`--roi_boundary True` (needs `--roi_threshold` or `--roi_threshold_frac`, and
+`--voxel_spacing`) adds "boundary" beside "detection": where the input's and
+the denoised volume's own segmentations put the lesion boundaries against the
+target's (guided_diffusion/metrics.py boundary, DESIGN.md 3.23: Dice, Jaccard,
+Hausdorff distance, its 95th percentile and the average symmetric surface
+distance in mm, from two exact distance transforms on the GPU), "boundary" in
+every region's "input" and "denoised" figures (mean, 95th percentile and
+maximum of the distance from that lesion's surface to the estimate's) and, with
+`--num_draws`, "draws": Dice and HD95 of every draw;
+`--roi_edge_profile_mm W` (needs `--target_samples`, `--voxel_spacing` and
+regions; W at least the smallest spacing) adds "edge_profile" to "roi": the
+mean of target, input, baselines and written volume in 3 shells of W mm inside
+and 5 outside the regions' boundary (`--roi_background`'s region is not
+foreground), the activity profile that shows spill-out
+(guided_diffusion/metrics.py edge_profile);
 `--trace True` (any path, any sampler, no other flag needed) records how every
 reverse step's pred_xstart moves (guided_diffusion/metrics.py StepTrace: one
 small reduction per step on the GPU, nothing waits inside the loop) and writes
@@ -232,7 +247,10 @@ def create_argparser():
                     roi_connectivity=26, roi_min_voxels=1,
                     # radial power spectra and Fourier shell correlation of every metric row (not in the reference;
                     # needs --target_samples and --voxel_spacing), and their window: hann or none
-                    spectrum=False, spectrum_window="hann")
+                    spectrum=False, spectrum_window="hann",
+                    # surface distances (Dice, HD, HD95, ASSD) of the input's and the denoised volume's segmentation
+                    # against the target's (not in the reference; needs a --roi_threshold and --voxel_spacing)
+                    roi_boundary=False)
     defaults.update(sr_model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
@@ -267,6 +285,9 @@ def create_argparser():
     # rotating maximum-intensity projections about the input file's axis 0, at the angles k * 360 / N, written as
     # mip_<name>.npz (needs --voxel_spacing, which then needs neither a target nor regions)
     parser.add_argument("--mip_angles", type=int, default=None, metavar="N")
+    # the mean of every scored volume in shells of this width in mm across the regions' boundary (needs
+    # --target_samples, --voxel_spacing and regions)
+    parser.add_argument("--roi_edge_profile_mm", type=float, default=None, metavar="W")
     return parser
 
 
@@ -292,10 +313,12 @@ def main(argv=None):
     _check_consistency(parser, args)
     _check_spectrum(parser, args)
     _check_mip(parser, args)
+    _check_boundary(parser, args)
     args.peak = _check_spacing(parser, args)
     args.texture = _check_texture(parser, args)
     args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
+    _plan_boundary(parser, args, vol)
     vol = _plan_mip(parser, args, vol)
     vol = _plan_regrid(parser, args, vol)
     _plan_consistency(parser, args)
@@ -518,6 +541,42 @@ def _write_mip(args, out_path, native, target, result, std):
         tiff_io.imwrite(path.replace(".npz", ".tif"), images[0])
         logger.log(f"Saved TIFF: {path.replace('.npz', '.tif')}")
     return path
+
+
+def _check_boundary(parser, args):
+    """--roi_boundary / --roi_edge_profile_mm, checked before any file is read"""
+    if args.roi_boundary:
+        if not _segmenting(args):
+            parser.error("--roi_boundary needs --roi_threshold or --roi_threshold_frac: it compares segmentations made "
+                         "at one threshold")
+        if args.voxel_spacing is None:
+            parser.error("--roi_boundary needs --voxel_spacing: its distances are in mm")
+    width = args.roi_edge_profile_mm
+    if width is None:
+        return
+    if not (np.isfinite(width) and width > 0):
+        parser.error("--roi_edge_profile_mm must be a positive finite width in mm (got %r)" % width)
+    if not args.target_samples:
+        parser.error("--roi_edge_profile_mm needs --target_samples: the profile is taken beside the target's")
+    if args.voxel_spacing is None:
+        parser.error("--roi_edge_profile_mm needs --voxel_spacing: the shells are in mm")
+    if not (args.roi_labels or _segmenting(args)):
+        parser.error("--roi_edge_profile_mm needs regions: give --roi_labels, --roi_threshold or --roi_threshold_frac")
+    spacing = args.voxel_spacing
+    if len(spacing) == 3 and all(np.isfinite(v) and v > 0 for v in spacing) and width < min(spacing):
+        parser.error("--roi_edge_profile_mm %g is below the smallest voxel spacing %g mm: a shell thinner than a voxel "
+                     "holds no voxel" % (width, min(spacing)))
+
+
+def _plan_boundary(parser, args, vol):
+    """--roi_boundary / --roi_edge_profile_mm: the distance transform's extent limit against the file's shape, the
+    grid the figures are taken on, before the model is built"""
+    if not (args.roi_boundary or args.roi_edge_profile_mm is not None):
+        return
+    if max(vol.shape) > _hip.EDT_MAX_EXTENT:
+        parser.error("%s: the distance transform takes extents up to %d (volume %s)"
+                     % ("--roi_boundary" if args.roi_boundary else "--roi_edge_profile_mm", _hip.EDT_MAX_EXTENT,
+                        tuple(vol.shape)))
 
 
 def _load_roi(parser, args, vol):
@@ -932,10 +991,12 @@ def _segment_target(parser, args, vol, target):
             "min_voxels": args.roi_min_voxels}
 
 
-def _detection_block(seg, regions, inp, den, draw_found):
+def _detection_block(seg, regions, inp, den, draw_found, edges=None, draw_edges=None):
     """"detection" of the "roi" entry: the target's lesions against the input's and the denoised volume's own
-    segmentation at the same threshold; every region gains "found" and "overlap" under "input" and "denoised"."""
-    out = {}
+    segmentation at the same threshold; every region gains "found" and "overlap" under "input" and "denoised".  With
+    --roi_boundary (edges = (the spacing, metrics.boundary_target of the labels)) the same two segmentations also give
+    "boundary", and every region "boundary" under "input" and "denoised".  -> the entries to add to "roi"."""
+    out, bound = {}, {}
     for name, x in (("input", inp), ("denoised", den)):
         est, _ = metrics.segment(x, seg["threshold"], connectivity=seg["connectivity"], min_voxels=seg["min_voxels"],
                                  keep=seg["keep"])
@@ -943,13 +1004,26 @@ def _detection_block(seg, regions, inp, den, draw_found):
         for r in range(seg["n"]):
             regions[str(r + 1)][name]["found"] = d["found"][r]
             regions[str(r + 1)][name]["overlap"] = d["overlap"][r]
+        if edges is not None:
+            b = metrics.boundary(seg["labels"], est, edges[0], index=edges[1])
+            for label, figures in b.pop("regions").items():
+                regions[str(label)][name]["boundary"] = figures
+            bound[name] = b
     if draw_found is not None:
         out["denoised"]["draws"] = draw_found
+    if edges is not None and draw_edges is not None:
+        bound["denoised"]["draws"] = draw_edges
     logger.log("  lesions: %d in the target; input finds %d, misses %d, %d false positives; denoised finds %d, "
                "misses %d, %d false positives"
                % (seg["n"], out["input"]["n_found"], out["input"]["n_missed"], out["input"]["false_positives"],
                   out["denoised"]["n_found"], out["denoised"]["n_missed"], out["denoised"]["false_positives"]))
-    return out
+    if edges is None:
+        return {"detection": out}
+    show = lambda v: "n/a" if v is None else "%.4g" % v
+    logger.log("  boundaries: " + "; ".join(
+        "%s Dice %s, HD95 %s mm, ASSD %s mm" % (name, show(b["dice"]), show(b["hd95_mm"]), show(b["assd_mm"]))
+        for name, b in bound.items()))
+    return {"detection": out, "boundary": bound}
 
 
 def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=None):
@@ -980,9 +1054,12 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
     if texture is not None:                    # the target's own figures once, for every report
         more.update(texture=texture,
                     target_texture=metrics.texture_figures(metrics.roi_texture(tgt, index, **texture)))
-    records = draw_found = None
+    edges = None
+    if seg is not None and args.roi_boundary:  # the target's surface and its distance map once, for every estimate
+        edges = (peak["spacing"], metrics.boundary_target(labels, peak["spacing"]))
+    records = draw_found = draw_edges = None
     if draws is not None:
-        records, draw_found = [], []
+        records, draw_found, draw_edges = [], [], []
         if peak is not None:
             more["draw_peaks"] = []
         if texture is not None:
@@ -998,6 +1075,9 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
                                          min_voxels=seg["min_voxels"], keep=keep)
                 found = metrics.detection(labels, est)
                 draw_found.append({"n_found": found["n_found"], "false_positives": found["false_positives"]})
+                if edges is not None:
+                    b = metrics.boundary(labels, est, edges[0], index=edges[1])
+                    draw_edges.append({"dice": b["dice"], "hd95_mm": b["hd95_mm"]})
     den_rep = metrics.roi_report(den, tgt, index, background=background, draws=records, **more)
     inp_rep = metrics.roi_report(inp, tgt, index, background=background,
                                  **{k: v for k, v in more.items() if k not in ("draw_peaks", "draw_texture")})
@@ -1033,11 +1113,22 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
             logger.log("  WARNING: more than 5 %% of a region of the target falls outside the grey levels: choose "
                        "--roi_texture_bin (and --roi_texture_levels / --roi_texture_lower) so that %d bins span the "
                        "target's values" % texture["levels"])
+    if args.roi_edge_profile_mm is not None:
+        # --roi_background's region is not foreground; the written volume is the mean of the draws with --num_draws
+        lesions = labels if args.roi_background <= 0 else th.where(labels == args.roi_background,
+                                                                   th.zeros_like(labels), labels)
+        spaced["edge_profile"] = prof = metrics.edge_profile(
+            {"target": tgt, "input": inp, **(baselines or {}), "denoised": den}, lesions, peak["spacing"],
+            args.roi_edge_profile_mm, keep=keep)
+        logger.log("  edge profile, %g mm shells (distance: target / input / denoised): %s"
+                   % (prof["width_mm"], ", ".join("%+g: %s / %s / %s" % (
+                       (r["distance_mm"],) + tuple(show(r["mean"][k]) for k in ("target", "input", "denoised")))
+                       for r in prof["rows"])))
     if seg is None:
         return {"labels": args.roi_labels, "background": background, "regions": regions, **spaced}
     return {"labels": labels_path, "background": None, "threshold": seg["threshold"],
             "connectivity": seg["connectivity"], "min_voxels": seg["min_voxels"], "regions": regions,
-            "detection": _detection_block(seg, regions, inp, den, draw_found), **spaced}
+            **_detection_block(seg, regions, inp, den, draw_found, edges, draw_edges), **spaced}
 
 
 def _write_metrics(args, out_path, target, vol, result, std=None, weight=None, roi=None, draws=None, quantiles=None):

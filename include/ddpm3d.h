@@ -1280,6 +1280,51 @@ int ddpm3d_project_table_fill(int H, int W, double s1, double s2, double pitch, 
 int ddpm3d_project(const float* vol, int B, int D, int H, int W, const ddpm3d_project_table* table, int mode,
                    float* out, void* stream);
 /*
+ * Exact squared Euclidean distance transform on anisotropic voxels (added within ABI 13; the reference has no such
+ * code): the primitive under the lesion boundary figures (Dice, Hausdorff, HD95, ASSD) and the
+ * activity profile across a lesion's edge.  mask: K device uint8 volumes [D][H][W], W innermost, K >= 1; a voxel is
+ * FOREGROUND iff (mask != 0) != invert.  out: fp32 [K][D][H][W]: for a foreground voxel the SQUARED distance in mm^2
+ * between its centre and the centre of the nearest background voxel of the same volume, with the spacings (s0, s1, s2)
+ * mm along D, H, W; 0 for a background voxel; +inf in every voxel of a volume without a background voxel.  This is
+ * scipy.ndimage.distance_transform_edt(mask, sampling=spacing) ** 2.
+ *
+ * Definition, in fp32, with sa = (float)s_a:
+ *   pass W: n = the count of voxels to the nearest background voxel of the row (an exact integer, 0 on background),
+ *           t = s2 * (float)n, f0 = t * t; +inf in a row without background
+ *   pass H: f1(y) = min over y' of fmaf(a, a, f0(y')), a = s1 * (float)(y - y')
+ *   pass D: the same rule on f1, with s0
+ * A minimum over a fixed set of fp32 values does not depend on the order it is taken in, and no NaN can arise (every
+ * term is a sum of non-negative numbers or +inf).  So the bits are the same on every run, for every K and launch
+ * geometry, and volume k does not depend on the stack.  The device scans outward from y and stops once a * a, rounded,
+ * is >= the best so far: fmaf(a, a, f) >= fl(a * a) for f >= 0 by the monotonicity of rounding, and |a| grows with
+ * the offset, so no later candidate can be strictly smaller and the bits are those of the full minimum.  (It tests the
+ * rule once per four offsets; the candidates a test at every offset would have cut cannot win either.)
+ *
+ * Error bound, against fp64 arithmetic on the fp32-rounded spacings (u = 2^-24): every finite output lies within a
+ * factor (1 + u)^5 of the exact squared distance.  t rounds once and f0 once more: f0 = (s2 n)^2 (1 + e)^3.  In pass
+ * H, a rounds once, so a^2 carries (1 + e)^2, and the fma rounds the sum once: f1 is a sum of two non-negative terms
+ * with relative errors within (1 + u)^3 and (1 + u)^2, times (1 + u), so within (1 + u)^4; pass D adds
+ * a^2 (1 + e)^2 to that and rounds once: (1 + u)^5.  Without the contraction into an fma the product a * a rounds
+ * too: a^2 (1 + e)^3 beside f0 (1 + e)^3, then the sum: (1 + u)^4, and (1 + u)^5 after pass D, the same bound.  The
+ * minimum of values each perturbed by a relative e is perturbed by at most e.  With unit spacings every value is an
+ * integer below 2^24 and the output is exact.  A product that overflows gives +inf, never NaN.
+ *
+ * Three launches on `stream`, passes H and D in place on out: no workspace.  Pass W: a wave per row, ballots over 64
+ * voxels at a time.  Passes H and D: a workgroup stages whole lines of DDPM3D_EDT_COLUMNS neighbouring columns in
+ * LDS, L * DDPM3D_EDT_COLUMNS * 4 bytes for lines of L voxels (64 KiB at the limit DDPM3D_EDT_MAX_EXTENT: two
+ * workgroups of four waves on a CU's 160 KiB; 27.5 KiB at L = 440: five), and a lane scans its own column.  No
+ * atomics.
+ *
+ * Returns DDPM3D_EINVAL before any launch for a NULL pointer, K, D, H or W below 1, an extent above
+ * DDPM3D_EDT_MAX_EXTENT, more than 2^31 - 1 voxels per volume, a stack of more workgroups than one launch takes
+ * (K D H / 4, K D ceil(W / 16) and K ceil(H W / 16) are at most 2^31 - 1 each), a spacing that is not positive and
+ * finite or whose fp32 value is 0 or +inf, and invert other than 0 or 1.
+ */
+#define DDPM3D_EDT_MAX_EXTENT 1024
+#define DDPM3D_EDT_COLUMNS 16
+int ddpm3d_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int invert, double s0, double s1, double s2,
+                       float* out, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
