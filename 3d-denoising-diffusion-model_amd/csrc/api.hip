@@ -1583,6 +1583,50 @@ int ddpm3d_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int inve
     return launched(ddpm3d_launch_distance_sq(mask, K, D, H, W, invert, sf, out, (hipStream_t)stream), "distance_sq");
 }
 
+// ------------------------------------------------- watershed basins and their saddle graph (added within ABI 13)
+static int watershed_args_ok(const char* what, int connectivity, int D, int H, int W) {
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(DDPM3D_EINVAL, "%s: connectivity %d (6, 18 or 26)", what, connectivity);
+    if (!volume_shape_ok(D, H, W))
+        return fail(DDPM3D_EINVAL, "%s: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)", what, D,
+                    H, W);
+    return DDPM3D_OK;
+}
+
+size_t ddpm3d_basins_workspace_bytes(int D, int H, int W) {
+    return volume_shape_ok(D, H, W) ? ddpm3d_watershed_workspace_bytes() : 0;
+}
+
+int ddpm3d_basins(const float* height, const int32_t* labels, int connectivity, int D, int H, int W, int32_t* peaks,
+                  void* ws, size_t ws_bytes, int32_t* status, void* stream) {
+    if (!height || !labels || !peaks || !status) return fail(DDPM3D_EINVAL, "basins: null pointer");
+    int rc = watershed_args_ok("basins", connectivity, D, H, W);
+    if (rc == DDPM3D_OK) rc = ws_ok("basins", ddpm3d_watershed_workspace_bytes(), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    const size_t bytes = (size_t)D * H * W * 4;
+    if (ranges_overlap(peaks, bytes, height, bytes) || ranges_overlap(peaks, bytes, labels, bytes))
+        return fail(DDPM3D_EINVAL, "basins: peaks overlaps an input (every voxel is read by its neighbours)");
+    return launched(ddpm3d_launch_basins(height, labels, connectivity, D, H, W, peaks, ws, status,
+                                         (hipStream_t)stream), "basins");
+}
+
+size_t ddpm3d_basin_saddles_workspace_bytes(int D, int H, int W) {
+    return volume_shape_ok(D, H, W) ? ddpm3d_watershed_workspace_bytes() : 0;
+}
+
+int ddpm3d_basin_saddles(const float* height, const int32_t* labels, const int32_t* peaks, int connectivity, int D,
+                         int H, int W, int cap, int32_t* pairs, float* saddle, void* ws, size_t ws_bytes,
+                         int32_t* status, void* stream) {
+    if (!height || !labels || !peaks || !status) return fail(DDPM3D_EINVAL, "basin_saddles: null pointer");
+    if (cap < 0) return fail(DDPM3D_EINVAL, "basin_saddles: capacity %d (0 or more records)", cap);
+    if (cap > 0 && (!pairs || !saddle)) return fail(DDPM3D_EINVAL, "basin_saddles: null record buffer");
+    int rc = watershed_args_ok("basin_saddles", connectivity, D, H, W);
+    if (rc == DDPM3D_OK) rc = ws_ok("basin_saddles", ddpm3d_watershed_workspace_bytes(), ws, ws_bytes);
+    if (rc != DDPM3D_OK) return rc;
+    return launched(ddpm3d_launch_basin_saddles(height, labels, peaks, connectivity, D, H, W, cap, pairs, saddle, ws,
+                                                status, (hipStream_t)stream), "basin_saddles");
+}
+
 // ------------------------------------------------- low-pass pull of x_start (added within ABI 13)
 static bool pull_shape_ok(int N, int D, int H, int W) {
     return N >= 1 && N <= 65535 && volume_shape_ok(D, H, W) && (int64_t)N * D * H * W <= 0x7fffffff;

@@ -185,6 +185,16 @@ hipError_t ddpm3d_launch_project(const float* vol, int B, int D, int H, int W, c
 // (the caller has checked the shape, the spacings and invert)
 hipError_t ddpm3d_launch_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int invert, const float s[3],
                                      float* out, hipStream_t st);
+// watershed.hip: peaks[v] = the peak that steepest ascent under key (height, -index) reaches from v within v's label,
+// and the records (a < b, min of the two heights) of neighbouring voxels in different basins, reduced per workgroup;
+// at most `cap` records are written, all are counted (the caller has checked the shape, the connectivity, the capacity
+// and the workspace of ddpm3d_watershed_workspace_bytes() bytes, which both entries use)
+size_t ddpm3d_watershed_workspace_bytes();
+hipError_t ddpm3d_launch_basins(const float* height, const int32_t* labels, int connectivity, int D, int H, int W,
+                                int32_t* peaks, void* ws, int32_t* status, hipStream_t st);
+hipError_t ddpm3d_launch_basin_saddles(const float* height, const int32_t* labels, const int32_t* peaks,
+                                       int connectivity, int D, int H, int W, int cap, int32_t* pairs, float* saddle,
+                                       void* ws, int32_t* status, hipStream_t st);
 // regrid.hip: B volumes of one shape onto another grid, passes along W, H, D with the tables of axes[] (D, H, W order)
 // in device memory (the caller has checked the shapes, the taps, the ratios and the workspace); stage[] gets the voxels
 // per volume after the W, the H and the D pass, of which the first two, times B, are the workspace's two buffers

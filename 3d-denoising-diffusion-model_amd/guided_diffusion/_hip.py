@@ -299,6 +299,10 @@ EXPORTS = {
                                             C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(ProjectTable)]),
     "ddpm3d_project": (C.c_int, [_fp] + [C.c_int] * 4 + [C.POINTER(ProjectTable), C.c_int, _fp, _fp]),
     "ddpm3d_distance_sq": (C.c_int, [_fp] + [C.c_int] * 5 + [C.c_double] * 3 + [_fp, _fp]),
+    "ddpm3d_basins_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ddpm3d_basins": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [_fp, _fp, C.c_size_t, _fp, _fp]),
+    "ddpm3d_basin_saddles_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ddpm3d_basin_saddles": (C.c_int, [_fp] * 3 + [C.c_int] * 5 + [_fp, _fp, _fp, C.c_size_t, _fp, _fp]),
     "ddpm3d_noise_fill": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_noise_bits": (C.c_int, [C.POINTER(NoiseKeyDesc), C.c_int, C.c_int, _fp, _fp]),
     "ddpm3d_p_sample_step_keyed": (C.c_int, [_fp, _fp, C.POINTER(NoiseKeyDesc), _fp, _fp, C.c_int, C.c_int, C.c_int,

@@ -57,6 +57,11 @@ transforms into Dice, Hausdorff, HD95 and ASSD figures of an estimate's segmenta
 per target region, with one device-to-host copy; edge_profile reduces every volume over shells of a given width
 inside and outside the labelled regions' boundary (roi_index, roi_moments).
 
+Splitting touching lesions: basins is one call of ddpm3d_basins (csrc/watershed.hip): every voxel
+of a labelled component climbs a height volume to a peak under the total order (height, -index); basin_saddles is
+ddpm3d_basin_saddles plus a reduction with torch sorts to the saddle graph between the basins; merge_basins merges
+basins by peak prominence on the host; split_components puts them together and relabels on the device.
+
 Credible intervals: interval_figures scores two per-voxel quantile maps of
 uncertainty.draw_quantiles against the target: the share of voxels the interval covers and its mean width.
 """
@@ -1780,3 +1785,212 @@ def edge_profile(volumes, labels, spacing, width_mm, inside=3, outside=5, keep=N
         rows.append({"distance_mm": (j - inside - 0.5) * width, "n": n,
                      "mean": {name: (rec[k][r][H.ROI_SUM_X] / n if n else None) for k, name in enumerate(names)}})
     return {"width_mm": width, "inside": inside, "outside": outside, "rows": rows}
+
+
+# ------------------------------------------------------------------------------------------------ watershed split
+def _check_watershed(what, height, labels, connectivity, peaks=None):
+    """the argument checks of basins / basin_saddles / split_components: ValueError before any launch"""
+    for name, t, dtype in (("height", height, torch.float32), ("labels", labels, torch.int32),
+                           ("peaks", peaks, torch.int32)):
+        if name == "peaks" and t is None:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ValueError("%s: %s must live on the GPU: this package runs on HIP kernels only (got %s)"
+                             % (what, name, getattr(t, "device", type(t))))
+        if t.dtype != dtype or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s tensor (D, H, W), got %s of shape %s"
+                             % (what, name, dtype, t.dtype, tuple(t.shape)))
+        if tuple(t.shape) != tuple(height.shape) or t.device != height.device:
+            raise ValueError("%s: %s of shape %s on %s against a height of shape %s on %s"
+                             % (what, name, tuple(t.shape), t.device, tuple(height.shape), height.device))
+    if connectivity not in (6, 18, 26):
+        raise ValueError("%s: connectivity %r (6, 18 or 26)" % (what, connectivity))
+    if height.numel() == 0 or height.numel() > 2 ** 31 - 1:
+        raise ValueError("%s: %d voxels (1..2^31 - 1)" % (what, height.numel()))
+    return tuple(int(v) for v in height.shape)
+
+
+def basins(height, labels, connectivity=26):
+    """The watershed basins of a device float32 height (D, H, W) inside the components of a device int32 label volume
+    of the same shape (0 = background; a NaN height is background too): every voxel climbs to the neighbour of
+    greatest key (height, -flat index) of its own label until it stands on a peak.  One call of ddpm3d_basins
+    (csrc/watershed.hip) and one copy of its status.  -> (peaks, n_basins): int32 (D, H, W) on the device, the flat
+    index of each voxel's peak and -1 on the background."""
+    D, Hh, W = _check_watershed("basins", height, labels, connectivity)
+    lib = H.load()
+    need = lib.ddpm3d_basins_workspace_bytes(D, Hh, W)
+    with torch.cuda.device(height.device):
+        ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=height.device)
+        peaks = torch.empty((D, Hh, W), dtype=torch.int32, device=height.device)
+        status = torch.empty(2, dtype=torch.int32, device=height.device)
+        H.check(lib.ddpm3d_basins(H.ptr(height), H.ptr(labels), connectivity, D, Hh, W, H.ptr(peaks), H.ptr(ws),
+                                  ws.numel() * 4, H.ptr(status), H.stream()))
+        overrun, n = status.cpu().tolist()
+    if overrun:
+        raise RuntimeError("basins: a device loop hit its iteration cap; the peaks are not valid")
+    return peaks, int(n)
+
+
+def _saddle_records(height, labels, peaks, connectivity, cap):
+    """one call of ddpm3d_basin_saddles with room for cap records -> (pairs, saddle, records needed)"""
+    D, Hh, W = (int(v) for v in height.shape)
+    lib = H.load()
+    need = lib.ddpm3d_basin_saddles_workspace_bytes(D, Hh, W)
+    ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=height.device)
+    pairs = torch.empty((cap, 2), dtype=torch.int32, device=height.device)
+    saddle = torch.empty(cap, dtype=torch.float32, device=height.device)
+    status = torch.empty(2, dtype=torch.int32, device=height.device)
+    H.check(lib.ddpm3d_basin_saddles(H.ptr(height), H.ptr(labels), H.ptr(peaks), connectivity, D, Hh, W, cap,
+                                     H.ptr(pairs), H.ptr(saddle), H.ptr(ws), ws.numel() * 4, H.ptr(status),
+                                     H.stream()))
+    overrun, needed = status.cpu().tolist()
+    if overrun:
+        raise RuntimeError("basin_saddles: a device loop hit its iteration cap; the records are not valid")
+    return pairs, saddle, int(needed)
+
+
+def reduce_saddles(pairs, saddle):
+    """A multiset of device records (pairs (E, 2) int32 with a < b, saddle (E,) float32) -> the unique pairs in
+    ascending order of (a, b), each with the maximum of its saddles; torch ops on the device."""
+    if pairs.shape[0] == 0:
+        return pairs.reshape(0, 2), saddle.reshape(0)
+    key = pairs[:, 0].to(torch.int64) << 32 | pairs[:, 1].to(torch.int64)
+    by_saddle = torch.sort(saddle, stable=True).indices
+    by_key = torch.sort(key.index_select(0, by_saddle), stable=True)          # within a pair the saddles ascend
+    order = by_saddle.index_select(0, by_key.indices)
+    _, counts = torch.unique_consecutive(by_key.values, return_counts=True)
+    last = order.index_select(0, torch.cumsum(counts, 0) - 1)                 # a pair's last record holds its maximum
+    return pairs.index_select(0, last).contiguous(), saddle.index_select(0, last).contiguous()
+
+
+def basin_saddles(height, labels, peaks, connectivity=26, capacity=None):
+    """The saddle graph of basins(): for every two basins a < b (peak indices) with neighbouring voxels p, q of one
+    label, the maximum over such pairs of min(height[p], height[q]).  ddpm3d_basin_saddles (csrc/watershed.hip) writes
+    a multiset of records, reduce_saddles makes it the graph.  The first call has room for `capacity` records (default:
+    an eighth of the voxels, at least 4096); if it reports a larger need, one more call has exactly that; never a
+    third.  -> (pairs (E, 2) int32, saddle (E,) float32) on the device, the pairs unique and ascending."""
+    _check_watershed("basin_saddles", height, labels, connectivity, peaks)
+    n = height.numel()
+    cap = max(n // 8, 4096) if capacity is None else int(capacity)
+    if not 0 <= cap <= 2 ** 31 - 1:
+        raise ValueError("basin_saddles: capacity %r (0..2^31 - 1 records)" % (capacity,))
+    with torch.cuda.device(height.device):
+        pairs, saddle, needed = _saddle_records(height, labels, peaks, connectivity, cap)
+        if needed > cap:
+            if needed >= 2 ** 31 - 1:
+                raise ValueError("basin_saddles: 2^31 - 1 or more records; smooth the height first")
+            cap = needed
+            pairs, saddle, needed = _saddle_records(height, labels, peaks, connectivity, cap)
+            if needed > cap:
+                raise RuntimeError("basin_saddles: the second call needs %d records, the first asked for %d"
+                                   % (needed, cap))
+        return reduce_saddles(pairs[:needed], saddle[:needed])
+
+
+def _check_prominence(what, prominence):
+    prominence = float(prominence)
+    if math.isnan(prominence) or prominence < 0:
+        raise ValueError("%s: prominence %r (0 or more; inf gives back the components)" % (what, prominence))
+    return prominence
+
+
+def merge_basins(peak_index, peak_height, pairs, saddle, prominence, first_voxel=None):
+    """Merges basins across their saddles by peak prominence, on the host in fp64.  peak_index: the basins' peaks
+    (flat indices, ascending); peak_height: their heights; pairs (E, 2), saddle (E,): the reduced saddle graph in
+    peak indices.  The edges are taken by saddle descending, then a and b ascending; a cluster's peak is its member
+    of greatest key (height, -index); an edge between two clusters unites them unless the lesser peak stands
+    `prominence` or more above the saddle (a NaN difference, inf - inf, unites).  Pieces are numbered 1..n in
+    ascending order of their lowest first_voxel (a basin's lowest voxel; default: its peak).
+    -> (piece, n): int32 per basin."""
+    prominence = _check_prominence("merge_basins", prominence)
+    index = np.asarray(peak_index, dtype=np.int64).reshape(-1)
+    height = np.asarray(peak_height, dtype=np.float64).reshape(-1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    saddle = np.asarray(saddle, dtype=np.float64).reshape(-1)
+    first = index if first_voxel is None else np.asarray(first_voxel, dtype=np.int64).reshape(-1)
+    nb = index.size
+    if height.size != nb or first.size != nb or saddle.size != pairs.shape[0]:
+        raise ValueError("merge_basins: %d peaks, %d heights, %d first voxels; %d pairs, %d saddles"
+                         % (nb, height.size, first.size, pairs.shape[0], saddle.size))
+    if nb > 1 and not (np.diff(index) > 0).all():
+        raise ValueError("merge_basins: peak_index must ascend")
+    a = np.searchsorted(index, pairs[:, 0])
+    b = np.searchsorted(index, pairs[:, 1])
+    if pairs.size and not (np.array_equal(index[np.minimum(a, nb - 1)], pairs[:, 0])
+                           and np.array_equal(index[np.minimum(b, nb - 1)], pairs[:, 1])):
+        raise ValueError("merge_basins: a pair names a voxel that is no peak")
+    with np.errstate(invalid="ignore"):
+        order = np.lexsort((b, a, -saddle))
+    root = list(range(nb))
+    top = list(range(nb))                                 # a cluster's peak, kept at its root
+    hl, sl = height.tolist(), saddle.tolist()
+    al, bl = a.tolist(), b.tolist()
+
+    def find(i):
+        r = i
+        while root[r] != r:
+            r = root[r]
+        while root[i] != r:
+            root[i], i = r, root[i]
+        return r
+
+    for e in order.tolist():
+        ra, rb = find(al[e]), find(bl[e])
+        if ra == rb:
+            continue
+        pa, pb = top[ra], top[rb]
+        a_greater = hl[pa] > hl[pb] or (hl[pa] == hl[pb] and pa < pb)       # basins ascend with their peak's index
+        hi, lo = (ra, rb) if a_greater else (rb, ra)
+        with np.errstate(invalid="ignore"):
+            stands = np.float64(hl[top[lo]]) - np.float64(sl[e]) >= prominence
+        if not stands:
+            root[lo] = hi
+    cluster = np.fromiter((find(i) for i in range(nb)), dtype=np.int64, count=nb)
+    lowest = np.full(nb, np.iinfo(np.int64).max, dtype=np.int64)
+    np.minimum.at(lowest, cluster, first)
+    roots = np.flatnonzero(lowest != np.iinfo(np.int64).max)
+    number = np.zeros(nb, dtype=np.int32)
+    number[roots[np.argsort(lowest[roots], kind="stable")]] = np.arange(1, roots.size + 1, dtype=np.int32)
+    return number[cluster], int(roots.size)
+
+
+def split_components(labels, height, prominence, connectivity=26, max_basins=1 << 20):
+    """Splits the components of a device int32 label volume (D, H, W) along the watershed of a device float32 height
+    of the same shape: basins() and basin_saddles() on the device, merge_basins on the host, and a relabelling through
+    a rank table and index_select.  prominence = 0 keeps every basin, inf gives back the components' voxels.
+    -> (labels int32 (D, H, W) on the device, n, info), the pieces numbered 1..n in raster order of their first voxel;
+    info = {"n_before", "n_basins", "n_edges", "n_after", "parent": the old label of each new piece}."""
+    prominence = _check_prominence("split_components", prominence)
+    if int(max_basins) != max_basins or max_basins < 1:
+        raise ValueError("split_components: max_basins must be an integer of at least 1 (got %r)" % (max_basins,))
+    _check_watershed("split_components", height, labels, connectivity)
+    peaks, n_basins = basins(height, labels, connectivity)
+    if n_basins > max_basins:
+        raise ValueError("split_components: %d basins, more than max_basins = %d: smooth the height first "
+                         "(pre-smoothing removes the noise's peaks) or, if the count is wanted, raise max_basins; a "
+                         "larger prominence merges them but does not lower this count" % (n_basins, max_basins))
+    with torch.cuda.device(height.device):
+        pairs, saddle = basin_saddles(height, labels, peaks, connectivity)
+        flat = peaks.reshape(-1)
+        is_peak = flat == torch.arange(flat.numel(), dtype=torch.int32, device=flat.device)
+        rank = torch.cumsum(is_peak, 0, dtype=torch.int32) - 1     # rank[peak] = its basin, in ascending peak index
+        voxels = torch.nonzero(flat >= 0).reshape(-1)
+        basin = rank.index_select(0, flat.index_select(0, voxels).to(torch.int64)).to(torch.int64)
+        peak_index = torch.nonzero(is_peak).reshape(-1)
+        # a basin's first voxel: the stable sort keeps the voxels of a basin in ascending order
+        by_basin = torch.sort(basin, stable=True)
+        _, counts = torch.unique_consecutive(by_basin.values, return_counts=True)
+        first = voxels.index_select(0, by_basin.indices.index_select(0, torch.cumsum(counts, 0) - counts))
+        old = labels.reshape(-1).index_select(0, peak_index)
+        peak_height = height.reshape(-1).index_select(0, peak_index)
+        n_before = int(labels.max()) if labels.numel() else 0
+        piece, n_after = merge_basins(peak_index.cpu().numpy(), peak_height.cpu().numpy(), pairs.cpu().numpy(),
+                                      saddle.cpu().numpy(), prominence, first_voxel=first.cpu().numpy())
+        parent = np.zeros(n_after, dtype=np.int64)
+        parent[piece - 1] = old.cpu().numpy()
+        table = torch.from_numpy(piece).to(flat.device)
+        out = torch.zeros_like(flat)
+        out[voxels] = table.index_select(0, basin)
+    info = {"n_before": n_before, "n_basins": int(n_basins), "n_edges": int(pairs.shape[0]), "n_after": int(n_after),
+            "parent": [int(p) for p in parent]}
+    return out.reshape(labels.shape), int(n_after), info

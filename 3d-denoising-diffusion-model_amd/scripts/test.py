@@ -70,6 +70,13 @@ roi_labels_<name>.npz, which `--roi_labels` reads back; the "roi" entry is built
 from them as from a file and also carries "detection": which of the target's
 lesions are still there in the input and in the denoised volume (and in every
 draw), and how many hot spots either has that the target has not;
+`--roi_split_prominence P` (positive, in the target's units; needs a
+`--roi_threshold`) splits touching lesions: every component is cut along the
+watershed of the target, or of its Gaussian smoothing at `--roi_split_fwhm MM`
+(needs `--voxel_spacing`), and basins whose peak stands less than P above the
+saddle to a higher one are merged (guided_diffusion/metrics.py
+split_components); the labels file holds the split labels, "roi" gains "split"
+and every region "component", the unsplit component it came from;
 `--voxel_spacing S0 S1 S2` (mm per voxel along the input file's axes (D, H, W);
 needs `--target_samples` and `--roi_labels` or a `--roi_threshold`) adds to
 every region's target, input and denoised figures its volume in ml (the MTV of
@@ -288,6 +295,10 @@ def create_argparser():
     # the mean of every scored volume in shells of this width in mm across the regions' boundary (needs
     # --target_samples, --voxel_spacing and regions)
     parser.add_argument("--roi_edge_profile_mm", type=float, default=None, metavar="W")
+    # split the target's components along the watershed of the target (or, with a FWHM above 0, of its Gaussian
+    # smoothing): basins whose peak stands less than P above the saddle to a higher one are merged
+    parser.add_argument("--roi_split_prominence", type=float, default=None, metavar="P")
+    parser.add_argument("--roi_split_fwhm", type=float, default=0.0, metavar="MM")
     return parser
 
 
@@ -315,6 +326,7 @@ def main(argv=None):
     _check_mip(parser, args)
     _check_boundary(parser, args)
     args.peak = _check_spacing(parser, args)
+    args.split = _check_split(parser, args)
     args.texture = _check_texture(parser, args)
     args.baselines = _check_baselines(parser, args)
     vol, target = _load_target(parser, args)
@@ -701,6 +713,36 @@ def _check_segmentation(parser, args):
         parser.error("--roi_threshold_frac must lie in (0, 1) (got %r)" % args.roi_threshold_frac)
 
 
+def _check_split(parser, args):
+    """--roi_split_prominence / --roi_split_fwhm, checked before any file is read (and after --voxel_spacing): None
+    without the first, else {"prominence", "fwhm", "taps": the smoothing's taps on the volumes' (H, W, Z) grid or
+    None}"""
+    p, fwhm = args.roi_split_prominence, args.roi_split_fwhm
+    if p is None:
+        if fwhm != 0.0:
+            parser.error("--roi_split_fwhm needs --roi_split_prominence: it smooths the height the split climbs")
+        return None
+    if not (np.isfinite(p) and p > 0):
+        parser.error("--roi_split_prominence must be a positive finite number, in the target's units (got %r)" % p)
+    if args.roi_labels:
+        parser.error("--roi_split_prominence splits the components the script makes itself: it cannot be combined "
+                     "with --roi_labels")
+    if not _segmenting(args):
+        parser.error("--roi_split_prominence needs --roi_threshold or --roi_threshold_frac: it splits their components")
+    if not (np.isfinite(fwhm) and fwhm >= 0):
+        parser.error("--roi_split_fwhm must be 0 or a positive finite number of mm (got %r)" % fwhm)
+    taps = None
+    if fwhm > 0:
+        if args.voxel_spacing is None:
+            parser.error("--roi_split_fwhm needs --voxel_spacing: the FWHM is in mm")
+        s0, s1, s2 = args.voxel_spacing
+        try:
+            taps = metrics.gaussian_taps(fwhm, (s1, s2, s0))                # (D, H, W) -> (H, W, Z)
+        except ValueError as e:
+            parser.error("--roi_split_fwhm: %s" % e)
+    return {"prominence": float(p), "fwhm": float(fwhm), "taps": taps}
+
+
 def _check_texture(parser, args):
     """--roi_texture_bin / _levels / _lower, checked before any file is read: None without the first, else
     roi_report's texture= dict"""
@@ -982,13 +1024,35 @@ def _segment_target(parser, args, vol, target):
     if n == 0:
         parser.error("the target has no region of at least %d voxels above the threshold %g (its maximum is %g): "
                      "lower the threshold or --roi_min_voxels" % (args.roi_min_voxels, threshold, float(target.max())))
+    split = getattr(args, "split", None)
+    if split is not None:
+        # the voxels the one-shot blend leaves at 0 are background in `labels` already
+        height = tgt if split["taps"] is None else metrics.gaussian_smooth(tgt, split["taps"])
+        try:
+            labels, n_split, info = metrics.split_components(labels, height, split["prominence"],
+                                                             connectivity=args.roi_connectivity)
+        except ValueError as e:
+            parser.error("--roi_split_prominence: %s (see --roi_split_fwhm)" % e)
+        if n_split > _hip.ROI_MAX_REGIONS:
+            parser.error("the target has %d regions above the threshold %g after the split at prominence %g (at most "
+                         "%d): raise --roi_split_prominence or --roi_split_fwhm, raise --roi_min_voxels to drop the "
+                         "specks, or raise the threshold"
+                         % (n_split, threshold, split["prominence"], _hip.ROI_MAX_REGIONS))
     if n > _hip.ROI_MAX_REGIONS:
         parser.error("the target has %d regions above the threshold %g (at most %d): raise --roi_min_voxels to drop "
                      "the specks, or raise the threshold" % (n, threshold, _hip.ROI_MAX_REGIONS))
     logger.log(f"target segmented at {threshold:g} (connectivity {args.roi_connectivity}, at least "
                f"{args.roi_min_voxels} voxels): {n} regions")
-    return {"labels": labels, "n": n, "keep": keep, "threshold": threshold, "connectivity": args.roi_connectivity,
-            "min_voxels": args.roi_min_voxels}
+    seg = {"labels": labels, "n": n, "keep": keep, "threshold": threshold, "connectivity": args.roi_connectivity,
+           "min_voxels": args.roi_min_voxels}
+    if split is not None:
+        logger.log(f"target split at prominence {split['prominence']:g} (height smoothed at {split['fwhm']:g} mm FWHM): "
+                   f"{n} components -> {info['n_basins']} basins -> {n_split} regions")
+        seg.update(n=n_split, component=info["parent"],
+                   split={"prominence": split["prominence"], "fwhm_mm": split["fwhm"],
+                          "connectivity": args.roi_connectivity, "n_components": n, "n_basins": info["n_basins"],
+                          "n_regions": n_split})
+    return seg
 
 
 def _detection_block(seg, regions, inp, den, draw_found, edges=None, draw_edges=None):
@@ -1126,8 +1190,13 @@ def _roi_block(args, roi, tgt, inp, den, keep, draws, out_path=None, baselines=N
                        for r in prof["rows"])))
     if seg is None:
         return {"labels": args.roi_labels, "background": background, "regions": regions, **spaced}
+    split = {}
+    if "split" in seg:
+        split = {"split": seg["split"]}
+        for label in index.labels:
+            regions[str(label)]["component"] = seg["component"][label - 1]
     return {"labels": labels_path, "background": None, "threshold": seg["threshold"],
-            "connectivity": seg["connectivity"], "min_voxels": seg["min_voxels"], "regions": regions,
+            "connectivity": seg["connectivity"], "min_voxels": seg["min_voxels"], **split, "regions": regions,
             **_detection_block(seg, regions, inp, den, draw_found, edges, draw_edges), **spaced}
 
 

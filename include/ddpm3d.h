@@ -1325,6 +1325,60 @@ int ddpm3d_project(const float* vol, int B, int D, int H, int W, const ddpm3d_pr
 int ddpm3d_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int invert, double s0, double s1, double s2,
                        float* out, void* stream);
 /*
+ * Watershed basins inside labelled components and the saddle graph between them (added within ABI 13; the reference
+ * has no such code): what splits two touching lesions that a threshold makes one component.
+ *   height        [D][H][W] fp32, W innermost
+ *   labels        [D][H][W] int32, 0 = background (e.g. ddpm3d_label_components' roots, ranked)
+ *   connectivity  c = 6, 18 or 26
+ * Definition:
+ *   1. A voxel is foreground iff labels > 0 and height == height: a NaN height makes the voxel background.
+ *   2. Two voxels are neighbours iff they are c-adjacent, both foreground and carry the same label.  Basins therefore
+ *      never straddle a component, whatever connectivity made the labels.
+ *   3. key(v) = (height[v], -flat index): the larger height wins, on equal heights the smaller index; +-inf are
+ *      ordinary values.  This is a total order on the voxels.
+ *   4. parent(v) = the voxel of greatest key among v and its neighbours; v is a peak iff parent(v) == v; peaks[v] =
+ *      the flat index of the peak v's parent chain ends in (the key strictly increases along it), -1 on background.
+ *      A basin is the set of voxels that share a peak.
+ *   5. For every unordered pair of neighbours p, q whose basins a < b differ, saddle(a, b) = the maximum over such
+ *      pairs of min(height[p], height[q]).
+ *   6. (host: guided_diffusion.metrics.merge_basins) Edges by saddle descending, then a, b ascending; a union-find
+ *      whose cluster peak is the member peak of greatest key; an edge between two clusters, lo the one with the
+ *      lesser peak key, unites them iff NOT height[peak(lo)] - saddle >= P in fp64 (a NaN difference unites).
+ *   7. Pieces are numbered 1.. in raster order of their first voxel, ddpm3d_label_components' rule.
+ * The total order makes parent(v), hence peaks and the saddle graph, a function of the input alone: the same bits on
+ * every run.
+ *
+ * ddpm3d_basins: peaks [D][H][W] int32 out; status DEVICE int32[2] out: {a device loop hit its iteration cap (always
+ * 0; anything else means the result must not be used), the number of peaks}.  A 16-byte clear and three launches on
+ * `stream`: a thread per voxel writes parent(v) into peaks[v]; a thread per voxel walks the parents from peaks[v] to
+ * a slot that holds its own index and stores that in place (every value a walker can read in a slot is an ancestor of
+ * that slot, so races change the path, never the answer; at most D * H * W links, and every index is checked
+ * against that count before it is followed); one thread copies the accumulated flag and count to status.
+ *
+ * ddpm3d_basin_saddles: peaks as ddpm3d_basins wrote it; cap >= 0 the capacity in records; pairs [cap][2] int32 out
+ * (a < b), saddle [cap] fp32 out (both may be NULL with cap = 0); status DEVICE int32[2] out: {a device loop hit its
+ * cap (always 0), the number of records the call needs, SATURATING at 2^31 - 1}.  min(needed, cap) records are
+ * written, in no fixed order; records beyond cap are counted, never written, so a call with a small cap (0 is legal)
+ * sizes the next.  The records are a multiset: every pair of step 5 occurs at least once and the maximum of a pair's
+ * records is its saddle; the needed count is the same on every run.  A clear and two launches: a thread per voxel
+ * looks at its 3, 9 or 13 forward neighbours; a workgroup of 256 consecutive voxels reduces its pairs in an LDS hash
+ * table (12 or 48 KiB) and takes consecutive record numbers with one 64-bit atomicAdd, so a pair occurs once per
+ * workgroup that sees it; one thread writes status.
+ *
+ * No value read from height, labels or peaks is used as an address.  No workgroup waits for another.
+ * ws: ddpm3d_*_workspace_bytes(D, H, W) bytes (16), 16-byte aligned, contents irrelevant; 0 is the answer for a shape
+ * the entry refuses.  Both return DDPM3D_EINVAL before any launch for a NULL pointer (pairs and saddle only when
+ * cap > 0), a connectivity other than 6 / 18 / 26, an extent below 1, more than 2^31 - 1 voxels, a negative
+ * capacity, a workspace that is NULL, too small or misaligned, and (ddpm3d_basins) peaks overlapping an input.
+ */
+size_t ddpm3d_basins_workspace_bytes(int D, int H, int W);
+int ddpm3d_basins(const float* height, const int32_t* labels, int connectivity, int D, int H, int W, int32_t* peaks,
+                  void* ws, size_t ws_bytes, int32_t* status, void* stream);
+size_t ddpm3d_basin_saddles_workspace_bytes(int D, int H, int W);
+int ddpm3d_basin_saddles(const float* height, const int32_t* labels, const int32_t* peaks, int connectivity, int D,
+                         int H, int W, int cap, int32_t* pairs, float* saddle, void* ws, size_t ws_bytes,
+                         int32_t* status, void* stream);
+/*
  * Device calibration (measurement only; replaces nothing in the reference).  Enqueues a
  * register-only MFMA loop -- no memory traffic, pseudo-random operands, `blocks` workgroups of four
  * waves, each wave holding the dominant conv kernel's 64 x 32 x 4 fp32 accumulator tile -- so the
