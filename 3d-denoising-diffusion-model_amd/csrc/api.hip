@@ -1281,6 +1281,16 @@ static bool volume_shape_ok(int D, int H, int W) {
     return D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H <= 0x7fffffff && (int64_t)D * H * W <= 0x7fffffff;
 }
 
+// the connectivity and the shape of the graph passes over a voxel volume: components, basins, basin saddles
+static int voxel_graph_ok(const char* what, int connectivity, int D, int H, int W) {
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(DDPM3D_EINVAL, "%s: connectivity %d (6, 18 or 26)", what, connectivity);
+    if (!volume_shape_ok(D, H, W))
+        return fail(DDPM3D_EINVAL, "%s: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)", what, D,
+                    H, W);
+    return DDPM3D_OK;
+}
+
 size_t ddpm3d_label_components_workspace_bytes(int D, int H, int W) {
     return volume_shape_ok(D, H, W) ? ddpm3d_ccl_workspace_bytes(D, H, W) : 0;
 }
@@ -1288,13 +1298,10 @@ size_t ddpm3d_label_components_workspace_bytes(int D, int H, int W) {
 int ddpm3d_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity, int D, int H,
                             int W, int32_t* roots, void* ws, size_t ws_bytes, int32_t* status, void* stream) {
     if (!vol || !roots || !status) return fail(DDPM3D_EINVAL, "label_components: null pointer");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return fail(DDPM3D_EINVAL, "label_components: connectivity %d (6, 18 or 26)", connectivity);
-    if (!volume_shape_ok(D, H, W))
-        return fail(DDPM3D_EINVAL, "label_components: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= "
-                                   "2^31 - 1)", D, H, W);
+    int rc = voxel_graph_ok("label_components", connectivity, D, H, W);
+    if (rc != DDPM3D_OK) return rc;
     if (threshold != threshold) return fail(DDPM3D_EINVAL, "label_components: the threshold is NaN");
-    const int rc = ws_ok("label_components", ddpm3d_ccl_workspace_bytes(D, H, W), ws, ws_bytes);
+    rc = ws_ok("label_components", ddpm3d_ccl_workspace_bytes(D, H, W), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_label_components(vol, keep, threshold, connectivity, D, H, W, roots, ws, status,
                                                    (hipStream_t)stream),
@@ -1584,15 +1591,6 @@ int ddpm3d_distance_sq(const uint8_t* mask, int K, int D, int H, int W, int inve
 }
 
 // ------------------------------------------------- watershed basins and their saddle graph (added within ABI 13)
-static int watershed_args_ok(const char* what, int connectivity, int D, int H, int W) {
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return fail(DDPM3D_EINVAL, "%s: connectivity %d (6, 18 or 26)", what, connectivity);
-    if (!volume_shape_ok(D, H, W))
-        return fail(DDPM3D_EINVAL, "%s: bad volume (D=%d H=%d W=%d; 1 or more each, D * H * W <= 2^31 - 1)", what, D,
-                    H, W);
-    return DDPM3D_OK;
-}
-
 size_t ddpm3d_basins_workspace_bytes(int D, int H, int W) {
     return volume_shape_ok(D, H, W) ? ddpm3d_watershed_workspace_bytes() : 0;
 }
@@ -1600,7 +1598,7 @@ size_t ddpm3d_basins_workspace_bytes(int D, int H, int W) {
 int ddpm3d_basins(const float* height, const int32_t* labels, int connectivity, int D, int H, int W, int32_t* peaks,
                   void* ws, size_t ws_bytes, int32_t* status, void* stream) {
     if (!height || !labels || !peaks || !status) return fail(DDPM3D_EINVAL, "basins: null pointer");
-    int rc = watershed_args_ok("basins", connectivity, D, H, W);
+    int rc = voxel_graph_ok("basins", connectivity, D, H, W);
     if (rc == DDPM3D_OK) rc = ws_ok("basins", ddpm3d_watershed_workspace_bytes(), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     const size_t bytes = (size_t)D * H * W * 4;
@@ -1620,7 +1618,7 @@ int ddpm3d_basin_saddles(const float* height, const int32_t* labels, const int32
     if (!height || !labels || !peaks || !status) return fail(DDPM3D_EINVAL, "basin_saddles: null pointer");
     if (cap < 0) return fail(DDPM3D_EINVAL, "basin_saddles: capacity %d (0 or more records)", cap);
     if (cap > 0 && (!pairs || !saddle)) return fail(DDPM3D_EINVAL, "basin_saddles: null record buffer");
-    int rc = watershed_args_ok("basin_saddles", connectivity, D, H, W);
+    int rc = voxel_graph_ok("basin_saddles", connectivity, D, H, W);
     if (rc == DDPM3D_OK) rc = ws_ok("basin_saddles", ddpm3d_watershed_workspace_bytes(), ws, ws_bytes);
     if (rc != DDPM3D_OK) return rc;
     return launched(ddpm3d_launch_basin_saddles(height, labels, peaks, connectivity, D, H, W, cap, pairs, saddle, ws,

@@ -152,7 +152,8 @@ hipError_t ddpm3d_launch_shell_spectrum(const float* est, const float* est_pivot
                                         const ddpm3d_dft_axis* axes, const ddpm3d_roi_index& ix, int64_t chunks,
                                         void* ws, double* out, hipStream_t st);
 // ccl.hip: connected components of vol > threshold (the caller has checked the shape, the connectivity and the
-// workspace; the workspace query takes valid shapes only)
+// workspace: voxel_forest.h's 16-byte status accumulator and a count word per flatten workgroup; the workspace query
+// takes valid shapes only)
 size_t ddpm3d_ccl_workspace_bytes(int D, int H, int W);
 hipError_t ddpm3d_launch_label_components(const float* vol, const uint8_t* keep, float threshold, int connectivity,
                                           int D, int H, int W, int32_t* roots, void* ws, int32_t* status,
@@ -188,7 +189,7 @@ hipError_t ddpm3d_launch_distance_sq(const uint8_t* mask, int K, int D, int H, i
 // watershed.hip: peaks[v] = the peak that steepest ascent under key (height, -index) reaches from v within v's label,
 // and the records (a < b, min of the two heights) of neighbouring voxels in different basins, reduced per workgroup;
 // at most `cap` records are written, all are counted (the caller has checked the shape, the connectivity, the capacity
-// and the workspace of ddpm3d_watershed_workspace_bytes() bytes, which both entries use)
+// and the workspace of ddpm3d_watershed_workspace_bytes() bytes, the same status accumulator, which both entries use)
 size_t ddpm3d_watershed_workspace_bytes();
 hipError_t ddpm3d_launch_basins(const float* height, const int32_t* labels, int connectivity, int D, int H, int W,
                                 int32_t* peaks, void* ws, int32_t* status, hipStream_t st);

@@ -1,9 +1,11 @@
 // Watershed basins of a height volume inside labelled components, and the saddle graph between them (DESIGN.md 3.24;
 // the definition is in include/ddpm3d.h).  Foreground: labels > 0 and a height that is no NaN.  Neighbours: adjacent
 // under the connectivity, both foreground, same label.  Order: key(v) = (height[v], -v).
-//   ddpm3d_basins         clear of the 16-byte accumulator, then
-//     parent    a thread per voxel writes the voxel of greatest key among itself and its neighbours into peaks[v]
-//     resolve   a thread per voxel walks the parents from peaks[v] to a slot that holds its own index (a peak) and
+// The neighbours, the walk, flatten, finish and the 16-byte status accumulator are voxel_forest.h's.
+//   ddpm3d_basins         clear of the accumulator, then
+//     parent    a thread per voxel writes the voxel of greatest key among itself and its neighbours into peaks[v]:
+//               key(parent(v)) > key(v) unless parent(v) == v, the order the shared walk needs
+//     flatten   a thread per voxel walks the parents from peaks[v] to a slot that holds its own index (a peak) and
 //               stores that: in place, so later walkers find shorter chains; peaks are counted per workgroup
 //     finish    one thread copies the accumulator (cap flag, count) into status
 //   ddpm3d_basin_saddles  clear, then
@@ -19,48 +21,17 @@
 #include <stdint.h>
 #include "ddpm3d.h"
 #include "ops.h"
+#include "voxel_forest.h"
 
 namespace {
 
 constexpr int WS_THREADS = 256;
 constexpr unsigned long long WS_EMPTY = ~0ull;            // no pair: basins are indices >= 0
 
-struct Dims {
-    int D, H, W;
-};
-
-// the accumulator in the workspace: both entries clear it first and copy it to status last
-struct Acc {
-    unsigned long long count;                             // peaks, or records needed
-    int32_t flag;                                         // a loop hit its cap
-    int32_t pad;
-};
-static_assert(sizeof(Acc) == 16, "ddpm3d_watershed_workspace_bytes");
-
-// the neighbours with at most ORDER non-zero components; FORWARD: only those that follow the voxel in raster order,
-// so that every unordered pair of voxels is looked at once (3, 9 or 13 directions)
-template <int ORDER, bool FORWARD, typename F>
-__device__ __forceinline__ void for_neighbours(F&& f) {
-#pragma unroll
-    for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int nz = (dz != 0) + (dy != 0) + (dx != 0);
-                const bool forward = dz > 0 || (dz == 0 && (dy > 0 || (dy == 0 && dx > 0)));
-                if (nz >= 1 && nz <= ORDER && (!FORWARD || forward)) f(dz, dy, dx);
-            }
-}
-
-__device__ __forceinline__ int load_slot(const int32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---------------------------------------------------------------------------------------------------- parent
 template <int ORDER>
 __global__ __launch_bounds__(WS_THREADS) void ws_parent_kernel(const float* __restrict__ height,
-                                                               const int32_t* __restrict__ labels, Dims g, int n,
+                                                               const int32_t* __restrict__ labels, Extents g, int n,
                                                                int32_t* __restrict__ peaks) {
     const int64_t v64 = (int64_t)blockIdx.x * WS_THREADS + threadIdx.x;
     if (v64 >= n) return;
@@ -71,10 +42,11 @@ __global__ __launch_bounds__(WS_THREADS) void ws_parent_kernel(const float* __re
         peaks[v] = -1;
         return;
     }
-    const int x = v % g.W, y = v / g.W % g.H, z = v / g.W / g.H;
+    const Voxel at = voxel_of(g, v);
+    const int z = at.z, y = at.y, x = at.x;
     int best = v;
     float bh = h;
-    for_neighbours<ORDER, false>([&](int dz, int dy, int dx) {
+    for_neighbours<ORDER>([&](int dz, int dy, int dx) {
         const int nz = z + dz, ny = y + dy, nx = x + dx;
         if (nz < 0 || nz >= g.D || ny < 0 || ny >= g.H || nx < 0 || nx >= g.W) return;
         const int u = v + (dz * g.H + dy) * g.W + dx;     // inside the volume: no overflow
@@ -86,55 +58,6 @@ __global__ __launch_bounds__(WS_THREADS) void ws_parent_kernel(const float* __re
         }
     });
     peaks[v] = best;
-}
-
-// ---------------------------------------------------------------------------------------------------- resolve
-// Slot v holds parent(v) at first and is written once more, by thread v alone, with the peak of v's chain.  Both are
-// ancestors of v (or v), so whatever a walker reads in a slot lies further up the same chain: races change the path,
-// never the end.  key(parent(u)) > key(u) unless parent(u) == u, so a chain has at most n links and the cap n is out
-// of reach; an index outside [0, n) cannot have been written here and stops the walk with the flag set.
-__global__ __launch_bounds__(WS_THREADS) void ws_resolve_kernel(int n, int32_t* peaks, Acc* __restrict__ acc) {
-    __shared__ int wave_count[WS_THREADS / 64];
-    const int64_t v64 = (int64_t)blockIdx.x * WS_THREADS + threadIdx.x;
-    int overrun = 0, mine = 0;
-    if (v64 < n) {
-        const int v = (int)v64;
-        const int p = peaks[v];                           // only this thread writes slot v in this launch
-        if (p == v) {
-            mine = 1;
-        } else if (p >= 0) {
-            int at = p;
-            bool done = false;
-            for (int it = 0; it < n; ++it) {
-                if ((unsigned)at >= (unsigned)n) break;
-                const int up = load_slot(peaks + at);
-                if (up == at) {
-                    done = true;
-                    break;
-                }
-                at = up;
-            }
-            if (!done) overrun = 1;
-            else if (at != p) __hip_atomic_store(peaks + v, at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = mine;
-    overrun = __syncthreads_or(overrun);
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int w = 0; w < WS_THREADS / 64; ++w) total += wave_count[w];
-        if (total) atomicAdd(&acc->count, (unsigned long long)total);
-        if (overrun) atomicOr(&acc->flag, 1);
-    }
-}
-
-__global__ void ws_finish_kernel(const Acc* __restrict__ acc, int32_t* __restrict__ status) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        status[0] = acc->flag ? 1 : 0;
-        status[1] = acc->count > (unsigned long long)INT_MAX ? INT_MAX : (int32_t)acc->count;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------- saddles
@@ -159,9 +82,10 @@ struct SaddleTable {
 template <int ORDER>
 __global__ __launch_bounds__(WS_THREADS) void ws_saddle_kernel(const float* __restrict__ height,
                                                                const int32_t* __restrict__ labels,
-                                                               const int32_t* __restrict__ peaks, Dims g, int n,
+                                                               const int32_t* __restrict__ peaks, Extents g, int n,
                                                                int cap, int32_t* __restrict__ pairs,
-                                                               float* __restrict__ saddle, Acc* __restrict__ acc) {
+                                                               float* __restrict__ saddle,
+                                                               ForestStatus* __restrict__ acc) {
     using T = SaddleTable<ORDER>;
     __shared__ unsigned long long keys[T::SLOTS];
     __shared__ unsigned vals[T::SLOTS];
@@ -178,7 +102,8 @@ __global__ __launch_bounds__(WS_THREADS) void ws_saddle_kernel(const float* __re
         const float h = height[v];
         if (!(l > 0) || h != h) return;
         const int32_t pv = peaks[v];
-        const int x = v % g.W, y = v / g.W % g.H, z = v / g.W / g.H;
+        const Voxel at = voxel_of(g, v);
+        const int z = at.z, y = at.y, x = at.x;
         for_neighbours<ORDER, true>([&](int dz, int dy, int dx) {
             const int nz = z + dz, ny = y + dy, nx = x + dx;
             if (nz >= g.D || ny < 0 || ny >= g.H || nx < 0 || nx >= g.W) return;     // forward: nz >= z
@@ -233,7 +158,7 @@ __global__ __launch_bounds__(WS_THREADS) void ws_saddle_kernel(const float* __re
     for (int w = 0; w < (tid >> 6); ++w) before += wave_total[w];
     if (tid == WS_THREADS - 1) {
         base = (long long)atomicAdd(&acc->count, (unsigned long long)(before + mine));
-        if (overrun) atomicOr(&acc->flag, 1);
+        if (overrun) flag_overrun(acc);
     }
     __syncthreads();
     int64_t at = base + before;
@@ -251,56 +176,47 @@ __global__ __launch_bounds__(WS_THREADS) void ws_saddle_kernel(const float* __re
 }
 
 template <int ORDER>
-hipError_t launch_basins(const float* height, const int32_t* labels, Dims g, int n, int32_t* peaks, Acc* acc,
+hipError_t launch_basins(const float* height, const int32_t* labels, Extents g, int32_t* peaks, ForestStatus* acc,
                          int32_t* status, hipStream_t st) {
+    const int n = (int)((int64_t)g.D * g.H * g.W);
     const unsigned blocks = (unsigned)(((int64_t)n + WS_THREADS - 1) / WS_THREADS);
-    hipError_t e = hipMemsetAsync(acc, 0, sizeof(Acc), st);
+    hipError_t e = forest_clear(acc, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ws_parent_kernel<ORDER>, dim3(blocks), dim3(WS_THREADS), 0, st, height, labels, g, n, peaks);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ws_resolve_kernel, dim3(blocks), dim3(WS_THREADS), 0, st, n, peaks, acc);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ws_finish_kernel, dim3(1), dim3(64), 0, st, acc, status);
-    return hipGetLastError();
+    return forest_flatten_and_finish<1>(n, peaks, acc, nullptr, status, st);
 }
 
 template <int ORDER>
-hipError_t launch_saddles(const float* height, const int32_t* labels, const int32_t* peaks, Dims g, int n, int cap,
-                          int32_t* pairs, float* saddle, Acc* acc, int32_t* status, hipStream_t st) {
+hipError_t launch_saddles(const float* height, const int32_t* labels, const int32_t* peaks, Extents g, int cap,
+                          int32_t* pairs, float* saddle, ForestStatus* acc, int32_t* status, hipStream_t st) {
+    const int n = (int)((int64_t)g.D * g.H * g.W);
     const unsigned blocks = (unsigned)(((int64_t)n + WS_THREADS - 1) / WS_THREADS);
-    hipError_t e = hipMemsetAsync(acc, 0, sizeof(Acc), st);
+    hipError_t e = forest_clear(acc, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ws_saddle_kernel<ORDER>, dim3(blocks), dim3(WS_THREADS), 0, st, height, labels, peaks, g, n,
                        cap, pairs, saddle, acc);
     e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ws_finish_kernel, dim3(1), dim3(64), 0, st, acc, status);
-    return hipGetLastError();
+    return e != hipSuccess ? e : forest_finish(acc, nullptr, 0, status, st);
 }
 
 }  // namespace
 
-size_t ddpm3d_watershed_workspace_bytes() { return sizeof(Acc); }
+size_t ddpm3d_watershed_workspace_bytes() { return sizeof(ForestStatus); }
 
 hipError_t ddpm3d_launch_basins(const float* height, const int32_t* labels, int connectivity, int D, int H, int W,
                                 int32_t* peaks, void* ws, int32_t* status, hipStream_t st) {
-    const Dims g = {D, H, W};
-    const int n = (int)((int64_t)D * H * W);
-    if (connectivity == 6) return launch_basins<1>(height, labels, g, n, peaks, (Acc*)ws, status, st);
-    if (connectivity == 18) return launch_basins<2>(height, labels, g, n, peaks, (Acc*)ws, status, st);
-    return launch_basins<3>(height, labels, g, n, peaks, (Acc*)ws, status, st);
+    return with_order(connectivity, [&](auto order) {
+        return launch_basins<decltype(order)::value>(height, labels, {D, H, W}, peaks, (ForestStatus*)ws, status, st);
+    });
 }
 
 hipError_t ddpm3d_launch_basin_saddles(const float* height, const int32_t* labels, const int32_t* peaks,
                                        int connectivity, int D, int H, int W, int cap, int32_t* pairs, float* saddle,
                                        void* ws, int32_t* status, hipStream_t st) {
-    const Dims g = {D, H, W};
-    const int n = (int)((int64_t)D * H * W);
-    if (connectivity == 6)
-        return launch_saddles<1>(height, labels, peaks, g, n, cap, pairs, saddle, (Acc*)ws, status, st);
-    if (connectivity == 18)
-        return launch_saddles<2>(height, labels, peaks, g, n, cap, pairs, saddle, (Acc*)ws, status, st);
-    return launch_saddles<3>(height, labels, peaks, g, n, cap, pairs, saddle, (Acc*)ws, status, st);
+    return with_order(connectivity, [&](auto order) {
+        return launch_saddles<decltype(order)::value>(height, labels, peaks, {D, H, W}, cap, pairs, saddle,
+                                                      (ForestStatus*)ws, status, st);
+    });
 }

@@ -1145,6 +1145,24 @@ def _check_labels(labels, what):
                          % (what, labels.dtype, tuple(labels.shape)))
 
 
+def _forest_call(what, noun, shape, device, call, then=None):
+    """One call of the entry ddpm3d_<what> over a (D, H, W) volume on `device` (csrc/voxel_forest.h's status
+    protocol): allocates its workspace and status, runs call(lib, ws, ws_bytes, status, stream) -> return code, then
+    then() if given (device work queued behind the entry), then makes the one device-to-host copy, of status.
+    -> (status[1], what then() gave); RuntimeError if the cap flag is set: the `noun` are not valid."""
+    lib = H.load()
+    need = getattr(lib, "ddpm3d_%s_workspace_bytes" % what)(*shape)
+    with torch.cuda.device(device):
+        ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=device)
+        status = torch.empty(2, dtype=torch.int32, device=device)
+        H.check(call(lib, H.ptr(ws), ws.numel() * 4, H.ptr(status), H.stream()))
+        rest = then() if then is not None else None
+        overrun, count = status.cpu().tolist()
+    if overrun:
+        raise RuntimeError("%s: a device loop hit its iteration cap; the %s are not valid" % (what, noun))
+    return int(count), rest
+
+
 def label_components(volume, threshold, connectivity=26, keep=None):
     """Connected components of volume > threshold (and keep != 0, an optional device uint8 tensor of the same shape)
     of a device float32 (D, H, W) tensor, connectivity 6, 18 or 26: one call of ddpm3d_label_components
@@ -1166,23 +1184,21 @@ def label_components(volume, threshold, connectivity=26, keep=None):
     D, Hh, W = (int(v) for v in volume.shape)
     if volume.numel() == 0 or volume.numel() > 2 ** 31 - 1:
         raise ValueError("label_components: %d voxels (1..2^31 - 1)" % volume.numel())
-    lib = H.load()
-    need = lib.ddpm3d_label_components_workspace_bytes(D, Hh, W)
-    with torch.cuda.device(volume.device):
-        ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=volume.device)
-        roots = torch.empty((D, Hh, W), dtype=torch.int32, device=volume.device)
-        status = torch.empty(2, dtype=torch.int32, device=volume.device)
-        H.check(lib.ddpm3d_label_components(H.ptr(volume), H.ptr(keep), threshold, connectivity, D, Hh, W,
-                                            H.ptr(roots), H.ptr(ws), ws.numel() * 4, H.ptr(status), H.stream()))
+    roots = torch.empty((D, Hh, W), dtype=torch.int32, device=volume.device)
+
+    def ranked():                                                  # queued behind the entry, before the status copy
         flat = roots.reshape(-1)
         is_root = flat == torch.arange(flat.numel(), dtype=torch.int32, device=volume.device)
         rank = torch.cumsum(is_root, 0, dtype=torch.int32)         # rank[root] = its 1-based number, in raster order
         labels = torch.where(flat >= 0, rank.index_select(0, flat.clamp(min=0)), torch.zeros_like(flat))
-        labels = labels.reshape(D, Hh, W)
-        overrun, n = status.cpu().tolist()                         # the one device-to-host copy
-    if overrun:
-        raise RuntimeError("label_components: a device loop hit its iteration cap; the labels are not valid")
-    return labels, int(n)
+        return labels.reshape(D, Hh, W)
+
+    n, labels = _forest_call(
+        "label_components", "labels", (D, Hh, W), volume.device,
+        lambda lib, *ws_status_stream: lib.ddpm3d_label_components(
+            H.ptr(volume), H.ptr(keep), threshold, connectivity, D, Hh, W, H.ptr(roots), *ws_status_stream),
+        then=ranked)
+    return labels, n
 
 
 def segment(volume, threshold, connectivity=26, min_voxels=1, keep=None):
@@ -1817,36 +1833,23 @@ def basins(height, labels, connectivity=26):
     (csrc/watershed.hip) and one copy of its status.  -> (peaks, n_basins): int32 (D, H, W) on the device, the flat
     index of each voxel's peak and -1 on the background."""
     D, Hh, W = _check_watershed("basins", height, labels, connectivity)
-    lib = H.load()
-    need = lib.ddpm3d_basins_workspace_bytes(D, Hh, W)
-    with torch.cuda.device(height.device):
-        ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=height.device)
-        peaks = torch.empty((D, Hh, W), dtype=torch.int32, device=height.device)
-        status = torch.empty(2, dtype=torch.int32, device=height.device)
-        H.check(lib.ddpm3d_basins(H.ptr(height), H.ptr(labels), connectivity, D, Hh, W, H.ptr(peaks), H.ptr(ws),
-                                  ws.numel() * 4, H.ptr(status), H.stream()))
-        overrun, n = status.cpu().tolist()
-    if overrun:
-        raise RuntimeError("basins: a device loop hit its iteration cap; the peaks are not valid")
-    return peaks, int(n)
+    peaks = torch.empty((D, Hh, W), dtype=torch.int32, device=height.device)
+    n, _ = _forest_call("basins", "peaks", (D, Hh, W), height.device,
+                        lambda lib, *ws_status_stream: lib.ddpm3d_basins(
+                            H.ptr(height), H.ptr(labels), connectivity, D, Hh, W, H.ptr(peaks), *ws_status_stream))
+    return peaks, n
 
 
 def _saddle_records(height, labels, peaks, connectivity, cap):
     """one call of ddpm3d_basin_saddles with room for cap records -> (pairs, saddle, records needed)"""
     D, Hh, W = (int(v) for v in height.shape)
-    lib = H.load()
-    need = lib.ddpm3d_basin_saddles_workspace_bytes(D, Hh, W)
-    ws = torch.empty(max(need, 16) // 4, dtype=torch.int32, device=height.device)
     pairs = torch.empty((cap, 2), dtype=torch.int32, device=height.device)
     saddle = torch.empty(cap, dtype=torch.float32, device=height.device)
-    status = torch.empty(2, dtype=torch.int32, device=height.device)
-    H.check(lib.ddpm3d_basin_saddles(H.ptr(height), H.ptr(labels), H.ptr(peaks), connectivity, D, Hh, W, cap,
-                                     H.ptr(pairs), H.ptr(saddle), H.ptr(ws), ws.numel() * 4, H.ptr(status),
-                                     H.stream()))
-    overrun, needed = status.cpu().tolist()
-    if overrun:
-        raise RuntimeError("basin_saddles: a device loop hit its iteration cap; the records are not valid")
-    return pairs, saddle, int(needed)
+    needed, _ = _forest_call("basin_saddles", "records", (D, Hh, W), height.device,
+                             lambda lib, *ws_status_stream: lib.ddpm3d_basin_saddles(
+                                 H.ptr(height), H.ptr(labels), H.ptr(peaks), connectivity, D, Hh, W, cap,
+                                 H.ptr(pairs), H.ptr(saddle), *ws_status_stream))
+    return pairs, saddle, needed
 
 
 def reduce_saddles(pairs, saddle):

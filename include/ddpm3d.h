@@ -1083,12 +1083,14 @@ int ddpm3d_shell_spectrum(const float* est, const float* est_pivot, const float*
  *                 their first voxel, which is scipy.ndimage.label's numbering.
  *   status        DEVICE int32[2] out: {a device loop hit its iteration cap (always 0; anything else means the result
  *                 must not be used), the number of roots}.  The kernels write both words; no need to clear them.
- * Four launches on `stream`: a workgroup per brick of DDPM3D_CCL_TILE_D x _H x _W voxels labels it in LDS; foreground
- * voxels on a brick's low faces unite the trees across brick borders (atomicMin on root slots only); every voxel
- * looks its root up; one workgroup folds per-workgroup root counts and cap flags from the workspace into status.  No
- * workgroup waits for another.
+ * A 16-byte clear and four launches on `stream`: a workgroup per brick of DDPM3D_CCL_TILE_D x _H x _W voxels labels
+ * it in LDS; foreground voxels on a brick's low faces unite the trees across brick borders (atomicMin on root slots
+ * only); every voxel looks its root up (the walk of ddpm3d_basins: every index checked against D * H * W before it is
+ * followed, and only a slot that holds its own index ends it); one workgroup sums the per-workgroup root counts from
+ * the workspace and writes them and the cap flag into status.  No workgroup waits for another.
  * ws: ddpm3d_label_components_workspace_bytes(D, H, W) bytes, 16-byte aligned; its contents before the call do not
- * matter (0 is the answer for a shape the entry refuses).  Returns DDPM3D_EINVAL before any launch for a NULL vol,
+ * matter (0 is the answer for a shape the entry refuses).  The need is 16 bytes and one 32-bit word per 1024 voxels,
+ * rounded up to 16: 0.5 MB at 700 x 440 x 440.  Returns DDPM3D_EINVAL before any launch for a NULL vol,
  * roots, status or ws, a connectivity other than 6 / 18 / 26, an extent below 1, D * H * W above 2^31 - 1 (labels are
  * 32-bit), a NaN threshold, and a workspace that is too small or misaligned.
  */

@@ -4,7 +4,8 @@ scipy.ndimage.label (tests/segment_ref.py), bit for bit, on volumes whose shapes
 so that they cross brick borders along every axis: random volumes just below the percolation threshold of each
 lattice and well above it, degenerate shapes, all foreground, all background, a serpentine through every brick, the
 checkerboard, voxel pairs that touch only across a brick corner or edge, NaN and threshold-valued voxels, a keep
-mask; the status words, independence of what the buffers held before, bit-repeatability; segment and detection
+mask; the status words, the root count across flatten workgroups, a short or missing workspace refused with every
+buffer untouched, independence of what the buffers held before, bit-repeatability; segment and detection
 against the yardstick; one device-to-host copy per detection; and the inference script's --roi_threshold_frac on
 two of its paths.  The labelling has one right answer: every comparison is equality.
 """
@@ -175,6 +176,40 @@ def test_result_does_not_depend_on_what_the_buffers_held(connectivity):
     filled = raw(vol, 0.5, connectivity, fill=0x7f)
     assert first[1] == again[1] == filled[1] and first[1][0] == 0
     assert first[0].tobytes() == again[0].tobytes() == filled[0].tobytes()
+
+
+def test_a_short_or_missing_workspace_is_refused():
+    """the need: the 16-byte status accumulator and one count word per 1024 voxels (the flatten's workgroups), not
+    the constant 16 bytes first planned: the labelling flatten measured slower with its counts in the accumulator"""
+    lib = _hip.load()
+    size = lib.ddpm3d_label_components_workspace_bytes
+    need = size(*SHAPE)
+    for shape in ((1, 1, 1), SHAPE):
+        voxels = shape[0] * shape[1] * shape[2]
+        assert size(*shape) % 16 == 0 and 16 < size(*shape) <= 16 + 16 + 4 * (voxels // 1024), shape
+    assert size(0, 4, 4) == size(4, 0, 4) == size(4, 4, 0) == 0
+    x = dev(volume_of(S.random_mask(SHAPE, 0.5, seed=1)))
+    ws = torch.full((need,), 0x5a, dtype=torch.uint8, device="cuda")
+    roots = torch.full(SHAPE, -77, dtype=torch.int32, device="cuda")
+    status = torch.full((2,), -7, dtype=torch.int32, device="cuda")
+    for ws_ptr, ws_bytes in ((_hip.ptr(ws), need - 1), (None, need)):
+        rc = lib.ddpm3d_label_components(_hip.ptr(x), None, 0.5, 26, *SHAPE, _hip.ptr(roots), ws_ptr, ws_bytes,
+                                         _hip.ptr(status), _hip.stream())
+        assert rc == _hip.E_INVAL, (rc, ws_bytes)
+        assert lib.ddpm3d_last_error().decode().startswith("label_components: needs %d bytes" % need)
+        torch.cuda.synchronize()
+        assert bool((roots == -77).all()) and status.tolist() == [-7, -7] and bool((ws == 0x5a).all())
+
+
+def test_root_count_across_flatten_workgroups():
+    """every foreground voxel of the 6-connected checkerboard is its own root, so every flatten workgroup (several,
+    the last one ragged) adds its share of the count; the number is numpy's"""
+    shape = (TD + 1, TH + 1, 2 * TW + 1)
+    mask = S.checkerboard(shape)
+    roots, status = raw(volume_of(mask), 0.5, 6, fill=0x7f)
+    assert status == [0, int(mask.sum())] and int(mask.sum()) > 4 * 1024
+    flat = np.arange(mask.size, dtype=np.int32).reshape(shape)
+    assert np.array_equal(roots, np.where(mask, flat, -1))
 
 
 def test_python_entry_refuses_what_it_cannot_take():

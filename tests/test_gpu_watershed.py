@@ -5,7 +5,8 @@ the reduced (pairs, saddle) with torch.equal, for connectivity 6, 18 and 26, on 
 workgroups of 256 voxels and a wave along every axis; random multi-label volumes with NaN and both infinities and
 with heights of four levels only; a ramp, a serpentine path whose chain crosses every workgroup, constant plateaus;
 the integer heights of a distance transform; split_components against the yardstick's split; the record capacity with
-guard words behind the buffers; and the same bits on a second run.
+guard words behind the buffers; a short or missing workspace refused with every buffer untouched; the labelling and
+the basins on one forest (ranked labels under a constant height); and the same bits on a second run.
 """
 
 import functools
@@ -243,6 +244,66 @@ def test_record_capacity(c):
         metrics._saddle_records = inner
     assert calls == [small, need]
     assert torch.equal(again[0], got_pairs) and torch.equal(again[1], got_saddle)
+
+
+@pytest.mark.parametrize("entry", ["basins", "basin_saddles"])
+def test_a_short_or_missing_workspace_is_refused(entry):
+    lib = _hip.load()
+    shape = (9, 9, 65)
+    h, lab = case_of(shape, 0)
+    dh, dl = dev(h), dev(lab)
+    need = getattr(lib, "ddpm3d_%s_workspace_bytes" % entry)(*shape)
+    assert need > 0 and need % 16 == 0
+    ws = torch.full((need,), 0x5a, dtype=torch.uint8, device="cuda")
+    peaks = torch.full(shape, -77, dtype=torch.int32, device="cuda")
+    pairs = torch.full((8, 2), -12345, dtype=torch.int32, device="cuda")
+    saddle = torch.full((8,), -777.0, dtype=torch.float32, device="cuda")
+    status = torch.full((2,), -7, dtype=torch.int32, device="cuda")
+    for ws_ptr, ws_bytes in ((_hip.ptr(ws), need - 1), (None, need)):
+        tail = (ws_ptr, ws_bytes, _hip.ptr(status), _hip.stream())
+        if entry == "basins":
+            rc = lib.ddpm3d_basins(_hip.ptr(dh), _hip.ptr(dl), 26, *shape, _hip.ptr(peaks), *tail)
+        else:
+            rc = lib.ddpm3d_basin_saddles(_hip.ptr(dh), _hip.ptr(dl), _hip.ptr(peaks), 26, *shape, 8, _hip.ptr(pairs),
+                                          _hip.ptr(saddle), *tail)
+        assert rc == _hip.E_INVAL, (rc, ws_bytes)
+        assert lib.ddpm3d_last_error().decode().startswith("%s: needs %d bytes" % (entry, need))
+        torch.cuda.synchronize()
+        assert bool((peaks == -77).all()) and status.tolist() == [-7, -7] and bool((ws == 0x5a).all())
+        assert bool((pairs == -12345).all()) and bool((saddle == -777.0).all())
+
+
+@pytest.mark.parametrize("c", CONNECTIVITIES)
+def test_labelling_and_basins_agree_on_one_forest(c):
+    """ddpm3d_label_components' ranked labels under a constant height: what the two definitions give, no more"""
+    import segment_ref
+    lib = _hip.load()
+    shape = (9, 9, 65)
+    mask = segment_ref.random_mask(shape, 0.5, seed=90 + c)
+    want_labels, n = segment_ref.label(mask, c)
+    vol = dev(np.where(mask, 1.0, 0.0).astype(np.float32))
+    need = lib.ddpm3d_label_components_workspace_bytes(*shape)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    roots = torch.empty(shape, dtype=torch.int32, device="cuda")
+    status = torch.full((2,), -7, dtype=torch.int32, device="cuda")
+    _hip.check(lib.ddpm3d_label_components(_hip.ptr(vol), None, 0.5, c, *shape, _hip.ptr(roots), _hip.ptr(ws), need,
+                                           _hip.ptr(status), _hip.stream()))
+    assert status.tolist() == [0, n]
+    assert np.array_equal(roots.cpu().numpy(), segment_ref.roots(want_labels))
+    labels, got_n = metrics.label_components(vol, 0.5, connectivity=c)
+    assert got_n == n and np.array_equal(labels.cpu().numpy(), want_labels)
+
+    height = np.full(shape, 2.5, dtype=np.float32)
+    want_peaks, n_peaks, _ = R.basins(height, want_labels, c)
+    peaks, status = raw_basins(dev(height), labels, c)
+    assert status.tolist() == [0, n_peaks] and n_peaks >= n
+    peaks = peaks.cpu().numpy()
+    assert np.array_equal(peaks, want_peaks)
+    assert np.array_equal(peaks >= 0, mask)
+    served = peaks[mask]                                                    # the peak of every foreground voxel
+    flat_labels, flat_peaks = want_labels.reshape(-1), peaks.reshape(-1)
+    assert np.array_equal(flat_labels[served], want_labels[mask]) and (flat_labels[served] > 0).all()
+    assert np.array_equal(flat_peaks[served], served)
 
 
 @pytest.mark.parametrize("c", CONNECTIVITIES)
